@@ -1,6 +1,12 @@
 """Benchmark of the hot path: ArrayPSFTransform.apply on a device-resident synthetic starfield.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--full [--no-cpu]] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, roofline.frac on the
+timed steps).  `--full` adds everything else the benchmark measures or checks, as before: the parity check against the
+CPU oracle (`--verify`), the new-frames loop, the HIP-event roofline loops, the end-to-end leg, the PMC traffic figure,
+the cpu_baseline leg and, for N > 1, the second seam mode.  `--dump-outputs DIR` writes the output of the last timed
+step as DIR/<name>.npy (float32; a fixed, seeded sample of the pixels when the output is larger than the budget).
 
 One "step" = one full device-resident apply (fused patch kernel + overlap-add) with image, output and packed transfer
 kernel resident in HBM.
@@ -73,6 +79,28 @@ def emit_json(line: dict) -> None:
         sys.stdout.flush()
     else:
         os.write(_REAL_STDOUT, data)
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: everything one run writes, over all ranks (under 64 MB)
+DUMP_SAMPLE_MAX = 1 << 21  # pixels in the sample of an output larger than its share of the budget
+
+
+def dump_outputs(directory: str, name: str, out: np.ndarray, share: int = 1) -> None:
+    """--dump-outputs: `out` (what the timed path returned in its last step) as DIR/<name>.npy, float32.  An output larger than its
+    share of the budget is written as a fixed sample instead: DIR/<name>_sample.npy (the values) and DIR/<name>_sample_index.npy
+    (their flat indices into `out`, float64), drawn by a seeded generator, so that two builds run with the same arguments write
+    the same pixels."""
+    d = pathlib.Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    out = np.ascontiguousarray(out, np.float32)
+    budget = DUMP_BUDGET_BYTES // max(1, share)
+    if out.nbytes <= budget:
+        np.save(d / f"{name}.npy", out)
+        return
+    count = min(DUMP_SAMPLE_MAX, budget // 12)  # 4 bytes per value + 8 per index
+    index = np.sort(np.random.default_rng(0).choice(out.size, count, replace=False))
+    np.save(d / f"{name}_sample.npy", out.reshape(-1)[index])
+    np.save(d / f"{name}_sample_index.npy", index.astype(np.float64))
 
 
 def cpu_model() -> str:
@@ -298,15 +326,19 @@ def run_batch(args, rank, world, device, comm):
         elapsed = comm.allreduce_max(elapsed)
     ms_per_step = 1e3 * elapsed / args.steps
     timed_region_ms = 1e3 * elapsed
-    iters = max(10, min(args.steps, 100))
-    total_ms, kernel_ms = plan.apply_batch_device_timed(d_in.ptr, d_out.ptr, frames, stride, stride, geom, iters)
-    kern_avg_ms = float(np.mean(kernel_ms))
+    if args.dump_outputs is not None:  # the frames of the last timed step, before anything else runs on the buffers
+        dump_outputs(args.dump_outputs, "output" if world == 1 else f"output_rank{rank}", d_out.download((frames, h, w)), world)
     alg_bytes = plan.transfer_bytes + frames * 2 * h * w * 4  # K once per batch + every frame read and written once
+    total_ms = kernel_ms = None
+    if args.full:
+        iters = max(10, min(args.steps, 100))
+        total_ms, kernel_ms = plan.apply_batch_device_timed(d_in.ptr, d_out.ptr, frames, stride, stride, geom, iters)
+        kern_avg_ms = float(np.mean(kernel_ms))
+        achieved_kernel = alg_bytes / (kern_avg_ms * 1e-3) / 1e9
     # the whole device-resident batch step (patch kernel + plane sum, fused or not), as for the single frames; the patch kernel
     # alone is kept as a second figure (with the fused sum they coincide)
-    step_ms = ms_per_step if world == 1 else float(np.mean(total_ms))
+    step_ms = ms_per_step if world == 1 or total_ms is None else float(np.mean(total_ms))
     achieved = alg_bytes / (step_ms * 1e-3) / 1e9
-    achieved_kernel = alg_bytes / (kern_avg_ms * 1e-3) / 1e9
     parity = None
     if args.verify:
         out = d_out.download((frames, h, w)).astype(np.float64)
@@ -347,12 +379,13 @@ def run_batch(args, rank, world, device, comm):
         "roofline": {
             "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None, "kernel": "patch_kernel2_256p" if n == 256 else "patch_kernel2_128p" if n == 128 else "patch_kernel",
-            "whole_step_ms": round(step_ms, 4), "frac_patch_kernel_only": round(achieved_kernel / HBM_PEAK_GBS, 4),
-            "kernel_avg_ms": round(kern_avg_ms, 4), "kernel_launches": iters, "algorithmic_bytes": int(alg_bytes),
+            "whole_step_ms": round(step_ms, 4), "algorithmic_bytes": int(alg_bytes),
             "bytes_model": "packed folded K read once per batch + every frame read once + every output written once",
-            "apply_avg_ms_events": round(float(np.mean(total_ms)), 4),
         },
     }
+    if total_ms is not None:  # --full: HIP events around the batch launches, after the timed loop
+        line["roofline"].update({"frac_patch_kernel_only": round(achieved_kernel / HBM_PEAK_GBS, 4), "kernel_avg_ms": round(kern_avg_ms, 4),
+                                 "kernel_launches": iters, "apply_avg_ms_events": round(float(np.mean(total_ms)), 4)})
     if parity:
         line["parity"] = parity
     if args.streamed and world == 1:
@@ -381,7 +414,7 @@ def run_batch(args, rank, world, device, comm):
             "pcie": {k: round(v, 4) for k, v in probe.items()}, "frame_bytes": h * w * 4,
             "process_bound_to_numa_node": bound_node, "device_numa_node": _native.device_numa_node(device),
         }
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         line["cpu_baseline"] = cpu_baseline(images[0], coords, k)
     emit_json(line)
 
@@ -482,31 +515,37 @@ def main() -> None:
                     help="N = 1: a 4096^2 frame with patches of this size instead of a numbered config - any size the reference takes (transform.py:151-155); "
                          "sizes other than 16, 32, 64, 128, 256 run the hipFFT fallback")
     ap.add_argument("--weak", action="store_true", help="N > 1: grow the image with the ranks instead of cutting one frame")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity against the CPU oracle, new-frames loop, HIP-event roofline loops, end-to-end leg, "
+                         "PMC traffic figure, cpu_baseline leg and (N > 1) the second seam mode; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step as DIR/<name>.npy (float32; a fixed, seeded pixel sample of outputs "
+                         "larger than the budget, with the flat pixel indices beside it)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--prewarm-ms", type=float, default=100.0,
                     help="untimed device activity before the W warm-up steps (clock ramp); 0 = off")
     ap.add_argument("--comm", choices=["rccl", "gloo"], default="rccl",
                     help="seam transport for N > 1; 'gloo' is a debug stand-in (host copies) used to exercise the "
                          "multi-rank flow on a box with fewer GPUs than ranks")
     ap.add_argument("--verify", action="store_true", default=None,
-                    help="check every rank's owned rows against the CPU oracle on one step outside the timed loops (default: on)")
+                    help="check every rank's owned rows against the CPU oracle on one step outside the timed loops (default: on with --full)")
     ap.add_argument("--no-verify", dest="verify", action="store_false")
     ap.add_argument("--second-leg-timeout", type=float, default=300.0,
                     help="N > 1: seconds the second seam leg may take before the headline line is emitted without it")
     ap.add_argument("--one-seam", action="store_true",
-                    help="N > 1: time only the --seam mode (default: the other seam mode is timed as a second leg in the same process)")
+                    help="N > 1, --full: time only the --seam mode (default with --full: the other seam mode is timed as a second leg in the same process)")
     ap.add_argument("--frames", type=int, default=8, help="config 5: frames per GPU in one batch")
     ap.add_argument("--streamed", action="store_true",
                     help="config 5, N = 1: also time the frames as HOST arrays in and out through the streamed entry point "
                          "(e2e_ms_per_frame, pcie_floor_ms in the line)")
     ap.add_argument("--no-bind", action="store_true", help="do not bind the process to the GPU's NUMA node for the end-to-end legs")
-    ap.add_argument("--no-e2e", action="store_true", help="N = 1: skip the end-to-end (host arrays in and out) leg")
+    ap.add_argument("--no-e2e", action="store_true", help="N = 1, --full: skip the end-to-end (host arrays in and out) leg")
     ap.add_argument("--rotate", type=int, default=1,
                     help="N = 1 only: this many DIFFERENT device-resident frames (and output buffers) are corrected in rotation.  "
                          "Default 1: the same frame every step, as in every earlier round - it then stays in the 256 MB Infinity "
                          "Cache between steps, which a stream of new frames would not (DESIGN.md, Measurement)")
     ap.add_argument("--new-frames", type=int, default=8,
-                    help="N = 1: after the timed loop, a second timed loop of K steps over this many different resident frames and "
+                    help="N = 1, --full: after the timed loop, a second timed loop of K steps over this many different resident frames and "
                          "outputs in rotation; reported as roofline.frac_new_frames / ms_per_step_new_frames next to the headline "
                          "(0 or 1: skip)")
     ap.add_argument("--in-flight", type=int, default=1,
@@ -529,6 +568,10 @@ def main() -> None:
                          "(BASELINE's halo reduce).  Measured band by band on one GPU with the product's own step (scripts/band_times.py, "
                          "profiles/r03e_*): 5.8x against 5.1x at eight bands, which is why recompute is the default (DESIGN.md 7)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and args.config == "construct":
+        ap.error("--dump-outputs: --config construct has no image output")
     quiet_stdout()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -545,7 +588,7 @@ def main() -> None:
     if args.config is None:
         args.config = 3 if world == 1 or args.weak else 4
     if args.verify is None:
-        args.verify = True
+        args.verify = args.full
 
     from oracle import regpsf_oracle as orc  # synthetic inputs + cpu_baseline only
     from regularizepsf_amd import _native
@@ -644,12 +687,12 @@ def main() -> None:
     overlap = False if args.no_overlap else {"pipeline": "pipeline", "two-plans": True, "plain": False}[args.exchange_mode]
     shard = ShardedApply(coords, kernel_for, n, height, w, rank, world, device, comm, pad_mode=pad, seam=args.seam,
                          overlap=overlap)
-    # N > 1: BOTH seam modes run in this process - the --seam one is the headline (timed first), the other a second leg with its own
+    # N > 1 with --full: BOTH seam modes run in this process - the --seam one is the headline (timed first), the other a second leg with its own
     # plans, K and buffers - so that the first run on a real multi-GPU node exercises the RCCL send / recv of the halo rows AND the
     # collective-free recompute, whichever of them is the default
     other_seam = {"recompute": "exchange", "exchange": "recompute"}[args.seam]
     shard2 = None
-    if world > 1 and not args.one_seam:
+    if world > 1 and args.full and not args.one_seam:
         shard2 = ShardedApply(coords, kernel_for, n, height, w, rank, world, device, comm, pad_mode=pad, seam=other_seam,
                               overlap=overlap)
     band = shard.band
@@ -710,6 +753,19 @@ def main() -> None:
         elapsed = comm.allreduce_max(elapsed)  # whole-job time = slowest rank
     ms_per_step = 1e3 * elapsed / args.steps
     timed_region_ms = 1e3 * elapsed
+    if args.dump_outputs is not None:  # the rows this rank owns after the last timed step, before anything else runs on the buffers
+        if rotation:
+            last = pairs[(spin[0] - 1) % len(pairs)][1]
+        elif pipeline:
+            last = plans[(turn[0] - 1) % len(plans)][1]
+        else:
+            last = None
+        if last is None:
+            rows = shard.owned_rows()
+        else:
+            _native.check(_native.lib().rpsf_device_synchronize(device))
+            rows = last.download((band.own_rows, w))
+        dump_outputs(args.dump_outputs, "output" if world == 1 else f"output_rank{rank}", rows, world)
 
     def verify_owned_rows(sh, label):
         """One step of `sh`, then every rank checks the rows it owns against the float64 oracle on the same inputs: the patches that
@@ -744,7 +800,7 @@ def main() -> None:
     # rotation.  The headline loop above corrects ONE frame K times (SURVEY.md 8d's timed region); that frame and part of its colour
     # planes then sit in the 256 MB Infinity Cache from step to step, which a production stream of frames does not have.
     new_frames_ms = new_frames_prefetch_ms = None
-    if world == 1 and not rotation and not pipeline and args.new_frames > 1:
+    if args.full and world == 1 and not rotation and not pipeline and args.new_frames > 1:
         extra = []
         for i in range(1, args.new_frames):
             frame = orc.starfield(h1, w, seed + 1000 * i)[band.image_row0:band.image_row0 + band.image_rows]
@@ -778,24 +834,32 @@ def main() -> None:
     # Algorithmic bytes: folded K read once (n N (N/2+1) complex64) + image read once + output written
     # once, over the whole device-resident apply of this rank (patch kernel + everything the overlap-add needs).  With
     # the plane sum fused into the patch launch (N = 256) the apply IS one launch of the dominant kernel.
+    # A plain run at N = 1 with one plan prices the timed steps themselves and runs no further loops; --full (and the cases whose
+    # roofline.frac is defined on the single apply by events: N > 1, --in-flight > 1) adds the event loops below.
+    events = args.full or world > 1 or bool(pipeline)
     iters = max(20, min(args.steps, 200))
-    # (the verification and the new-frames set-up above kept the host busy for seconds: the GPU has idled back to low clocks)
-    prewarm(lambda: plan.apply_device(d_img.ptr, d_out.ptr, geom), plan.synchronize, args.prewarm_ms)
-    loop_ms = plan.apply_device_loop_ms(d_img.ptr, d_out.ptr, geom, iters)
-    total_ms, kernel_ms = plan.apply_device_timed(d_img.ptr, d_out.ptr, geom, iters)
-    kern_avg_ms, apply_avg_ms = float(np.mean(kernel_ms)), float(np.mean(total_ms))
+    loop_ms = apply_avg_ms = None
+    kern_avg_ms = timed_loop_event_ms
+    if events:
+        # (the verification and the new-frames set-up above kept the host busy for seconds: the GPU has idled back to low clocks)
+        prewarm(lambda: plan.apply_device(d_img.ptr, d_out.ptr, geom), plan.synchronize, args.prewarm_ms)
+        loop_ms = plan.apply_device_loop_ms(d_img.ptr, d_out.ptr, geom, iters)
+        total_ms, kernel_ms = plan.apply_device_timed(d_img.ptr, d_out.ptr, geom, iters)
+        kern_avg_ms, apply_avg_ms = float(np.mean(kernel_ms)), float(np.mean(total_ms))
     # (each per-apply event pair puts a marker packet between two launches, ~8 us of the 184 here: the loop as the device sees it is one pair of
     # events around `iters` back-to-back applies; with the plane sum fused into the patch launch - N = 128, 256 - an apply IS one launch of the kernel)
     sweep = plan.sweep_info() if n <= 64 else {"regions": 0}
     one_launch = compiled and (n >= 128 or sweep["regions"] > 0)  # the whole apply is one launch of the dominant kernel
     if one_launch:
         kern_avg_ms = timed_loop_event_ms if timed_loop_event_ms is not None else loop_ms
+    elif not events:
+        kern_avg_ms = None  # (several launches per apply: the per-launch figure needs the event loops of --full)
     my_patches = plan.n_patches
     alg_bytes = my_patches * n * (n // 2 + 1) * 8 + band.image_rows * w * 4 + band.out_rows * w * 4
     # one rank's apply; at N = 1 the wall-clock step itself (with --in-flight > 1 the steps overlap: the single apply by events)
     step_ms = ms_per_step if world == 1 and not pipeline else apply_avg_ms
     achieved = alg_bytes / (step_ms * 1e-3) / 1e9
-    achieved_kernel = alg_bytes / (kern_avg_ms * 1e-3) / 1e9
+    achieved_kernel = alg_bytes / (kern_avg_ms * 1e-3) / 1e9 if kern_avg_ms is not None else None
 
     rccl_ranks = None
     if comm is not None and not isinstance(comm, GlooSeam):
@@ -828,17 +892,21 @@ def main() -> None:
             "kernel": ("hipFFT fallback: generic_gather + hipFFT C2C forward + generic_multiply + hipFFT C2C inverse + 4 x generic_scatter (colour classes) per chunk"
                        if not compiled else
                        "patch_kernel2_256p" if n == 256 else "patch_kernel2_128p" if n == 128 else "sweep_kernel" if sweep["regions"] else "patch_kernel"),
-            "whole_apply_ms": round(step_ms, 4), "kernel_avg_ms": round(kern_avg_ms, 4), "kernel_launches": iters,
-            "frac_patch_kernel_only": round(achieved_kernel / HBM_PEAK_GBS, 4),
+            "whole_apply_ms": round(step_ms, 4),
             "algorithmic_bytes": int(alg_bytes), "packed_k_bytes": int(plan.transfer_bytes),
             "bytes_model": "SURVEY 8d: folded K (n N (N/2+1) complex64) read once + image read once + output written once "
                            "(rank 0's band), divided by the whole device-resident apply",
-            "apply_avg_ms_events": round(apply_avg_ms, 4), "apply_avg_ms_event_loop": round(loop_ms, 4), "patches_this_rank": my_patches,
-            "kernel_avg_ms_from": ("one HIP event pair around the K back-to-back launches of the timed region itself (apply = one launch)" if one_launch and timed_loop_event_ms is not None else
-                                   "one HIP event pair around back-to-back launches after the timed loop (apply = one launch)" if one_launch else
-                                   "HIP event pairs around every patch-kernel launch"),
+            "patches_this_rank": my_patches,
         },
     }
+    if kern_avg_ms is not None:
+        line["roofline"].update({
+            "kernel_avg_ms": round(kern_avg_ms, 4), "frac_patch_kernel_only": round(achieved_kernel / HBM_PEAK_GBS, 4),
+            "kernel_avg_ms_from": ("one HIP event pair around the K back-to-back launches of the timed region itself (apply = one launch)" if one_launch and timed_loop_event_ms is not None else
+                                   "one HIP event pair around back-to-back launches after the timed loop (apply = one launch)" if one_launch else
+                                   "HIP event pairs around every patch-kernel launch")})
+    if events:
+        line["roofline"].update({"kernel_launches": iters, "apply_avg_ms_events": round(apply_avg_ms, 4), "apply_avg_ms_event_loop": round(loop_ms, 4)})
     if not compiled:  # the path the reference allows for every N: what it costs, with the bytes it really moves beside the algorithmic ones
         per = n * n * 8
         line["roofline"]["fallback"] = {
@@ -850,7 +918,7 @@ def main() -> None:
     if sweep["regions"]:  # third generation: how the lattice was cut (patches on region borders are computed by both neighbours)
         line["config"]["sweep"] = {"regions": sweep["regions"], "jobs": sweep["jobs"], "slabs_per_phase": sweep["slabs_per_phase"],
                                    "recompute_factor": round(sweep["patch_slots"] / max(1, my_patches), 3)}
-    if n == 256 and world == 1:  # what this kernel STRUCTURE can reach, as measured: not a tuning target but a bound
+    if args.full and n == 256 and world == 1:  # what this kernel STRUCTURE can reach, as measured: not a tuning target but a bound
         line["roofline"]["structure_ceiling"] = {
             "frac": 0.32, "ms": 0.165,
             "floors_ms": {"memory_system_alone": [0.145, 0.158], "on_chip_chain_alone": [0.153, 0.165], "without_lock_step_barriers": 0.167},
@@ -941,7 +1009,7 @@ def main() -> None:
             line["roofline"]["ms_per_step_new_frames_with_image_prefetch"] = round(new_frames_prefetch_ms, 4)
     if pipeline:  # the overlapped steps priced on the same bytes (not roofline.frac: SURVEY 8d's t is one device-resident apply)
         line["roofline"]["frac_steps_in_flight"] = round(alg_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-    if world == 1 and not args.no_e2e:
+    if args.full and world == 1 and not args.no_e2e:
         affinity = os.sched_getaffinity(0)
         try:  # (an auxiliary leg: whatever goes wrong in it must not cost the run its headline line)
             # one host-array apply(), end to end: what every caller of the class API gets (float32 frame in, float64 out as the reference
@@ -977,11 +1045,11 @@ def main() -> None:
         finally:
             os.sched_setaffinity(0, affinity)
     traffic_file = ROOT / "profiles" / ("traffic_latest.json" if args.config == 3 else f"traffic_config{args.config}.json")
-    if world == 1 and traffic_file.exists():  # PMC counters cannot be read from inside the process
+    if args.full and world == 1 and traffic_file.exists():  # PMC counters cannot be read from inside the process
         tr = json.loads(traffic_file.read_text())
         line["roofline"]["traffic"] = tr["traffic_bytes_per_launch"]
         line["roofline"]["traffic_source"] = tr["source"]
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         line["cpu_baseline"] = cpu_baseline(band_image, coords, kernel_for(list(range(len(coords)))))
     emit_json(line)
     if second_leg_note is not None:  # the headline leg is complete and reported; the failed second leg must still show in the exit code
