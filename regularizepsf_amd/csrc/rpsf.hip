@@ -25,9 +25,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #define RPSF_HOST_TU 1
@@ -88,20 +90,41 @@ static void py_slice(long start, long stop, long n, long* lo, long* hi) {
   *hi = std::min(stop, n);
 }
 
-// Device allocation that is freed on every exit path of the entry points that make temporaries
+// One device allocation of T[count], owned by the handle (move-only) and freed with it.  Free = hipHostFree: page-locked host memory.
+template <class T, hipError_t (*Free)(void*) = hipFree>
 struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-  void* release() {
-    void* q = p;
-    p = nullptr;
-    return q;
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p);
+    return *this;
   }
+  ~DevBuf() { reset(); }
+  void reset() {
+    if (p) (void)Free(p);
+    p = nullptr;
+  }
+  hipError_t alloc(size_t count) {
+    reset();
+    return hipMalloc(&p, count * sizeof(T));
+  }
+  hipError_t upload(const T* host, size_t count) {
+    const hipError_t e = alloc(count);
+    return e != hipSuccess ? e : hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice);
+  }
+  operator T*() const { return p; }
 };
 
+struct PipeRelease {
+  void operator()(rpsf_host::HostPipe* q) const {
+    q->destroy();
+    delete q;
+  }
+};
+struct FftPlanRelease {
+  void operator()(void* h) const;  // hipfftDestroy (g_hipfft, below)
+};
 
 // Host scratch of the saturation branch (rpsf_apply_host_saturated), per staging slot, kept between calls
 struct SatScratch {
@@ -117,53 +140,44 @@ struct SatScratch {
 // ------------------------------------------------------------------------------------------------
 // plan
 // ------------------------------------------------------------------------------------------------
-struct rpsf_plan {
-  int device = 0, N = 0, n_patches = 0;
-  int32_t* d_coords = nullptr;
-  uint16_t* d_tab = nullptr;
-  uint32_t* d_pairtab = nullptr;
-  cf* d_tw = nullptr;
-  float* d_win = nullptr;
-  cf* d_g = nullptr;
-  cf* d_gs = nullptr;
-  rpsf_host::HostPipe* pipe = nullptr;  // host-array entry points: staging slots, copy streams (rpsf_hostpipe.hpp)
-  // Views: a plan over a subset of another plan's patches that shares its tables, its packed K (desc.z = the patch's index in the
-  // parent) and its stream - the row bands a single large host frame is cut into so that its upload, its patches and its download
-  // overlap (host_one_frame).  Owned by the parent, built for one frame shape.
-  std::vector<SatScratch> sat;  // rpsf_apply_host_saturated: per staging slot, the 2N-padded float64 frame, its mask and the raw values (host scratch, kept between calls)
-  rpsf_plan* parent = nullptr;
-  std::vector<int32_t> k_index;           // view: patch i of this plan is patch k_index[i] of the parent
-  std::vector<rpsf_plan*> bands;          // parent: its row-band views
-  std::vector<int> band_rows;             // bands.size() + 1 output row boundaries
-  std::vector<int> band_in_rows;          // per band: image rows [0, band_in_rows[b]) must be resident before it runs
-  int bands_h = 0, bands_w = 0, bands_mode = -1, bands_want = -1;
-  bool have_k = false;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+// The fallback through hipFFT: any patch size without a compiled kernel
+struct FftPath {
+  DevBuf<cf> d_kfull;       // the caller's K, (n, N, N) complex64, unfolded
+  DevBuf<cf> d_buf;         // chunk x N x N complex work buffer
+  DevBuf<float> d_win;
+  DevBuf<uint8_t> d_colour;  // colour class per patch when the corners allow one (generic_colours), else null: atomic adds
+  std::unique_ptr<void, FftPlanRelease> plan;  // hipfftHandle for `chunk` patches
+  int chunk = 0;
+};
+
+// The patch kernels: first generation (N = 16 ... 64, colour planes or atomics) and second (N = 128, 256: fused plane sum, persistent
+// queues, opt-in direct mode).  A view's tables and packed K are its parent's (owner()).
+struct PatchPath {
+  DevBuf<uint16_t> d_tab;
+  DevBuf<uint32_t> d_pairtab;
+  DevBuf<cf> d_tw;
+  DevBuf<cf> d_g, d_gs;
   size_t g_elems = 0, gs_elems = 0;
-  std::vector<int32_t> h_coords;
-  // overlap-add strategy: on regular half-overlap lattices direct accumulation through the XCD's L2 (three-stage
-  // plans) or colour planes + plane sum (the small-patch plans); float atomics for any other corner list
-  int overlap_mode = 0;  // 0 auto, 1 atomics, 2 planes, 3 direct
-  int stagger_us = -1, cu_count = 256;  // -1: automatic (12 us for persistent launches of 256 patches and more, else none)
+  DevBuf<unsigned long long> d_stamps;
+  DevBuf<float> d_sink;  // write-only scratch for the out-of-image pixels of rim patches
+  int stagger_us = -1;  // -1: automatic (12 us for persistent launches of 256 patches and more, else none)
   int round_capacity = 0;  // patches the chip holds at once (CUs x resident workgroups x patches per workgroup)
-  bool lattice = false;
   bool direct_ok = false;  // lattice and one patch per workgroup
   bool v2 = false;         // second-generation kernel (rpsf_core2.hpp): N = 128, 256
   // Fused plane sum (second-generation kernels, one frame, aligned geometry): the workgroups behind the patches in the
   // grid sum a lattice tile as soon as all its contributors have published their (write-through) plane stores, so
   // the sum runs on the CUs the partial last round leaves idle and no second kernel is needed.
-  uint32_t* d_tile_done = nullptr;   // per tile: contributors done, never reset (epoch * contributors after every apply)
-  uint32_t* d_sum_order = nullptr;   // all tiles, the ones whose contributors run first first
+  DevBuf<uint32_t> d_tile_done;   // per tile: contributors done, never reset (epoch * contributors after every apply)
+  DevBuf<uint32_t> d_sum_order;   // all tiles, the ones whose contributors run first first
   uint32_t done_epoch = 0;
   size_t done_frames = 1;            // frames the tile counters are sized for (batches: one set per frame)
   int done_last_frames = 1;          // frames of the last fused launch (the counters restart when the number changes)
-  uint32_t* d_sum_queue = nullptr;   // position in d_sum_order, never reset
+  DevBuf<uint32_t> d_sum_queue;   // position in d_sum_order, never reset
   uint32_t sum_queue_base = 0;
   bool no_fuse = false;
   int sum_first = -1;                // RPSF_SUM_FIRST override of sum_first_for(), -1 = none
   bool prefetch = false;             // persistent launches: head summing workgroups touch the image first (RPSF_PREFETCH)
-  uint32_t* d_prefetch_tiles = nullptr;  // per chunk: lattice tiles in the order the chunk's patches first need them
+  DevBuf<uint32_t> d_prefetch_tiles;  // per chunk: lattice tiles in the order the chunk's patches first need them
   uint32_t prefetch_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   int head_patches = 0;              // (measured neutral, profiles/r03i: off) persistent launches: patches a head summing workgroup computes before it sums (RPSF_HEAD_PATCHES)
   bool fuse_pays = false;            // the second-generation plans (N = 128, 256)
@@ -171,54 +185,99 @@ struct rpsf_plan {
   bool persist = false;
   bool k_cached = false;             // 128-pixel persistent launches take patch_kernel2_128pc (plain loads of the pair words): see rpsf_plan_create
   int reserved_cus = 0;              // persistent launches leave this many CUs without a patch workgroup (rpsf_plan_set_reserved_cus)
-  uint32_t* d_xq = nullptr;          // 8 counters, one per 128-byte line
+  DevBuf<uint32_t> d_xq;          // 8 counters, one per 128-byte line
   uint32_t xq_base[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint4* d_quads = nullptr;        // per processing-order slot: quadrant words (rpsf_core.hpp, store_patch_direct)
-  uint8_t* d_tile_info = nullptr;  // per lattice tile: static side mask | 16 if any patch covers it
-  uint32_t* d_flags = nullptr;     // per (frame, tile)
-  uint32_t* d_dyn = nullptr;       // per (frame, tile)
-  uint32_t* d_chunk_xcc = nullptr; // 8 words
+  DevBuf<uint4> d_quads;        // per processing-order slot: quadrant words (rpsf_core.hpp, store_patch_direct)
+  DevBuf<uint8_t> d_tile_info;  // per lattice tile: static side mask | 16 if any patch covers it
+  DevBuf<uint32_t> d_flags;     // per (frame, tile)
+  DevBuf<uint32_t> d_dyn;       // per (frame, tile)
+  DevBuf<uint32_t> d_chunk_xcc; // 8 words
   size_t flag_frames = 0;
   uint32_t epoch = 0;
   int orphan_mod = 0;              // testing aid (RPSF_OPT_DEBUG_ORPHAN)
-  int plane_nt_opt = -1, host_bands_opt = -1, stream_group_opt = 0, stream_depth_opt = 0;  // rpsf_plan_set_option; -1 / 0: the library decides
-  int last_host_bands = 0;  // row bands the last single host frame was cut into (rpsf_plan_host_bands)
-  hipEvent_t ev_busy = nullptr;    // end of the last apply (applies on different streams are serialised)
-  hipStream_t last_stream = nullptr;
-  bool busy_valid = false;
-  int lat_r0 = 0, lat_c0 = 0, nti = 0, ntj = 0;
-  uint8_t* d_cover = nullptr;
-  int4* d_desc = nullptr;
-  std::vector<int32_t> h_order;
-  unsigned long long* d_stamps = nullptr;
-  float* d_sink = nullptr;  // write-only scratch for the out-of-image pixels of rim patches
-  // generic (hipFFT) plans: any patch size without a compiled kernel
-  int corner_min[2] = {0, 0}, corner_max[2] = {0, 0};  // extreme patch corners (row, col)
-  bool generic = false;
-  cf* d_kfull = nullptr;       // the caller's K, (n, N, N) complex64, unfolded
-  cf* d_fft_buf = nullptr;     // fft_chunk x N x N complex work buffer
-  float* d_win_generic = nullptr;
-  uint8_t* d_colour_generic = nullptr;  // colour class per patch when the corners allow one (generic_colours), else null: atomic adds
-  void* fft_plan = nullptr;    // hipfftHandle for fft_chunk patches
-  int fft_chunk = 0;
-  // third generation (rpsf_kernels3.hpp, N <= 64 on a complete lattice of at least 2 x 2 patches): regions, job lists, packed K
-  bool sweep_ok = false;
-  Job3* d_jobs3 = nullptr;
-  Region3* d_regions3 = nullptr;
-  int n_regions3 = 0, ks3 = 0, par_j3 = 0;
-  std::vector<int32_t> slot3;  // lattice cell -> transfer-kernel slot
-  long slabs3 = 0, patch_slots3 = 0;
-  float* d_k3 = nullptr;      // n_patches x Cfg3::K_FLOATS (a view shares its parent's)
-  float* d_zero3 = nullptr;   // 16 bytes of zeros
-  uint32_t* h_err3 = nullptr;  // page-locked word the sweep kernel sets when a job waited for its predecessors beyond the bound (a view uses its parent's)
-  uint32_t* d_err3 = nullptr;  // ... as the device sees it
-  bool owns_err3 = false;
-  unsigned long long* d_stamps3 = nullptr;  // development builds (-DRPSF3_STAMPS)
-  size_t k3_floats = 0;
-  float* d_planes = nullptr;
+  int plane_nt_opt = -1;           // rpsf_plan_set_option; -1: the library decides
+  DevBuf<float> d_planes;
   size_t planes_floats = 0;  // per plane
   size_t planes_frames = 0;  // frames the allocation holds (4 planes each)
 };
+
+// The sweep kernel (third generation, rpsf_kernels3.hpp, N <= 64 on a complete lattice of at least 2 x 2 patches): regions, job lists,
+// packed K.  A view's packed K and error word are its parent's (owner()).
+struct SweepPath {
+  bool ok = false;
+  DevBuf<Job3> d_jobs;
+  DevBuf<Region3> d_regions;
+  int n_regions = 0, ks = 0, par_j = 0;
+  std::vector<int32_t> slot;  // lattice cell -> transfer-kernel slot
+  long slabs = 0, patch_slots = 0;
+  DevBuf<float> d_k3;      // n_patches x Cfg3::K_FLOATS
+  size_t k3_floats = 0;
+  DevBuf<float> d_zero;    // 16 bytes of zeros
+  DevBuf<uint32_t, hipHostFree> err;  // page-locked word the sweep kernel sets when a job waited for its predecessors beyond the bound
+  uint32_t* d_err = nullptr;          // ... as the device sees it
+  DevBuf<unsigned long long> d_stamps;  // development builds (-DRPSF3_STAMPS)
+};
+
+// The plan's stream and events: a base, so that they are destroyed after the plan's buffers (members go before bases)
+struct PlanStream {
+  hipStream_t stream = nullptr;
+  bool borrowed_stream = false;  // a view runs on its parent's
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev_busy = nullptr;    // end of the last apply (applies on different streams are serialised)
+  ~PlanStream() {
+    if (ev_busy) (void)hipEventDestroy(ev_busy);
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (stream && !borrowed_stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+struct rpsf_plan : PlanStream {
+  int device = 0, N = 0, n_patches = 0;
+  DevBuf<int32_t> d_coords;
+  DevBuf<float> d_win;  // read by the patch kernels and the sweep kernel; uploaded with the first-generation tables (a view reads its parent's)
+  std::unique_ptr<rpsf_host::HostPipe, PipeRelease> pipe;  // host-array entry points: staging slots, copy streams (rpsf_hostpipe.hpp)
+  std::vector<SatScratch> sat;  // rpsf_apply_host_saturated: per staging slot, the 2N-padded float64 frame, its mask and the raw values (host scratch, kept between calls)
+  // Views: a plan over a subset of another plan's patches that shares its tables, its packed K (desc.z = the patch's index in the
+  // parent), its error word and its stream - the row bands a single large host frame is cut into so that its upload, its patches and
+  // its download overlap (host_one_frame).  Owned by the parent, which destroys them before its own buffers; built for one frame shape.
+  rpsf_plan* parent = nullptr;
+  std::vector<int32_t> k_index;           // view: patch i of this plan is patch k_index[i] of the parent
+  std::vector<std::unique_ptr<rpsf_plan>> bands;  // parent: its row-band views
+  std::vector<int> band_rows;             // bands.size() + 1 output row boundaries
+  std::vector<int> band_in_rows;          // per band: image rows [0, band_in_rows[b]) must be resident before it runs
+  int bands_h = 0, bands_w = 0, bands_mode = -1, bands_want = -1;
+  bool have_k = false;
+  std::vector<int32_t> h_coords;
+  // overlap-add strategy: on regular half-overlap lattices direct accumulation through the XCD's L2 (three-stage
+  // plans) or colour planes + plane sum (the small-patch plans); float atomics for any other corner list
+  int overlap_mode = 0;  // 0 auto, 1 atomics, 2 planes, 3 direct
+  int cu_count = 256;
+  bool lattice = false;
+  int host_bands_opt = -1, stream_group_opt = 0, stream_depth_opt = 0;  // rpsf_plan_set_option; -1 / 0: the library decides
+  int last_host_bands = 0;  // row bands the last single host frame was cut into (rpsf_plan_host_bands)
+  hipStream_t last_stream = nullptr;
+  bool busy_valid = false;
+  // the lattice (setup_lattice): read by the planes, the sweep kernel and host_one_frame
+  int lat_r0 = 0, lat_c0 = 0, nti = 0, ntj = 0;
+  DevBuf<uint8_t> d_cover;
+  DevBuf<int4> d_desc;
+  std::vector<int32_t> h_order;
+  int corner_min[2] = {0, 0}, corner_max[2] = {0, 0};  // extreme patch corners (row, col)
+  bool generic = false;
+  FftPath fft;
+  PatchPath patch;
+  SweepPath sweep;
+
+  ~rpsf_plan() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    bands.clear();
+  }
+};
+
+// The plan whose tables, packed K and sweep error word a plan reads: a view borrows its parent's
+static const rpsf_plan* owner(const rpsf_plan* p) { return p->parent ? p->parent : p; }
 
 enum OverlapKind { OV_ATOMIC = 0, OV_PLANES = 1, OV_DIRECT = 2, OV_SWEEP = 3 };
 static OverlapKind overlap_kind(const rpsf_plan* p);
@@ -241,35 +300,27 @@ static int build_sweep_lists(rpsf_plan* p, int target_regions) {
   const int nli = p->nti - 1, nlj = p->ntj - 1;
   Plan3 plan;
   const bool built = dispatch_v3(p->N, [&]<class C>() -> int {
-    return plan3_build(C::N, C::KSMAX, C::WAVES, nli, nlj, p->slot3.data(), p->par_j3, target_regions, plan) ? RPSF_OK : RPSF_E_STATE;
+    return plan3_build(C::N, C::KSMAX, C::WAVES, nli, nlj, p->sweep.slot.data(), p->sweep.par_j, target_regions, plan) ? RPSF_OK : RPSF_E_STATE;
   }) == RPSF_OK;
   if (!built) return RPSF_OK;  // (the plan keeps its other paths)
-  (void)hipFree(p->d_jobs3), (void)hipFree(p->d_regions3);
-  p->d_jobs3 = nullptr, p->d_regions3 = nullptr, p->sweep_ok = false;
-  HIP_TRY(hipMalloc(&p->d_jobs3, plan.jobs.size() * sizeof(Job3)));
-  HIP_TRY(hipMemcpy(p->d_jobs3, plan.jobs.data(), plan.jobs.size() * sizeof(Job3), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&p->d_regions3, plan.regions.size() * sizeof(Region3)));
-  HIP_TRY(hipMemcpy(p->d_regions3, plan.regions.data(), plan.regions.size() * sizeof(Region3), hipMemcpyHostToDevice));
-  if (!p->d_zero3) {
-    HIP_TRY(hipMalloc(&p->d_zero3, 64));
-    HIP_TRY(hipMemset(p->d_zero3, 0, 64));
+  SweepPath& sw = p->sweep;
+  sw.ok = false;
+  HIP_TRY(sw.d_jobs.upload(plan.jobs.data(), plan.jobs.size()));
+  HIP_TRY(sw.d_regions.upload(plan.regions.data(), plan.regions.size()));
+  if (!sw.d_zero) {
+    HIP_TRY(sw.d_zero.alloc(16));
+    HIP_TRY(hipMemset(sw.d_zero, 0, 64));
   }
-  if (!p->h_err3) {
-    if (p->parent && p->parent->h_err3) {
-      p->h_err3 = p->parent->h_err3, p->d_err3 = p->parent->d_err3;
-    } else {
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->h_err3), 64, hipHostMallocMapped));
-      std::memset(p->h_err3, 0, 64);
-      HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&p->d_err3), p->h_err3, 0));
-      p->owns_err3 = true;
-    }
+  if (!p->parent && !sw.err) {  // (a view's kernel reports through its parent's word)
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sw.err.p), 64, hipHostMallocMapped));
+    std::memset(sw.err, 0, 64);
+    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&sw.d_err), sw.err, 0));
   }
-  p->n_regions3 = (int)plan.regions.size(), p->ks3 = plan.ks, p->slabs3 = plan.slabs, p->patch_slots3 = plan.patch_slots;
-  p->sweep_ok = true;
+  p->sweep.n_regions = (int)plan.regions.size(), p->sweep.ks = plan.ks, p->sweep.slabs = plan.slabs, p->sweep.patch_slots = plan.patch_slots;
+  p->sweep.ok = true;
 #if defined(RPSF3_STAMPS) || defined(RPSF3_DUMP)
-  (void)hipFree(p->d_stamps3);
-  HIP_TRY(hipMalloc(&p->d_stamps3, (size_t)std::max(512, p->n_regions3) * 8 * 8 * 16 * sizeof(unsigned long long)));
-  HIP_TRY(hipMemset(p->d_stamps3, 0, (size_t)std::max(512, p->n_regions3) * 8 * 8 * 16 * sizeof(unsigned long long)));
+  HIP_TRY(p->sweep.d_stamps.alloc((size_t)std::max(512, p->sweep.n_regions) * 8 * 8 * 16));
+  HIP_TRY(hipMemset(p->sweep.d_stamps, 0, (size_t)std::max(512, p->sweep.n_regions) * 8 * 8 * 16 * sizeof(unsigned long long)));
 #endif
   return RPSF_OK;
 }
@@ -309,7 +360,7 @@ static int setup_lattice(rpsf_plan* p) {
   p->lattice = ok;
   const int t = p->N * p->N / 2 / 64, teams = t >= 64 ? 1 : 64 / t;
   const int chunk = ((n + 7) / 8 + teams - 1) / teams * teams;  // as launch_patches cuts the order
-  p->direct_ok = ok && teams == 1;
+  p->patch.direct_ok = ok && teams == 1;
   // ---- processing order: 8 chunks, one per XCD (workgroups b and b + 8 share one) ----
   p->h_order.resize(n);
   if (ok) {
@@ -376,16 +427,15 @@ static int setup_lattice(rpsf_plan* p) {
       int i = p->h_order[s2];
       desc[s2] = make_int4(p->h_coords[2 * i], p->h_coords[2 * i + 1], p->k_index.empty() ? i : p->k_index[i], ok ? cls[i] : 0);
     }
-    HIP_TRY(hipMalloc(&p->d_desc, sizeof(int4) * n));
-    HIP_TRY(hipMemcpy(p->d_desc, desc.data(), sizeof(int4) * n, hipMemcpyHostToDevice));
+    HIP_TRY(p->d_desc.upload(desc.data(), n));
   }
   if (!ok) return RPSF_OK;
   p->lat_r0 = r0, p->lat_c0 = c0, p->nti = nti, p->ntj = ntj;
   // ---- third generation: regions and job lists (rpsf_plan3.hpp) when every lattice cell has its patch ----
   if (has_v3(p->N) && nli >= 2 && nlj >= 2 && (size_t)nli * nlj == (size_t)n) {
-    p->slot3.resize((size_t)nli * nlj);
-    for (size_t c = 0; c < p->slot3.size(); ++c) p->slot3[c] = p->k_index.empty() ? cell[c] : p->k_index[cell[c]];
-    p->par_j3 = par_j;
+    p->sweep.slot.resize((size_t)nli * nlj);
+    for (size_t c = 0; c < p->sweep.slot.size(); ++c) p->sweep.slot[c] = p->k_index.empty() ? cell[c] : p->k_index[cell[c]];
+    p->sweep.par_j = par_j;
     const int rc3 = build_sweep_lists(p, std::max(8, p->cu_count));
     if (rc3 != RPSF_OK) return rc3;
   }
@@ -419,7 +469,7 @@ static int setup_lattice(rpsf_plan* p) {
         const int i = who[k];
         const int li = (p->h_coords[2 * i] - r0) / half, lj = (p->h_coords[2 * i + 1] - c0) / half;
         const int q = 2 * (ti - li) + (tj - lj);
-        if (p->direct_ok && chunk_of[i] == owner) {
+        if (p->patch.direct_ok && chunk_of[i] == owner) {
           quad_of[(size_t)i * 4 + q] = quad_word(QUAD_DIRECT, (uint32_t)rank++, (uint32_t)tile);
         } else {
           quad_of[(size_t)i * 4 + q] = quad_word(QUAD_SIDE, 0, (uint32_t)tile);
@@ -428,9 +478,8 @@ static int setup_lattice(rpsf_plan* p) {
       }
       tile_info[tile] = (uint8_t)(side | (nwho ? 16 : 0));
     }
-  HIP_TRY(hipMalloc(&p->d_cover, cover.size()));
-  HIP_TRY(hipMemcpy(p->d_cover, cover.data(), cover.size(), hipMemcpyHostToDevice));
-  if (p->v2) {  // fused plane sum: tile order (by the slot of the last contributor: the dispatch order inside a chunk) and counters
+  HIP_TRY(p->d_cover.upload(cover.data(), cover.size()));
+  if (p->patch.v2) {  // fused plane sum: tile order (by the slot of the last contributor: the dispatch order inside a chunk) and counters
     std::vector<std::pair<int, uint32_t>> keyed;
     for (int ti = 0; ti < nti; ++ti)
       for (int tj = 0; tj < ntj; ++tj) {
@@ -447,18 +496,17 @@ static int setup_lattice(rpsf_plan* p) {
     std::stable_sort(keyed.begin(), keyed.end(), [](const auto& a2, const auto& b2) { return a2.first < b2.first; });
     std::vector<uint32_t> order(keyed.size());
     for (size_t i = 0; i < keyed.size(); ++i) order[i] = keyed[i].second;
-    HIP_TRY(hipMalloc(&p->d_sum_order, order.size() * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(p->d_sum_order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&p->d_tile_done, order.size() * sizeof(uint32_t)));
-    HIP_TRY(hipMemset(p->d_tile_done, 0, order.size() * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&p->d_sum_queue, sizeof(uint32_t)));
-    HIP_TRY(hipMemset(p->d_sum_queue, 0, sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&p->d_xq, 8 * 32 * sizeof(uint32_t)));
-    HIP_TRY(hipMemset(p->d_xq, 0, 8 * 32 * sizeof(uint32_t)));
+    HIP_TRY(p->patch.d_sum_order.upload(order.data(), order.size()));
+    HIP_TRY(p->patch.d_tile_done.alloc(order.size()));
+    HIP_TRY(hipMemset(p->patch.d_tile_done, 0, order.size() * sizeof(uint32_t)));
+    HIP_TRY(p->patch.d_sum_queue.alloc(1));
+    HIP_TRY(hipMemset(p->patch.d_sum_queue, 0, sizeof(uint32_t)));
+    HIP_TRY(p->patch.d_xq.alloc(8 * 32));
+    HIP_TRY(hipMemset(p->patch.d_xq, 0, 8 * 32 * sizeof(uint32_t)));
     {  // image prefetch lists: for every chunk, each lattice tile once, in the order the chunk's slots first touch it
       std::vector<uint32_t> tiles;
       for (int x = 0; x < 8; ++x) {
-        p->prefetch_first[x] = (uint32_t)tiles.size();
+        p->patch.prefetch_first[x] = (uint32_t)tiles.size();
         std::vector<char> seen((size_t)nti * ntj, 0);
         for (int s2 = std::min(n, x * chunk); s2 < std::min(n, (x + 1) * chunk); ++s2) {
           const int i = p->h_order[s2];
@@ -470,23 +518,21 @@ static int setup_lattice(rpsf_plan* p) {
         }
       }
 
-      p->prefetch_first[8] = (uint32_t)tiles.size();
-      HIP_TRY(hipMalloc(&p->d_prefetch_tiles, std::max<size_t>(1, tiles.size()) * sizeof(uint32_t)));
-      HIP_TRY(hipMemcpy(p->d_prefetch_tiles, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      p->patch.prefetch_first[8] = (uint32_t)tiles.size();
+      HIP_TRY(p->patch.d_prefetch_tiles.alloc(std::max<size_t>(1, tiles.size())));
+      HIP_TRY(hipMemcpy(p->patch.d_prefetch_tiles, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
   }
-  if (p->direct_ok) {
+  if (p->patch.direct_ok) {
     std::vector<uint4> quads(n);
     for (int s2 = 0; s2 < n; ++s2) {
       const uint32_t* q = &quad_of[(size_t)p->h_order[s2] * 4];
       quads[s2] = make_uint4(q[0], q[1], q[2], q[3]);
     }
-    HIP_TRY(hipMalloc(&p->d_quads, sizeof(uint4) * n));
-    HIP_TRY(hipMemcpy(p->d_quads, quads.data(), sizeof(uint4) * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&p->d_tile_info, tile_info.size()));
-    HIP_TRY(hipMemcpy(p->d_tile_info, tile_info.data(), tile_info.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&p->d_chunk_xcc, 8 * sizeof(uint32_t)));
-    HIP_TRY(hipMemset(p->d_chunk_xcc, 0, 8 * sizeof(uint32_t)));
+    HIP_TRY(p->patch.d_quads.upload(quads.data(), n));
+    HIP_TRY(p->patch.d_tile_info.upload(tile_info.data(), tile_info.size()));
+    HIP_TRY(p->patch.d_chunk_xcc.alloc(8));
+    HIP_TRY(hipMemset(p->patch.d_chunk_xcc, 0, 8 * sizeof(uint32_t)));
   }
   return RPSF_OK;
 }
@@ -524,7 +570,7 @@ static void host_tables(int N, std::vector<cf>& tw, std::vector<float>& win) {
 }
 
 template <class C>
-static int upload_tables(int device, uint16_t** d_tab, cf** d_tw, float** d_win, uint32_t** d_pairtab = nullptr) {
+static int upload_tables(int device, DevBuf<uint16_t>& d_tab, DevBuf<cf>& d_tw, DevBuf<float>* d_win = nullptr, DevBuf<uint32_t>* d_pairtab = nullptr) {
   std::vector<uint16_t> tab((size_t)C::T * C::NSLOT * 2);
   build_slot_table<C>(tab.data());
   std::vector<uint32_t> pt((size_t)C::PT_WORDS + 1);
@@ -533,28 +579,15 @@ static int upload_tables(int device, uint16_t** d_tab, cf** d_tw, float** d_win,
   std::vector<float> win;
   host_tables(C::N, tw, win);
   HIP_TRY(hipSetDevice(device));
-  DevBuf b_pt, b_tab, b_tw, b_win;  // handed over only when everything has been uploaded: nothing leaks on an error
-  if (d_pairtab) {
-    HIP_TRY(b_pt.alloc(pt.size() * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(b_pt.p, pt.data(), pt.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  HIP_TRY(b_tab.alloc(tab.size() * sizeof(uint16_t)));
-  HIP_TRY(hipMemcpy(b_tab.p, tab.data(), tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  HIP_TRY(b_tw.alloc(tw.size() * sizeof(cf)));
-  HIP_TRY(hipMemcpy(b_tw.p, tw.data(), tw.size() * sizeof(cf), hipMemcpyHostToDevice));
-  if (d_win) {
-    HIP_TRY(b_win.alloc(win.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(b_win.p, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  if (d_pairtab) *d_pairtab = static_cast<uint32_t*>(b_pt.release());
-  *d_tab = static_cast<uint16_t*>(b_tab.release());
-  *d_tw = static_cast<cf*>(b_tw.release());
-  if (d_win) *d_win = static_cast<float*>(b_win.release());
+  if (d_pairtab) HIP_TRY(d_pairtab->upload(pt.data(), pt.size()));
+  HIP_TRY(d_tab.upload(tab.data(), tab.size()));
+  HIP_TRY(d_tw.upload(tw.data(), tw.size()));
+  if (d_win) HIP_TRY(d_win->upload(win.data(), win.size()));
   return RPSF_OK;
 }
 
 template <class C>
-static int upload_tables2(int device, uint16_t** d_tab, cf** d_tw, float** d_win, uint32_t** d_ot) {
+static int upload_tables2(int device, DevBuf<uint16_t>& d_tab, DevBuf<cf>& d_tw, DevBuf<float>& d_win, DevBuf<uint32_t>& d_ot) {
   std::vector<uint16_t> tab((size_t)C::T * C::NSLOT * 2);
   build_slot_table2<C>(tab.data());
   std::vector<uint32_t> ot((size_t)C::ORBIT_ROUNDS * 64);
@@ -564,19 +597,10 @@ static int upload_tables2(int device, uint16_t** d_tab, cf** d_tw, float** d_win
   std::vector<float> win;
   host_tables(C::N, tw, win);
   HIP_TRY(hipSetDevice(device));
-  DevBuf b_ot, b_tab, b_tw, b_win;
-  HIP_TRY(b_ot.alloc(ot.size() * sizeof(uint32_t)));
-  HIP_TRY(hipMemcpy(b_ot.p, ot.data(), ot.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_TRY(b_tab.alloc(tab.size() * sizeof(uint16_t)));
-  HIP_TRY(hipMemcpy(b_tab.p, tab.data(), tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  HIP_TRY(b_tw.alloc(tw.size() * sizeof(cf)));
-  HIP_TRY(hipMemcpy(b_tw.p, tw.data(), tw.size() * sizeof(cf), hipMemcpyHostToDevice));
-  HIP_TRY(b_win.alloc(win.size() * sizeof(float)));
-  HIP_TRY(hipMemcpy(b_win.p, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
-  *d_ot = static_cast<uint32_t*>(b_ot.release());
-  *d_tab = static_cast<uint16_t*>(b_tab.release());
-  *d_tw = static_cast<cf*>(b_tw.release());
-  *d_win = static_cast<float*>(b_win.release());
+  HIP_TRY(d_ot.upload(ot.data(), ot.size()));
+  HIP_TRY(d_tab.upload(tab.data(), tab.size()));
+  HIP_TRY(d_tw.upload(tw.data(), tw.size()));
+  HIP_TRY(d_win.upload(win.data(), win.size()));
   return RPSF_OK;
 }
 
@@ -663,6 +687,9 @@ struct HipfftApi {
   }
 };
 static HipfftApi g_hipfft;
+void FftPlanRelease::operator()(void* h) const {
+  if (g_hipfft.destroy) (void)g_hipfft.destroy(h);
+}
 
 static void set_corner_extremes(rpsf_plan* p) {
   for (int d = 0; d < 2; ++d) p->corner_min[d] = p->corner_max[d] = p->h_coords[d];
@@ -693,37 +720,35 @@ static int plan_create_impl(rpsf_plan** out, int device, int patch_size, int n_p
     HIP_TRY(hipSetDevice(device));
     if (parent) {
       if (p->generic) return fail(RPSF_E_UNSUPPORTED, "views need a compiled plan");
-      p->stream = parent->stream;
+      p->stream = parent->stream, p->borrowed_stream = true;
     } else {
       HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
     }
     for (auto& e : p->ev) HIP_TRY(hipEventCreate(&e));
     if (p->generic) {
-      HIP_TRY(hipMalloc(&p->d_coords, sizeof(int32_t) * 2 * n_patches));
-      HIP_TRY(hipMemcpy(p->d_coords, coords_rc, sizeof(int32_t) * 2 * n_patches, hipMemcpyHostToDevice));
+      HIP_TRY(p->d_coords.upload(coords_rc, 2 * (size_t)n_patches));
       p->h_coords.assign(coords_rc, coords_rc + 2 * (size_t)n_patches);
       set_corner_extremes(p);
       std::vector<float> win(N);
       for (int i = 0; i < N; ++i) win[i] = (float)std::sin((i + 0.5) * M_PI / N);  // transform.py:151-155
-      HIP_TRY(hipMalloc(&p->d_win_generic, sizeof(float) * N));
-      HIP_TRY(hipMemcpy(p->d_win_generic, win.data(), sizeof(float) * N, hipMemcpyHostToDevice));
+      HIP_TRY(p->fft.d_win.upload(win.data(), N));
       {
         std::vector<uint8_t> colours;
         if (generic_colours(N, p->h_coords.data(), n_patches, colours)) {
-          HIP_TRY(hipMalloc(&p->d_colour_generic, colours.size()));
-          HIP_TRY(hipMemcpy(p->d_colour_generic, colours.data(), colours.size(), hipMemcpyHostToDevice));
+          HIP_TRY(p->fft.d_colour.upload(colours.data(), colours.size()));
           p->lattice = true;  // (what rpsf_plan_set_overlap_mode(2) and the automatic mode ask for)
         }
       }
       const size_t per = (size_t)N * N;
-      HIP_TRY(hipMalloc(&p->d_kfull, per * n_patches * sizeof(cf)));
-      p->g_elems = per * n_patches;
-      p->fft_chunk = (int)std::min<size_t>((size_t)n_patches, std::max<size_t>(1, ((size_t)256 << 20) / (per * sizeof(cf))));
-      HIP_TRY(hipMalloc(&p->d_fft_buf, per * p->fft_chunk * sizeof(cf)));
+      HIP_TRY(p->fft.d_kfull.alloc(per * n_patches));
+      p->fft.chunk = (int)std::min<size_t>((size_t)n_patches, std::max<size_t>(1, ((size_t)256 << 20) / (per * sizeof(cf))));
+      HIP_TRY(p->fft.d_buf.alloc(per * p->fft.chunk));
       int dims[2] = {N, N};
-      if (g_hipfft.plan_many(&p->fft_plan, 2, dims, nullptr, 1, (int)per, nullptr, 1, (int)per, /*HIPFFT_C2C*/ 0x29, p->fft_chunk) != 0)
-        return fail(RPSF_E_HIP, "hipfftPlanMany failed");
-      if (g_hipfft.set_stream(p->fft_plan, p->stream) != 0) return fail(RPSF_E_HIP, "hipfftSetStream failed");
+      void* fft_plan = nullptr;
+      const int made = g_hipfft.plan_many(&fft_plan, 2, dims, nullptr, 1, (int)per, nullptr, 1, (int)per, /*HIPFFT_C2C*/ 0x29, p->fft.chunk);
+      p->fft.plan.reset(fft_plan);
+      if (made != 0) return fail(RPSF_E_HIP, "hipfftPlanMany failed");
+      if (g_hipfft.set_stream(p->fft.plan.get(), p->stream) != 0) return fail(RPSF_E_HIP, "hipfftSetStream failed");
       return RPSF_OK;
     }
     {
@@ -731,35 +756,34 @@ static int plan_create_impl(rpsf_plan** out, int device, int patch_size, int n_p
       HIP_TRY(hipGetDeviceProperties(&prop, device));
       p->cu_count = prop.multiProcessorCount;
     }
-    HIP_TRY(hipMalloc(&p->d_coords, sizeof(int32_t) * 2 * n_patches));
-    HIP_TRY(hipMemcpy(p->d_coords, coords_rc, sizeof(int32_t) * 2 * n_patches, hipMemcpyHostToDevice));
+    HIP_TRY(p->d_coords.upload(coords_rc, 2 * (size_t)n_patches));
     p->h_coords.assign(coords_rc, coords_rc + 2 * (size_t)n_patches);
     set_corner_extremes(p);
-    HIP_TRY(hipMalloc(&p->d_sink, 128 * sizeof(float)));
+    HIP_TRY(p->patch.d_sink.alloc(128));
 #if defined(RPSF_STAMPS)
 #if defined(RPSF_WAVE_STAMPS)
     constexpr size_t STAMP_WAVES = 8;
 #else
     constexpr size_t STAMP_WAVES = 1;
 #endif
-    HIP_TRY(hipMalloc(&p->d_stamps, sizeof(unsigned long long) * 16 * STAMP_WAVES * (size_t)n_patches));
-    HIP_TRY(hipMemset(p->d_stamps, 0, sizeof(unsigned long long) * 16 * STAMP_WAVES * (size_t)n_patches));
+    HIP_TRY(p->patch.d_stamps.alloc(16 * STAMP_WAVES * (size_t)n_patches));
+    HIP_TRY(hipMemset(p->patch.d_stamps, 0, sizeof(unsigned long long) * 16 * STAMP_WAVES * (size_t)n_patches));
 #endif
-    p->v2 = has_v2(N);
-    p->no_fuse = false;  // (rpsf_plan_set_option RPSF_OPT_FUSE)
+    p->patch.v2 = has_v2(N);
+    p->patch.no_fuse = false;  // (rpsf_plan_set_option RPSF_OPT_FUSE)
     // (measured, profiles/r02u, r02v: 32 of them are worth -1 % at 4096^2 and -2.5 % at 8192^2; 48 cost more patch time than they hide)
-    p->sum_first = -1;  // decided per launch (sum_first_for) unless the environment pins it
-    if (const char* e = dev_env("RPSF_SUM_FIRST")) p->sum_first = std::max(0, std::atoi(e)) / 8 * 8;
-    if (const char* e = dev_env("RPSF_HEAD_PATCHES")) p->head_patches = std::atoi(e) > 0 ? 1 : 0;
-    if (const char* e = dev_env("RPSF_PREFETCH")) p->prefetch = std::atoi(e) != 0;
-    if (const char* e = dev_env("RPSF_STAGGER_US")) p->stagger_us = std::max(0, std::atoi(e));  // development sweeps
-    if (const char* e = dev_env("RPSF_RESERVED_CUS")) p->reserved_cus = std::min(128, std::max(0, std::atoi(e)));
+    p->patch.sum_first = -1;  // decided per launch (sum_first_for) unless the environment pins it
+    if (const char* e = dev_env("RPSF_SUM_FIRST")) p->patch.sum_first = std::max(0, std::atoi(e)) / 8 * 8;
+    if (const char* e = dev_env("RPSF_HEAD_PATCHES")) p->patch.head_patches = std::atoi(e) > 0 ? 1 : 0;
+    if (const char* e = dev_env("RPSF_PREFETCH")) p->patch.prefetch = std::atoi(e) != 0;
+    if (const char* e = dev_env("RPSF_STAGGER_US")) p->patch.stagger_us = std::max(0, std::atoi(e));  // development sweeps
+    if (const char* e = dev_env("RPSF_RESERVED_CUS")) p->patch.reserved_cus = std::min(128, std::max(0, std::atoi(e)));
     // (until the plane stores were kept in the Infinity Cache the fused sum cost the 128-pixel plan 3 %; now it gains 3 ... 6 %)
-    p->fuse_pays = N >= 128 || dev_env("RPSF_FUSE_ALWAYS") != nullptr;
+    p->patch.fuse_pays = N >= 128 || dev_env("RPSF_FUSE_ALWAYS") != nullptr;
     // (256-pixel plan: profiles/r02ag, -3.7 % per apply at 4096^2 from the re-entry alone; 128-pixel plan, whose four workgroups per CU
     // hide one another's dispatch: 8 x 2048^2 0.334 vs 0.343 ms, single frames unchanged)
-    p->persist = N == 256 || N == 128;  // (rpsf_plan_set_option RPSF_OPT_PERSIST)
-    if (p->persist) {
+    p->patch.persist = N == 256 || N == 128;  // (rpsf_plan_set_option RPSF_OPT_PERSIST)
+    if (p->patch.persist) {
       if (N == 256)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_kernel2_256p), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)Launch2<Cfg256v2>::LDS_BYTES));
@@ -772,68 +796,63 @@ static int plan_create_impl(rpsf_plan** out, int device, int patch_size, int n_p
                                     (int)Launch2<Cfg128v2>::LDS_BYTES));
         // Plain instead of streaming loads of the pair words where the plan's K (66,560 B per patch) fits the 256 MiB Infinity Cache beside the
         // planes: measured (profiles/r04av) -6 % per apply at 72 MB of K, +6.6 % at 160 MB; RPSF_K_CACHED=0/1 overrides (tests run both forms).
-        p->k_cached = (size_t)(parent ? parent->n_patches : n_patches) * Cfg128v2::G_PER_PATCH * sizeof(cf) <= ((size_t)96 << 20);
+        p->patch.k_cached = (size_t)(parent ? parent->n_patches : n_patches) * Cfg128v2::G_PER_PATCH * sizeof(cf) <= ((size_t)96 << 20);
       }
     }
-    int rl = p->v2 ? dispatch_v2(N, [&]<class C>() -> int {
+    int rl = p->patch.v2 ? dispatch_v2(N, [&]<class C>() -> int {
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_kernel2<C>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)Launch2<C>::LDS_BYTES));
       int per_cu = 0;
       HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, patch_kernel2<C>, Launch2<C>::WG, Launch2<C>::LDS_BYTES));
-      p->round_capacity = p->cu_count * std::max(1, per_cu);
+      p->patch.round_capacity = p->cu_count * std::max(1, per_cu);
       return RPSF_OK;
     }) : dispatch_n(N, [&]<class C>() -> int {
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_kernel<C>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)Launch<C>::LDS_BYTES));
       int per_cu = 0;
       HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, patch_kernel<C>, Launch<C>::WG, Launch<C>::LDS_BYTES));
-      p->round_capacity = p->cu_count * std::max(1, per_cu) * Launch<C>::TEAMS;
+      p->patch.round_capacity = p->cu_count * std::max(1, per_cu) * Launch<C>::TEAMS;
       return RPSF_OK;
     });
     if (rl != RPSF_OK) return rl;
     HIP_TRY(hipEventCreateWithFlags(&p->ev_busy, hipEventDisableTiming));
     rl = setup_lattice(p);
     if (rl != RPSF_OK) return rl;
-    if (p->sweep_ok) {
+    if (p->sweep.ok) {
       rl = dispatch_v3(N, [&]<class C>() -> int {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_kernel_kc<C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
         if (!parent) {
-          p->k3_floats = (size_t)C::K_FLOATS * n_patches;
-          HIP_TRY(hipMalloc(&p->d_k3, p->k3_floats * sizeof(float)));
+          p->sweep.k3_floats = (size_t)C::K_FLOATS * n_patches;
+          HIP_TRY(p->sweep.d_k3.alloc(p->sweep.k3_floats));
         }
         return RPSF_OK;
       });
       if (rl != RPSF_OK) return rl;
-      if (parent) {
-        if (parent->d_k3) p->d_k3 = parent->d_k3, p->k3_floats = parent->k3_floats;
-        else p->sweep_ok = false;  // (the parent's lattice was not complete: it has no third-generation K)
-      }
+      if (parent && !parent->sweep.d_k3) p->sweep.ok = false;  // (the parent's lattice was not complete: it has no third-generation K)
     }
-    if (parent) {  // tables and packed K are the parent's
-      p->d_tab = parent->d_tab, p->d_pairtab = parent->d_pairtab, p->d_tw = parent->d_tw, p->d_win = parent->d_win;
-      p->d_g = parent->d_g, p->d_gs = parent->d_gs, p->g_elems = parent->g_elems, p->gs_elems = parent->gs_elems;
+    if (parent) {  // tables, packed K and error word are the parent's (owner())
       p->have_k = parent->have_k;
-      p->overlap_mode = parent->overlap_mode, p->stagger_us = parent->stagger_us;
+      p->overlap_mode = parent->overlap_mode, p->patch.stagger_us = parent->patch.stagger_us;
       return RPSF_OK;
     }
-    if (p->v2)
+    if (p->patch.v2)
       return dispatch_v2(N, [&]<class C>() -> int {
-        int r2 = upload_tables2<C>(device, &p->d_tab, &p->d_tw, &p->d_win, &p->d_pairtab);
+        int r2 = upload_tables2<C>(device, p->patch.d_tab, p->patch.d_tw, p->d_win, p->patch.d_pairtab);
         if (r2 != RPSF_OK) return r2;
-        p->g_elems = (size_t)C::G_PER_PATCH * n_patches;
-        p->gs_elems = (size_t)C::GS_PER_PATCH * n_patches;
-        HIP_TRY(hipMalloc(&p->d_g, p->g_elems * sizeof(cf)));
-        HIP_TRY(hipMalloc(&p->d_gs, (p->gs_elems + 1) * sizeof(cf)));
+        p->patch.g_elems = (size_t)C::G_PER_PATCH * n_patches;
+        p->patch.gs_elems = (size_t)C::GS_PER_PATCH * n_patches;
+        HIP_TRY(p->patch.d_g.alloc(p->patch.g_elems));
+        HIP_TRY(p->patch.d_gs.alloc(p->patch.gs_elems + 1));
         return RPSF_OK;
       });
     return dispatch_n(N, [&]<class C>() -> int {
-      int r2 = upload_tables<C>(device, &p->d_tab, &p->d_tw, &p->d_win, &p->d_pairtab);
+      int r2 = upload_tables<C>(device, p->patch.d_tab, p->patch.d_tw, &p->d_win, &p->patch.d_pairtab);
       if (r2 != RPSF_OK) return r2;
-      p->g_elems = (size_t)C::G_PER_PATCH * n_patches;
-      p->gs_elems = (size_t)C::GS_PER_PATCH * n_patches;
-      HIP_TRY(hipMalloc(&p->d_g, p->g_elems * sizeof(cf)));
-      HIP_TRY(hipMalloc(&p->d_gs, (p->gs_elems + 1) * sizeof(cf)));
+      p->patch.g_elems = (size_t)C::G_PER_PATCH * n_patches;
+      p->patch.gs_elems = (size_t)C::GS_PER_PATCH * n_patches;
+      HIP_TRY(p->patch.d_g.alloc(p->patch.g_elems));
+      HIP_TRY(p->patch.d_gs.alloc(p->patch.gs_elems + 1));
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_kernel<C>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)Launch<C>::LDS_BYTES));
       return RPSF_OK;
@@ -842,7 +861,7 @@ static int plan_create_impl(rpsf_plan** out, int device, int patch_size, int n_p
   const int rc = body();
   if (rc != RPSF_OK) {
     std::string keep = g_err;
-    rpsf_plan_destroy(p);
+    delete p;
     g_err = keep;
     return rc;
   }
@@ -856,190 +875,113 @@ extern "C" int rpsf_plan_create(rpsf_plan** out, int device, int patch_size, int
 
 extern "C" void* rpsf_plan_stream(rpsf_plan* p) { return p ? (void*)p->stream : nullptr; }
 
-extern "C" void rpsf_plan_destroy(rpsf_plan* p) {
-  if (!p) return;
-  (void)hipSetDevice(p->device);
-  if (p->stream) (void)hipStreamSynchronize(p->stream);
-  for (rpsf_plan* band : p->bands) rpsf_plan_destroy(band);
-  p->bands.clear();
-  (void)hipFree(p->d_coords);
-  if (!p->parent) {
-    (void)hipFree(p->d_tab);
-    (void)hipFree(p->d_pairtab);
-    (void)hipFree(p->d_tw);
-    (void)hipFree(p->d_win);
-    (void)hipFree(p->d_g);
-    (void)hipFree(p->d_gs);
-  }
-  if (p->pipe) {
-    p->pipe->destroy();
-    delete p->pipe;
-  }
-  (void)hipFree(p->d_jobs3);
-  (void)hipFree(p->d_regions3);
-  (void)hipFree(p->d_zero3);
-  if (p->owns_err3) (void)hipHostFree(p->h_err3);
-  (void)hipFree(p->d_stamps3);
-  if (!p->parent) (void)hipFree(p->d_k3);
-  (void)hipFree(p->d_cover);
-  (void)hipFree(p->d_desc);
-  (void)hipFree(p->d_stamps);
-  (void)hipFree(p->d_sink);
-  (void)hipFree(p->d_kfull);
-  (void)hipFree(p->d_fft_buf);
-  (void)hipFree(p->d_win_generic);
-  (void)hipFree(p->d_colour_generic);
-  if (p->fft_plan && g_hipfft.destroy) (void)g_hipfft.destroy(p->fft_plan);
-  (void)hipFree(p->d_planes);
-  (void)hipFree(p->d_prefetch_tiles);
-  (void)hipFree(p->d_quads);
-  (void)hipFree(p->d_tile_info);
-  (void)hipFree(p->d_flags);
-  (void)hipFree(p->d_dyn);
-  (void)hipFree(p->d_chunk_xcc);
-  (void)hipFree(p->d_tile_done);
-  (void)hipFree(p->d_sum_order);
-  (void)hipFree(p->d_sum_queue);
-  (void)hipFree(p->d_xq);
-  if (p->ev_busy) (void)hipEventDestroy(p->ev_busy);
-  for (auto& e : p->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (p->stream && !p->parent) (void)hipStreamDestroy(p->stream);
-  delete p;
-}
+extern "C" void rpsf_plan_destroy(rpsf_plan* p) { delete p; }
 
 static void drop_bands(rpsf_plan* p) {
-  for (rpsf_plan* band : p->bands) rpsf_plan_destroy(band);
   p->bands.clear(), p->band_rows.clear(), p->band_in_rows.clear();
   p->bands_h = p->bands_w = 0, p->bands_mode = -1, p->bands_want = -1;
 }
 
-static int pack_range(rpsf_plan* p, const cf* d_kfull, int first_patch, int count) {
-  if (p->d_k3 && !p->parent) {
-    const int rc3 = dispatch_v3(p->N, [&]<class C>() -> int {
-      const size_t total = (size_t)(C::K_FLOATS / 2) * count;
-      pack_kernel3<C><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream>>>(
-          d_kfull, count, reinterpret_cast<cf*>(p->d_k3 + (size_t)first_patch * C::K_FLOATS));
-      HIP_TRY(hipGetLastError());
-      return RPSF_OK;
-    });
-    if (rc3 != RPSF_OK) return rc3;
+// Where install_transfer reads K from: the caller's full K, or the spectra it is built from (transform.py:78-82 evaluated where the packer
+// reads K)
+struct KSource {
+  const cf* k = nullptr;  // (n, N, N) complex64, unfolded: on the device (the packers read nothing else), or on the host for the fallback's copy
+  hipMemcpyKind k_kind = hipMemcpyDeviceToDevice;
+  const cf *s = nullptr, *t = nullptr;
+  double alpha = 0.0, epsilon = 0.0;
+};
+
+// K of patches [first, first + count) - `src` holds these patches only, from its start - into every representation the plan holds: the
+// fallback's unfolded copy, or the patch kernels' (first generation, or second) and the sweep kernel's beside them.  The plan and its views
+// have K once its last patch is in.
+static int install_transfer(rpsf_plan* p, const KSource& src, int first, int count) {
+  if (p->parent) return fail(RPSF_E_STATE, "a view shares its parent's transfer kernel");
+  const size_t at = (size_t)first * p->N * p->N;
+  const cf *k = src.k, *s = src.s, *t = src.t;
+  const float alpha = (float)src.alpha, epsilon = (float)src.epsilon;
+  auto grid = [](size_t total) { return dim3((unsigned)((total + 255) / 256)); };
+  int rc = RPSF_OK;
+  if (p->generic) {  // the fallback multiplies by the caller's unfolded K
+    const size_t elems = (size_t)p->N * p->N * count;
+    if (k) HIP_TRY(hipMemcpy(p->fft.d_kfull + at, k, elems * sizeof(cf), src.k_kind));
+    else rc = rpsf_build_transfer_device(p->device, elems, s, t, 0, src.alpha, src.epsilon, p->fft.d_kfull + at, p->stream);
+  } else {
+    if (p->sweep.d_k3)
+      rc = dispatch_v3(p->N, [&]<class C>() -> int {
+        cf* k3 = reinterpret_cast<cf*>(p->sweep.d_k3 + (size_t)first * C::K_FLOATS);
+        const dim3 g = grid((size_t)(C::K_FLOATS / 2) * count);
+        if (k) pack_kernel3<C><<<g, dim3(256), 0, p->stream>>>(k, count, k3);
+        else pack_spectra_kernel3<C><<<g, dim3(256), 0, p->stream>>>(s, t, alpha, epsilon, count, k3);
+        HIP_TRY(hipGetLastError());
+        return RPSF_OK;
+      });
+    if (rc == RPSF_OK && p->patch.v2)
+      rc = dispatch_v2(p->N, [&]<class C>() -> int {
+        cf *g = p->patch.d_g + (size_t)first * C::G_PER_PATCH, *gs = p->patch.d_gs + (size_t)first * C::GS_PER_PATCH;
+        const dim3 gr = grid(((size_t)C::G_PER_PATCH + C::GS_PER_PATCH) * count);
+        if (k) pack_kernel2<C><<<gr, dim3(256), 0, p->stream>>>(k, count, p->patch.d_tab, p->patch.d_pairtab, g, gs);
+        else pack_spectra_kernel2<C><<<gr, dim3(256), 0, p->stream>>>(s, t, alpha, epsilon, count, p->patch.d_tab, p->patch.d_pairtab, g, gs);
+        HIP_TRY(hipGetLastError());
+        return RPSF_OK;
+      });
+    else if (rc == RPSF_OK)
+      rc = dispatch_n(p->N, [&]<class C>() -> int {
+        cf *g = p->patch.d_g + (size_t)first * C::G_PER_PATCH, *gs = p->patch.d_gs + (size_t)first * C::GS_PER_PATCH;
+        const dim3 gr = grid((size_t)C::G_PER_PATCH * count);
+        if (k) pack_kernel<C><<<gr, dim3(256), 0, p->stream>>>(k, count, p->patch.d_tab, p->patch.d_pairtab, g, gs);
+        else pack_spectra_kernel<C><<<gr, dim3(256), 0, p->stream>>>(s, t, alpha, epsilon, count, p->patch.d_tab, p->patch.d_pairtab, g, gs);
+        HIP_TRY(hipGetLastError());
+        return RPSF_OK;
+      });
   }
-  if (p->v2)
-    return dispatch_v2(p->N, [&]<class C>() -> int {
-      const size_t total = ((size_t)C::G_PER_PATCH + C::GS_PER_PATCH) * count;
-      pack_kernel2<C><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream>>>(
-          d_kfull, count, p->d_tab, p->d_pairtab, p->d_g + (size_t)first_patch * C::G_PER_PATCH,
-          p->d_gs + (size_t)first_patch * C::GS_PER_PATCH);
-      HIP_TRY(hipGetLastError());
-      return RPSF_OK;
-    });
-  return dispatch_n(p->N, [&]<class C>() -> int {
-    size_t total = (size_t)C::G_PER_PATCH * count;
-    int block = 256;
-    size_t grid = (total + block - 1) / block;
-    pack_kernel<C><<<dim3((unsigned)grid), dim3(block), 0, p->stream>>>(
-        d_kfull, count, p->d_tab, p->d_pairtab, p->d_g + (size_t)first_patch * C::G_PER_PATCH,
-        p->d_gs + (size_t)first_patch * C::GS_PER_PATCH);
-    HIP_TRY(hipGetLastError());
-    return RPSF_OK;
-  });
+  if (rc != RPSF_OK) return rc;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (first + count == p->n_patches) {
+    p->have_k = true;
+    for (auto& band : p->bands) band->have_k = true;
+  }
+  return RPSF_OK;
 }
 
 extern "C" int rpsf_plan_set_transfer(rpsf_plan* p, const float* k_host) {
   if (!p || !k_host) return fail(RPSF_E_BADARG, "null argument");
   HIP_TRY(hipSetDevice(p->device));
+  const cf* k = reinterpret_cast<const cf*>(k_host);
+  if (p->generic) return install_transfer(p, KSource{k, hipMemcpyHostToDevice}, 0, p->n_patches);
+  // the packers read K from the device: it goes up 64 MiB at a time
   const size_t per = (size_t)p->N * p->N;
-  if (p->generic) {
-    HIP_TRY(hipMemcpy(p->d_kfull, k_host, per * p->n_patches * sizeof(cf), hipMemcpyHostToDevice));
-    p->have_k = true;
-    return RPSF_OK;
+  const int chunk = std::min(p->n_patches, (int)std::max<size_t>(1, (size_t)(64u << 20) / (per * sizeof(cf))));
+  DevBuf<cf> d_tmp;
+  HIP_TRY(d_tmp.alloc(per * chunk));
+  for (int first = 0; first < p->n_patches; first += chunk) {
+    const int cnt = std::min(chunk, p->n_patches - first);
+    HIP_TRY(hipMemcpyAsync(d_tmp, k + (size_t)first * per, per * sizeof(cf) * cnt, hipMemcpyHostToDevice, p->stream));
+    const int rc = install_transfer(p, KSource{d_tmp}, first, cnt);
+    if (rc != RPSF_OK) return rc;
   }
-  int chunk = (int)std::max<size_t>(1, (size_t)(64u << 20) / (per * sizeof(cf)));
-  if (chunk > p->n_patches) chunk = p->n_patches;
-  DevBuf b_tmp;
-  HIP_TRY(b_tmp.alloc(per * sizeof(cf) * chunk));
-  cf* d_tmp = b_tmp.as<cf>();
-  int rc = RPSF_OK;
-  for (int first = 0; first < p->n_patches && rc == RPSF_OK; first += chunk) {
-    int cnt = std::min(chunk, p->n_patches - first);
-    hipError_t e = hipMemcpyAsync(d_tmp, reinterpret_cast<const cf*>(k_host) + (size_t)first * per,
-                                  per * sizeof(cf) * cnt, hipMemcpyHostToDevice, p->stream);
-    if (e != hipSuccess) { rc = fail(RPSF_E_HIP, hipGetErrorString(e)); break; }
-    rc = pack_range(p, d_tmp, first, cnt);
-    if (rc == RPSF_OK) {
-      e = hipStreamSynchronize(p->stream);
-      if (e != hipSuccess) rc = fail(RPSF_E_HIP, hipGetErrorString(e));
-    }
-  }
-  if (rc == RPSF_OK) p->have_k = true;
-  for (rpsf_plan* band : p->bands) band->have_k = p->have_k;
-  return rc;
+  return RPSF_OK;
 }
 
 extern "C" int rpsf_plan_set_transfer_device(rpsf_plan* p, const void* k_dev) {
   if (!p || !k_dev) return fail(RPSF_E_BADARG, "null argument");
   HIP_TRY(hipSetDevice(p->device));
-  if (p->generic) {
-    HIP_TRY(hipMemcpy(p->d_kfull, k_dev, (size_t)p->N * p->N * p->n_patches * sizeof(cf), hipMemcpyDeviceToDevice));
-    p->have_k = true;
-    return RPSF_OK;
-  }
-  int rc = pack_range(p, reinterpret_cast<const cf*>(k_dev), 0, p->n_patches);
-  if (rc != RPSF_OK) return rc;
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  p->have_k = true;
-  return RPSF_OK;
+  return install_transfer(p, KSource{reinterpret_cast<const cf*>(k_dev)}, 0, p->n_patches);
 }
 
-// construct -> pack in one pass (transform.py:78-82 evaluated where the packer reads K): complex64 spectra of the plan's patches on its device
+// construct -> pack in one pass: complex64 spectra of the plan's patches on its device
 extern "C" int rpsf_plan_set_transfer_spectra_device(rpsf_plan* p, const void* s_c64_dev, const void* t_c64_dev, double alpha, double epsilon) {
   if (!p || !s_c64_dev || !t_c64_dev) return fail(RPSF_E_BADARG, "null argument");
-  if (p->parent) return fail(RPSF_E_STATE, "a view shares its parent's transfer kernel");
   HIP_TRY(hipSetDevice(p->device));
-  const cf* s = reinterpret_cast<const cf*>(s_c64_dev);
-  const cf* t = reinterpret_cast<const cf*>(t_c64_dev);
-  int rc = RPSF_OK;
-  if (p->generic) {  // the fallback multiplies by the caller's unfolded K: K2 straight into the plan's copy
-    rc = rpsf_build_transfer_device(p->device, (size_t)p->N * p->N * p->n_patches, s, t, 0, alpha, epsilon, p->d_kfull, p->stream);
-  } else if (p->v2) {
-    rc = dispatch_v2(p->N, [&]<class C>() -> int {
-      const size_t total = ((size_t)C::G_PER_PATCH + C::GS_PER_PATCH) * p->n_patches;
-      pack_spectra_kernel2<C><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream>>>(s, t, (float)alpha, (float)epsilon, p->n_patches,
-                                                                                                 p->d_tab, p->d_pairtab, p->d_g, p->d_gs);
-      HIP_TRY(hipGetLastError());
-      return RPSF_OK;
-    });
-  } else {
-    if (p->d_k3) {
-      rc = dispatch_v3(p->N, [&]<class C>() -> int {
-        const size_t total = (size_t)(C::K_FLOATS / 2) * p->n_patches;
-        pack_spectra_kernel3<C><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream>>>(s, t, (float)alpha, (float)epsilon, p->n_patches,
-                                                                                                   reinterpret_cast<cf*>(p->d_k3));
-        HIP_TRY(hipGetLastError());
-        return RPSF_OK;
-      });
-      if (rc != RPSF_OK) return rc;
-    }
-    rc = dispatch_n(p->N, [&]<class C>() -> int {
-      const size_t total = (size_t)C::G_PER_PATCH * p->n_patches;
-      pack_spectra_kernel<C><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream>>>(s, t, (float)alpha, (float)epsilon, p->n_patches,
-                                                                                                p->d_tab, p->d_pairtab, p->d_g, p->d_gs);
-      HIP_TRY(hipGetLastError());
-      return RPSF_OK;
-    });
-  }
-  if (rc != RPSF_OK) return rc;
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  p->have_k = true;
-  for (rpsf_plan* band : p->bands) band->have_k = true;
-  return RPSF_OK;
+  return install_transfer(p, KSource{nullptr, hipMemcpyDeviceToDevice, reinterpret_cast<const cf*>(s_c64_dev), reinterpret_cast<const cf*>(t_c64_dev),
+                                     alpha, epsilon}, 0, p->n_patches);
 }
 
 extern "C" int rpsf_plan_transfer_bytes(const rpsf_plan* p, size_t* bytes) {
   if (!p || !bytes) return fail(RPSF_E_BADARG, "null argument");
   // (the representation the plan's applies read: the third generation's when the sweep kernel runs them)
-  *bytes = p->sweep_ok && overlap_kind(p) == OV_SWEEP ? p->k3_floats * sizeof(float) : (p->g_elems + p->gs_elems) * sizeof(cf);
+  if (p->generic) *bytes = (size_t)p->N * p->N * p->n_patches * sizeof(cf);
+  else if (p->sweep.ok && overlap_kind(p) == OV_SWEEP) *bytes = p->sweep.k3_floats * sizeof(float);
+  else *bytes = (p->patch.g_elems + p->patch.gs_elems) * sizeof(cf);
   return RPSF_OK;
 }
 
@@ -1068,14 +1010,14 @@ static int check_geometry(const rpsf_plan* p, const rpsf_geometry* g) {
 
 static SumParams make_sum_params(const rpsf_plan* p, float* d_out, const rpsf_geometry& g, int row_begin, int row_end) {
   SumParams sp;
-  sp.planes = p->d_planes, sp.plane_stride = p->planes_floats, sp.out = d_out;
+  sp.planes = p->patch.d_planes, sp.plane_stride = p->patch.planes_floats, sp.out = d_out;
   sp.rows = row_end - row_begin, sp.row_begin = row_begin;
   sp.W = g.width, sp.ld_planes = g.width, sp.ld_out = g.ld_out, sp.row0 = g.out_row0;
   sp.lat_r0 = p->lat_r0 + g.origin_row, sp.lat_c0 = p->lat_c0 + g.origin_col;
   sp.half_shift = 0;
   while ((1 << (sp.half_shift + 1)) < p->N) ++sp.half_shift;
   sp.nti = p->nti, sp.ntj = p->ntj, sp.cover = p->d_cover;
-  sp.planes_frame_floats = 4 * p->planes_floats, sp.out_frame_floats = 0;
+  sp.planes_frame_floats = 4 * p->patch.planes_floats, sp.out_frame_floats = 0;
   return sp;
 }
 
@@ -1094,7 +1036,7 @@ struct Batch {
 // against 0.218 ms with the separate sum kernel; 2048^2 0.067 ms with 0 ... 24 against 0.069; 8 x 2048^2 0.372 / 0.360 / 0.352 /
 // 0.343 / 0.340 ms with 8 / 32 / 64 / 128 / 192 against 0.362.
 static int sum_first_for(const rpsf_plan* p, int frames) {
-  if (p->sum_first >= 0) return p->sum_first;
+  if (p->patch.sum_first >= 0) return p->patch.sum_first;
   const long work = (long)p->n_patches * frames;
   if (p->N == 128) return work >= 4096 ? 160 : work >= 2048 ? 128 : work >= 512 ? 8 : 0;  // (160 from 4096 patch-frames on: -2 ... -4 %, profiles/r04bf)
   return work >= 2048 ? 32 : work >= 1024 ? 16 : work >= 512 ? 8 : 0;
@@ -1109,73 +1051,74 @@ static int sum_first_for(const rpsf_plan* p, int frames) {
 static bool hot_geometry(const rpsf_plan* p, const float* d_img, const rpsf_geometry& g, size_t im_stride) {
   return (g.pad_mode == RPSF_PAD_CONSTANT || g.pad_mode == RPSF_PAD_SYMMETRIC || g.pad_mode == RPSF_PAD_WRAP) && g.width % 4 == 0 &&
          g.ld_image % 4 == 0 && g.origin_col % 4 == 0 && im_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(d_img) & 15) == 0 &&
-         p->lattice && ((long)p->lat_c0 + g.origin_col) % 4 == 0 && p->planes_floats % 4 == 0;
+         p->lattice && ((long)p->lat_c0 + g.origin_col) % 4 == 0 && p->patch.planes_floats % 4 == 0;
 }
 
-// fused: the plane sum runs in this launch (see rpsf_plan::d_tile_done)
+// fused: the plane sum runs in this launch (see PatchPath::d_tile_done)
 static int launch_patches(rpsf_plan* p, const float* d_img, float* d_out, const rpsf_geometry& g, OverlapKind kind,
                           hipStream_t st, Batch b = Batch(), bool fused = false) {
   auto fill = [&](PatchParams& pp, int teams) {
     const int count = p->n_patches;
     pp.im = ImageView{d_img, g.height, g.width, g.ld_image, g.pad_mode, g.pad_value, g.image_row0, g.image_rows};
     if (kind != OV_ATOMIC)
-      pp.ov = OutView{p->d_planes, g.height, g.width, g.width, g.out_row0, g.out_rows, p->planes_floats, p->d_sink};
+      pp.ov = OutView{p->patch.d_planes, g.height, g.width, g.width, g.out_row0, g.out_rows, p->patch.planes_floats, p->patch.d_sink};
     else
-      pp.ov = OutView{d_out, g.height, g.width, g.ld_out, g.out_row0, g.out_rows, 0, p->d_sink};
+      pp.ov = OutView{d_out, g.height, g.width, g.ld_out, g.out_row0, g.out_rows, 0, p->patch.d_sink};
     pp.origin_row = g.origin_row, pp.origin_col = g.origin_col;
     pp.desc = p->d_desc, pp.n_patches = count, pp.seq_base = 0;
-    pp.tab = p->d_tab, pp.pairtab = p->d_pairtab, pp.tw = p->d_tw, pp.win = p->d_win, pp.g = p->d_g, pp.gs = p->d_gs;
-    pp.stamps = p->d_stamps;
+    const rpsf_plan* o = owner(p);
+    pp.tab = o->patch.d_tab, pp.pairtab = o->patch.d_pairtab, pp.tw = o->patch.d_tw, pp.win = o->d_win, pp.g = o->patch.d_g, pp.gs = o->patch.d_gs;
+    pp.stamps = p->patch.d_stamps;
     pp.chunk = ((count + 7) / 8 + teams - 1) / teams * teams;  // patches per XCD, whole workgroups
-    pp.stagger_ticks = std::max(0, p->stagger_us) * 100;
+    pp.stagger_ticks = std::max(0, p->patch.stagger_us) * 100;
     pp.n_frames = b.frames, pp.im_frame_floats = b.im_stride;
-    pp.ov_frame_floats = kind != OV_ATOMIC ? 4 * p->planes_floats : b.out_stride;
+    pp.ov_frame_floats = kind != OV_ATOMIC ? 4 * p->patch.planes_floats : b.out_stride;
     pp.dv = OutView{nullptr, 0, 0, 0, 0, 0, 0, nullptr};
     if (kind == OV_DIRECT) {
-      pp.dv = OutView{d_out, g.height, g.width, g.ld_out, g.out_row0, g.out_rows, 0, p->d_sink};
+      pp.dv = OutView{d_out, g.height, g.width, g.ld_out, g.out_row0, g.out_rows, 0, p->patch.d_sink};
       pp.dv_frame_floats = b.out_stride;
-      pp.quads = p->d_quads, pp.flags = p->d_flags, pp.dyn_side = p->d_dyn, pp.chunk_xcc = p->d_chunk_xcc;
-      pp.flag_epoch = p->epoch, pp.n_tiles = (uint32_t)(p->nti * p->ntj), pp.orphan_mod = p->orphan_mod;
+      pp.quads = p->patch.d_quads, pp.flags = p->patch.d_flags, pp.dyn_side = p->patch.d_dyn, pp.chunk_xcc = p->patch.d_chunk_xcc;
+      pp.flag_epoch = p->patch.epoch, pp.n_tiles = (uint32_t)(p->nti * p->ntj), pp.orphan_mod = p->patch.orphan_mod;
     }
   };
-  if (p->v2)
+  if (p->patch.v2)
     return dispatch_v2(p->N, [&]<class C>() -> int {
       PatchParams pp{};
       fill(pp, 1);
-      pp.stagger_blocks = p->round_capacity;
+      pp.stagger_blocks = p->patch.round_capacity;
       size_t blocks = (size_t)8 * pp.chunk * b.frames;
       if (blocks > 0x7fffffffu) return fail(RPSF_E_BADARG, "batch too large for one launch");
       pp.slot0 = 0, pp.patch_blocks = (int)blocks;
       if (fused) {
         const int n_tiles = p->nti * p->ntj;
-        pp.tile_done = p->d_tile_done, pp.quads = p->d_quads, pp.n_tiles = (uint32_t)n_tiles;
+        pp.tile_done = p->patch.d_tile_done, pp.quads = p->patch.d_quads, pp.n_tiles = (uint32_t)n_tiles;
         TileSum& ts = pp.ts;
-        ts.planes = p->d_planes, ts.plane_stride = p->planes_floats, ts.ld_planes = g.width;
+        ts.planes = p->patch.d_planes, ts.plane_stride = p->patch.planes_floats, ts.ld_planes = g.width;
         ts.out = d_out, ts.ld_out = g.ld_out;
         ts.rows = g.out_rows, ts.W = g.width, ts.row0 = g.out_row0;
         ts.lat_r0 = p->lat_r0 + g.origin_row, ts.lat_c0 = p->lat_c0 + g.origin_col, ts.half = p->N / 2, ts.ntj = p->ntj;
-        ts.cover = p->d_cover, ts.tiles = p->d_sum_order, ts.count = n_tiles * b.frames;
-        ts.done = p->d_tile_done, ts.epoch = p->done_epoch;
+        ts.cover = p->d_cover, ts.tiles = p->patch.d_sum_order, ts.count = n_tiles * b.frames;
+        ts.done = p->patch.d_tile_done, ts.epoch = p->patch.done_epoch;
         ts.n_frames = b.frames, ts.n_tiles = (uint32_t)n_tiles, ts.n_tiles_listed = (uint32_t)n_tiles;
         // Persistent batches whose planes would not fit the Infinity Cache side by side run frame after frame in one launch: every
         // frame keeps the cache behaviour of a single apply, and the next frame's patches take the CUs the previous one's last
         // patches leave idle (RPSF_FRAME_MAJOR=0/1 overrides).
-        bool frame_major = std::is_same_v<C, Cfg256v2> && p->persist && b.frames > 1 && p->n_patches >= 1024 &&
-                           16.0 * (double)p->planes_floats * b.frames > 256.0 * 1048576.0;  // (8 x 2048^2: 0.056 ms per frame side by side, 0.061 in turn)
+        bool frame_major = std::is_same_v<C, Cfg256v2> && p->patch.persist && b.frames > 1 && p->n_patches >= 1024 &&
+                           16.0 * (double)p->patch.planes_floats * b.frames > 256.0 * 1048576.0;  // (8 x 2048^2: 0.056 ms per frame side by side, 0.061 in turn)
         if (const char* e = dev_env("RPSF_FRAME_MAJOR"))  // development sweeps: 0 = never, 2 = any persistent batch
-          frame_major = std::atoi(e) == 2 ? (p->persist && b.frames > 1) : (frame_major && std::atoi(e) != 0);
+          frame_major = std::atoi(e) == 2 ? (p->patch.persist && b.frames > 1) : (frame_major && std::atoi(e) != 0);
         pp.frame_major = ts.frame_major = frame_major ? 1 : 0;
         // Frames of a batch side by side keep the planes of ALL of them live at once (8 x 2048^2: 537 MB against a 256 MiB Infinity Cache): the 128-pixel
         // kernels then store them with the streaming hint - 0.3156 -> 0.3009 ms (-4.7 %); a single frame loses 8 % that way, and so does the 256-pixel
         // plan at either size (profiles/r04bd).  RPSF_PLANE_NT=0/1 overrides (development sweeps).
         // (needs the plain-load form of K - a batch shares it - and planes well beyond the Infinity Cache: 4 x 2048^2, 268 MB, still loses 3 %; 6 x, 403 MB, gains 5 %)
-        pp.plane_nt = std::is_same_v<C, Cfg128v2> && p->k_cached && b.frames > 1 && !frame_major && 16.0 * (double)p->planes_floats * b.frames > 300.0 * 1048576.0;
-        if (p->plane_nt_opt >= 0) pp.plane_nt = p->plane_nt_opt != 0 && std::is_same_v<C, Cfg128v2> && p->k_cached;  // (RPSF_OPT_PLANE_NT)
+        pp.plane_nt = std::is_same_v<C, Cfg128v2> && p->patch.k_cached && b.frames > 1 && !frame_major && 16.0 * (double)p->patch.planes_floats * b.frames > 300.0 * 1048576.0;
+        if (p->patch.plane_nt_opt >= 0) pp.plane_nt = p->patch.plane_nt_opt != 0 && std::is_same_v<C, Cfg128v2> && p->patch.k_cached;  // (RPSF_OPT_PLANE_NT)
         const int tune_frames = b.frames;  // (the settings of a single apply measured worse here: 0.203 vs 0.186 ms per frame at 8 x 4096^2)
         pp.sum_first = sum_first_for(p, tune_frames);
-        ts.planes_frame_floats = 4 * p->planes_floats, ts.out_frame_floats = b.out_stride;
-        int nsum = std::max(8, std::min(ts.count, p->round_capacity));  // at the tail: as many summing workgroups as the chip holds
-        ts.queue = p->d_sum_queue, ts.queue_base = p->sum_queue_base;
+        ts.planes_frame_floats = 4 * p->patch.planes_floats, ts.out_frame_floats = b.out_stride;
+        int nsum = std::max(8, std::min(ts.count, p->patch.round_capacity));  // at the tail: as many summing workgroups as the chip holds
+        ts.queue = p->patch.d_sum_queue, ts.queue_base = p->patch.sum_queue_base;
         {
           // persistent form: as many patch workgroups as the chip holds beside the summing ones; each works through the slots
           // of its XCD's chunk and ends as a summing workgroup itself (no workgroups behind the patches).
@@ -1191,15 +1134,15 @@ static int launch_patches(rpsf_plan* p, const float* d_img, float* d_out, const 
           // patch-frames on, sum_first_for); concurrent persistent launches therefore cannot starve one another unless their head summing
           // workgroups alone fill the chip (tests: test_two_persistent_plans_on_two_streams, 256- and 128-pixel plans).
           // (queue positions of an XCD: chunk slots x frames, the frames of a slot side by side)
-          const int rows = std::min(pp.chunk * b.frames, std::max(1, (p->round_capacity - pp.sum_first - p->reserved_cus) / 8));
-          if (p->persist && rows > 0 && hot_geometry(p, d_img, g, b.im_stride)) {
-            pp.persist = rows, pp.xq = p->d_xq;
+          const int rows = std::min(pp.chunk * b.frames, std::max(1, (p->patch.round_capacity - pp.sum_first - p->patch.reserved_cus) / 8));
+          if (p->patch.persist && rows > 0 && hot_geometry(p, d_img, g, b.im_stride)) {
+            pp.persist = rows, pp.xq = p->patch.d_xq;
             // a head summing workgroup would idle through the first patch period (no tile is complete before that): it computes one patch
             // of its XCD's chunk first (RPSF_HEAD_PATCHES=0: off)
-            pp.head_patches = p->head_patches;
-            pp.prefetch = p->prefetch && p->d_prefetch_tiles ? 1 : 0;
-            pp.prefetch_tiles = p->d_prefetch_tiles;
-            for (int x = 0; x < 9; ++x) pp.prefetch_first[x] = p->prefetch_first[x];
+            pp.head_patches = p->patch.head_patches;
+            pp.prefetch = p->patch.prefetch && p->patch.d_prefetch_tiles ? 1 : 0;
+            pp.prefetch_tiles = p->patch.d_prefetch_tiles;
+            for (int x = 0; x < 9; ++x) pp.prefetch_first[x] = p->patch.prefetch_first[x];
             // persistent workgroups keep the phase they start with: holding the resident ones back by up to 10 us spreads the
             // store bursts of the chip over the patch period (profiles/r02ai, r02ak: -2..3 % from four rounds of patches on; with the
             // plane stores kept in the Infinity Cache, r02av: 0.210 / 0.208 / 0.193 / 0.190 / 0.189 / 0.191 / 0.195 ms at 0 / 5 / 8 / 10 / 12 / 15 / 20 us)
@@ -1207,7 +1150,7 @@ static int launch_patches(rpsf_plan* p, const float* d_img, float* d_out, const 
             // (long launches take more: 8192^2 0.736 / 0.726 / 0.714 / 0.703 / 0.698 / 0.719 ms at 6 / 12 / 18 / 24 / 30 / 36 us)
             // (round 4, seven-barrier pass, profiles/r04az: 4096^2 at 12 / 16 / 20 us - the repeated frame 0.1835 / 0.1843 / 0.1880 ms, a NEW frame every step
             // 0.2019 / 0.1962 / 0.1933: 16 us from 1024 patches of the 256-pixel plan on; 8192^2 0.714 / 0.688 / 0.691 / 0.690 at 12 / 16 / 20 / 24)
-            if (p->stagger_us < 0 && (long)p->n_patches * tune_frames >= 256) {
+            if (p->patch.stagger_us < 0 && (long)p->n_patches * tune_frames >= 256) {
               const long work = (long)p->n_patches * tune_frames;
               pp.stagger_ticks = work >= 2048 ? 2400 : (work >= 1024 && std::is_same_v<C, Cfg256v2>) ? 1600 : 1200;
               // The 128-pixel plan - four workgroups per CU, out of step with one another anyway - is better off WITHOUT it since round 4 (profiles/r04ba):
@@ -1216,17 +1159,17 @@ static int launch_patches(rpsf_plan* p, const float* d_img, float* d_out, const 
               if constexpr (std::is_same_v<C, Cfg128v2>) pp.stagger_ticks = tune_frames == 1 && p->n_patches >= 4096 ? 600 : 0;
             }
             for (int x = 0; x < 8; ++x) {
-              pp.xq_base[x] = p->xq_base[x];
+              pp.xq_base[x] = p->patch.xq_base[x];
               // draws of this launch: one per slot and frame, plus the one past the end that tells each of the chunk's workgroups to stop
               // (the first sum_first / 8 positions of a chunk go to the head summing workgroups without a draw when those compute a patch first)
               const int slots_x = std::min(pp.chunk, std::max(0, p->n_patches - x * pp.chunk)) * b.frames;
-              p->xq_base[x] += (uint32_t)(std::max(0, slots_x - (pp.head_patches ? pp.sum_first / 8 : 0)) + rows);
+              p->patch.xq_base[x] += (uint32_t)(std::max(0, slots_x - (pp.head_patches ? pp.sum_first / 8 : 0)) + rows);
             }
             const int wgs = pp.sum_first + 8 * rows;
-            p->sum_queue_base += (uint32_t)(ts.count + wgs);  // every workgroup draws one position past the end
-            if (p->k_cached && pp.plane_nt)
+            p->patch.sum_queue_base += (uint32_t)(ts.count + wgs);  // every workgroup draws one position past the end
+            if (p->patch.k_cached && pp.plane_nt)
               PersistentKernel2<C>::fn_k_cached_planes_nt<<<dim3((unsigned)wgs), dim3(Launch2<C>::WG), Launch2<C>::LDS_BYTES, st>>>(pp);
-            else if (p->k_cached)
+            else if (p->patch.k_cached)
               PersistentKernel2<C>::fn_k_cached<<<dim3((unsigned)wgs), dim3(Launch2<C>::WG), Launch2<C>::LDS_BYTES, st>>>(pp);
             else
               PersistentKernel2<C>::fn<<<dim3((unsigned)wgs), dim3(Launch2<C>::WG), Launch2<C>::LDS_BYTES, st>>>(pp);
@@ -1235,7 +1178,7 @@ static int launch_patches(rpsf_plan* p, const float* d_img, float* d_out, const 
           }
         }
         nsum += pp.sum_first;
-        p->sum_queue_base += (uint32_t)(ts.count + nsum);  // every workgroup draws one position past the end
+        p->patch.sum_queue_base += (uint32_t)(ts.count + nsum);  // every workgroup draws one position past the end
         blocks += (size_t)nsum;
       }
       patch_kernel2<C><<<dim3((unsigned)blocks), dim3(Launch2<C>::WG), Launch2<C>::LDS_BYTES, st>>>(pp);
@@ -1257,12 +1200,12 @@ static int launch_patches(rpsf_plan* p, const float* d_img, float* d_out, const 
 
 static int launch_fixup(rpsf_plan* p, float* d_out, const rpsf_geometry& g, hipStream_t st, Batch b) {
   FixParams fp{};
-  fp.planes = p->d_planes, fp.plane_stride = p->planes_floats, fp.planes_frame_floats = 4 * p->planes_floats, fp.ld_planes = g.width;
+  fp.planes = p->patch.d_planes, fp.plane_stride = p->patch.planes_floats, fp.planes_frame_floats = 4 * p->patch.planes_floats, fp.ld_planes = g.width;
   fp.out = d_out, fp.ld_out = g.ld_out, fp.out_frame_floats = b.out_stride;
   fp.rows = g.out_rows, fp.W = g.width, fp.row0 = g.out_row0;
   fp.lat_r0 = p->lat_r0 + g.origin_row, fp.lat_c0 = p->lat_c0 + g.origin_col, fp.half = p->N / 2, fp.ntj = p->ntj;
-  fp.tile_info = p->d_tile_info, fp.flags = p->d_flags, fp.dyn_side = p->d_dyn;
-  fp.epoch = p->epoch, fp.n_tiles = (uint32_t)(p->nti * p->ntj);
+  fp.tile_info = p->patch.d_tile_info, fp.flags = p->patch.d_flags, fp.dyn_side = p->patch.d_dyn;
+  fp.epoch = p->patch.epoch, fp.n_tiles = (uint32_t)(p->nti * p->ntj);
   for (int f0 = 0; f0 < b.frames; f0 += 65535) {  // grid.y limit
     FixParams q = fp;
     q.planes += (size_t)f0 * q.planes_frame_floats, q.out += (size_t)f0 * q.out_frame_floats;
@@ -1295,7 +1238,7 @@ static OverlapKind overlap_kind(const rpsf_plan* p) {
     case 2: return OV_PLANES;
     case 3: return OV_DIRECT;
     case 4: return OV_SWEEP;
-    default: return p->sweep_ok ? OV_SWEEP : p->lattice ? OV_PLANES : OV_ATOMIC;  // direct stays opt-in until it beats the planes
+    default: return p->sweep.ok ? OV_SWEEP : p->lattice ? OV_PLANES : OV_ATOMIC;  // direct stays opt-in until it beats the planes
   }
 }
 static size_t plane_floats_needed(const rpsf_geometry& g) { return ((size_t)g.out_rows * g.width + 3) & ~(size_t)3; }
@@ -1306,7 +1249,7 @@ static int launch_apply_generic(rpsf_plan* p, const float* d_img, float* d_out, 
     return fail(RPSF_E_UNSUPPORTED, "row-band windows need a patch size with a compiled plan (16, 32, 64, 128, 256)");
   if (st != p->stream) {
     HIP_TRY(hipStreamSynchronize(p->stream));  // the FFT plan is bound to one stream at a time
-    if (g_hipfft.set_stream(p->fft_plan, st) != 0) return fail(RPSF_E_HIP, "hipfftSetStream failed");
+    if (g_hipfft.set_stream(p->fft.plan.get(), st) != 0) return fail(RPSF_E_HIP, "hipfftSetStream failed");
   }
   const size_t per = (size_t)p->N * p->N;
   const float scale = 1.0f / (float)per;  // hipFFT's inverse is unnormalised
@@ -1315,26 +1258,26 @@ static int launch_apply_generic(rpsf_plan* p, const float* d_img, float* d_out, 
     const float* img = d_img + (size_t)f * b.im_stride;
     float* out = d_out + (size_t)f * b.out_stride;
     HIP_TRY(hipMemset2DAsync(out, (size_t)g.ld_out * sizeof(float), 0, (size_t)g.width * sizeof(float), g.out_rows, st));
-    for (int first = 0; first < p->n_patches; first += p->fft_chunk) {
+    for (int first = 0; first < p->n_patches; first += p->fft.chunk) {
       GenericGeom gg;
-      gg.N = p->N, gg.first = first, gg.count = std::min(p->fft_chunk, p->n_patches - first);
+      gg.N = p->N, gg.first = first, gg.count = std::min(p->fft.chunk, p->n_patches - first);
       gg.origin_row = g.origin_row, gg.origin_col = g.origin_col;
       gg.im = ImageView{img, g.height, g.width, g.ld_image, g.pad_mode, g.pad_value, 0, g.height};
       gg.ov = OutView{out, g.height, g.width, g.ld_out, 0, g.height, 0, nullptr};
       const size_t total = per * gg.count;
       const unsigned grid = (unsigned)((total + 255) / 256);
-      generic_gather_kernel<<<dim3(grid), dim3(256), 0, st>>>(gg, p->d_coords, p->d_win_generic, p->d_fft_buf);
+      generic_gather_kernel<<<dim3(grid), dim3(256), 0, st>>>(gg, p->d_coords, p->fft.d_win, p->fft.d_buf);
       // a short last chunk still runs the full-size plan: the surplus patches hold stale data and are never scattered
-      if (g_hipfft.exec_c2c(p->fft_plan, p->d_fft_buf, p->d_fft_buf, /*HIPFFT_FORWARD*/ -1) != 0)
+      if (g_hipfft.exec_c2c(p->fft.plan.get(), p->fft.d_buf, p->fft.d_buf, /*HIPFFT_FORWARD*/ -1) != 0)
         return fail(RPSF_E_HIP, "hipfftExecC2C (forward) failed");
-      generic_multiply_kernel<<<dim3(grid), dim3(256), 0, st>>>(p->d_fft_buf, p->d_kfull + (size_t)first * per, total, scale);
-      if (g_hipfft.exec_c2c(p->fft_plan, p->d_fft_buf, p->d_fft_buf, /*HIPFFT_BACKWARD*/ 1) != 0)
+      generic_multiply_kernel<<<dim3(grid), dim3(256), 0, st>>>(p->fft.d_buf, p->fft.d_kfull + (size_t)first * per, total, scale);
+      if (g_hipfft.exec_c2c(p->fft.plan.get(), p->fft.d_buf, p->fft.d_buf, /*HIPFFT_BACKWARD*/ 1) != 0)
         return fail(RPSF_E_HIP, "hipfftExecC2C (inverse) failed");
-      if (p->d_colour_generic && overlap_kind(p) != OV_ATOMIC) {
+      if (p->fft.d_colour && overlap_kind(p) != OV_ATOMIC) {
         for (int colour = 0; colour < 4; ++colour)
-          generic_scatter_kernel<<<dim3(grid), dim3(256), 0, st>>>(gg, p->d_coords, p->d_win_generic, p->d_fft_buf, p->d_colour_generic, colour);
+          generic_scatter_kernel<<<dim3(grid), dim3(256), 0, st>>>(gg, p->d_coords, p->fft.d_win, p->fft.d_buf, p->fft.d_colour, colour);
       } else {
-        generic_scatter_kernel<<<dim3(grid), dim3(256), 0, st>>>(gg, p->d_coords, p->d_win_generic, p->d_fft_buf, nullptr, -1);
+        generic_scatter_kernel<<<dim3(grid), dim3(256), 0, st>>>(gg, p->d_coords, p->fft.d_win, p->fft.d_buf, nullptr, -1);
       }
       HIP_TRY(hipGetLastError());
     }
@@ -1342,7 +1285,7 @@ static int launch_apply_generic(rpsf_plan* p, const float* d_img, float* d_out, 
   if (ev_k1) HIP_TRY(hipEventRecord(ev_k1, st));
   if (st != p->stream) {
     HIP_TRY(hipStreamSynchronize(st));
-    if (g_hipfft.set_stream(p->fft_plan, p->stream) != 0) return fail(RPSF_E_HIP, "hipfftSetStream failed");
+    if (g_hipfft.set_stream(p->fft.plan.get(), p->stream) != 0) return fail(RPSF_E_HIP, "hipfftSetStream failed");
   }
   return RPSF_OK;
 }
@@ -1363,11 +1306,12 @@ static int launch_sweep(rpsf_plan* p, const float* d_img, float* d_out, const rp
   const int aligned_out = col_aligned && g.ld_out % 4 == 0 && b.out_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0;
   sp.fl = Flush3{d_out, g.ld_out, g.out_row0, g.out_rows, g.height, g.width, aligned_out};
   sp.lat_r0 = (int)r0, sp.lat_c0 = (int)c0;
-  sp.jobs = p->d_jobs3, sp.regions = p->d_regions3, sp.n_regions = p->n_regions3, sp.group = (p->n_regions3 + 7) / 8;
-  sp.k3 = p->d_k3, sp.win = p->d_win, sp.zeros = p->d_zero3, sp.err = p->d_err3, sp.stamps = p->d_stamps3;
+  sp.jobs = p->sweep.d_jobs, sp.regions = p->sweep.d_regions, sp.n_regions = p->sweep.n_regions, sp.group = (p->sweep.n_regions + 7) / 8;
+  const rpsf_plan* o = owner(p);
+  sp.k3 = o->sweep.d_k3, sp.win = o->d_win, sp.zeros = p->sweep.d_zero, sp.err = o->sweep.d_err, sp.stamps = p->sweep.d_stamps;
   sp.im_frame_floats = b.im_stride, sp.out_frame_floats = b.out_stride;
   // K by plain loads when frames share it or it is small enough to stay in the Infinity Cache from one apply to the next, else streamed
-  const bool k_plain = b.frames > 1 || p->k3_floats * sizeof(float) <= ((size_t)96 << 20);
+  const bool k_plain = b.frames > 1 || o->sweep.k3_floats * sizeof(float) <= ((size_t)96 << 20);
   if (ev_k0) HIP_TRY(hipEventRecord(ev_k0, st));
   for (int f0 = 0; f0 < b.frames; f0 += 65535) {  // grid.y limit
     SweepParams q = sp;
@@ -1390,44 +1334,41 @@ static int launch_apply(rpsf_plan* p, const float* d_img, float* d_out, const rp
   if (p->generic) return launch_apply_generic(p, d_img, d_out, g, st, ev_k0, ev_k1, b);
   const OverlapKind kind = overlap_kind(p);
   if (kind == OV_SWEEP) {
-    if (!p->sweep_ok) return fail(RPSF_E_STATE, "the sweep kernel needs a 16-, 32- or 64-pixel patch on a complete lattice of at least 2 x 2 patches");
+    if (!p->sweep.ok) return fail(RPSF_E_STATE, "the sweep kernel needs a 16-, 32- or 64-pixel patch on a complete lattice of at least 2 x 2 patches");
     return launch_sweep(p, d_img, d_out, g, st, ev_k0, ev_k1, b);
   }
   if (kind != OV_ATOMIC && !p->lattice) return fail(RPSF_E_STATE, "colour planes need a regular half-overlap lattice of patch corners");
-  if (kind == OV_DIRECT && !p->direct_ok) return fail(RPSF_E_STATE, "direct overlap-add needs a lattice and a 128- or 256-pixel patch");
+  if (kind == OV_DIRECT && !p->patch.direct_ok) return fail(RPSF_E_STATE, "direct overlap-add needs a lattice and a 128- or 256-pixel patch");
   if (kind == OV_DIRECT && (size_t)g.out_rows * g.ld_out * sizeof(float) >= ((size_t)1 << 32))
     return fail(RPSF_E_UNSUPPORTED, "direct overlap-add addresses the output through a 32-bit buffer offset: frame too large");
   // The plan's scratch (planes, flags) serves one apply at a time: an apply on another stream waits for the last one.
   if (p->busy_valid && st != p->last_stream) HIP_TRY(hipStreamWaitEvent(st, p->ev_busy, 0));
   if (kind != OV_ATOMIC) {
     const size_t need = plane_floats_needed(g);
-    if (need > p->planes_floats || (size_t)b.frames > p->planes_frames) {  // four planes per frame in flight
-      const size_t per = std::max(need, p->planes_floats), frames = std::max((size_t)b.frames, p->planes_frames);
+    if (need > p->patch.planes_floats || (size_t)b.frames > p->patch.planes_frames) {  // four planes per frame in flight
+      const size_t per = std::max(need, p->patch.planes_floats), frames = std::max((size_t)b.frames, p->patch.planes_frames);
       HIP_TRY(hipDeviceSynchronize());  // earlier applies, on whatever stream, may still use the old planes
-      (void)hipFree(p->d_planes);
-      p->d_planes = nullptr, p->planes_floats = 0, p->planes_frames = 0;
-      HIP_TRY(hipMalloc(&p->d_planes, 4 * per * frames * sizeof(float)));
-      p->planes_floats = per, p->planes_frames = frames;
+      p->patch.planes_floats = 0, p->patch.planes_frames = 0;
+      HIP_TRY(p->patch.d_planes.alloc(4 * per * frames));
+      p->patch.planes_floats = per, p->patch.planes_frames = frames;
     }
   }
   bool clear = kind == OV_ATOMIC;
   if (kind == OV_DIRECT) {
     const size_t n_tiles = (size_t)p->nti * p->ntj;
-    if ((size_t)b.frames > p->flag_frames) {
+    if ((size_t)b.frames > p->patch.flag_frames) {
       HIP_TRY(hipDeviceSynchronize());
-      (void)hipFree(p->d_flags);
-      (void)hipFree(p->d_dyn);
-      p->d_flags = p->d_dyn = nullptr, p->flag_frames = 0;
-      HIP_TRY(hipMalloc(&p->d_flags, n_tiles * b.frames * sizeof(uint32_t)));
-      HIP_TRY(hipMalloc(&p->d_dyn, n_tiles * b.frames * sizeof(uint32_t)));
-      HIP_TRY(hipMemset(p->d_flags, 0, n_tiles * b.frames * sizeof(uint32_t)));
-      HIP_TRY(hipMemset(p->d_dyn, 0, n_tiles * b.frames * sizeof(uint32_t)));
-      p->flag_frames = (size_t)b.frames;
+      p->patch.d_flags.reset(), p->patch.d_dyn.reset(), p->patch.flag_frames = 0;
+      HIP_TRY(p->patch.d_flags.alloc(n_tiles * b.frames));
+      HIP_TRY(p->patch.d_dyn.alloc(n_tiles * b.frames));
+      HIP_TRY(hipMemset(p->patch.d_flags, 0, n_tiles * b.frames * sizeof(uint32_t)));
+      HIP_TRY(hipMemset(p->patch.d_dyn, 0, n_tiles * b.frames * sizeof(uint32_t)));
+      p->patch.flag_frames = (size_t)b.frames;
     }
-    if (++p->epoch >= (1u << 24) - 1) {  // the epoch field of the flag words is 24 bits wide
-      HIP_TRY(hipMemsetAsync(p->d_flags, 0, n_tiles * p->flag_frames * sizeof(uint32_t), st));
-      HIP_TRY(hipMemsetAsync(p->d_chunk_xcc, 0, 8 * sizeof(uint32_t), st));
-      p->epoch = 1;
+    if (++p->patch.epoch >= (1u << 24) - 1) {  // the epoch field of the flag words is 24 bits wide
+      HIP_TRY(hipMemsetAsync(p->patch.d_flags, 0, n_tiles * p->patch.flag_frames * sizeof(uint32_t), st));
+      HIP_TRY(hipMemsetAsync(p->patch.d_chunk_xcc, 0, 8 * sizeof(uint32_t), st));
+      p->patch.epoch = 1;
     }
     // pixels of the resident window that no lattice tile covers are never written by the kernels below
     const int half = p->N / 2;
@@ -1441,29 +1382,27 @@ static int launch_apply(rpsf_plan* p, const float* d_img, float* d_out, const rp
                                (size_t)g.width * sizeof(float), g.out_rows, st));
   // Fused plane sum: one frame, every plane line written whole by one store instruction (see sum_tile)
   const long tile_r0 = (long)p->lat_r0 + g.origin_row, tile_c0 = (long)p->lat_c0 + g.origin_col;
-  const bool fused = kind == OV_PLANES && p->v2 && p->fuse_pays && p->d_tile_done && !p->no_fuse && b.frames <= 255 && g.width % 32 == 0 &&
+  const bool fused = kind == OV_PLANES && p->patch.v2 && p->patch.fuse_pays && p->patch.d_tile_done && !p->patch.no_fuse && b.frames <= 255 && g.width % 32 == 0 &&
                      g.ld_out % 4 == 0 && tile_c0 % 32 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0 &&
                      16 * plane_floats_needed(g) < ((size_t)1 << 32);  // the planes are addressed through one 32-bit buffer offset
   if (fused) {
     const size_t n_tiles = (size_t)p->nti * p->ntj;
-    if ((size_t)b.frames > p->done_frames) {  // one set of tile counters per frame of a batch
+    if ((size_t)b.frames > p->patch.done_frames) {  // one set of tile counters per frame of a batch
       HIP_TRY(hipDeviceSynchronize());
-      (void)hipFree(p->d_tile_done);
-      p->d_tile_done = nullptr;
-      HIP_TRY(hipMalloc(&p->d_tile_done, n_tiles * b.frames * sizeof(uint32_t)));
-      HIP_TRY(hipMemset(p->d_tile_done, 0, n_tiles * b.frames * sizeof(uint32_t)));
-      p->done_frames = (size_t)b.frames, p->done_epoch = 0;
+      HIP_TRY(p->patch.d_tile_done.alloc(n_tiles * b.frames));
+      HIP_TRY(hipMemset(p->patch.d_tile_done, 0, n_tiles * b.frames * sizeof(uint32_t)));
+      p->patch.done_frames = (size_t)b.frames, p->patch.done_epoch = 0;
     }
     // A launch advances the counters of frames [0, b.frames) only, and a tile is complete at epoch x contributors: when the frame
     // count differs from the previous fused launch's (batch -> single apply -> batch, or the short last group of a batch) the
     // counters of the higher frames would lag behind the epoch for ever - and the summing workgroups would wait for ever.
     // Start a new count whenever the frame count changes (and when the epoch would overflow the counters).
-    if (b.frames != p->done_last_frames || p->done_epoch + 1 >= (1u << 29)) {  // the counters hold epoch * contributors
-      HIP_TRY(hipMemsetAsync(p->d_tile_done, 0, n_tiles * p->done_frames * sizeof(uint32_t), st));
-      p->done_epoch = 0;
+    if (b.frames != p->patch.done_last_frames || p->patch.done_epoch + 1 >= (1u << 29)) {  // the counters hold epoch * contributors
+      HIP_TRY(hipMemsetAsync(p->patch.d_tile_done, 0, n_tiles * p->patch.done_frames * sizeof(uint32_t), st));
+      p->patch.done_epoch = 0;
     }
-    p->done_last_frames = b.frames;
-    ++p->done_epoch;
+    p->patch.done_last_frames = b.frames;
+    ++p->patch.done_epoch;
     // the tile sums write lattice tiles only: pixels of the window outside the tile grid are cleared here
     const int half = p->N / 2;
     if (tile_r0 > g.out_row0 || tile_r0 + (long)p->nti * half < (long)g.out_row0 + g.out_rows || tile_c0 > 0 ||
@@ -1486,9 +1425,9 @@ static int launch_apply(rpsf_plan* p, const float* d_img, float* d_out, const rp
 
 extern "C" int rpsf_plan_set_overlap_mode(rpsf_plan* p, int mode) {
   if (!p || mode < 0 || mode > 4) return fail(RPSF_E_BADARG, "mode must be 0 (auto), 1 (atomics), 2 (colour planes), 3 (direct) or 4 (sweep)");
-  if (mode == 4 && !p->sweep_ok) return fail(RPSF_E_STATE, "the sweep kernel needs a 16-, 32- or 64-pixel patch on a complete lattice of at least 2 x 2 patches");
+  if (mode == 4 && !p->sweep.ok) return fail(RPSF_E_STATE, "the sweep kernel needs a 16-, 32- or 64-pixel patch on a complete lattice of at least 2 x 2 patches");
   if (mode == 2 && !p->lattice) return fail(RPSF_E_STATE, "colour planes need a regular half-overlap lattice of patch corners");
-  if (mode == 3 && !p->direct_ok) return fail(RPSF_E_STATE, "direct overlap-add needs a regular half-overlap lattice and a 128- or 256-pixel patch");
+  if (mode == 3 && !p->patch.direct_ok) return fail(RPSF_E_STATE, "direct overlap-add needs a regular half-overlap lattice and a 128- or 256-pixel patch");
   p->overlap_mode = mode;
   drop_bands(p);
   return RPSF_OK;
@@ -1500,19 +1439,19 @@ extern "C" int rpsf_plan_set_option(rpsf_plan* p, int option, int value) {
   switch (option) {
     case RPSF_OPT_PERSIST:
       if (value != 0 && value != 1) return fail(RPSF_E_BADARG, "RPSF_OPT_PERSIST takes 0 or 1");
-      p->persist = value != 0 && (p->N == 256 || p->N == 128);
+      p->patch.persist = value != 0 && (p->N == 256 || p->N == 128);
       break;
     case RPSF_OPT_FUSE:
       if (value != 0 && value != 1) return fail(RPSF_E_BADARG, "RPSF_OPT_FUSE takes 0 or 1");
-      p->no_fuse = value == 0;
+      p->patch.no_fuse = value == 0;
       break;
     case RPSF_OPT_K_CACHED:
       if (value != 0 && value != 1) return fail(RPSF_E_BADARG, "RPSF_OPT_K_CACHED takes 0 or 1");
-      p->k_cached = value != 0;
+      p->patch.k_cached = value != 0;
       break;
     case RPSF_OPT_PLANE_NT:
       if (value < -1 || value > 1) return fail(RPSF_E_BADARG, "RPSF_OPT_PLANE_NT takes -1 (automatic), 0 or 1");
-      p->plane_nt_opt = value;
+      p->patch.plane_nt_opt = value;
       break;
     case RPSF_OPT_HOST_BANDS:
       if (value < -1 || value > 64) return fail(RPSF_E_BADARG, "RPSF_OPT_HOST_BANDS takes -1 (automatic) or 0..64");
@@ -1528,7 +1467,7 @@ extern "C" int rpsf_plan_set_option(rpsf_plan* p, int option, int value) {
       break;
     case RPSF_OPT_DEBUG_ORPHAN:
       if (value < 0) return fail(RPSF_E_BADARG, "RPSF_OPT_DEBUG_ORPHAN takes 0 (off) or a positive modulus");
-      p->orphan_mod = value;
+      p->patch.orphan_mod = value;
       break;
     default: return fail(RPSF_E_BADARG, "unknown plan option");
   }
@@ -1538,7 +1477,7 @@ extern "C" int rpsf_plan_set_option(rpsf_plan* p, int option, int value) {
 
 extern "C" int rpsf_plan_set_sweep_regions(rpsf_plan* p, int target_regions) {
   if (!p || target_regions < 1 || target_regions > (1 << 20)) return fail(RPSF_E_BADARG, "target_regions must be 1..2^20");
-  if (!p->sweep_ok) return fail(RPSF_E_STATE, "the sweep kernel needs a 16-, 32- or 64-pixel patch on a complete lattice of at least 2 x 2 patches");
+  if (!p->sweep.ok) return fail(RPSF_E_STATE, "the sweep kernel needs a 16-, 32- or 64-pixel patch on a complete lattice of at least 2 x 2 patches");
   HIP_TRY(hipSetDevice(p->device));
   HIP_TRY(hipStreamSynchronize(p->stream));
   HIP_TRY(hipDeviceSynchronize());  // (applies on other streams may still read the old lists)
@@ -1552,23 +1491,23 @@ extern "C" int rpsf_plan_host_bands(const rpsf_plan* p, int* bands) {
 }
 extern "C" int rpsf_plan_sweep_info(const rpsf_plan* p, int* regions, long* jobs, long* patch_slots, int* slabs_per_phase) {
   if (!p) return fail(RPSF_E_BADARG, "null plan");
-  if (regions) *regions = p->sweep_ok ? p->n_regions3 : 0;
-  if (jobs) *jobs = p->sweep_ok ? p->slabs3 : 0;
-  if (patch_slots) *patch_slots = p->sweep_ok ? p->patch_slots3 : 0;
-  if (slabs_per_phase) *slabs_per_phase = p->sweep_ok ? p->ks3 : 0;
+  if (regions) *regions = p->sweep.ok ? p->sweep.n_regions : 0;
+  if (jobs) *jobs = p->sweep.ok ? p->sweep.slabs : 0;
+  if (patch_slots) *patch_slots = p->sweep.ok ? p->sweep.patch_slots : 0;
+  if (slabs_per_phase) *slabs_per_phase = p->sweep.ok ? p->sweep.ks : 0;
   return RPSF_OK;
 }
 
 extern "C" int rpsf_plan_debug_stamps(rpsf_plan* p, unsigned long long* host, size_t count) {
   if (!p || !host) return fail(RPSF_E_BADARG, "null argument");
-  if (p->d_stamps3) {  // third generation: [region][wave][job slot < 8][16]
+  if (p->sweep.d_stamps) {  // third generation: [region][wave][job slot < 8][16]
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipDeviceSynchronize());
-    count = std::min(count, (size_t)std::max(512, p->n_regions3) * 8 * 8 * 16);
-    HIP_TRY(hipMemcpy(host, p->d_stamps3, count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    count = std::min(count, (size_t)std::max(512, p->sweep.n_regions) * 8 * 8 * 16);
+    HIP_TRY(hipMemcpy(host, p->sweep.d_stamps, count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return RPSF_OK;
   }
-  if (!p->d_stamps) return fail(RPSF_E_STATE, "phase timestamps exist only in builds with -DRPSF_STAMPS");
+  if (!p->patch.d_stamps) return fail(RPSF_E_STATE, "phase timestamps exist only in builds with -DRPSF_STAMPS");
   HIP_TRY(hipSetDevice(p->device));
   HIP_TRY(hipDeviceSynchronize());
 #if defined(RPSF_WAVE_STAMPS)
@@ -1576,14 +1515,14 @@ extern "C" int rpsf_plan_debug_stamps(rpsf_plan* p, unsigned long long* host, si
 #else
   count = std::min(count, (size_t)16 * p->n_patches);
 #endif
-  HIP_TRY(hipMemcpy(host, p->d_stamps, count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(host, p->patch.d_stamps, count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return RPSF_OK;
 }
 
 
 extern "C" int rpsf_plan_set_reserved_cus(rpsf_plan* p, int cus) {
   if (!p || cus < 0 || cus > 128) return fail(RPSF_E_BADARG, "reserved CUs must be 0..128");
-  p->reserved_cus = cus;
+  p->patch.reserved_cus = cus;
   return RPSF_OK;
 }
 
@@ -1602,14 +1541,14 @@ extern "C" int rpsf_plan_set_cu_mask(rpsf_plan* p, const uint32_t* mask, int wor
   drop_bands(p);
   hipStream_t masked = nullptr;
   HIP_TRY(hipExtStreamCreateWithCUMask(&masked, (uint32_t)words, mask));
-  if (p->generic && g_hipfft.set_stream(p->fft_plan, masked) != 0) {
+  if (p->generic && g_hipfft.set_stream(p->fft.plan.get(), masked) != 0) {
     (void)hipStreamDestroy(masked);
     return fail(RPSF_E_HIP, "hipfftSetStream failed");
   }
   (void)hipStreamDestroy(p->stream);
   p->stream = masked;
   p->busy_valid = false;
-  if (p->cu_count > 0) p->round_capacity = p->round_capacity / p->cu_count * cus;
+  if (p->cu_count > 0) p->patch.round_capacity = p->patch.round_capacity / p->cu_count * cus;
   p->cu_count = cus;
   return RPSF_OK;
 }
@@ -1632,13 +1571,13 @@ extern "C" int rpsf_stream_destroy(void* stream) {
 
 extern "C" int rpsf_plan_set_image_prefetch(rpsf_plan* p, int on) {
   if (!p) return fail(RPSF_E_BADARG, "null plan");
-  p->prefetch = on != 0;
+  p->patch.prefetch = on != 0;
   return RPSF_OK;
 }
 
 extern "C" int rpsf_plan_set_stagger(rpsf_plan* p, int microseconds) {
   if (!p || microseconds < 0 || microseconds > 1000) return fail(RPSF_E_BADARG, "stagger must be 0..1000 us");
-  p->stagger_us = microseconds;
+  p->patch.stagger_us = microseconds;
   drop_bands(p);
   return RPSF_OK;
 }
@@ -1766,7 +1705,7 @@ using rpsf_host::HostPipe;
 using rpsf_host::HostPool;
 
 static int pipe_ensure(rpsf_plan* p, size_t slot_floats, int depth) {
-  if (!p->pipe) p->pipe = new HostPipe;
+  if (!p->pipe) p->pipe.reset(new HostPipe);
   HostPipe& q = *p->pipe;
   if (!q.st_in) {
     HIP_TRY(hipStreamCreateWithFlags(&q.st_in, hipStreamNonBlocking));
@@ -1818,8 +1757,9 @@ static bool all_pinned(const void* const* ptrs, int n) {
 // The sweep kernel bounds every wait of a job for its predecessors (a protocol error must not hang the GPU) and reports a wait that ran out through a
 // page-locked word; every entry point that has just waited for the plan's work looks at it, so such an apply fails instead of returning a wrong image.
 static int sweep_check(rpsf_plan* p) {
-  if (!p->h_err3 || *reinterpret_cast<volatile uint32_t*>(p->h_err3) == 0) return RPSF_OK;
-  *reinterpret_cast<volatile uint32_t*>(p->h_err3) = 0;
+  volatile uint32_t* word = owner(p)->sweep.err;
+  if (!word || *word == 0) return RPSF_OK;
+  *word = 0;
   return fail(RPSF_E_HIP, "sweep kernel: a job waited for the jobs it follows beyond the bound (internal protocol error; the output of this apply is not valid)");
 }
 
@@ -1855,7 +1795,7 @@ static int ensure_bands(rpsf_plan* p, const rpsf_geometry& g, int want) {
   cut[B] = H;
   for (int b = 0; b < B; ++b)
     if (cut[b + 1] <= cut[b]) return 0;
-  std::vector<rpsf_plan*> bands;
+  std::vector<std::unique_ptr<rpsf_plan>> bands;
   std::vector<int> in_rows;
   for (int b = 0; b < B; ++b) {
     std::vector<int32_t> idx, coords;
@@ -1871,13 +1811,10 @@ static int ensure_bands(rpsf_plan* p, const rpsf_geometry& g, int want) {
     // (every np.pad mode but 'wrap' maps a row beyond the image edge to a row within the patch's own reach, so rows [0, in_hi) suffice)
     const int rc = idx.empty() ? fail(RPSF_E_STATE, "empty row band") :
                                  plan_create_impl(&view, p->device, N, (int)idx.size(), coords.data(), p, idx.data());
-    if (rc != RPSF_OK) {
-      for (rpsf_plan* v : bands) rpsf_plan_destroy(v);
-      return 0;
-    }
-    bands.push_back(view), in_rows.push_back(std::max(in_hi, cut[b + 1]));
+    if (rc != RPSF_OK) return 0;
+    bands.emplace_back(view), in_rows.push_back(std::max(in_hi, cut[b + 1]));
   }
-  p->bands = bands, p->band_rows = cut, p->band_in_rows = in_rows;
+  p->bands = std::move(bands), p->band_rows = cut, p->band_in_rows = in_rows;
   return B;
 }
 
@@ -1976,7 +1913,7 @@ static int host_one_frame_banded(rpsf_plan* p, const void* image, int in_f64, vo
           err = hipEventRecord(q.ev_band_in[b], q.st_in);
           if (err == hipSuccess) err = hipStreamWaitEvent(p->stream, q.ev_band_in[b], 0);
           float* const host_out = direct_out ? static_cast<float*>(out) : q.h_out[0];
-          if (err == hipSuccess && launch_apply(p->bands[b], q.d_in[0], q.d_out[0] + (size_t)R0 * W, gb, p->stream, nullptr) != RPSF_OK)
+          if (err == hipSuccess && launch_apply(p->bands[b].get(), q.d_in[0], q.d_out[0] + (size_t)R0 * W, gb, p->stream, nullptr) != RPSF_OK)
             err = hipErrorUnknown;
           if (err == hipSuccess) err = hipEventRecord(q.ev_band_k[b], p->stream);
           // (one download stream: a second one for every other band - to hide the 20 us between two copies of a stream - made the frame 8 % slower,
@@ -2096,7 +2033,7 @@ static int host_one_frame(rpsf_plan* p, const void* image, int in_f64, void* out
   // the caller's own page-locked array) - no download behind the launch, whose start-up and 1 MiB are a fifth of such a frame's time (512^2 / 64:
   // 0.140 -> see profiles/r06zu_small_frame_zero_copy_out.log).  Only where every pixel of the window is written by the launch (the lattice covers it).
   float* zc_out = nullptr;
-  if (one_stream && err == hipSuccess && overlap_kind(p) == OV_SWEEP && p->sweep_ok && !dev_env("RPSF_NO_ZC_OUT")) {
+  if (one_stream && err == hipSuccess && overlap_kind(p) == OV_SWEEP && p->sweep.ok && !dev_env("RPSF_NO_ZC_OUT")) {
     const int half = p->N / 2;
     const long r0 = (long)p->lat_r0 + g.origin_row, c0 = (long)p->lat_c0 + g.origin_col;
     const bool covered = r0 <= g.out_row0 && r0 + (long)p->nti * half >= (long)g.out_row0 + g.out_rows && c0 <= 0 && c0 + (long)p->ntj * half >= g.width;
@@ -2633,7 +2570,7 @@ extern "C" int rpsf_pcie_probe(int device, size_t bytes, int iters, double* h2d_
   HIP_TRY(hipSetDevice(device));
   struct Res {
     void *h0 = nullptr, *h1 = nullptr;
-    DevBuf d0, d1;
+    DevBuf<char> d0, d1;
     hipStream_t s0 = nullptr, s1 = nullptr;
     hipEvent_t e[4] = {};
     ~Res() {
@@ -2734,11 +2671,10 @@ extern "C" int rpsf_build_transfer(int device, size_t count, const void* s_host,
   HIP_TRY(hipSetDevice(device));
   const size_t esz = is_f64 ? 16 : 8;
   const size_t chunk = std::min<size_t>(count, (size_t)8 << 20);  // 8 Mi elements per round
-  DevBuf bs, bt, bk;
-  HIP_TRY(bs.alloc(chunk * esz));
-  HIP_TRY(bt.alloc(chunk * esz));
-  HIP_TRY(bk.alloc(chunk * esz));
-  char *ds = bs.as<char>(), *dt = bt.as<char>(), *dk = bk.as<char>();
+  DevBuf<char> ds, dt, dk;
+  HIP_TRY(ds.alloc(chunk * esz));
+  HIP_TRY(dt.alloc(chunk * esz));
+  HIP_TRY(dk.alloc(chunk * esz));
   int rc = RPSF_OK;
   for (size_t first = 0; first < count && rc == RPSF_OK; first += chunk) {
     size_t cnt = std::min(chunk, count - first);
@@ -2766,32 +2702,30 @@ static int psf_fft_impl(int device, int patch_size, int count, const float* valu
   if (count <= 0) return count == 0 ? RPSF_OK : fail(RPSF_E_BADARG, "negative count");
   return dispatch_n(patch_size, [&]<class C>() -> int {
     HIP_TRY(hipSetDevice(device));
-    uint16_t* d_tab = nullptr;
-    cf* d_tw = nullptr;
-    int rc = upload_tables<C>(device, &d_tab, &d_tw, nullptr);
+    DevBuf<uint16_t> d_tab;
+    DevBuf<cf> d_tw;
+    int rc = upload_tables<C>(device, d_tab, d_tw);
     if (rc != RPSF_OK) return rc;
-    DevBuf keep_tab, keep_tw, b_in, b_out, b_par;
-    keep_tab.p = d_tab, keep_tw.p = d_tw;
+    DevBuf<float> b_in;
+    DevBuf<cf> b_out;
+    DevBuf<double> b_par;
     const size_t per = (size_t)C::N * C::N;
     int chunk = (int)std::max<size_t>(1, (size_t)(64u << 20) / (per * sizeof(cf)));
     if (chunk > count) chunk = count;
-    if (!(model >= 0 && values_dev)) HIP_TRY(b_in.alloc(per * sizeof(float) * chunk));  // (rasterised straight into values_dev otherwise)
-    if (!fft_dev) HIP_TRY(b_out.alloc(per * sizeof(cf) * chunk));
-    if (model >= 0) {
-      HIP_TRY(b_par.alloc(sizeof(double) * RPSF_MODEL_PARAMS_DEV * (size_t)count));
-      HIP_TRY(hipMemcpy(b_par.p, params_host, sizeof(double) * RPSF_MODEL_PARAMS_DEV * (size_t)count, hipMemcpyHostToDevice));
-    }
+    if (!(model >= 0 && values_dev)) HIP_TRY(b_in.alloc(per * chunk));  // (rasterised straight into values_dev otherwise)
+    if (!fft_dev) HIP_TRY(b_out.alloc(per * chunk));
+    if (model >= 0) HIP_TRY(b_par.upload(params_host, RPSF_MODEL_PARAMS_DEV * (size_t)count));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&psf_fft_kernel<C>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)Launch<C>::LDS_BYTES));
     for (int first = 0; first < count && rc == RPSF_OK; first += chunk) {
       int cnt = std::min(chunk, count - first);
-      cf* d_out = fft_dev ? static_cast<cf*>(fft_dev) + (size_t)first * per : b_out.as<cf>();
-      float* d_in = model >= 0 && values_dev ? static_cast<float*>(values_dev) + (size_t)first * per : b_in.as<float>();
+      cf* d_out = fft_dev ? static_cast<cf*>(fft_dev) + (size_t)first * per : b_out;
+      float* d_in = model >= 0 && values_dev ? static_cast<float*>(values_dev) + (size_t)first * per : b_in;
       hipError_t e = hipSuccess;
       if (model < 0) {
         e = hipMemcpy(d_in, values_host + (size_t)first * per, per * sizeof(float) * cnt, hipMemcpyHostToDevice);
       } else {
-        rasterize_kernel<<<dim3((unsigned)cnt), dim3(256), 0, nullptr>>>(model, C::N, b_par.as<double>() + (size_t)first * RPSF_MODEL_PARAMS_DEV,
+        rasterize_kernel<<<dim3((unsigned)cnt), dim3(256), 0, nullptr>>>(model, C::N, b_par + (size_t)first * RPSF_MODEL_PARAMS_DEV,
                                                                       normalize, d_in);
         e = hipGetLastError();
       }

@@ -158,3 +158,93 @@ def test_saturated_frames_in_sequence_equal_the_loop(n, shape, frames):
     assert np.array_equal(t.apply_batch(np.stack(stack), dtype=np.float32, **kwargs), loop.astype(np.float32), equal_nan=True)
     _compare(loop[0], orc.apply_transfer(stack[0], coords, k, **kwargs))
     _compare(loop[-1], orc.apply_transfer(stack[-1], coords, k, **kwargs))
+
+
+def _device_free_bytes():
+    """Free device memory as the HIP runtime that librpsf_hip.so loaded reports it (hipMemGetInfo)."""
+    import ctypes
+    import gc
+
+    from regularizepsf_amd import _native
+
+    _native.lib()
+    with open("/proc/self/maps") as maps:
+        hip = sorted({line.split()[-1] for line in maps if "libamdhip64" in line})
+    assert hip, "the HIP runtime is not loaded"
+    gc.collect()  # (plans of earlier tests that are only waiting for the collector)
+    free, total = ctypes.c_size_t(), ctypes.c_size_t()
+    assert ctypes.CDLL(hip[0]).hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
+    return free.value
+
+
+def _teardown_cases():
+    """(name, round): one round creates a plan of one apply path, sets K, applies once and closes the plan."""
+    from regularizepsf_amd import _native
+
+    sym = _native.PAD_MODES["symmetric"]
+
+    def plan_of(shape, n, k=None, coords=None, edit=None):
+        c, kk = orc.synthetic_transfer(*shape, n, alpha=1.0, epsilon=0.1)
+        coords, k = np.asarray(coords if coords is not None else c), k if k is not None else kk
+        if edit is not None:
+            coords, k = edit(coords.copy(), k)
+        return coords, k
+
+    def run(n, coords, k, image, mode=None, apply=lambda plan, im: plan.apply(im, sym), check=None):
+        def one_round():
+            plan = _native.Plan(n, coords)
+            try:
+                if mode:
+                    plan.set_overlap_mode(mode)
+                plan.set_transfer(k)
+                out = apply(plan, image)
+                assert np.isfinite(out).all()
+                if check:
+                    check(plan)
+            finally:
+                plan.close()
+        return one_round
+
+    def shift_one(coords, k):  # one corner off the half-overlap lattice: float atomics
+        coords[len(coords) // 2, 0] += 3
+        return coords, k
+
+    def drop_one(coords, k):  # an incomplete lattice: colour planes, no sweep kernel
+        keep = np.arange(len(coords)) != len(coords) // 2
+        return coords[keep], k[keep]
+
+    cases = []
+    for name, n, shape, edit, mode in [("fallback_96", 96, (288, 288), None, None), ("atomics_32", 32, (160, 192), shift_one, None),
+                                       ("planes_64", 64, (256, 320), drop_one, None), ("sweep_32", 32, (160, 192), None, None),
+                                       ("fused_128", 128, (512, 640), None, None), ("persistent_256", 256, (1024, 1280), None, None),
+                                       ("direct_256", 256, (1024, 1280), None, "direct")]:
+        coords, k = plan_of(shape, n, edit=edit)
+        cases.append((name, run(n, coords, k, orc.starfield(*shape, seed=n), mode)))
+    # a 4096^2 host frame is cut into row bands: views of the plan that borrow its tables, packed K and error word
+    big = np.asarray(rp.calculate_covering((4096, 4096), 64))
+    k_big = np.ones((len(big), 64, 64), np.complex64)
+
+    def banded(plan):
+        assert plan.host_bands() >= 2
+
+    cases.append(("host_bands_64", run(64, big, k_big, orc.starfield(4096, 4096, seed=5), check=banded)))
+    coords, k = plan_of((96, 128), 32)
+    hot = orc.starfield(96, 128, seed=9).astype(np.float64)
+    hot[40:44, 50:55] = 7.0e4
+    cases.append(("saturated_32", run(32, coords, k, hot, apply=lambda plan, im: plan.apply_host_saturated(im, sym, 5.0e4, 1, 7))))
+    return cases
+
+
+def test_plans_of_every_apply_path_give_back_all_device_memory():
+    """20 rounds of create / set K / apply / close on every apply path leave device memory as one warm-up round of each left it
+    (code objects, the process-wide host pool and hipFFT's own state are allocated once per process, not per plan)."""
+    cases = _teardown_cases()
+    for name, one_round in cases:
+        print(name)  # (shown with a failure: which path)
+        one_round()
+    before = _device_free_bytes()
+    for name, one_round in cases:
+        for _ in range(20):
+            one_round()
+        after = _device_free_bytes()
+        assert after >= before, f"{name}: {before - after} bytes of device memory not given back after 20 plans"
