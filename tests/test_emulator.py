@@ -3,6 +3,7 @@ second-generation 128/256-pixel plans) on the CPU, thread by thread, and check t
 kernel (digit layouts, LDS addressing, slot table, packed-K format) without needing a GPU."""
 
 import ctypes
+import functools
 import pathlib
 import shutil
 import subprocess
@@ -10,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests.helpers import APPLY_CASES, load_apply_case, rel_errors
+from tests.helpers import APPLY_CASES, KERNEL_PAD_MODES, MARGIN, LocalCase, load_apply_case, local_error, per_patch_reference, rel_errors
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 EMU_SRC = ROOT / "tests" / "emu" / "emu.cpp"
@@ -215,3 +216,108 @@ def test_sweep_recompute_factor_at_the_benchmark_sizes(emu3):
         stats = (ctypes.c_int64 * 4)()
         assert emu3.emu3_check_plan(n, ksmax, 8, lattice, lattice, 256, stats) == 0
         assert stats[2] / (lattice * lattice) <= bound, (n, list(stats))
+
+
+# ---- local parity: the emulated kernel phases on frames that span six decades, per patch neighbourhood -----------------------------
+# The tests above bound the error by 1e-5 of the brightest pixel of the frame; the reference treats every patch on its own, so a correct
+# float32 implementation errs at a pixel by ~2e-7 of what the (at most four) patches over that pixel carry.  Below: max |d| / local scale
+# (tests/helpers.py) of every emulator against the same quantity of the float32 yardstick (the oracle's own steps in single precision),
+# at most MARGIN x; every case has at least 10 % of its pixels below 1e-3 of the frame's largest scale (asserted from the float64 oracle
+# alone in LocalCase).  And exact homogeneity: a power-of-two factor on the frame comes out as that factor on every pixel, bit for bit.
+
+LOCAL_SEEDS = {128: 129, 256: 272}  # HDR seeds for which every pad mode leaves >= 10 % of the frame dim (asserted per case)
+
+
+@functools.lru_cache(maxsize=8)
+def _local_case(shape, n, seed, mode):
+    return LocalCase(shape, n, seed, mode)
+
+
+def _run_emu(lib, case, image):
+    out = np.zeros(case.shape, np.float32)
+    c = np.ascontiguousarray(np.array(case.coords, np.int32))
+    vp = ctypes.c_void_p
+    img = np.ascontiguousarray(image, np.float32)
+    rc = lib.emu_apply(case.n, len(case.coords), c.ctypes.data_as(vp), *case.shape, MODES[case.pad_mode], ctypes.c_float(0.0),
+                       img.ctypes.data_as(vp), case.k.ctypes.data_as(vp), out.ctypes.data_as(vp))
+    assert rc == 0
+    return out
+
+
+def _run_emu2(lib, case, image, direct):
+    out = np.zeros(case.shape, np.float32)
+    c = np.ascontiguousarray(np.array(case.coords, np.int32))
+    vp = ctypes.c_void_p
+    img = np.ascontiguousarray(image, np.float32)
+    rc = lib.emu2_apply(case.n, len(case.coords), c.ctypes.data_as(vp), *case.shape, MODES[case.pad_mode], ctypes.c_float(0.0),
+                        img.ctypes.data_as(vp), case.k.ctypes.data_as(vp), out.ctypes.data_as(vp), direct)
+    assert rc == 0
+    return out
+
+
+def _run_emu3(lib, case, image, target_regions, order_seed=0):
+    out = np.full(case.shape, np.nan, np.float32)
+    c = np.ascontiguousarray(np.array(case.coords, np.int32))
+    vp = ctypes.c_void_p
+    img = np.ascontiguousarray(image, np.float32)
+    stats = (ctypes.c_int64 * 4)()
+    rc = lib.emu3_apply(case.n, len(case.coords), c.ctypes.data_as(vp), *case.shape, MODES[case.pad_mode], ctypes.c_float(0.0),
+                        img.ctypes.data_as(vp), case.k.ctypes.data_as(vp), out.ctypes.data_as(vp), target_regions, order_seed,
+                        int(case.shape[1] % 4 == 0), stats)
+    assert rc == 0, rc
+    return out
+
+
+def _local_bound_and_homogeneity(case, run, what):
+    """The 1e-5 bar of the tests above, the local bound, and run(s x frame) == s x run(frame) bit for bit for s = 2^10 and 2^-10."""
+    out = run(case.image)
+    rel_max, rel_l2 = rel_errors(out, case.ref)
+    ratio = case.ratio(out)
+    print(f"{what}: dim share {case.share:.2f}, yardstick {case.yardstick:.2e}, local error {ratio:.2f} x yardstick, global {rel_max:.2e}")
+    assert rel_max <= 1e-5 and rel_l2 <= 1e-5, (rel_max, rel_l2)
+    case.check(out, MARGIN, what)
+    for s in (np.float32(1024.0), np.float32(1.0 / 1024.0)):
+        assert np.array_equal(run(s * case.image), s * out), (what, float(s))
+
+
+def test_per_patch_reference_is_the_pinned_oracle_and_its_float32_form_is_homogeneous():
+    """The helper every local bound rests on: its float64 result equals orc.apply_transfer to rounding (asserted inside the helper, on
+    every call, here once per pad mode and on a golden case with a non-random K), its float32 form stays in single precision, and a
+    power-of-two factor on the frame goes through the float32 steps exactly."""
+    for mode in KERNEL_PAD_MODES:
+        case = _local_case((130, 203), 32, 32, mode)
+        yard, none = per_patch_reference(case.image, case.coords, case.k, mode, np.float32)
+        assert none is None and yard.dtype == np.float32
+        assert 1e-7 < local_error(yard, case.ref, case.scale) < 5e-7
+        for s in (np.float32(1024.0), np.float32(1.0 / 1024.0)):
+            assert np.array_equal(per_patch_reference(s * case.image, case.coords, case.k, mode, np.float32)[0], s * yard)
+    fx, coords, k = load_apply_case("n64_sym")
+    ref, scale = per_patch_reference(fx["image"], coords, k, "symmetric", np.float64)
+    assert np.abs(ref - fx["expected"]).max() <= 1e-12 * np.abs(fx["expected"]).max()
+    assert scale.shape == ref.shape and (scale > 0).all()
+
+
+@pytest.mark.parametrize("mode", KERNEL_PAD_MODES)
+def test_first_generation_emulator_local_parity_and_homogeneity(emu, mode):
+    case = _local_case((130, 203), 32, 32, mode)
+    _local_bound_and_homogeneity(case, lambda image: _run_emu(emu, case, image), f"emu N=32 {mode}")
+
+
+@pytest.mark.parametrize("direct", [0, 1, 2])
+@pytest.mark.parametrize("mode", KERNEL_PAD_MODES)
+@pytest.mark.parametrize(("n", "shape", "seed"), [(128, (520, 650), LOCAL_SEEDS[128]), (256, (520, 770), LOCAL_SEEDS[256])])
+def test_second_generation_emulator_local_parity_and_homogeneity(emu2, n, shape, seed, mode, direct):
+    """Plain adds, first-store-then-accumulate and the four colour planes; rim patches and a width that is no multiple of four."""
+    case = _local_case(shape, n, seed, mode)
+    _local_bound_and_homogeneity(case, lambda image: _run_emu2(emu2, case, image, direct), f"emu2 N={n} direct={direct} {mode}")
+
+
+@pytest.mark.parametrize("mode", KERNEL_PAD_MODES)
+@pytest.mark.parametrize(("n", "shape", "seed"), [(16, (100, 135), 16), (16, (100, 136), 16), (32, (300, 500), 32), (32, (130, 203), 32),
+                                                  (64, (333, 390), 64), (64, (320, 392), 64)])
+def test_sweep_emulator_local_parity_and_homogeneity(emu3, n, shape, seed, mode):
+    """The sweep kernel's lane phases (128 / N patches in a wave, two rows in one complex transform, the LDS ring) cut into one region
+    and into many, widths that take the 16-byte paths and widths that do not."""
+    case = _local_case(shape, n, seed, mode)
+    for target in (1, 8):
+        _local_bound_and_homogeneity(case, lambda image: _run_emu3(emu3, case, image, target, target), f"emu3 N={n} {shape} regions={target} {mode}")
