@@ -168,7 +168,9 @@ class LocalCase:
     """One HDR case with everything the local bound needs, computed once: frame, corners, K, float64 oracle, local scale, the yardstick's
     local error.  ``check(out)`` returns (ratio to the yardstick, local error) after asserting the bound."""
 
-    def __init__(self, shape, n, seed, pad_mode="symmetric", image=None, coords=None, k=None, dim=DIM, min_share=0.10):
+    def __init__(self, shape, n, seed, pad_mode="symmetric", image=None, coords=None, k=None, dim=DIM, min_share=0.10, yardstick_k=None):
+        """``yardstick_k``: the K the float32 yardstick applies, where it is not ``k`` rounded to complex64 (a chain test: ``k`` is the
+        K of the chain done in float64, ``yardstick_k`` what the reference's own float32 chain makes of the same samples)."""
         self.shape, self.n, self.pad_mode = tuple(shape), n, pad_mode
         if coords is None:
             coords, k = random_transfer(shape, n, seed + 1000)
@@ -177,7 +179,7 @@ class LocalCase:
         self.ref, self.scale = per_patch_reference(self.image, coords, k, pad_mode, np.float64)
         self.share = dim_share(self.scale, dim)
         assert self.share >= min_share, f"only {self.share:.2f} of the pixels are dim: the case proves nothing ({shape}, N={n}, seed {seed}, {pad_mode})"
-        yard, _ = per_patch_reference(self.image, coords, k, pad_mode, np.float32)
+        yard, _ = per_patch_reference(self.image, coords, k if yardstick_k is None else yardstick_k, pad_mode, np.float32)
         self.yardstick = local_error(yard, self.ref, self.scale)
         assert 0 < self.yardstick < 1e-6, self.yardstick  # float32 rounding, nothing else
 
@@ -189,3 +191,223 @@ class LocalCase:
         ratio = self.ratio(out)
         assert ratio <= margin, f"{what}: local error {ratio:.2f} x the float32 yardstick ({self.yardstick:.2e}), margin {margin}"
         return ratio
+
+
+# ---- construct parity: what makes K (PSF samples -> spectra -> transfer kernel) judged per PSF and per frequency bin ------------------------
+PSF_KINDS = ("gauss", "coma", "normal", "delta", "constant")
+
+
+def psf_cube(n, count, seed, kinds=PSF_KINDS):
+    """(float32 cube, kind of every PSF): cycles through narrow Gaussians (sigma 0.6 ... 0.9, unit sum), orc.coma_psf somewhere on a frame of
+    8 N x 8 N pixels, standard-normal samples, a single 1 at a random pixel, a constant; each PSF times 10**k, k a seeded integer in [-3, 3]."""
+    rng = np.random.default_rng(seed)
+    frame = 8 * n
+    cube = np.empty((count, n, n), np.float32)
+    names = []
+    for i in range(count):
+        kind = kinds[i % len(kinds)]
+        if kind == "gauss":
+            p = orc.gaussian_psf(n, float(rng.uniform(0.6, 0.9)))
+        elif kind == "coma":
+            r, c = (int(v) for v in rng.integers(-n // 2, frame - n // 2, 2))
+            p = orc.coma_psf(n, r, c, frame, frame)
+        elif kind == "normal":
+            p = rng.standard_normal((n, n))
+        elif kind == "delta":
+            p = np.zeros((n, n))
+            p[tuple(rng.integers(0, n, 2))] = 1.0
+        else:
+            p = np.ones((n, n))
+        cube[i] = p * 10.0 ** rng.integers(-3, 4)
+        names.append(kind)
+    return cube, names
+
+
+def spectrum_errors(got, truth):
+    """Per PSF: max over bins |got - truth| / max over bins |truth| - every PSF against its OWN peak."""
+    d = np.abs(np.asarray(got).astype(np.complex128) - truth).max(axis=(1, 2))
+    return d / np.abs(truth).max(axis=(1, 2))
+
+
+def dim_psf_share(truth, dim=DIM):
+    """Share of the PSFs whose spectral peak is at most ``dim`` x the largest of the cube."""
+    peaks = np.abs(truth).max(axis=(1, 2))
+    return float(np.count_nonzero(peaks <= dim * peaks.max()) / peaks.size)
+
+
+def broadband_psfs(n, coords):
+    """Per patch a Gaussian core (sigma 0.6 ... 0.9) plus a weak displaced blob, unit sum, float32: spectra without a noise floor
+    (min|S| / max|S| ~ 2e-3), so that the reference's own float32 chain samples -> spectra -> K is well-conditioned."""
+    x = np.arange(n) - n // 2
+    out = []
+    for r, c in coords:
+        s = 0.6 + 0.3 * ((r + c) % 7) / 7
+        d = 1 + ((r * 3 + c) % 5) / 3
+        p = np.exp(-(x[:, None] ** 2 + x[None, :] ** 2) / (2 * s * s)) + 0.2 * np.exp(-((x[:, None] - d) ** 2 + (x[None, :] + d / 2) ** 2) / 2.0)
+        out.append(p / p.sum())
+    return np.stack(out).astype(np.float32)
+
+
+CONSTRUCT_ALPHAS = (0.0, 0.5, 1.0, 1.5, 2.0, 2.5, 3.0, 4.0, 5.0, 7.0)
+CONSTRUCT_EPSILONS = (1.0, 0.1, 1e-3)
+CONSTRUCT_SIZES = (32, 64, 256)
+#: source / target pairs of the K2 cases: the suite's coma and Gaussian pairs, the chain's broadband PSFs, and the coma sources against the
+#: Gaussians and comas of psf_cube (amplitudes 1e-3 ... 1e3, so that |T| and |S| are decades apart)
+CONSTRUCT_INPUTS = ("coma", "gauss", "broadband", "scaled")
+RANGE_F32 = (2.0 ** -120, 2.0 ** 120)  # a normal float32 number with room to spare
+RANGE_F64 = (2.0 ** -1000, 2.0 ** 1000)
+#: what a same-precision evaluation of the formula may err by per in-range bin, in units of the format's epsilon, for a case to count as
+#: "rounding and nothing else" in double: |S| and eps |T| carry up to 1.5 epsilon each (hypot within an ulp, one product) and enter to
+#: the power alpha + 1 <= 8, 2 x 8 x 1.5 = 24, plus half an epsilon for each of the remaining dozen operations.  (In float32 the bound
+#: is the 2e-6 = 17 epsilon that the cases were chosen by.)
+YARDSTICK_EPSILONS_F64 = 32.0
+
+
+def pow_branch(e):
+    """The branch of the kernels' np_pow that an exponent takes (rpsf_kernels.hpp)."""
+    fast = {0.0: "1", 1.0: "x", 2.0: "x*x", 0.5: "sqrt", -1.0: "1/x"}
+    return fast.get(e, "float64 product" if e in (3.0, 4.0, 5.0, 6.0, 8.0) else "pow")
+
+
+def pow_branches(alpha, double=False):
+    """'branch of alpha - 1 / branch of alpha + 1' (the double kernel has no product branch: its 3 ... 8 go to pow)."""
+    names = [pow_branch(alpha - 1), pow_branch(alpha + 1)]
+    return " / ".join("pow" if double and b == "float64 product" else b for b in names)
+
+
+def construct_samples(kind, n, count=None):
+    """(source, target) float32 samples of one K2 input kind; two patch rows of a covering by default (a handful of PSFs at every N)."""
+    shape = (n, 3 * n)
+    coords = [tuple(int(v) for v in c) for c in orc.calculate_covering(shape, n)]
+    if count is not None:
+        rows = -(-count // 4)
+        shape = (n * rows, 2 * n)
+        coords = [tuple(int(v) for v in c) for c in orc.calculate_covering(shape, n)][:count]
+        assert len(coords) == count
+    if kind in ("coma", "gauss"):
+        src, tgt = make_psfs(kind, coords, n, *shape)
+    elif kind == "broadband":
+        src = broadband_psfs(n, coords)
+        tgt = np.broadcast_to(orc.gaussian_psf(n, 0.9), src.shape)
+    else:
+        src = make_psfs("coma", coords, n, *shape)[0]
+        tgt = psf_cube(n, len(coords), n, kinds=PSF_KINDS[:2])[0]
+    return np.ascontiguousarray(src, np.float32), np.ascontiguousarray(tgt, np.float32)
+
+
+def construct_spectra(kind, n, dtype=np.complex64, count=None):
+    """The spectra a K2 case reads: scipy.fft.fft2 of the float32 samples (complex64, noise bins included), or of the same samples promoted
+    to float64 (complex128) for the double kernel."""
+    import scipy.fft
+
+    src, tgt = construct_samples(kind, n, count)
+    real = np.float32 if np.dtype(dtype) == np.complex64 else np.float64
+    s, t = scipy.fft.fft2(src.astype(real)), scipy.fft.fft2(tgt.astype(real))
+    assert s.dtype == t.dtype == np.dtype(dtype)
+    return s, t
+
+
+def transfer_terms(s, t, alpha, eps):
+    """(K, every real quantity orc.construct_transfer forms on the way), in the precision of ``s`` and ``t``: the oracle's expressions one by
+    one, so K is its K bit for bit (tests/test_construct_cases.py asserts that)."""
+    with np.errstate(all="ignore"):
+        sabs, tabs = abs(s), abs(t)
+        p1, p2, p3 = sabs ** (alpha - 1), sabs ** (alpha + 1), (eps * tabs) ** (alpha + 1)
+        num = s.conjugate() * p1
+        den = p2 + p3
+        quo = num / den
+        k = quo * t
+        return k, (sabs, tabs, p1, p2, p3, abs(num), den, abs(quo), abs(k))
+
+
+def in_range_bins(s, t, alpha, eps, bounds=RANGE_F32):
+    """(truth K, mask, zero mask).  mask: the bins where every quantity of the formula, evaluated in the precision of ``s`` / ``t`` (the
+    truth's), is finite and inside ``bounds`` - where the kernel's number format neither underflows nor overflows, so that a few ulp per
+    bin is owed.  zero mask: the bins where the truth is exactly 0 (S or T is) with the denominator in range and every other quantity
+    exactly 0 or in range - nothing underflows in the kernel's format on the way there either, so K has to be exactly 0.  (Where, say,
+    |S|**8 underflows in float32 beside a T of 0, the reference's own complex64 evaluation gives 0 / 0 = NaN.)"""
+    k, terms = transfer_terms(s, t, alpha, eps)
+    with np.errstate(invalid="ignore"):
+        mask = np.ones(s.shape, bool)
+        zero = (k == 0)
+        for i, q in enumerate(terms):
+            inside = np.isfinite(q) & (q >= bounds[0]) & (q <= bounds[1])
+            mask &= inside
+            zero &= inside if i == 6 else inside | (q == 0)
+    return k, mask, zero
+
+
+def bin_error(k, truth, mask) -> float:
+    """max over the bins of ``mask`` of |k - truth| / |truth|."""
+    d = np.abs(np.asarray(k)[mask].astype(truth.dtype) - truth[mask]) / np.abs(truth[mask])
+    return float(d.max()) if np.isfinite(d).all() else float("inf")
+
+
+class TransferCase:
+    """One K2 case: spectra, truth (orc.construct_transfer one precision up), in-range bins, yardstick (orc.construct_transfer evaluated by NumPy
+    in the kernel's precision on the same arrays, same bins)."""
+
+    def __init__(self, s, t, alpha, eps, wide=None, label=""):
+        self.s, self.t, self.alpha, self.eps, self.label = s, t, alpha, eps, label
+        double = s.dtype == np.complex128
+        wide = wide or (np.clongdouble if double else np.complex128)
+        self.truth, self.mask, self.zero = in_range_bins(s.astype(wide), np.broadcast_to(t, s.shape).astype(wide), alpha, eps, RANGE_F64 if double else RANGE_F32)
+        self.share = float(self.mask.mean())
+        with np.errstate(all="ignore"):
+            self.same_precision = orc.construct_transfer(s, np.broadcast_to(t, s.shape), alpha, eps)
+        assert self.same_precision.dtype == s.dtype
+        self.yardstick = bin_error(self.same_precision, self.truth, self.mask) if self.mask.any() else float("nan")
+
+    def decades(self) -> float:
+        mag = np.abs(self.truth[self.mask]).astype(np.float64)
+        return float(np.log10(mag.max() / mag.min()))
+
+    def ratio(self, k) -> float:
+        return bin_error(k, self.truth, self.mask) / self.yardstick
+
+    def check(self, k, margin=MARGIN, what=""):
+        """The per-bin bound on the in-range bins; exact zeros (in_range_bins); and the non-finite pattern where the truth itself is not finite."""
+        assert k.shape == self.truth.shape and k.dtype == self.s.dtype
+        ratio = self.ratio(k)
+        assert ratio <= margin, f"{what} {self.label}: per-bin error {ratio:.2f} x the same-precision yardstick ({self.yardstick:.2e}), margin {margin}"
+        assert np.array_equal(k[self.zero], np.zeros(int(self.zero.sum()), k.dtype)), f"{what} {self.label}: a bin that is exactly 0 is not"
+        for part in (np.real, np.imag):
+            bad = ~np.isfinite(part(self.truth))
+            got, want = part(k)[bad], part(self.same_precision)[bad]
+            assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what} {self.label}: NaN pattern where the truth is not finite"
+            inf = np.isinf(want)
+            assert np.array_equal(np.isinf(got), inf) and np.array_equal(got[inf], want[inf]), f"{what} {self.label}: Inf pattern"
+        return ratio
+
+
+# (N, shape, HDR seed) of the chain cases: shapes and seeds of tests/test_gpu_local_parity.py, so that the launch forms are the ones labelled there
+CHAIN_CASES = [(32, (130, 203), 32), (64, (333, 390), 64), (128, (520, 640), 129), (256, (520, 768), 272), (24, (100, 130), 24)]
+CHAIN_PARAMETERS = [(3.0, 0.1), (1.0, 0.05)]
+
+
+def chain_samples(n, shape):
+    """(corner list of the covering, broadband source samples, Gaussian 0.9 target samples), float32."""
+    coords = [tuple(int(v) for v in c) for c in orc.calculate_covering(shape, n)]
+    src = broadband_psfs(n, coords)
+    tgt = np.ascontiguousarray(np.broadcast_to(orc.gaussian_psf(n, 0.9).astype(np.float32), src.shape))
+    return coords, src, tgt
+
+
+def chain_transfer(src, tgt, alpha, eps, real):
+    """The reference's chain samples -> spectra -> K carried out in ``real`` (float64: the truth; float32: the yardstick, scipy.fft and NumPy
+    stay in single precision)."""
+    import scipy.fft
+
+    s, t = scipy.fft.fft2(src.astype(real)), scipy.fft.fft2(tgt.astype(real))
+    k = orc.construct_transfer(s, t, alpha, eps)
+    assert k.dtype == (np.complex128 if np.dtype(real) == np.float64 else np.complex64)
+    return s, k
+
+
+def chain_case(n, shape, seed, alpha, eps, image=None, min_share=0.10):
+    """LocalCase whose truth is the whole chain in float64 and whose yardstick is the whole chain in float32; also returns the float32 samples."""
+    coords, src, tgt = chain_samples(n, shape)
+    k64 = chain_transfer(src, tgt, alpha, eps, np.float64)[1]
+    k32 = chain_transfer(src, tgt, alpha, eps, np.float32)[1]
+    case = LocalCase(shape, n, seed, "symmetric", image=image, coords=coords, k=k64, yardstick_k=k32, min_share=min_share)
+    return case, src, tgt
