@@ -82,6 +82,12 @@ static int dispatch_v3(int N, F&& f) {
 }
 static bool has_v3(int N) { return N == 64 || N == 32 || N == 16; }
 
+// Patches one workgroup of the patch kernels processes (first generation: 64-thread workgroups shared by several small patches), and
+// the patches per XCD chunk that follow from it: an eighth of the plan's, in whole workgroups.  The processing order, the prefetch
+// lists and the fused tile order are cut by it (setup_lattice) and the kernels index by it (PatchParams::chunk).
+static constexpr int patch_teams(int N) { return N * N / 2 / 64 >= 64 ? 1 : 64 / (N * N / 2 / 64); }
+static int chunk_patches(int n_patches, int teams) { return ((n_patches + 7) / 8 + teams - 1) / teams * teams; }
+
 // Python's slice arithmetic for [start, stop) over a length-n axis (a negative bound wraps once): the window rule of the saturation fill
 static void py_slice(long start, long stop, long n, long* lo, long* hi) {
   if (start < 0) start = std::max(start + n, 0L);
@@ -251,7 +257,7 @@ struct rpsf_plan : PlanStream {
   std::vector<int32_t> h_coords;
   // overlap-add strategy: on regular half-overlap lattices direct accumulation through the XCD's L2 (three-stage
   // plans) or colour planes + plane sum (the small-patch plans); float atomics for any other corner list
-  int overlap_mode = 0;  // 0 auto, 1 atomics, 2 planes, 3 direct
+  int overlap_mode = 0;  // 0 auto, 1 atomics, 2 planes, 3 direct, 4 sweep
   int cu_count = 256;
   bool lattice = false;
   int host_bands_opt = -1, stream_group_opt = 0, stream_depth_opt = 0;  // rpsf_plan_set_option; -1 / 0: the library decides
@@ -358,9 +364,8 @@ static int setup_lattice(rpsf_plan* p) {
     }
   }
   p->lattice = ok;
-  const int t = p->N * p->N / 2 / 64, teams = t >= 64 ? 1 : 64 / t;
-  const int chunk = ((n + 7) / 8 + teams - 1) / teams * teams;  // as launch_patches cuts the order
-  p->patch.direct_ok = ok && teams == 1;
+  const int chunk = chunk_patches(n, patch_teams(p->N));
+  p->patch.direct_ok = ok && patch_teams(p->N) == 1;
   // ---- processing order: 8 chunks, one per XCD (workgroups b and b + 8 share one) ----
   p->h_order.resize(n);
   if (ok) {
@@ -549,11 +554,30 @@ static int dispatch_n(int N, F&& f) {
   }
 }
 
+// A compiled patch plan as the host sees it: the first generation (Gen2 = false: every N; N = 128, 256 only under the RPSF_V1 development
+// switch) or the second (N = 128, 256)
+template <class C, bool Gen2>
+struct PatchPlan {
+  using Cfg = C;
+  using L = std::conditional_t<Gen2, Launch2<C>, Launch<C>>;
+  static constexpr bool V2 = Gen2;
+  static constexpr int WG = L::WG, TEAMS = WG / C::T;  // (Launch<C>::TEAMS; the second generation has one patch per workgroup)
+  static constexpr size_t LDS_BYTES = L::LDS_BYTES;
+  static constexpr size_t PACK_PER_PATCH = C::G_PER_PATCH + (Gen2 ? C::GS_PER_PATCH : 0);  // elements one thread each of the pack kernels writes
+  static_assert(TEAMS == patch_teams(C::N), "setup_lattice cuts the chunks by patch_teams()");
+  // (functions, not members: only the generation's own templates are instantiated for C)
+  static constexpr auto kernel() { if constexpr (Gen2) return &patch_kernel2<C>; else return &patch_kernel<C>; }
+  static constexpr auto pack() { if constexpr (Gen2) return &pack_kernel2<C>; else return &pack_kernel<C>; }
+  static constexpr auto pack_spectra() { if constexpr (Gen2) return &pack_spectra_kernel2<C>; else return &pack_spectra_kernel<C>; }
+};
+
+// The patch plan a rpsf_plan runs (v2 = PatchPath::v2); dispatch_n: the first-generation configurations alone (psf_fft_impl runs their forward half for every N)
 template <class F>
-static int dispatch_v2(int N, F&& f) {
+static int dispatch_patch(bool v2, int N, F&& f) {
+  if (!v2) return dispatch_n(N, [&]<class C>() -> int { return f.template operator()<PatchPlan<C, false>>(); });
   switch (N) {
-    case 256: return f.template operator()<Cfg256v2>();
-    case 128: return f.template operator()<Cfg128v2>();
+    case 256: return f.template operator()<PatchPlan<Cfg256v2, true>>();
+    case 128: return f.template operator()<PatchPlan<Cfg128v2, true>>();
     default: return fail(RPSF_E_UNSUPPORTED, "no second-generation plan for this patch size");
   }
 }
@@ -569,12 +593,23 @@ static void host_tables(int N, std::vector<cf>& tw, std::vector<float>& win) {
   }
 }
 
-template <class C>
+// Slot table, twiddles and (d_win) window of a compiled plan; d_pairtab: the bin pairs of the special slots (first generation, two-stage plans) or
+// of the self-paired groups (second)
+template <class T>
 static int upload_tables(int device, DevBuf<uint16_t>& d_tab, DevBuf<cf>& d_tw, DevBuf<float>* d_win = nullptr, DevBuf<uint32_t>* d_pairtab = nullptr) {
+  using C = typename T::Cfg;
   std::vector<uint16_t> tab((size_t)C::T * C::NSLOT * 2);
-  build_slot_table<C>(tab.data());
-  std::vector<uint32_t> pt((size_t)C::PT_WORDS + 1);
-  if (d_pairtab && build_pair_table<C>(tab.data(), pt.data()) > C::NP) return fail(RPSF_E_STATE, "pair table overflow (internal)");
+  std::vector<uint32_t> pt;
+  if constexpr (T::V2) {
+    build_slot_table2<C>(tab.data());
+    pt.resize((size_t)C::ORBIT_ROUNDS * 64);
+    if (special_slots2<C>() > 64 || build_orbit_table2<C>(tab.data(), pt.data()) != C::NORBIT)
+      return fail(RPSF_E_STATE, "slot / orbit table inconsistent (internal)");
+  } else {
+    build_slot_table<C>(tab.data());
+    pt.resize((size_t)C::PT_WORDS + 1);
+    if (d_pairtab && build_pair_table<C>(tab.data(), pt.data()) > C::NP) return fail(RPSF_E_STATE, "pair table overflow (internal)");
+  }
   std::vector<cf> tw;
   std::vector<float> win;
   host_tables(C::N, tw, win);
@@ -583,24 +618,6 @@ static int upload_tables(int device, DevBuf<uint16_t>& d_tab, DevBuf<cf>& d_tw, 
   HIP_TRY(d_tab.upload(tab.data(), tab.size()));
   HIP_TRY(d_tw.upload(tw.data(), tw.size()));
   if (d_win) HIP_TRY(d_win->upload(win.data(), win.size()));
-  return RPSF_OK;
-}
-
-template <class C>
-static int upload_tables2(int device, DevBuf<uint16_t>& d_tab, DevBuf<cf>& d_tw, DevBuf<float>& d_win, DevBuf<uint32_t>& d_ot) {
-  std::vector<uint16_t> tab((size_t)C::T * C::NSLOT * 2);
-  build_slot_table2<C>(tab.data());
-  std::vector<uint32_t> ot((size_t)C::ORBIT_ROUNDS * 64);
-  if (special_slots2<C>() > 64 || build_orbit_table2<C>(tab.data(), ot.data()) != C::NORBIT)
-    return fail(RPSF_E_STATE, "slot / orbit table inconsistent (internal)");
-  std::vector<cf> tw;
-  std::vector<float> win;
-  host_tables(C::N, tw, win);
-  HIP_TRY(hipSetDevice(device));
-  HIP_TRY(d_ot.upload(ot.data(), ot.size()));
-  HIP_TRY(d_tab.upload(tab.data(), tab.size()));
-  HIP_TRY(d_tw.upload(tw.data(), tw.size()));
-  HIP_TRY(d_win.upload(win.data(), win.size()));
   return RPSF_OK;
 }
 
@@ -770,7 +787,6 @@ static int plan_create_impl(rpsf_plan** out, int device, int patch_size, int n_p
     HIP_TRY(hipMemset(p->patch.d_stamps, 0, sizeof(unsigned long long) * 16 * STAMP_WAVES * (size_t)n_patches));
 #endif
     p->patch.v2 = has_v2(N);
-    p->patch.no_fuse = false;  // (rpsf_plan_set_option RPSF_OPT_FUSE)
     // (measured, profiles/r02u, r02v: 32 of them are worth -1 % at 4096^2 and -2.5 % at 8192^2; 48 cost more patch time than they hide)
     p->patch.sum_first = -1;  // decided per launch (sum_first_for) unless the environment pins it
     if (const char* e = dev_env("RPSF_SUM_FIRST")) p->patch.sum_first = std::max(0, std::atoi(e)) / 8 * 8;
@@ -799,19 +815,11 @@ static int plan_create_impl(rpsf_plan** out, int device, int patch_size, int n_p
         p->patch.k_cached = (size_t)(parent ? parent->n_patches : n_patches) * Cfg128v2::G_PER_PATCH * sizeof(cf) <= ((size_t)96 << 20);
       }
     }
-    int rl = p->patch.v2 ? dispatch_v2(N, [&]<class C>() -> int {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_kernel2<C>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)Launch2<C>::LDS_BYTES));
+    int rl = dispatch_patch(p->patch.v2, N, [&]<class T>() -> int {
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(T::kernel()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::LDS_BYTES));
       int per_cu = 0;
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, patch_kernel2<C>, Launch2<C>::WG, Launch2<C>::LDS_BYTES));
-      p->patch.round_capacity = p->cu_count * std::max(1, per_cu);
-      return RPSF_OK;
-    }) : dispatch_n(N, [&]<class C>() -> int {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_kernel<C>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)Launch<C>::LDS_BYTES));
-      int per_cu = 0;
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, patch_kernel<C>, Launch<C>::WG, Launch<C>::LDS_BYTES));
-      p->patch.round_capacity = p->cu_count * std::max(1, per_cu) * Launch<C>::TEAMS;
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, T::kernel(), T::WG, T::LDS_BYTES));
+      p->patch.round_capacity = p->cu_count * std::max(1, per_cu) * T::TEAMS;
       return RPSF_OK;
     });
     if (rl != RPSF_OK) return rl;
@@ -836,25 +844,13 @@ static int plan_create_impl(rpsf_plan** out, int device, int patch_size, int n_p
       p->overlap_mode = parent->overlap_mode, p->patch.stagger_us = parent->patch.stagger_us;
       return RPSF_OK;
     }
-    if (p->patch.v2)
-      return dispatch_v2(N, [&]<class C>() -> int {
-        int r2 = upload_tables2<C>(device, p->patch.d_tab, p->patch.d_tw, p->d_win, p->patch.d_pairtab);
-        if (r2 != RPSF_OK) return r2;
-        p->patch.g_elems = (size_t)C::G_PER_PATCH * n_patches;
-        p->patch.gs_elems = (size_t)C::GS_PER_PATCH * n_patches;
-        HIP_TRY(p->patch.d_g.alloc(p->patch.g_elems));
-        HIP_TRY(p->patch.d_gs.alloc(p->patch.gs_elems + 1));
-        return RPSF_OK;
-      });
-    return dispatch_n(N, [&]<class C>() -> int {
-      int r2 = upload_tables<C>(device, p->patch.d_tab, p->patch.d_tw, &p->d_win, &p->patch.d_pairtab);
+    return dispatch_patch(p->patch.v2, N, [&]<class T>() -> int {
+      int r2 = upload_tables<T>(device, p->patch.d_tab, p->patch.d_tw, &p->d_win, &p->patch.d_pairtab);
       if (r2 != RPSF_OK) return r2;
-      p->patch.g_elems = (size_t)C::G_PER_PATCH * n_patches;
-      p->patch.gs_elems = (size_t)C::GS_PER_PATCH * n_patches;
+      p->patch.g_elems = (size_t)T::Cfg::G_PER_PATCH * n_patches;
+      p->patch.gs_elems = (size_t)T::Cfg::GS_PER_PATCH * n_patches;
       HIP_TRY(p->patch.d_g.alloc(p->patch.g_elems));
       HIP_TRY(p->patch.d_gs.alloc(p->patch.gs_elems + 1));
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_kernel<C>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)Launch<C>::LDS_BYTES));
       return RPSF_OK;
     });
   };
@@ -915,21 +911,13 @@ static int install_transfer(rpsf_plan* p, const KSource& src, int first, int cou
         HIP_TRY(hipGetLastError());
         return RPSF_OK;
       });
-    if (rc == RPSF_OK && p->patch.v2)
-      rc = dispatch_v2(p->N, [&]<class C>() -> int {
+    if (rc == RPSF_OK)
+      rc = dispatch_patch(p->patch.v2, p->N, [&]<class T>() -> int {
+        using C = typename T::Cfg;
         cf *g = p->patch.d_g + (size_t)first * C::G_PER_PATCH, *gs = p->patch.d_gs + (size_t)first * C::GS_PER_PATCH;
-        const dim3 gr = grid(((size_t)C::G_PER_PATCH + C::GS_PER_PATCH) * count);
-        if (k) pack_kernel2<C><<<gr, dim3(256), 0, p->stream>>>(k, count, p->patch.d_tab, p->patch.d_pairtab, g, gs);
-        else pack_spectra_kernel2<C><<<gr, dim3(256), 0, p->stream>>>(s, t, alpha, epsilon, count, p->patch.d_tab, p->patch.d_pairtab, g, gs);
-        HIP_TRY(hipGetLastError());
-        return RPSF_OK;
-      });
-    else if (rc == RPSF_OK)
-      rc = dispatch_n(p->N, [&]<class C>() -> int {
-        cf *g = p->patch.d_g + (size_t)first * C::G_PER_PATCH, *gs = p->patch.d_gs + (size_t)first * C::GS_PER_PATCH;
-        const dim3 gr = grid((size_t)C::G_PER_PATCH * count);
-        if (k) pack_kernel<C><<<gr, dim3(256), 0, p->stream>>>(k, count, p->patch.d_tab, p->patch.d_pairtab, g, gs);
-        else pack_spectra_kernel<C><<<gr, dim3(256), 0, p->stream>>>(s, t, alpha, epsilon, count, p->patch.d_tab, p->patch.d_pairtab, g, gs);
+        const dim3 gr = grid(T::PACK_PER_PATCH * count);
+        if (k) T::pack()<<<gr, dim3(256), 0, p->stream>>>(k, count, p->patch.d_tab, p->patch.d_pairtab, g, gs);
+        else T::pack_spectra()<<<gr, dim3(256), 0, p->stream>>>(s, t, alpha, epsilon, count, p->patch.d_tab, p->patch.d_pairtab, g, gs);
         HIP_TRY(hipGetLastError());
         return RPSF_OK;
       });
@@ -1008,25 +996,41 @@ static int check_geometry(const rpsf_plan* p, const rpsf_geometry* g) {
   return RPSF_OK;
 }
 
-static SumParams make_sum_params(const rpsf_plan* p, float* d_out, const rpsf_geometry& g, int row_begin, int row_end) {
-  SumParams sp;
-  sp.planes = p->patch.d_planes, sp.plane_stride = p->patch.planes_floats, sp.out = d_out;
-  sp.rows = row_end - row_begin, sp.row_begin = row_begin;
-  sp.W = g.width, sp.ld_planes = g.width, sp.ld_out = g.ld_out, sp.row0 = g.out_row0;
-  sp.lat_r0 = p->lat_r0 + g.origin_row, sp.lat_c0 = p->lat_c0 + g.origin_col;
-  sp.half_shift = 0;
-  while ((1 << (sp.half_shift + 1)) < p->N) ++sp.half_shift;
-  sp.nti = p->nti, sp.ntj = p->ntj, sp.cover = p->d_cover;
-  sp.planes_frame_floats = 4 * p->patch.planes_floats, sp.out_frame_floats = 0;
-  return sp;
-}
-
 // A batch of frames that share the plan's transfer kernel: frame f at image + f*im_stride, out + f*out_stride (floats)
 struct Batch {
   int frames = 1;
   size_t im_stride = 0, out_stride = 0;
 };
 
+// Whether the lattice tiles cover the resident output window.  The plane sums, the direct mode's fix-up and the sweep kernel write lattice tiles
+// only: pixels of the window that no tile covers are written by nobody (the reference leaves them zero), so the window is cleared first.
+static bool lattice_covers_window(const rpsf_plan* p, const rpsf_geometry& g) {
+  const int half = p->N / 2;
+  const long r0 = (long)p->lat_r0 + g.origin_row, c0 = (long)p->lat_c0 + g.origin_col;
+  return r0 <= g.out_row0 && r0 + (long)p->nti * half >= (long)g.out_row0 + g.out_rows && c0 <= 0 && c0 + (long)p->ntj * half >= g.width;
+}
+
+// Zeroes the resident output window of every frame
+static int clear_window(float* d_out, const rpsf_geometry& g, Batch b, hipStream_t st) {
+  for (int f = 0; f < b.frames; ++f)
+    HIP_TRY(hipMemset2DAsync(d_out + (size_t)f * b.out_stride, (size_t)g.ld_out * sizeof(float), 0, (size_t)g.width * sizeof(float), g.out_rows, st));
+  return RPSF_OK;
+}
+
+// Kernels that take the frames of a batch along grid.y: launch(first frame, frames) for [0, frames) in slices within the grid.y limit
+template <class F>
+static void for_frame_slices(int frames, F&& launch) {
+  for (int f0 = 0; f0 < frames; f0 += 65535) launch(f0, (unsigned)std::min(65535, frames - f0));
+}
+
+// The planes, the output window and the lattice origin as TileSum, SumParams and FixParams all hold them
+template <class P>
+static void fill_plane_sum(P& s, const rpsf_plan* p, float* d_out, const rpsf_geometry& g, Batch b) {
+  s.planes = p->patch.d_planes, s.plane_stride = p->patch.planes_floats, s.planes_frame_floats = 4 * p->patch.planes_floats, s.ld_planes = g.width;
+  s.out = d_out, s.ld_out = g.ld_out, s.out_frame_floats = b.out_stride;
+  s.rows = g.out_rows, s.W = g.width, s.row0 = g.out_row0;
+  s.lat_r0 = p->lat_r0 + g.origin_row, s.lat_c0 = p->lat_c0 + g.origin_col, s.ntj = p->ntj;
+}
 
 // Summing workgroups that run beside the patches from the start of a fused launch (multiple of 8: one per XCD), by the
 // amount of work in the launch.  256-pixel plan (512-thread workgroups, one per CU): r02y, a band of 520 patches 130-138 us
@@ -1054,184 +1058,210 @@ static bool hot_geometry(const rpsf_plan* p, const float* d_img, const rpsf_geom
          p->lattice && ((long)p->lat_c0 + g.origin_col) % 4 == 0 && p->patch.planes_floats % 4 == 0;
 }
 
+// What the patch launch of one apply is: decided by patch_launch_for from the plan as it stands, committed by launch_apply (the queue positions the
+// launch takes) and turned into PatchParams and a kernel by launch_patches.
+struct PatchLaunch {
+  // first generation / second generation, patches only / fused: summing workgroups behind (and sum_first beside) the patches / persistent: patch
+  // workgroups that draw their slots from per-XCD queues and end as summing ones
+  enum Form { GEN1, GEN2, FUSED, PERSISTENT } form;
+  enum Variant { PLAIN, K_CACHED, K_CACHED_PLANES_NT } variant;  // persistent: PersistentKernel2's fn / fn_k_cached / fn_k_cached_planes_nt
+  unsigned grid;      // workgroups
+  int chunk;          // patches per XCD chunk
+  int patch_blocks;   // second generation: workgroups [sum_first, sum_first + patch_blocks) of a launch that is not persistent process patches
+  int stagger_ticks, stagger_blocks;
+  int sum_first, frame_major, plane_nt;  // fused and persistent
+  int rows, head_patches, prefetch;      // persistent: patch workgroups per XCD, ...
+  uint32_t xq_base[8], xq_draws[8];      // persistent: where this launch's draws from the slot queue of each XCD start, and how many it makes
+  uint32_t sum_queue_base, sum_queue_draws;  // fused and persistent: the same for the tile queue
+};
+
+// A patch launch is one grid of at most 2^31 - 1 workgroups: one per frame and patch_teams() patches of each chunk
+static bool patch_launch_too_large(const rpsf_plan* p, int frames) {
+  const int teams = patch_teams(p->N);
+  return (size_t)8 * (chunk_patches(p->n_patches, teams) / teams) * frames > 0x7fffffffu;
+}
+
 // fused: the plane sum runs in this launch (see PatchPath::d_tile_done)
-static int launch_patches(rpsf_plan* p, const float* d_img, float* d_out, const rpsf_geometry& g, OverlapKind kind,
-                          hipStream_t st, Batch b = Batch(), bool fused = false) {
-  auto fill = [&](PatchParams& pp, int teams) {
-    const int count = p->n_patches;
-    pp.im = ImageView{d_img, g.height, g.width, g.ld_image, g.pad_mode, g.pad_value, g.image_row0, g.image_rows};
-    if (kind != OV_ATOMIC)
-      pp.ov = OutView{p->patch.d_planes, g.height, g.width, g.width, g.out_row0, g.out_rows, p->patch.planes_floats, p->patch.d_sink};
-    else
-      pp.ov = OutView{d_out, g.height, g.width, g.ld_out, g.out_row0, g.out_rows, 0, p->patch.d_sink};
-    pp.origin_row = g.origin_row, pp.origin_col = g.origin_col;
-    pp.desc = p->d_desc, pp.n_patches = count, pp.seq_base = 0;
-    const rpsf_plan* o = owner(p);
-    pp.tab = o->patch.d_tab, pp.pairtab = o->patch.d_pairtab, pp.tw = o->patch.d_tw, pp.win = o->d_win, pp.g = o->patch.d_g, pp.gs = o->patch.d_gs;
-    pp.stamps = p->patch.d_stamps;
-    pp.chunk = ((count + 7) / 8 + teams - 1) / teams * teams;  // patches per XCD, whole workgroups
-    pp.stagger_ticks = std::max(0, p->patch.stagger_us) * 100;
-    pp.n_frames = b.frames, pp.im_frame_floats = b.im_stride;
-    pp.ov_frame_floats = kind != OV_ATOMIC ? 4 * p->patch.planes_floats : b.out_stride;
-    pp.dv = OutView{nullptr, 0, 0, 0, 0, 0, 0, nullptr};
-    if (kind == OV_DIRECT) {
-      pp.dv = OutView{d_out, g.height, g.width, g.ld_out, g.out_row0, g.out_rows, 0, p->patch.d_sink};
-      pp.dv_frame_floats = b.out_stride;
-      pp.quads = p->patch.d_quads, pp.flags = p->patch.d_flags, pp.dyn_side = p->patch.d_dyn, pp.chunk_xcc = p->patch.d_chunk_xcc;
-      pp.flag_epoch = p->patch.epoch, pp.n_tiles = (uint32_t)(p->nti * p->ntj), pp.orphan_mod = p->patch.orphan_mod;
-    }
-  };
-  if (p->patch.v2)
-    return dispatch_v2(p->N, [&]<class C>() -> int {
-      PatchParams pp{};
-      fill(pp, 1);
-      pp.stagger_blocks = p->patch.round_capacity;
-      size_t blocks = (size_t)8 * pp.chunk * b.frames;
-      if (blocks > 0x7fffffffu) return fail(RPSF_E_BADARG, "batch too large for one launch");
-      pp.slot0 = 0, pp.patch_blocks = (int)blocks;
-      if (fused) {
-        const int n_tiles = p->nti * p->ntj;
-        pp.tile_done = p->patch.d_tile_done, pp.quads = p->patch.d_quads, pp.n_tiles = (uint32_t)n_tiles;
-        TileSum& ts = pp.ts;
-        ts.planes = p->patch.d_planes, ts.plane_stride = p->patch.planes_floats, ts.ld_planes = g.width;
-        ts.out = d_out, ts.ld_out = g.ld_out;
-        ts.rows = g.out_rows, ts.W = g.width, ts.row0 = g.out_row0;
-        ts.lat_r0 = p->lat_r0 + g.origin_row, ts.lat_c0 = p->lat_c0 + g.origin_col, ts.half = p->N / 2, ts.ntj = p->ntj;
-        ts.cover = p->d_cover, ts.tiles = p->patch.d_sum_order, ts.count = n_tiles * b.frames;
-        ts.done = p->patch.d_tile_done, ts.epoch = p->patch.done_epoch;
-        ts.n_frames = b.frames, ts.n_tiles = (uint32_t)n_tiles, ts.n_tiles_listed = (uint32_t)n_tiles;
-        // Persistent batches whose planes would not fit the Infinity Cache side by side run frame after frame in one launch: every
-        // frame keeps the cache behaviour of a single apply, and the next frame's patches take the CUs the previous one's last
-        // patches leave idle (RPSF_FRAME_MAJOR=0/1 overrides).
-        bool frame_major = std::is_same_v<C, Cfg256v2> && p->patch.persist && b.frames > 1 && p->n_patches >= 1024 &&
-                           16.0 * (double)p->patch.planes_floats * b.frames > 256.0 * 1048576.0;  // (8 x 2048^2: 0.056 ms per frame side by side, 0.061 in turn)
-        if (const char* e = dev_env("RPSF_FRAME_MAJOR"))  // development sweeps: 0 = never, 2 = any persistent batch
-          frame_major = std::atoi(e) == 2 ? (p->patch.persist && b.frames > 1) : (frame_major && std::atoi(e) != 0);
-        pp.frame_major = ts.frame_major = frame_major ? 1 : 0;
-        // Frames of a batch side by side keep the planes of ALL of them live at once (8 x 2048^2: 537 MB against a 256 MiB Infinity Cache): the 128-pixel
-        // kernels then store them with the streaming hint - 0.3156 -> 0.3009 ms (-4.7 %); a single frame loses 8 % that way, and so does the 256-pixel
-        // plan at either size (profiles/r04bd).  RPSF_PLANE_NT=0/1 overrides (development sweeps).
-        // (needs the plain-load form of K - a batch shares it - and planes well beyond the Infinity Cache: 4 x 2048^2, 268 MB, still loses 3 %; 6 x, 403 MB, gains 5 %)
-        pp.plane_nt = std::is_same_v<C, Cfg128v2> && p->patch.k_cached && b.frames > 1 && !frame_major && 16.0 * (double)p->patch.planes_floats * b.frames > 300.0 * 1048576.0;
-        if (p->patch.plane_nt_opt >= 0) pp.plane_nt = p->patch.plane_nt_opt != 0 && std::is_same_v<C, Cfg128v2> && p->patch.k_cached;  // (RPSF_OPT_PLANE_NT)
-        const int tune_frames = b.frames;  // (the settings of a single apply measured worse here: 0.203 vs 0.186 ms per frame at 8 x 4096^2)
-        pp.sum_first = sum_first_for(p, tune_frames);
-        ts.planes_frame_floats = 4 * p->patch.planes_floats, ts.out_frame_floats = b.out_stride;
-        int nsum = std::max(8, std::min(ts.count, p->patch.round_capacity));  // at the tail: as many summing workgroups as the chip holds
-        ts.queue = p->patch.d_sum_queue, ts.queue_base = p->patch.sum_queue_base;
-        {
-          // persistent form: as many patch workgroups as the chip holds beside the summing ones; each works through the slots
-          // of its XCD's chunk and ends as a summing workgroup itself (no workgroups behind the patches).
-          // FORWARD PROGRESS.  HIP promises neither that a grid is resident as a whole nor an order of dispatch, and other launches
-          // (a second plan on another stream, RCCL's kernels) may hold CUs.  What this launch needs: (1) every patch slot is drawn
-          // from its chunk's queue - none is tied to a particular workgroup - so the slots of chunk x are worked off by whichever
-          // workgroups with blockIdx % 8 == x are resident, and a workgroup turns to summing only when its chunk's queue is empty,
-          // i.e. when every remaining patch of the chunk is in the hands of a resident workgroup that does not wait for anything;
-          // (2) summing workgroups wait (poll + s_sleep) only for tiles whose patches are drawn or will be drawn by (1).  So the
-          // launch completes as soon as, for every chunk, ONE patch workgroup gets a CU: in dispatch order the first sum_first + 8
-          // workgroups.  The only workgroups that hold a CU without progress of their own are the sum_first head summing ones (<= 32 of
-          // 512 threads for the 256-pixel plan; up to 160 of 128 threads - four to a CU, 40 CUs' worth - for the 128-pixel plan from 4096
-          // patch-frames on, sum_first_for); concurrent persistent launches therefore cannot starve one another unless their head summing
-          // workgroups alone fill the chip (tests: test_two_persistent_plans_on_two_streams, 256- and 128-pixel plans).
-          // (queue positions of an XCD: chunk slots x frames, the frames of a slot side by side)
-          const int rows = std::min(pp.chunk * b.frames, std::max(1, (p->patch.round_capacity - pp.sum_first - p->patch.reserved_cus) / 8));
-          if (p->patch.persist && rows > 0 && hot_geometry(p, d_img, g, b.im_stride)) {
-            pp.persist = rows, pp.xq = p->patch.d_xq;
-            // a head summing workgroup would idle through the first patch period (no tile is complete before that): it computes one patch
-            // of its XCD's chunk first (RPSF_HEAD_PATCHES=0: off)
-            pp.head_patches = p->patch.head_patches;
-            pp.prefetch = p->patch.prefetch && p->patch.d_prefetch_tiles ? 1 : 0;
-            pp.prefetch_tiles = p->patch.d_prefetch_tiles;
-            for (int x = 0; x < 9; ++x) pp.prefetch_first[x] = p->patch.prefetch_first[x];
-            // persistent workgroups keep the phase they start with: holding the resident ones back by up to 10 us spreads the
-            // store bursts of the chip over the patch period (profiles/r02ai, r02ak: -2..3 % from four rounds of patches on; with the
-            // plane stores kept in the Infinity Cache, r02av: 0.210 / 0.208 / 0.193 / 0.190 / 0.189 / 0.191 / 0.195 ms at 0 / 5 / 8 / 10 / 12 / 15 / 20 us)
-            // (and smaller launches too: 2048^2 0.0811 -> 0.0787 ms, 3072^2 0.138 -> 0.131 ms, a band of 520 patches 128 -> 121 us)
-            // (long launches take more: 8192^2 0.736 / 0.726 / 0.714 / 0.703 / 0.698 / 0.719 ms at 6 / 12 / 18 / 24 / 30 / 36 us)
-            // (round 4, seven-barrier pass, profiles/r04az: 4096^2 at 12 / 16 / 20 us - the repeated frame 0.1835 / 0.1843 / 0.1880 ms, a NEW frame every step
-            // 0.2019 / 0.1962 / 0.1933: 16 us from 1024 patches of the 256-pixel plan on; 8192^2 0.714 / 0.688 / 0.691 / 0.690 at 12 / 16 / 20 / 24)
-            if (p->patch.stagger_us < 0 && (long)p->n_patches * tune_frames >= 256) {
-              const long work = (long)p->n_patches * tune_frames;
-              pp.stagger_ticks = work >= 2048 ? 2400 : (work >= 1024 && std::is_same_v<C, Cfg256v2>) ? 1600 : 1200;
-              // The 128-pixel plan - four workgroups per CU, out of step with one another anyway - is better off WITHOUT it since round 4 (profiles/r04ba):
-              // 2048^2 0.0655 -> 0.0603 ms (-8 %), 3072^2 -6 %, 8 x 2048^2 0.3252 -> 0.3198; only single frames of 4096^2 and more still take a short one
-              // (6 us: -1 ... -3 %).
-              if constexpr (std::is_same_v<C, Cfg128v2>) pp.stagger_ticks = tune_frames == 1 && p->n_patches >= 4096 ? 600 : 0;
-            }
-            for (int x = 0; x < 8; ++x) {
-              pp.xq_base[x] = p->patch.xq_base[x];
-              // draws of this launch: one per slot and frame, plus the one past the end that tells each of the chunk's workgroups to stop
-              // (the first sum_first / 8 positions of a chunk go to the head summing workgroups without a draw when those compute a patch first)
-              const int slots_x = std::min(pp.chunk, std::max(0, p->n_patches - x * pp.chunk)) * b.frames;
-              p->patch.xq_base[x] += (uint32_t)(std::max(0, slots_x - (pp.head_patches ? pp.sum_first / 8 : 0)) + rows);
-            }
-            const int wgs = pp.sum_first + 8 * rows;
-            p->patch.sum_queue_base += (uint32_t)(ts.count + wgs);  // every workgroup draws one position past the end
-            if (p->patch.k_cached && pp.plane_nt)
-              PersistentKernel2<C>::fn_k_cached_planes_nt<<<dim3((unsigned)wgs), dim3(Launch2<C>::WG), Launch2<C>::LDS_BYTES, st>>>(pp);
-            else if (p->patch.k_cached)
-              PersistentKernel2<C>::fn_k_cached<<<dim3((unsigned)wgs), dim3(Launch2<C>::WG), Launch2<C>::LDS_BYTES, st>>>(pp);
-            else
-              PersistentKernel2<C>::fn<<<dim3((unsigned)wgs), dim3(Launch2<C>::WG), Launch2<C>::LDS_BYTES, st>>>(pp);
-            HIP_TRY(hipGetLastError());
-            return RPSF_OK;
-          }
-        }
-        nsum += pp.sum_first;
-        p->patch.sum_queue_base += (uint32_t)(ts.count + nsum);  // every workgroup draws one position past the end
-        blocks += (size_t)nsum;
+template <class T>
+static PatchLaunch patch_launch_for(const rpsf_plan* p, const float* d_img, const rpsf_geometry& g, Batch b, bool fused) {
+  constexpr bool N256 = T::V2 && T::Cfg::N == 256, N128 = T::V2 && T::Cfg::N == 128;
+  PatchLaunch L{};
+  L.chunk = chunk_patches(p->n_patches, T::TEAMS);
+  L.stagger_ticks = std::max(0, p->patch.stagger_us) * 100;
+  L.grid = (unsigned)((size_t)8 * (L.chunk / T::TEAMS) * b.frames);  // (patch_launch_too_large: it fits)
+  L.form = T::V2 ? PatchLaunch::GEN2 : PatchLaunch::GEN1;
+  L.stagger_blocks = T::V2 ? p->patch.round_capacity : p->cu_count * std::max(1, 512 / T::WG);
+  L.patch_blocks = T::V2 ? (int)L.grid : 0;  // (the first-generation kernel does not read it)
+  if (!fused) return L;                      // (fused: second-generation plans only, launch_apply)
+  const int count = p->nti * p->ntj * b.frames;  // positions of the tile list
+  // Persistent batches whose planes would not fit the Infinity Cache side by side run frame after frame in one launch: every
+  // frame keeps the cache behaviour of a single apply, and the next frame's patches take the CUs the previous one's last
+  // patches leave idle (RPSF_FRAME_MAJOR=0/1 overrides).
+  bool frame_major = N256 && p->patch.persist && b.frames > 1 && p->n_patches >= 1024 &&
+                     16.0 * (double)p->patch.planes_floats * b.frames > 256.0 * 1048576.0;  // (8 x 2048^2: 0.056 ms per frame side by side, 0.061 in turn)
+  if (const char* e = dev_env("RPSF_FRAME_MAJOR"))  // development sweeps: 0 = never, 2 = any persistent batch
+    frame_major = std::atoi(e) == 2 ? (p->patch.persist && b.frames > 1) : (frame_major && std::atoi(e) != 0);
+  L.frame_major = frame_major ? 1 : 0;
+  // Frames of a batch side by side keep the planes of ALL of them live at once (8 x 2048^2: 537 MB against a 256 MiB Infinity Cache): the 128-pixel
+  // kernels then store them with the streaming hint - 0.3156 -> 0.3009 ms (-4.7 %); a single frame loses 8 % that way, and so does the 256-pixel
+  // plan at either size (profiles/r04bd).  RPSF_PLANE_NT=0/1 overrides (development sweeps).
+  // (needs the plain-load form of K - a batch shares it - and planes well beyond the Infinity Cache: 4 x 2048^2, 268 MB, still loses 3 %; 6 x, 403 MB, gains 5 %)
+  L.plane_nt = N128 && p->patch.k_cached && b.frames > 1 && !frame_major && 16.0 * (double)p->patch.planes_floats * b.frames > 300.0 * 1048576.0;
+  if (p->patch.plane_nt_opt >= 0) L.plane_nt = p->patch.plane_nt_opt != 0 && N128 && p->patch.k_cached;  // (RPSF_OPT_PLANE_NT)
+  const int tune_frames = b.frames;  // (the settings of a single apply measured worse here: 0.203 vs 0.186 ms per frame at 8 x 4096^2)
+  L.sum_first = sum_first_for(p, tune_frames);
+  L.sum_queue_base = p->patch.sum_queue_base;
+  // persistent form: as many patch workgroups as the chip holds beside the summing ones; each works through the slots
+  // of its XCD's chunk and ends as a summing workgroup itself (no workgroups behind the patches).
+  // FORWARD PROGRESS.  HIP promises neither that a grid is resident as a whole nor an order of dispatch, and other launches
+  // (a second plan on another stream, RCCL's kernels) may hold CUs.  What this launch needs: (1) every patch slot is drawn
+  // from its chunk's queue - none is tied to a particular workgroup - so the slots of chunk x are worked off by whichever
+  // workgroups with blockIdx % 8 == x are resident, and a workgroup turns to summing only when its chunk's queue is empty,
+  // i.e. when every remaining patch of the chunk is in the hands of a resident workgroup that does not wait for anything;
+  // (2) summing workgroups wait (poll + s_sleep) only for tiles whose patches are drawn or will be drawn by (1).  So the
+  // launch completes as soon as, for every chunk, ONE patch workgroup gets a CU: in dispatch order the first sum_first + 8
+  // workgroups.  The only workgroups that hold a CU without progress of their own are the sum_first head summing ones (<= 32 of
+  // 512 threads for the 256-pixel plan; up to 160 of 128 threads - four to a CU, 40 CUs' worth - for the 128-pixel plan from 4096
+  // patch-frames on, sum_first_for); concurrent persistent launches therefore cannot starve one another unless their head summing
+  // workgroups alone fill the chip (tests: test_two_persistent_plans_on_two_streams, 256- and 128-pixel plans).
+  // (queue positions of an XCD: chunk slots x frames, the frames of a slot side by side)
+  const int rows = std::min(L.chunk * b.frames, std::max(1, (p->patch.round_capacity - L.sum_first - p->patch.reserved_cus) / 8));
+  if (!(p->patch.persist && rows > 0 && hot_geometry(p, d_img, g, b.im_stride))) {
+    L.form = PatchLaunch::FUSED;
+    const int nsum = std::max(8, std::min(count, p->patch.round_capacity)) + L.sum_first;  // at the tail: as many summing workgroups as the chip holds
+    L.sum_queue_draws = (uint32_t)(count + nsum);  // every workgroup draws one position past the end
+    L.grid += (unsigned)nsum;
+    return L;
+  }
+  L.form = PatchLaunch::PERSISTENT, L.rows = rows;
+  L.variant = !p->patch.k_cached ? PatchLaunch::PLAIN : L.plane_nt ? PatchLaunch::K_CACHED_PLANES_NT : PatchLaunch::K_CACHED;
+  // a head summing workgroup would idle through the first patch period (no tile is complete before that): it computes one patch
+  // of its XCD's chunk first (RPSF_HEAD_PATCHES=0: off)
+  L.head_patches = p->patch.head_patches;
+  L.prefetch = p->patch.prefetch && p->patch.d_prefetch_tiles ? 1 : 0;
+  // persistent workgroups keep the phase they start with: holding the resident ones back by up to 10 us spreads the
+  // store bursts of the chip over the patch period (profiles/r02ai, r02ak: -2..3 % from four rounds of patches on; with the
+  // plane stores kept in the Infinity Cache, r02av: 0.210 / 0.208 / 0.193 / 0.190 / 0.189 / 0.191 / 0.195 ms at 0 / 5 / 8 / 10 / 12 / 15 / 20 us)
+  // (and smaller launches too: 2048^2 0.0811 -> 0.0787 ms, 3072^2 0.138 -> 0.131 ms, a band of 520 patches 128 -> 121 us)
+  // (long launches take more: 8192^2 0.736 / 0.726 / 0.714 / 0.703 / 0.698 / 0.719 ms at 6 / 12 / 18 / 24 / 30 / 36 us)
+  // (round 4, seven-barrier pass, profiles/r04az: 4096^2 at 12 / 16 / 20 us - the repeated frame 0.1835 / 0.1843 / 0.1880 ms, a NEW frame every step
+  // 0.2019 / 0.1962 / 0.1933: 16 us from 1024 patches of the 256-pixel plan on; 8192^2 0.714 / 0.688 / 0.691 / 0.690 at 12 / 16 / 20 / 24)
+  if (p->patch.stagger_us < 0 && (long)p->n_patches * tune_frames >= 256) {
+    const long work = (long)p->n_patches * tune_frames;
+    L.stagger_ticks = work >= 2048 ? 2400 : (work >= 1024 && N256) ? 1600 : 1200;
+    // The 128-pixel plan - four workgroups per CU, out of step with one another anyway - is better off WITHOUT it since round 4 (profiles/r04ba):
+    // 2048^2 0.0655 -> 0.0603 ms (-8 %), 3072^2 -6 %, 8 x 2048^2 0.3252 -> 0.3198; only single frames of 4096^2 and more still take a short one
+    // (6 us: -1 ... -3 %).
+    if (N128) L.stagger_ticks = tune_frames == 1 && p->n_patches >= 4096 ? 600 : 0;
+  }
+  for (int x = 0; x < 8; ++x) {
+    L.xq_base[x] = p->patch.xq_base[x];
+    // draws of this launch: one per slot and frame, plus the one past the end that tells each of the chunk's workgroups to stop
+    // (the first sum_first / 8 positions of a chunk go to the head summing workgroups without a draw when those compute a patch first)
+    const int slots_x = std::min(L.chunk, std::max(0, p->n_patches - x * L.chunk)) * b.frames;
+    L.xq_draws[x] = (uint32_t)(std::max(0, slots_x - (L.head_patches ? L.sum_first / 8 : 0)) + rows);
+  }
+  const int wgs = L.sum_first + 8 * rows;
+  L.sum_queue_draws = (uint32_t)(count + wgs);  // every workgroup draws one position past the end
+  L.grid = (unsigned)wgs;
+  return L;
+}
+
+static PatchParams patch_params(const rpsf_plan* p, const PatchLaunch& L, const float* d_img, float* d_out, const rpsf_geometry& g, OverlapKind kind,
+                                Batch b) {
+  PatchParams pp{};
+  pp.im = ImageView{d_img, g.height, g.width, g.ld_image, g.pad_mode, g.pad_value, g.image_row0, g.image_rows};
+  if (kind != OV_ATOMIC)
+    pp.ov = OutView{p->patch.d_planes, g.height, g.width, g.width, g.out_row0, g.out_rows, p->patch.planes_floats, p->patch.d_sink};
+  else
+    pp.ov = OutView{d_out, g.height, g.width, g.ld_out, g.out_row0, g.out_rows, 0, p->patch.d_sink};
+  pp.origin_row = g.origin_row, pp.origin_col = g.origin_col;
+  pp.desc = p->d_desc, pp.n_patches = p->n_patches, pp.seq_base = 0;
+  const rpsf_plan* o = owner(p);
+  pp.tab = o->patch.d_tab, pp.pairtab = o->patch.d_pairtab, pp.tw = o->patch.d_tw, pp.win = o->d_win, pp.g = o->patch.d_g, pp.gs = o->patch.d_gs;
+  pp.stamps = p->patch.d_stamps;
+  pp.chunk = L.chunk, pp.slot0 = 0, pp.patch_blocks = L.patch_blocks;
+  pp.stagger_ticks = L.stagger_ticks, pp.stagger_blocks = L.stagger_blocks;
+  pp.n_frames = b.frames, pp.im_frame_floats = b.im_stride;
+  pp.ov_frame_floats = kind != OV_ATOMIC ? 4 * p->patch.planes_floats : b.out_stride;
+  pp.dv = OutView{nullptr, 0, 0, 0, 0, 0, 0, nullptr};
+  if (kind == OV_DIRECT) {
+    pp.dv = OutView{d_out, g.height, g.width, g.ld_out, g.out_row0, g.out_rows, 0, p->patch.d_sink};
+    pp.dv_frame_floats = b.out_stride;
+    pp.quads = p->patch.d_quads, pp.flags = p->patch.d_flags, pp.dyn_side = p->patch.d_dyn, pp.chunk_xcc = p->patch.d_chunk_xcc;
+    pp.flag_epoch = p->patch.epoch, pp.n_tiles = (uint32_t)(p->nti * p->ntj), pp.orphan_mod = p->patch.orphan_mod;
+  }
+  if (L.form != PatchLaunch::FUSED && L.form != PatchLaunch::PERSISTENT) return pp;
+  const int n_tiles = p->nti * p->ntj;
+  pp.tile_done = p->patch.d_tile_done, pp.quads = p->patch.d_quads, pp.n_tiles = (uint32_t)n_tiles;
+  pp.sum_first = L.sum_first, pp.frame_major = L.frame_major, pp.plane_nt = L.plane_nt;
+  TileSum& ts = pp.ts;
+  fill_plane_sum(ts, p, d_out, g, b);
+  ts.half = p->N / 2, ts.cover = p->d_cover, ts.tiles = p->patch.d_sum_order, ts.count = n_tiles * b.frames;
+  ts.done = p->patch.d_tile_done, ts.epoch = p->patch.done_epoch;
+  ts.n_frames = b.frames, ts.n_tiles = (uint32_t)n_tiles, ts.n_tiles_listed = (uint32_t)n_tiles, ts.frame_major = L.frame_major;
+  ts.queue = p->patch.d_sum_queue, ts.queue_base = L.sum_queue_base;
+  if (L.form != PatchLaunch::PERSISTENT) return pp;
+  pp.persist = L.rows, pp.xq = p->patch.d_xq;
+  pp.head_patches = L.head_patches, pp.prefetch = L.prefetch, pp.prefetch_tiles = p->patch.d_prefetch_tiles;
+  for (int x = 0; x < 9; ++x) pp.prefetch_first[x] = p->patch.prefetch_first[x];
+  for (int x = 0; x < 8; ++x) pp.xq_base[x] = L.xq_base[x];
+  return pp;
+}
+
+// The patch kernels of one apply, in the form patch_launch_for decided (the FORWARD PROGRESS argument of the persistent form is there)
+static int launch_patches(const rpsf_plan* p, const PatchLaunch& L, const float* d_img, float* d_out, const rpsf_geometry& g, OverlapKind kind,
+                          hipStream_t st, Batch b) {
+  const PatchParams pp = patch_params(p, L, d_img, d_out, g, kind, b);
+  return dispatch_patch(p->patch.v2, p->N, [&]<class T>() -> int {
+    const dim3 grid(L.grid), wg(T::WG);
+    if (L.form != PatchLaunch::PERSISTENT) T::kernel()<<<grid, wg, T::LDS_BYTES, st>>>(pp);
+    else if constexpr (T::V2) {
+      using Persistent = PersistentKernel2<typename T::Cfg>;
+      switch (L.variant) {
+        case PatchLaunch::PLAIN: Persistent::fn<<<grid, wg, T::LDS_BYTES, st>>>(pp); break;
+        case PatchLaunch::K_CACHED: Persistent::fn_k_cached<<<grid, wg, T::LDS_BYTES, st>>>(pp); break;
+        case PatchLaunch::K_CACHED_PLANES_NT: Persistent::fn_k_cached_planes_nt<<<grid, wg, T::LDS_BYTES, st>>>(pp); break;
       }
-      patch_kernel2<C><<<dim3((unsigned)blocks), dim3(Launch2<C>::WG), Launch2<C>::LDS_BYTES, st>>>(pp);
-      HIP_TRY(hipGetLastError());
-      return RPSF_OK;
-    });
-  return dispatch_n(p->N, [&]<class C>() -> int {
-    PatchParams pp{};
-    constexpr int TEAMS = Launch<C>::TEAMS;
-    fill(pp, TEAMS);
-    pp.stagger_blocks = p->cu_count * std::max(1, 512 / Launch<C>::WG);
-    const size_t blocks = (size_t)8 * (pp.chunk / TEAMS) * b.frames;
-    if (blocks > 0x7fffffffu) return fail(RPSF_E_BADARG, "batch too large for one launch");
-    patch_kernel<C><<<dim3((unsigned)blocks), dim3(Launch<C>::WG), Launch<C>::LDS_BYTES, st>>>(pp);
+    }
     HIP_TRY(hipGetLastError());
     return RPSF_OK;
   });
 }
 
-static int launch_fixup(rpsf_plan* p, float* d_out, const rpsf_geometry& g, hipStream_t st, Batch b) {
+static int launch_fixup(const rpsf_plan* p, float* d_out, const rpsf_geometry& g, hipStream_t st, Batch b) {
   FixParams fp{};
-  fp.planes = p->patch.d_planes, fp.plane_stride = p->patch.planes_floats, fp.planes_frame_floats = 4 * p->patch.planes_floats, fp.ld_planes = g.width;
-  fp.out = d_out, fp.ld_out = g.ld_out, fp.out_frame_floats = b.out_stride;
-  fp.rows = g.out_rows, fp.W = g.width, fp.row0 = g.out_row0;
-  fp.lat_r0 = p->lat_r0 + g.origin_row, fp.lat_c0 = p->lat_c0 + g.origin_col, fp.half = p->N / 2, fp.ntj = p->ntj;
+  fill_plane_sum(fp, p, d_out, g, b);
+  fp.half = p->N / 2;
   fp.tile_info = p->patch.d_tile_info, fp.flags = p->patch.d_flags, fp.dyn_side = p->patch.d_dyn;
   fp.epoch = p->patch.epoch, fp.n_tiles = (uint32_t)(p->nti * p->ntj);
-  for (int f0 = 0; f0 < b.frames; f0 += 65535) {  // grid.y limit
+  for_frame_slices(b.frames, [&](int f0, unsigned frames) {
     FixParams q = fp;
     q.planes += (size_t)f0 * q.planes_frame_floats, q.out += (size_t)f0 * q.out_frame_floats;
     q.flags += (size_t)f0 * q.n_tiles, q.dyn_side += (size_t)f0 * q.n_tiles;
-    fixup_kernel<<<dim3(fp.n_tiles * FIX_SUB, (unsigned)std::min(65535, b.frames - f0)), dim3(256), 0, st>>>(q);
-  }
+    fixup_kernel<<<dim3(fp.n_tiles * FIX_SUB, frames), dim3(256), 0, st>>>(q);
+  });
   HIP_TRY(hipGetLastError());
   return RPSF_OK;
 }
 
-static int launch_sum(rpsf_plan* p, float* d_out, const rpsf_geometry& g, int row_begin, int row_end, hipStream_t st,
-                      Batch b = Batch()) {
-  if (row_end <= row_begin) return RPSF_OK;
-  SumParams sp = make_sum_params(p, d_out, g, row_begin, row_end);
-  sp.out_frame_floats = b.out_stride;
-  size_t total = (size_t)((g.width + 3) / 4) * sp.rows;
-  for (int f0 = 0; f0 < b.frames; f0 += 65535) {  // grid.y limit
+// The separate plane sum over the whole resident window
+static int launch_sum(const rpsf_plan* p, float* d_out, const rpsf_geometry& g, hipStream_t st, Batch b) {
+  SumParams sp{};
+  fill_plane_sum(sp, p, d_out, g, b);
+  sp.row_begin = 0, sp.nti = p->nti, sp.cover = p->d_cover;
+  sp.half_shift = 0;
+  while ((1 << (sp.half_shift + 1)) < p->N) ++sp.half_shift;
+  const size_t total = (size_t)((g.width + 3) / 4) * sp.rows;
+  for_frame_slices(b.frames, [&](int f0, unsigned frames) {
     SumParams q = sp;
     q.planes += (size_t)f0 * q.planes_frame_floats, q.out += (size_t)f0 * q.out_frame_floats;
-      sum_planes_kernel<<<dim3((unsigned)((total + 255) / 256), (unsigned)std::min(65535, b.frames - f0)), dim3(256), 0, st>>>(q);
-  }
+    sum_planes_kernel<<<dim3((unsigned)((total + 255) / 256), frames), dim3(256), 0, st>>>(q);
+  });
   HIP_TRY(hipGetLastError());
   return RPSF_OK;
 }
 
-// One apply.  ev_k0 / ev_k1 (optional) bracket the patch-kernel launches for timing.
 static OverlapKind overlap_kind(const rpsf_plan* p) {
   switch (p->overlap_mode) {
     case 1: return OV_ATOMIC;
@@ -1257,7 +1287,7 @@ static int launch_apply_generic(rpsf_plan* p, const float* d_img, float* d_out, 
   for (int f = 0; f < b.frames; ++f) {
     const float* img = d_img + (size_t)f * b.im_stride;
     float* out = d_out + (size_t)f * b.out_stride;
-    HIP_TRY(hipMemset2DAsync(out, (size_t)g.ld_out * sizeof(float), 0, (size_t)g.width * sizeof(float), g.out_rows, st));
+    if (const int rc = clear_window(out, g, Batch(), st); rc != RPSF_OK) return rc;
     for (int first = 0; first < p->n_patches; first += p->fft.chunk) {
       GenericGeom gg;
       gg.N = p->N, gg.first = first, gg.count = std::min(p->fft.chunk, p->n_patches - first);
@@ -1293,12 +1323,8 @@ static int launch_apply_generic(rpsf_plan* p, const float* d_img, float* d_out, 
 // Third generation (N <= 64): the whole apply is this one launch (rpsf_kernels3.hpp); frames of a batch along grid.y
 static int launch_sweep(rpsf_plan* p, const float* d_img, float* d_out, const rpsf_geometry& g, hipStream_t st, hipEvent_t ev_k0, hipEvent_t ev_k1,
                         Batch b) {
-  const int half = p->N / 2;
   const long r0 = (long)p->lat_r0 + g.origin_row, c0 = (long)p->lat_c0 + g.origin_col;
-  // pixels of the resident window that the lattice does not cover are written by nobody: the reference leaves them zero
-  if (r0 > g.out_row0 || r0 + (long)p->nti * half < (long)g.out_row0 + g.out_rows || c0 > 0 || c0 + (long)p->ntj * half < g.width)
-    for (int f = 0; f < b.frames; ++f)
-      HIP_TRY(hipMemset2DAsync(d_out + (size_t)f * b.out_stride, (size_t)g.ld_out * sizeof(float), 0, (size_t)g.width * sizeof(float), g.out_rows, st));
+  if (const int rc = lattice_covers_window(p, g) ? RPSF_OK : clear_window(d_out, g, b, st); rc != RPSF_OK) return rc;
   SweepParams sp{};
   sp.im = ImageView{d_img, g.height, g.width, g.ld_image, g.pad_mode, g.pad_value, g.image_row0, g.image_rows};
   const bool col_aligned = (c0 & 3) == 0;
@@ -1313,22 +1339,24 @@ static int launch_sweep(rpsf_plan* p, const float* d_img, float* d_out, const rp
   // K by plain loads when frames share it or it is small enough to stay in the Infinity Cache from one apply to the next, else streamed
   const bool k_plain = b.frames > 1 || o->sweep.k3_floats * sizeof(float) <= ((size_t)96 << 20);
   if (ev_k0) HIP_TRY(hipEventRecord(ev_k0, st));
-  for (int f0 = 0; f0 < b.frames; f0 += 65535) {  // grid.y limit
+  for_frame_slices(b.frames, [&](int f0, unsigned frames) {
     SweepParams q = sp;
     q.im.img += (size_t)f0 * b.im_stride, q.fl.out += (size_t)f0 * b.out_stride;
-    const dim3 grid((unsigned)(8 * sp.group), (unsigned)std::min(65535, b.frames - f0));
-    const int rc = dispatch_v3(p->N, [&]<class C>() -> int {
+    const dim3 grid((unsigned)(8 * sp.group), frames);
+    (void)dispatch_v3(p->N, [&]<class C>() -> int {  // (a plan with sweep lists has a third-generation configuration)
       if (k_plain) sweep_kernel_kc<C><<<grid, dim3(C::WG), C::LDS_BYTES, st>>>(q);
       else sweep_kernel<C><<<grid, dim3(C::WG), C::LDS_BYTES, st>>>(q);
-      HIP_TRY(hipGetLastError());
       return RPSF_OK;
     });
-    if (rc != RPSF_OK) return rc;
-  }
+  });
+  HIP_TRY(hipGetLastError());
   if (ev_k1) HIP_TRY(hipEventRecord(ev_k1, st));
   return RPSF_OK;
 }
 
+// One apply.  ev_k0 / ev_k1 (optional) bracket the patch-kernel launches for timing.
+// In this order: every refusal; growth of the plan's scratch (harmless before a launch that fails); the decision, which reads the scratch sizes; then
+// what a launch must not be refused after - epochs, counter restarts, queue positions -; the clear; the launches.
 static int launch_apply(rpsf_plan* p, const float* d_img, float* d_out, const rpsf_geometry& g, hipStream_t st,
                         hipEvent_t ev_k0, hipEvent_t ev_k1 = nullptr, Batch b = Batch()) {
   if (p->generic) return launch_apply_generic(p, d_img, d_out, g, st, ev_k0, ev_k1, b);
@@ -1341,6 +1369,12 @@ static int launch_apply(rpsf_plan* p, const float* d_img, float* d_out, const rp
   if (kind == OV_DIRECT && !p->patch.direct_ok) return fail(RPSF_E_STATE, "direct overlap-add needs a lattice and a 128- or 256-pixel patch");
   if (kind == OV_DIRECT && (size_t)g.out_rows * g.ld_out * sizeof(float) >= ((size_t)1 << 32))
     return fail(RPSF_E_UNSUPPORTED, "direct overlap-add addresses the output through a 32-bit buffer offset: frame too large");
+  if (patch_launch_too_large(p, b.frames)) return fail(RPSF_E_BADARG, "batch too large for one launch");
+  // Fused plane sum: one frame, every plane line written whole by one store instruction (see sum_tile)
+  const bool fused = kind == OV_PLANES && p->patch.v2 && p->patch.fuse_pays && p->patch.d_tile_done && !p->patch.no_fuse && b.frames <= 255 && g.width % 32 == 0 &&
+                     g.ld_out % 4 == 0 && ((long)p->lat_c0 + g.origin_col) % 32 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0 &&
+                     16 * plane_floats_needed(g) < ((size_t)1 << 32);  // the planes are addressed through one 32-bit buffer offset
+  const size_t n_tiles = (size_t)p->nti * p->ntj;
   // The plan's scratch (planes, flags) serves one apply at a time: an apply on another stream waits for the last one.
   if (p->busy_valid && st != p->last_stream) HIP_TRY(hipStreamWaitEvent(st, p->ev_busy, 0));
   if (kind != OV_ATOMIC) {
@@ -1353,69 +1387,52 @@ static int launch_apply(rpsf_plan* p, const float* d_img, float* d_out, const rp
       p->patch.planes_floats = per, p->patch.planes_frames = frames;
     }
   }
-  bool clear = kind == OV_ATOMIC;
-  if (kind == OV_DIRECT) {
-    const size_t n_tiles = (size_t)p->nti * p->ntj;
-    if ((size_t)b.frames > p->patch.flag_frames) {
-      HIP_TRY(hipDeviceSynchronize());
-      p->patch.d_flags.reset(), p->patch.d_dyn.reset(), p->patch.flag_frames = 0;
-      HIP_TRY(p->patch.d_flags.alloc(n_tiles * b.frames));
-      HIP_TRY(p->patch.d_dyn.alloc(n_tiles * b.frames));
-      HIP_TRY(hipMemset(p->patch.d_flags, 0, n_tiles * b.frames * sizeof(uint32_t)));
-      HIP_TRY(hipMemset(p->patch.d_dyn, 0, n_tiles * b.frames * sizeof(uint32_t)));
-      p->patch.flag_frames = (size_t)b.frames;
-    }
-    if (++p->patch.epoch >= (1u << 24) - 1) {  // the epoch field of the flag words is 24 bits wide
-      HIP_TRY(hipMemsetAsync(p->patch.d_flags, 0, n_tiles * p->patch.flag_frames * sizeof(uint32_t), st));
-      HIP_TRY(hipMemsetAsync(p->patch.d_chunk_xcc, 0, 8 * sizeof(uint32_t), st));
-      p->patch.epoch = 1;
-    }
-    // pixels of the resident window that no lattice tile covers are never written by the kernels below
-    const int half = p->N / 2;
-    const long tr0 = (long)p->lat_r0 + g.origin_row, tc0 = (long)p->lat_c0 + g.origin_col;
-    clear = tr0 > g.out_row0 || tr0 + (long)p->nti * half < (long)g.out_row0 + g.out_rows || tc0 > 0 ||
-            tc0 + (long)p->ntj * half < g.width;
+  if (kind == OV_DIRECT && (size_t)b.frames > p->patch.flag_frames) {
+    HIP_TRY(hipDeviceSynchronize());
+    p->patch.d_flags.reset(), p->patch.d_dyn.reset(), p->patch.flag_frames = 0;
+    HIP_TRY(p->patch.d_flags.alloc(n_tiles * b.frames));
+    HIP_TRY(p->patch.d_dyn.alloc(n_tiles * b.frames));
+    HIP_TRY(hipMemset(p->patch.d_flags, 0, n_tiles * b.frames * sizeof(uint32_t)));
+    HIP_TRY(hipMemset(p->patch.d_dyn, 0, n_tiles * b.frames * sizeof(uint32_t)));
+    p->patch.flag_frames = (size_t)b.frames;
   }
-  if (clear)
-    for (int f = 0; f < b.frames; ++f)
-      HIP_TRY(hipMemset2DAsync(d_out + (size_t)f * b.out_stride, (size_t)g.ld_out * sizeof(float), 0,
-                               (size_t)g.width * sizeof(float), g.out_rows, st));
-  // Fused plane sum: one frame, every plane line written whole by one store instruction (see sum_tile)
-  const long tile_r0 = (long)p->lat_r0 + g.origin_row, tile_c0 = (long)p->lat_c0 + g.origin_col;
-  const bool fused = kind == OV_PLANES && p->patch.v2 && p->patch.fuse_pays && p->patch.d_tile_done && !p->patch.no_fuse && b.frames <= 255 && g.width % 32 == 0 &&
-                     g.ld_out % 4 == 0 && tile_c0 % 32 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0 &&
-                     16 * plane_floats_needed(g) < ((size_t)1 << 32);  // the planes are addressed through one 32-bit buffer offset
+  if (fused && (size_t)b.frames > p->patch.done_frames) {  // one set of tile counters per frame of a batch
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(p->patch.d_tile_done.alloc(n_tiles * b.frames));
+    HIP_TRY(hipMemset(p->patch.d_tile_done, 0, n_tiles * b.frames * sizeof(uint32_t)));
+    p->patch.done_frames = (size_t)b.frames;  // (more frames than any launch before, the last one included: a new count starts below)
+  }
+  PatchLaunch L{};
+  (void)dispatch_patch(p->patch.v2, p->N, [&]<class T>() -> int {
+    L = patch_launch_for<T>(p, d_img, g, b, fused);
+    return RPSF_OK;
+  });
+  // ---- nothing refuses the launch from here on: the plan's epochs, counters and queue positions advance ----
+  if (kind == OV_DIRECT && ++p->patch.epoch >= (1u << 24) - 1) {  // the epoch field of the flag words is 24 bits wide
+    HIP_TRY(hipMemsetAsync(p->patch.d_flags, 0, n_tiles * p->patch.flag_frames * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(p->patch.d_chunk_xcc, 0, 8 * sizeof(uint32_t), st));
+    p->patch.epoch = 1;
+  }
   if (fused) {
-    const size_t n_tiles = (size_t)p->nti * p->ntj;
-    if ((size_t)b.frames > p->patch.done_frames) {  // one set of tile counters per frame of a batch
-      HIP_TRY(hipDeviceSynchronize());
-      HIP_TRY(p->patch.d_tile_done.alloc(n_tiles * b.frames));
-      HIP_TRY(hipMemset(p->patch.d_tile_done, 0, n_tiles * b.frames * sizeof(uint32_t)));
-      p->patch.done_frames = (size_t)b.frames, p->patch.done_epoch = 0;
-    }
     // A launch advances the counters of frames [0, b.frames) only, and a tile is complete at epoch x contributors: when the frame
     // count differs from the previous fused launch's (batch -> single apply -> batch, or the short last group of a batch) the
     // counters of the higher frames would lag behind the epoch for ever - and the summing workgroups would wait for ever.
     // Start a new count whenever the frame count changes (and when the epoch would overflow the counters).
-    if (b.frames != p->patch.done_last_frames || p->patch.done_epoch + 1 >= (1u << 29)) {  // the counters hold epoch * contributors
-      HIP_TRY(hipMemsetAsync(p->patch.d_tile_done, 0, n_tiles * p->patch.done_frames * sizeof(uint32_t), st));
-      p->patch.done_epoch = 0;
-    }
+    const bool restart = b.frames != p->patch.done_last_frames || p->patch.done_epoch + 1 >= (1u << 29);  // the counters hold epoch * contributors
+    if (restart) HIP_TRY(hipMemsetAsync(p->patch.d_tile_done, 0, n_tiles * p->patch.done_frames * sizeof(uint32_t), st));
     p->patch.done_last_frames = b.frames;
-    ++p->patch.done_epoch;
-    // the tile sums write lattice tiles only: pixels of the window outside the tile grid are cleared here
-    const int half = p->N / 2;
-    if (tile_r0 > g.out_row0 || tile_r0 + (long)p->nti * half < (long)g.out_row0 + g.out_rows || tile_c0 > 0 ||
-        tile_c0 + (long)p->ntj * half < g.width)
-      for (int f = 0; f < b.frames; ++f)
-        HIP_TRY(hipMemset2DAsync(d_out + (size_t)f * b.out_stride, (size_t)g.ld_out * sizeof(float), 0, (size_t)g.width * sizeof(float),
-                                 g.out_rows, st));
+    p->patch.done_epoch = restart ? 1 : p->patch.done_epoch + 1;
   }
+  for (int x = 0; x < 8; ++x) p->patch.xq_base[x] += L.xq_draws[x];
+  p->patch.sum_queue_base += L.sum_queue_draws;
+  // atomics accumulate into the output; the tile sums and the direct mode's fix-up write lattice tiles only
+  const bool clear = kind == OV_ATOMIC || ((kind == OV_DIRECT || fused) && !lattice_covers_window(p, g));
+  if (const int rc = clear ? clear_window(d_out, g, b, st) : RPSF_OK; rc != RPSF_OK) return rc;
   if (ev_k0) HIP_TRY(hipEventRecord(ev_k0, st));
-  int rc = launch_patches(p, d_img, d_out, g, kind, st, b, fused);
+  int rc = launch_patches(p, L, d_img, d_out, g, kind, st, b);
   if (rc != RPSF_OK) return rc;
   if (ev_k1) HIP_TRY(hipEventRecord(ev_k1, st));
-  if (kind == OV_PLANES && !fused) rc = launch_sum(p, d_out, g, 0, g.out_rows, st, b);
+  if (kind == OV_PLANES && !fused) rc = launch_sum(p, d_out, g, st, b);
   if (kind == OV_DIRECT) rc = launch_fixup(p, d_out, g, st, b);
   if (rc != RPSF_OK) return rc;
   HIP_TRY(hipEventRecord(p->ev_busy, st));
@@ -1433,7 +1450,6 @@ extern "C" int rpsf_plan_set_overlap_mode(rpsf_plan* p, int mode) {
   return RPSF_OK;
 }
 
-// Diagnostic builds only (-DRPSF_STAMPS): copy out the 16 per-patch phase timestamps (10 ns ticks).
 extern "C" int rpsf_plan_set_option(rpsf_plan* p, int option, int value) {
   if (!p) return fail(RPSF_E_BADARG, "null plan");
   switch (option) {
@@ -1498,6 +1514,7 @@ extern "C" int rpsf_plan_sweep_info(const rpsf_plan* p, int* regions, long* jobs
   return RPSF_OK;
 }
 
+// Diagnostic builds only (-DRPSF_STAMPS): copy out the 16 per-patch phase timestamps (10 ns ticks).
 extern "C" int rpsf_plan_debug_stamps(rpsf_plan* p, unsigned long long* host, size_t count) {
   if (!p || !host) return fail(RPSF_E_BADARG, "null argument");
   if (p->sweep.d_stamps) {  // third generation: [region][wave][job slot < 8][16]
@@ -2034,11 +2051,8 @@ static int host_one_frame(rpsf_plan* p, const void* image, int in_f64, void* out
   // 0.140 -> see profiles/r06zu_small_frame_zero_copy_out.log).  Only where every pixel of the window is written by the launch (the lattice covers it).
   float* zc_out = nullptr;
   if (one_stream && err == hipSuccess && overlap_kind(p) == OV_SWEEP && p->sweep.ok && !dev_env("RPSF_NO_ZC_OUT")) {
-    const int half = p->N / 2;
-    const long r0 = (long)p->lat_r0 + g.origin_row, c0 = (long)p->lat_c0 + g.origin_col;
-    const bool covered = r0 <= g.out_row0 && r0 + (long)p->nti * half >= (long)g.out_row0 + g.out_rows && c0 <= 0 && c0 + (long)p->ntj * half >= g.width;
     void* dev = nullptr;
-    if (covered && hipHostGetDevicePointer(&dev, direct_out ? out : static_cast<void*>(q.h_out[0]), 0) == hipSuccess) zc_out = static_cast<float*>(dev);
+    if (lattice_covers_window(p, g) && hipHostGetDevicePointer(&dev, direct_out ? out : static_cast<void*>(q.h_out[0]), 0) == hipSuccess) zc_out = static_cast<float*>(dev);
     else (void)hipGetLastError();
   }
   if (err == hipSuccess && launch_apply(p, q.d_in[0], zc_out ? zc_out : q.d_out[0], g, p->stream, nullptr) != RPSF_OK) err = hipErrorUnknown;
@@ -2704,7 +2718,7 @@ static int psf_fft_impl(int device, int patch_size, int count, const float* valu
     HIP_TRY(hipSetDevice(device));
     DevBuf<uint16_t> d_tab;
     DevBuf<cf> d_tw;
-    int rc = upload_tables<C>(device, d_tab, d_tw);
+    int rc = upload_tables<PatchPlan<C, false>>(device, d_tab, d_tw);
     if (rc != RPSF_OK) return rc;
     DevBuf<float> b_in;
     DevBuf<cf> b_out;
