@@ -284,6 +284,42 @@ int rpsf_psf_fft_device(int device, int patch_size, int count, const float* valu
 int rpsf_psf_model_fft_device(int device, int model, int patch_size, int count, const double* params_host, int normalize,
                               void* values_f32_dev, void* fft_c64_dev);
 
+/* ArrayPSFBuilder.build downstream of the star list (regularizepsf/builder.py:139-265): a builder owns a device stack of float32
+ * N x N star patches (background-subtracted, not normalised), filled frame by frame and then averaged per lattice cell.  Star finding
+ * (sep, image_processing.py:65-74), the cell membership (builder.py:45-51) and the final per-cell clean-up (builder.py:231-260) stay with
+ * the caller.  N from 4 to 128, odd sizes included (anything else: RPSF_E_UNSUPPORTED); `capacity` patches are allocated at once, the
+ * stack grows by itself beyond that.  INVARIANT: every patch of the stack is finite and has a non-zero centre pixel [N/2][N/2]. */
+typedef struct rpsf_builder rpsf_builder;
+int rpsf_builder_create(rpsf_builder** out, int device, int patch_size, size_t capacity);
+void rpsf_builder_destroy(rpsf_builder* builder);
+/* The per-star loop of _find_patches (image_processing.py:95-121) for one frame, kernel B1: the frame is uploaded once as float32; star i
+ * has the rounded corner corners_i32[i] = (row, col) (:96) and the shift amounts frac_f64[i] (:101), both computed by the caller with the
+ * reference's expressions.  Per star: the patch through np.pad's reflect map (:82-100), scipy.ndimage.shift(order 3, mode 'mirror') (:102),
+ * the background plane of calculate_background (:13-46) subtracted (:110-112), the tests of :117-119.  accepted_u8_host[i] receives
+ * 1: accepted and appended to the stack (in star order), 0: rejected (a pixel not below saturation_threshold, the centre not strictly
+ * inside (star_minimum, star_maximum), a zero or non-finite pixel), 2: fewer than three usable border pixels (or all on one line) for the
+ * plane - nothing the reference defines; the caller decides. */
+int rpsf_builder_add_frame(rpsf_builder* builder, const void* image_host, int image_is_f64, int height, int width, int n_stars,
+                           const int32_t* corners_i32, const double* frac_f64, double saturation_threshold, double star_minimum,
+                           double star_maximum, uint8_t* accepted_u8_host);
+int rpsf_builder_count(const rpsf_builder* builder, size_t* count);
+/* Patches first .. first + count of the stack, count x N x N float32. */
+int rpsf_builder_patches(rpsf_builder* builder, size_t first, size_t count, float* host);
+/* Append patches the caller already has (count x N x N float32); RPSF_E_BADARG for a non-finite pixel or a zero centre. */
+int rpsf_builder_load_patches(rpsf_builder* builder, size_t count, const float* host);
+/* _average_patches (builder.py:53-125), kernel B2: cell c averages the patches members_i32[cell_offsets_i64[c] .. cell_offsets_i64[c + 1])
+ * (indices into the stack, in the order the reference meets them), every sample being (double)pixel / (double)centre of its patch
+ * (:61,:87).  Mean: the additions of :66 in list order, divided by the count.  Median / percentile (0..100): exact selection, NumPy's
+ * rules (mean of the two middle samples; the default linear method).  A cell without members is all zeros (:119-123).
+ * cells_f64_host: n_cells x N x N float64. */
+#define RPSF_AVERAGE_MEAN 0
+#define RPSF_AVERAGE_MEDIAN 1
+#define RPSF_AVERAGE_PERCENTILE 2
+int rpsf_builder_average(rpsf_builder* builder, int method, double percentile, int n_cells, const int64_t* cell_offsets_i64,
+                         const int32_t* members_i32, double* cells_f64_host);
+/* Device time of the last B1 and the last B2 launch, milliseconds (either pointer may be NULL). */
+int rpsf_builder_kernel_ms(const rpsf_builder* builder, double* patch_ms, double* average_ms);
+
 /* Host-side helper for the saturation branch of apply (transform.py:135-138): sequential, row-major
  * NaN-ignoring neighbourhood-mean fill of the masked pixels of the float64 padded image (no GPU involved). */
 int rpsf_saturation_fill(double* padded, int rows, int cols, const uint8_t* mask, int neighborhood_width);

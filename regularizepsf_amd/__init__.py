@@ -1,7 +1,7 @@
 """MI355X-native patch-wise Fourier PSF correction with the regularizepsf class API.
 
-Drop-in for the ``ArrayPSF`` / ``ArrayPSFTransform`` / ``IndexedCube`` / ``calculate_covering`` path (and the functional
-PSF models that feed it) of
+Drop-in for the ``ArrayPSFBuilder`` / ``ArrayPSF`` / ``ArrayPSFTransform`` / ``IndexedCube`` / ``calculate_covering`` path (and
+the functional PSF models that feed it) of
 punch-mission/regularizepsf (regularizepsf/__init__.py:5-16 re-exports the same names); the compute
 runs in hand-written HIP kernels behind the C ABI of include/rpsf.h.
 """
@@ -24,6 +24,7 @@ from regularizepsf_amd.functional import (
     varied_functional_psf,
 )
 from regularizepsf_amd._native import pinned_empty
+from regularizepsf_amd.builder import ArrayPSFBuilder
 from regularizepsf_amd.psf import ArrayPSF
 from regularizepsf_amd.transform import ArrayPSFTransform
 from regularizepsf_amd.util import IndexedCube, calculate_covering
@@ -32,6 +33,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "ArrayPSF",
+    "ArrayPSFBuilder",
     "ArrayPSFTransform",
     "FunctionParameterMismatchError",
     "IncorrectShapeError",

@@ -96,6 +96,15 @@ _PROTOTYPES = {
     "rpsf_psf_fft": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
     "rpsf_psf_fft_device": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
     "rpsf_psf_model_fft_device": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "rpsf_builder_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_size_t]),
+    "rpsf_builder_destroy": (None, [c_void_p]),
+    "rpsf_builder_add_frame": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double, c_double,
+                                       c_void_p]),
+    "rpsf_builder_count": (c_int, [c_void_p, POINTER(c_size_t)]),
+    "rpsf_builder_patches": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p]),
+    "rpsf_builder_load_patches": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "rpsf_builder_average": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    "rpsf_builder_kernel_ms": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
     "rpsf_saturation_fill": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
     "rpsf_dev_alloc": (c_int, [c_int, c_size_t, POINTER(c_void_p)]),
     "rpsf_dev_free": (c_int, [c_int, c_void_p]),

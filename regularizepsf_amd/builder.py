@@ -1,0 +1,304 @@
+"""Build a PSF model from star patches (API of regularizepsf/builder.py:128-265).
+
+What the reference does per star in a Python loop (image_processing.py:95-121: slice the reflect-padded frame, spline-shift the
+patch onto the pixel grid, subtract a background plane, test) and per lattice cell over Python lists (builder.py:53-102:
+``np.nansum`` / ``np.nanmedian`` / ``np.nanpercentile``) runs in two HIP kernels behind ``rpsf_builder_*`` (include/rpsf.h).
+The host keeps what is bookkeeping: the rounded corners and shift amounts (Python's half-to-even ``round``), the cell
+membership of every patch, and the final per-cell clean-up (builder.py:231-260), which is a few ``scipy.ndimage`` calls on at
+most a few thousand small float64 arrays.
+
+The boundary of the feature is the star list: ``build(..., stars=[...])`` takes the ``(row, col)`` positions ``sep.extract``
+returns; without it ``sep`` is imported and called as the reference calls it.
+"""
+
+from __future__ import annotations
+
+import ctypes
+import pathlib
+from collections.abc import Generator
+
+import numpy as np
+
+from regularizepsf_amd.exceptions import IncorrectShapeError, PSFBuilderError
+from regularizepsf_amd.psf import ArrayPSF
+from regularizepsf_amd.util import IndexedCube, calculate_covering
+
+AVERAGE_METHODS = {"mean": 0, "median": 1, "percentile": 2}
+REJECTED, ACCEPTED, DEGENERATE_RING = 0, 1, 2
+
+
+def _frames(images) -> list[np.ndarray]:
+    """``_convert_to_generator`` (builder.py:17-43) as a list of 2-D frames.  A single 2-D array is one frame (the reference
+    yields it forever)."""
+    if isinstance(images, Generator):
+        frames = list(images)
+    elif isinstance(images, np.ndarray):
+        if images.ndim == 3:
+            frames = list(images)
+        elif images.ndim == 2:
+            frames = [images]
+        else:
+            msg = "Image data array must be 3D"
+            raise IncorrectShapeError(msg)
+    elif isinstance(images, list) and len(images) > 0 and isinstance(images[0], (str, pathlib.Path)):
+        msg = "Reading frames from FITS files needs astropy, which this package does not depend on: load the arrays and pass them"
+        raise NotImplementedError(msg)
+    elif isinstance(images, list) and len(images) > 0 and all(isinstance(f, np.ndarray) for f in images):
+        frames = images
+    else:
+        msg = "Unsupported type for `images`"
+        raise TypeError(msg)
+    for frame in frames:
+        if not isinstance(frame, np.ndarray) or frame.ndim != 2:
+            msg = "Every frame must be a two-dimensional array"
+            raise IncorrectShapeError(msg)
+    shape = None
+    for frame in frames:  # the reference's message, builder.py:218-221
+        if shape is None:
+            shape = frame.shape
+        elif shape != frame.shape:
+            msg = ("Images must all be the same shape."
+                   f"Found both {shape} and {frame.shape}.")
+            raise PSFBuilderError(msg)
+    if not frames:
+        msg = "No frames to build a PSF model from"
+        raise PSFBuilderError(msg)
+    return frames
+
+
+def _find_stars(frame: np.ndarray, star_threshold: float, star_mask) -> np.ndarray:
+    """image_processing.py:65-74 on the host (UNVERIFIED here: sep is not among this package's test dependencies)."""
+    try:
+        import sep
+    except ImportError as error:
+        msg = "Star finding needs the `sep` package; install it, or pass the star positions yourself with stars=[(k, 2) arrays of (row, col)]"
+        raise ImportError(msg) from error
+    background = sep.Background(frame)
+    try:
+        found = sep.extract(frame - background, star_threshold, err=background.globalrms, mask=star_mask)
+    except Exception:  # noqa: BLE001  (the reference treats any failure as "no stars")
+        return np.zeros((0, 2))
+    return np.stack([np.asarray(found["y"], np.float64), np.asarray(found["x"], np.float64)], axis=-1)
+
+
+def star_geometry(positions: np.ndarray, psf_size: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Per star of one frame: the float corner ``position - N / 2`` that keys the patch (image_processing.py:76-79), the rounded
+    corner (:96; ``np.rint`` rounds half to even exactly as Python's ``round``) and the shift amounts (:101)."""
+    positions = np.asarray(positions, np.float64).reshape(-1, 2)
+    corner = positions - psf_size / 2
+    rounded = np.rint(corner)
+    shift = -corner + rounded - 0.5
+    return corner, rounded.astype(np.int64), shift
+
+
+def cell_membership(patch_corners: np.ndarray, cell_corners: np.ndarray, psf_size: int) -> tuple[np.ndarray, np.ndarray]:
+    """``_find_matches`` (builder.py:45-51) for every patch at once, as a CSR list: ``offsets`` (cells + 1, int64) and ``members``
+    (int32 patch indices), cells in the order of ``cell_corners``, patches inside a cell in the order given.
+
+    A patch belongs to a cell when its centre ``corner + N // 2`` lies in ``[cell, cell + N)`` on both axes.  The cells of a
+    covering are the full product of their distinct rows and columns, so the rows and the columns are matched separately."""
+    n_cells = len(cell_corners)
+    centre = np.asarray(patch_corners, np.float64).reshape(-1, 2) + psf_size // 2
+    rows, row_of = np.unique(cell_corners[:, 0], return_inverse=True)
+    cols, col_of = np.unique(cell_corners[:, 1], return_inverse=True)
+    table = np.full((len(rows), len(cols)), -1, np.int64)
+    table[row_of, col_of] = np.arange(n_cells)
+    pairs_cell, pairs_patch = [], []
+    # lower <= centre < lower + N  <=>  lower in (centre - N, centre]
+    r_lo, r_hi = np.searchsorted(rows, centre[:, 0] - psf_size, "right"), np.searchsorted(rows, centre[:, 0], "right")
+    c_lo, c_hi = np.searchsorted(cols, centre[:, 1] - psf_size, "right"), np.searchsorted(cols, centre[:, 1], "right")
+    patch_index = np.arange(len(centre))
+    for dr in range(int((r_hi - r_lo).max(initial=0))):
+        for dc in range(int((c_hi - c_lo).max(initial=0))):
+            ok = (r_lo + dr < r_hi) & (c_lo + dc < c_hi)
+            cells = table[(r_lo + dr)[ok], (c_lo + dc)[ok]]
+            present = cells >= 0
+            pairs_cell.append(cells[present])
+            pairs_patch.append(patch_index[ok][present])
+    cell = np.concatenate(pairs_cell) if pairs_cell else np.zeros(0, np.int64)
+    patch = np.concatenate(pairs_patch) if pairs_patch else np.zeros(0, np.int64)
+    order = np.lexsort((patch, cell))
+    offsets = np.zeros(n_cells + 1, np.int64)
+    np.cumsum(np.bincount(cell, minlength=n_cells), out=offsets[1:])
+    return offsets, patch[order].astype(np.int32)
+
+
+def background_plane(patch: np.ndarray) -> np.ndarray:
+    """``calculate_background`` (image_processing.py:13-46) with the same SciPy calls, float64."""
+    import scipy.linalg
+    from scipy.ndimage import binary_dilation, binary_erosion
+
+    rows, cols = np.indices(patch.shape)
+    inner = binary_erosion(patch != 0)
+    inner[0, :] = inner[-1, :] = False
+    inner[:, 0] = inner[:, -1] = False
+    ring = binary_dilation(inner) & ~inner
+    ring &= patch < patch[patch.shape[1] // 2, patch.shape[0] // 2]
+    design = np.c_[cols[ring], rows[ring], np.ones_like(cols[ring])]
+    fit = scipy.linalg.lstsq(design, patch[ring])[0]
+    plane = fit[0] * cols + fit[1] * rows + fit[2]
+    plane[patch == 0] = np.nan
+    return plane
+
+
+def clean_cell(cell: np.ndarray) -> np.ndarray:
+    """The per-cell clean-up of builder.py:238-258 on one averaged cell (float64; the input is not modified): second background
+    fit, everything below 0.5 % of the centre dropped (eroded mask), the connected component of the centre kept and dilated
+    by one pixel, unit sum."""
+    from scipy.ndimage import binary_dilation, binary_erosion, label
+
+    with np.errstate(invalid="ignore", divide="ignore"):
+        patch = cell - background_plane(cell)
+        patch[patch == 0] = np.nan
+        centre = patch[patch.shape[0] // 2, patch.shape[1] // 2]
+        patch[binary_erosion(patch < 0.005 * centre, border_value=1)] = np.nan
+        patch[~np.isfinite(patch)] = 0
+        labels = label(patch)[0]
+        core = binary_dilation(labels == labels[labels.shape[0] // 2, labels.shape[1] // 2])
+        patch = patch * core
+        return patch / np.nansum(patch)
+
+
+class _Stack:
+    """A native builder handle: the device stack of accepted float32 patches."""
+
+    def __init__(self, psf_size: int, device: int, capacity: int) -> None:
+        from regularizepsf_amd import _native
+
+        self._native, self.psf_size = _native, int(psf_size)
+        self._handle = ctypes.c_void_p()
+        _native.check(_native.lib().rpsf_builder_create(ctypes.byref(self._handle), device, self.psf_size, max(1, int(capacity))))
+
+    def add_frame(self, frame: np.ndarray, rounded: np.ndarray, shift: np.ndarray, saturation_threshold: float, star_minimum: float,
+                  star_maximum: float) -> np.ndarray:
+        n = self._native
+        if frame.dtype != np.float32:
+            frame = frame.astype(np.float64, copy=False)
+        frame = np.ascontiguousarray(frame)
+        corners = np.ascontiguousarray(rounded, np.int32).reshape(-1, 2)
+        frac = np.ascontiguousarray(shift, np.float64).reshape(-1, 2)
+        flags = np.zeros(len(corners), np.uint8)
+        n.check(n.lib().rpsf_builder_add_frame(self._handle, n._ptr(frame), int(frame.dtype == np.float64), frame.shape[0], frame.shape[1],
+                                               len(corners), n._ptr(corners), n._ptr(frac), float(saturation_threshold),
+                                               float(star_minimum), float(star_maximum), n._ptr(flags)))
+        return flags
+
+    def load(self, patches: np.ndarray) -> None:
+        p = np.ascontiguousarray(patches, np.float32).reshape(-1, self.psf_size, self.psf_size)
+        self._native.check(self._native.lib().rpsf_builder_load_patches(self._handle, len(p), self._native._ptr(p)))
+
+    def __len__(self) -> int:
+        count = ctypes.c_size_t(0)
+        self._native.check(self._native.lib().rpsf_builder_count(self._handle, ctypes.byref(count)))
+        return count.value
+
+    def patches(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        count = len(self) - first if count is None else count
+        out = np.empty((count, self.psf_size, self.psf_size), np.float32)
+        self._native.check(self._native.lib().rpsf_builder_patches(self._handle, first, count, self._native._ptr(out)))
+        return out
+
+    def average(self, method: str, percentile: float, offsets: np.ndarray, members: np.ndarray) -> np.ndarray:
+        n = self._native
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        members = np.ascontiguousarray(members, np.int32)
+        cells = np.empty((len(offsets) - 1, self.psf_size, self.psf_size), np.float64)
+        n.check(n.lib().rpsf_builder_average(self._handle, AVERAGE_METHODS[method], float(percentile), len(offsets) - 1, n._ptr(offsets),
+                                             n._ptr(members), n._ptr(cells)))
+        return cells
+
+    def kernel_ms(self) -> tuple[float, float]:
+        """Device time of the last patch (B1) and the last averaging (B2) launch."""
+        b1, b2 = ctypes.c_double(0), ctypes.c_double(0)
+        self._native.check(self._native.lib().rpsf_builder_kernel_ms(self._handle, ctypes.byref(b1), ctypes.byref(b2)))
+        return b1.value, b2.value
+
+    def close(self) -> None:
+        if self._handle is not None and self._handle.value:
+            self._native.lib().rpsf_builder_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self) -> None:
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+class ArrayPSFBuilder:
+    """A builder that takes a series of images and constructs an ArrayPSF to represent their implicit PSF."""
+
+    def __init__(self, psf_size: int, device: int = 0) -> None:
+        self._psf_size = psf_size
+        self._device = device
+
+    @property
+    def psf_size(self) -> int:
+        return self._psf_size
+
+    def build(self, images, sep_mask=None, hdu_choice: int | None = 0, num_workers: int | None = None,  # noqa: ARG002
+              interpolation_scale: int = 1, star_threshold: int = 3, average_method: str = "median", percentile: float = 50,
+              saturation_threshold: float = np.inf, image_mask: np.ndarray | None = None, star_minimum: float = 0,
+              star_maximum: float = np.inf, sqrt_compressed: bool = False, return_patches: bool = False, *,
+              stars: list[np.ndarray] | None = None):
+        """Build the PSF model: ``(ArrayPSF, counts)`` or, with ``return_patches``, ``(ArrayPSF, counts, patches)``.
+
+        Parameters, their order and their defaults are the reference's (builder.py:139-153); ``num_workers`` is accepted and
+        ignored (the patches are cut on the GPU).  ``stars`` is this package's addition: one ``(k, 2)`` float array of
+        ``(row, col)`` star positions per frame - the ``y``, ``x`` columns of ``sep.extract`` - which skips star finding.
+        ``patches`` maps ``(frame, row - N / 2, col - N / 2)`` to the float64 copy of the float32 patch kept on the device
+        (background-subtracted, not normalised); ``counts`` maps every corner of the covering to its number of stars.
+        """
+        size = self._psf_size
+        if interpolation_scale != 1:
+            msg = "interpolation_scale != 1 is not implemented (the reference resamples with scikit-image, which this package does not depend on)"
+            raise NotImplementedError(msg)
+        if image_mask is not None:
+            msg = "image_mask is not implemented (the reference spline-shifts the boolean mask; what that yields is defined by SciPy's cast only)"
+            raise NotImplementedError(msg)
+        if sqrt_compressed:
+            msg = "sqrt_compressed=True is not implemented (the decompression scale comes from a FITS header)"
+            raise NotImplementedError(msg)
+        if average_method not in AVERAGE_METHODS:
+            msg = f"Unknown method {average_method}."
+            raise PSFBuilderError(msg)
+        frames = _frames(images)
+        if stars is None:
+            masks = [None] * len(frames) if sep_mask is None else _frames(sep_mask)
+            stars = [_find_stars(frame, star_threshold, mask) for frame, mask in zip(frames, masks)]
+        elif len(stars) != len(frames):
+            msg = f"stars has {len(stars)} entries for {len(frames)} frames"
+            raise ValueError(msg)
+
+        stack = _Stack(size, self._device, sum(len(np.asarray(s).reshape(-1, 2)) for s in stars))
+        try:
+            keys: dict[tuple[int, float, float], int] = {}  # patch key -> index into the device stack, in insertion order
+            for i, (frame, positions) in enumerate(zip(frames, stars)):
+                corner, rounded, shift = star_geometry(positions, size)
+                # equal keys of one frame: dict.update keeps the first position and the last value - the same patch either way
+                _, first = np.unique(corner, axis=0, return_index=True)
+                first.sort()
+                flags = stack.add_frame(frame, rounded[first], shift[first], saturation_threshold, star_minimum, star_maximum)
+                if np.any(flags == DEGENERATE_RING):
+                    bad = corner[first][flags == DEGENERATE_RING][0] + size / 2
+                    msg = (f"Frame {i}: the patch of the star at {tuple(float(v) for v in bad)} has fewer than three border pixels below "
+                           "its centre (or all on one line), so no background plane can be fitted.")
+                    raise PSFBuilderError(msg)
+                for row, col in corner[first][flags == ACCEPTED].tolist():
+                    keys[(i, row, col)] = len(keys)
+            corners = calculate_covering(frames[0].shape, size)
+            offsets, members = cell_membership(np.array([k[1:] for k in keys], np.float64).reshape(-1, 2), corners, size)
+            method = "median" if (average_method == "percentile" and percentile == 50) else average_method
+            cells = stack.average(method, percentile, offsets, members)
+            patches = None
+            if return_patches:
+                values = stack.patches().astype(np.float64)
+                patches = {key: values[index] for key, index in keys.items()}
+        finally:
+            stack.close()
+
+        counts = {tuple(corner): int(offsets[c + 1] - offsets[c]) for c, corner in enumerate(corners)}
+        coordinates = [(corner[0], corner[1]) for corner in corners]
+        values = np.stack([clean_cell(cell) for cell in cells])
+        psf = ArrayPSF(IndexedCube(coordinates, values))
+        return (psf, counts, patches) if return_patches else (psf, counts)

@@ -1,0 +1,312 @@
+// builder.hip - the PSF builder: ArrayPSFBuilder.build of the reference downstream of the star list
+// (regularizepsf/image_processing.py:76-121 per star, regularizepsf/builder.py:53-125 per lattice cell).
+//
+//   B1  builder_patch_kernel    one workgroup per star, the N x N patch in LDS as float64 (N = 128: 141 KiB of the 160 KiB),
+//                               phases of rpsf_core_builder.hpp separated by barriers; writes the float32 patch to a staging
+//                               slot and one flag byte.  A small copy kernel appends the accepted patches to the stack.
+//   B2  builder_average_kernel  one lane per pixel of a cell, the cell's member list walked in CSR order.
+//
+// INVARIANT: every patch in the stack is finite and has a non-zero centre.  B1 accepts nothing else (a zero or non-finite
+// pixel, or a value outside float32, rejects the patch), rpsf_builder_load_patches refuses anything else - so every sample
+// (double)p / (double)centre B2 sees is finite and the order-preserving key of rpsf_core_builder.hpp is total.
+// No atomics anywhere: flags are plain stores of one value, sums run in list order - two builds of one input agree bit for bit.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/rpsf.h"
+#include "rpsf_core_builder.hpp"
+
+using namespace rpsfb;
+
+int rpsf_detail_fail(int code, const std::string& msg);  // rpsf.hip: sets rpsf_last_error of the calling thread
+static int fail(int code, const std::string& msg) { return rpsf_detail_fail(code, msg); }
+#define HIP_TRY(expr)                                                                                               \
+  do {                                                                                                              \
+    hipError_t e_ = (expr);                                                                                         \
+    if (e_ != hipSuccess)                                                                                           \
+      return fail(e_ == hipErrorOutOfMemory ? RPSF_E_NOMEM : RPSF_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+struct B1Params {
+  const float* image;
+  int height, width, N;
+  const int32_t* corners;  // n x 2 rounded corners (row, col)
+  const double* frac;      // n x 2 shift amounts
+  double saturation, star_minimum, star_maximum;
+  float* staging;  // n x N x N
+  uint8_t* flags;  // n
+};
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void builder_patch_kernel(B1Params q) {
+  extern __shared__ double builder_lds[];
+  const int N = q.N, tid = threadIdx.x, star = blockIdx.x;
+  const Lds s = carve(builder_lds, N);
+  b1_tables(tid, N, q.frac[2 * star], q.frac[2 * star + 1], s);
+  b1_gather(tid, THREADS, N, q.image, q.height, q.width, q.corners[2 * star], q.corners[2 * star + 1], s);
+  __syncthreads();
+  b1_prefilter(tid, N, 0, s);
+  __syncthreads();
+  b1_prefilter(tid, N, 1, s);
+  __syncthreads();
+  double v[MAX_PPT];
+  for (int axis = 0; axis < 2; ++axis) {
+    b1_taps_read(tid, THREADS, N, axis, s, v);
+    __syncthreads();
+    b1_taps_write(tid, THREADS, N, s, v);
+    __syncthreads();
+  }
+  b1_scan(tid, THREADS, N, s);
+  __syncthreads();
+  b1_plane(tid, N, s);
+  __syncthreads();
+  b1_finish(tid, THREADS, N, q.saturation, s, q.staging + (size_t)star * N * N);
+  __syncthreads();
+  if (tid == 0) q.flags[star] = b1_verdict(N, q.star_minimum, q.star_maximum, s);
+}
+
+// accepted patch i of the frame: staging slot source[i] -> stack slot first + i
+__global__ __launch_bounds__(256) void builder_append_kernel(const float* staging, const int32_t* source, float* stack, int npix) {
+  const float* from = staging + (size_t)source[blockIdx.x] * npix;
+  float* to = stack + (size_t)blockIdx.x * npix;
+  for (int p = threadIdx.x; p < npix; p += 256) to[p] = from[p];
+}
+
+__global__ __launch_bounds__(256) void builder_average_kernel(const float* stack, const int64_t* offsets, const int32_t* members, int N,
+                                                              int method, double quantile, double* cells) {
+  const int cell = blockIdx.x, pixel = blockIdx.y * 256 + threadIdx.x;
+  if (pixel >= N * N) return;
+  const int64_t first = offsets[cell];
+  cells[(size_t)cell * N * N + pixel] = b2_pixel(stack, members + first, (long)(offsets[cell + 1] - first), N, pixel, method, quantile);
+}
+
+namespace {
+template <class T>
+struct Buf {  // a device array that only ever grows
+  T* p = nullptr;
+  size_t cap = 0;
+  hipError_t reserve(size_t count) {
+    if (count <= cap) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr, cap = 0;
+    const hipError_t e = hipMalloc(&p, count * sizeof(T));
+    if (e == hipSuccess) cap = count;
+    return e;
+  }
+  ~Buf() {
+    if (p) (void)hipFree(p);
+  }
+};
+}  // namespace
+
+struct rpsf_builder {
+  int device = 0, N = 0;
+  size_t count = 0;
+  float* stack = nullptr;
+  size_t capacity = 0;
+  Buf<float> frame, staging;
+  Buf<int32_t> corners, source, members;
+  Buf<double> frac, cells;
+  Buf<uint8_t> flags;
+  Buf<int64_t> offsets;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  double patch_ms = 0, average_ms = 0;
+  ~rpsf_builder() {
+    if (stack) (void)hipFree(stack);
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+static int grow_stack(rpsf_builder* b, size_t need) {
+  if (need <= b->capacity) return RPSF_OK;
+  size_t cap = b->capacity ? b->capacity : 1;
+  while (cap < need) cap *= 2;
+  const size_t npix = (size_t)b->N * b->N;
+  float* bigger = nullptr;
+  HIP_TRY(hipMalloc(&bigger, cap * npix * sizeof(float)));
+  if (b->count) {
+    const hipError_t e = hipMemcpy(bigger, b->stack, b->count * npix * sizeof(float), hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(bigger);
+      HIP_TRY(e);
+    }
+  }
+  if (b->stack) (void)hipFree(b->stack);
+  b->stack = bigger, b->capacity = cap;
+  return RPSF_OK;
+}
+
+static int elapsed(rpsf_builder* b, double* ms) {
+  float t = 0;
+  HIP_TRY(hipEventSynchronize(b->ev[1]));
+  HIP_TRY(hipEventElapsedTime(&t, b->ev[0], b->ev[1]));
+  *ms = t;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_builder_create(rpsf_builder** out, int device, int patch_size, size_t capacity) {
+  if (!out) return fail(RPSF_E_BADARG, "null argument");
+  if (patch_size < MIN_N || patch_size > MAX_N)
+    return fail(RPSF_E_UNSUPPORTED, "builder patch size " + std::to_string(patch_size) + " is outside 4..128");
+  HIP_TRY(hipSetDevice(device));
+  rpsf_builder* b = new rpsf_builder;
+  b->device = device, b->N = patch_size;
+  auto made = [&]() -> int {
+    for (auto& e : b->ev) HIP_TRY(hipEventCreate(&e));
+    if (patch_size > 64) {
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&builder_patch_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds_bytes(MAX_N)));
+    } else {
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&builder_patch_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds_bytes(64)));
+    }
+    return grow_stack(b, capacity ? capacity : 1);
+  }();
+  if (made != RPSF_OK) {
+    delete b;
+    return made;
+  }
+  *out = b;
+  return RPSF_OK;
+}
+
+extern "C" void rpsf_builder_destroy(rpsf_builder* b) {
+  if (!b) return;
+  (void)hipSetDevice(b->device);
+  delete b;
+}
+
+extern "C" int rpsf_builder_add_frame(rpsf_builder* b, const void* image_host, int image_is_f64, int height, int width, int n_stars,
+                                      const int32_t* corners_i32, const double* frac_f64, double saturation_threshold,
+                                      double star_minimum, double star_maximum, uint8_t* accepted_u8_host) {
+  if (!b || !image_host) return fail(RPSF_E_BADARG, "null argument");
+  if (height < 2 || width < 2) return fail(RPSF_E_BADARG, "a frame needs at least 2 x 2 pixels");
+  if (n_stars < 0) return fail(RPSF_E_BADARG, "n_stars is negative");
+  if (n_stars == 0) return RPSF_OK;
+  if (!corners_i32 || !frac_f64 || !accepted_u8_host) return fail(RPSF_E_BADARG, "null argument");
+  const int N = b->N;
+  const size_t npix = (size_t)N * N, fpix = (size_t)height * width;
+  for (int i = 0; i < 2 * n_stars; ++i) {
+    // the reference's corner is round(position - N / 2) of a position inside the frame; anything within one frame of it is gathered
+    // through the mirror map, anything farther is a caller's mistake
+    const long limit = i % 2 ? width : height;
+    if (corners_i32[i] < -N - limit || corners_i32[i] > 2 * limit) return fail(RPSF_E_BADARG, "a star's corner lies far outside the frame");
+    if (!(std::fabs(frac_f64[i]) <= 2.0)) return fail(RPSF_E_BADARG, "a shift amount is not within two pixels");
+  }
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(b->frame.reserve(fpix));
+  if (image_is_f64) {  // the frame crosses PCIe once, as float32 - what every apply path of the library uploads
+    std::vector<float> narrow(fpix);
+    const double* src = static_cast<const double*>(image_host);
+    for (size_t i = 0; i < fpix; ++i) narrow[i] = (float)src[i];
+    HIP_TRY(hipMemcpy(b->frame.p, narrow.data(), fpix * sizeof(float), hipMemcpyHostToDevice));
+  } else {
+    HIP_TRY(hipMemcpy(b->frame.p, image_host, fpix * sizeof(float), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(b->corners.reserve(2 * (size_t)n_stars));
+  HIP_TRY(b->frac.reserve(2 * (size_t)n_stars));
+  HIP_TRY(b->flags.reserve(n_stars));
+  HIP_TRY(b->staging.reserve((size_t)n_stars * npix));
+  HIP_TRY(hipMemcpy(b->corners.p, corners_i32, 2 * (size_t)n_stars * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->frac.p, frac_f64, 2 * (size_t)n_stars * sizeof(double), hipMemcpyHostToDevice));
+  const B1Params q{b->frame.p, height, width, N, b->corners.p, b->frac.p, saturation_threshold, star_minimum, star_maximum,
+                   b->staging.p, b->flags.p};
+  HIP_TRY(hipEventRecord(b->ev[0], nullptr));
+  if (N > 64) {
+    hipLaunchKernelGGL(builder_patch_kernel<1024>, dim3(n_stars), dim3(1024), lds_bytes(N), nullptr, q);
+  } else {
+    hipLaunchKernelGGL(builder_patch_kernel<256>, dim3(n_stars), dim3(256), lds_bytes(N), nullptr, q);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(b->ev[1], nullptr));
+  HIP_TRY(hipMemcpy(accepted_u8_host, b->flags.p, n_stars, hipMemcpyDeviceToHost));
+  if (const int rc = elapsed(b, &b->patch_ms)) return rc;
+  std::vector<int32_t> source;
+  for (int i = 0; i < n_stars; ++i)
+    if (accepted_u8_host[i] == ACCEPTED) source.push_back(i);
+  if (source.empty()) return RPSF_OK;
+  if (const int rc = grow_stack(b, b->count + source.size())) return rc;
+  HIP_TRY(b->source.reserve(source.size()));
+  HIP_TRY(hipMemcpy(b->source.p, source.data(), source.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(builder_append_kernel, dim3((unsigned)source.size()), dim3(256), 0, nullptr, b->staging.p, b->source.p,
+                     b->stack + b->count * npix, (int)npix);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  b->count += source.size();
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_builder_count(const rpsf_builder* b, size_t* count) {
+  if (!b || !count) return fail(RPSF_E_BADARG, "null argument");
+  *count = b->count;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_builder_patches(rpsf_builder* b, size_t first, size_t count, float* host) {
+  if (!b || (!host && count)) return fail(RPSF_E_BADARG, "null argument");
+  if (first > b->count || count > b->count - first) return fail(RPSF_E_BADARG, "patch range outside the stack");
+  if (!count) return RPSF_OK;
+  const size_t npix = (size_t)b->N * b->N;
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipMemcpy(host, b->stack + first * npix, count * npix * sizeof(float), hipMemcpyDeviceToHost));
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_builder_load_patches(rpsf_builder* b, size_t count, const float* host) {
+  if (!b || (!host && count)) return fail(RPSF_E_BADARG, "null argument");
+  if (!count) return RPSF_OK;
+  const size_t npix = (size_t)b->N * b->N, centre = (size_t)(b->N / 2) * b->N + b->N / 2;
+  for (size_t i = 0; i < count * npix; ++i)
+    if (!std::isfinite(host[i])) return fail(RPSF_E_BADARG, "patch " + std::to_string(i / npix) + " has a non-finite pixel");
+  for (size_t i = 0; i < count; ++i)
+    if (host[i * npix + centre] == 0.0f) return fail(RPSF_E_BADARG, "patch " + std::to_string(i) + " has a zero centre pixel");
+  HIP_TRY(hipSetDevice(b->device));
+  if (const int rc = grow_stack(b, b->count + count)) return rc;
+  HIP_TRY(hipMemcpy(b->stack + b->count * npix, host, count * npix * sizeof(float), hipMemcpyHostToDevice));
+  b->count += count;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_builder_average(rpsf_builder* b, int method, double percentile, int n_cells, const int64_t* cell_offsets_i64,
+                                    const int32_t* members_i32, double* cells_f64_host) {
+  if (!b || !cell_offsets_i64 || !cells_f64_host) return fail(RPSF_E_BADARG, "null argument");
+  if (method != RPSF_AVERAGE_MEAN && method != RPSF_AVERAGE_MEDIAN && method != RPSF_AVERAGE_PERCENTILE)
+    return fail(RPSF_E_BADARG, "unknown averaging method " + std::to_string(method));
+  if (method == RPSF_AVERAGE_PERCENTILE && !(percentile >= 0.0 && percentile <= 100.0))
+    return fail(RPSF_E_BADARG, "percentile outside 0..100");
+  if (n_cells <= 0) return fail(RPSF_E_BADARG, "n_cells must be positive");
+  if (cell_offsets_i64[0] != 0) return fail(RPSF_E_BADARG, "cell_offsets[0] must be 0");
+  for (int c = 0; c < n_cells; ++c)
+    if (cell_offsets_i64[c + 1] < cell_offsets_i64[c]) return fail(RPSF_E_BADARG, "cell_offsets must not decrease");
+  const size_t total = (size_t)cell_offsets_i64[n_cells];
+  if (total && !members_i32) return fail(RPSF_E_BADARG, "null argument");
+  for (size_t i = 0; i < total; ++i)
+    if (members_i32[i] < 0 || (size_t)members_i32[i] >= b->count)
+      return fail(RPSF_E_BADARG, "member " + std::to_string(i) + " is not a patch of the stack");
+  const size_t npix = (size_t)b->N * b->N;
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(b->offsets.reserve((size_t)n_cells + 1));
+  HIP_TRY(b->members.reserve(total ? total : 1));
+  HIP_TRY(b->cells.reserve((size_t)n_cells * npix));
+  HIP_TRY(hipMemcpy(b->offsets.p, cell_offsets_i64, ((size_t)n_cells + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  if (total) HIP_TRY(hipMemcpy(b->members.p, members_i32, total * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipEventRecord(b->ev[0], nullptr));
+  hipLaunchKernelGGL(builder_average_kernel, dim3(n_cells, (unsigned)((npix + 255) / 256)), dim3(256), 0, nullptr, b->stack, b->offsets.p,
+                     b->members.p, b->N, method, percentile / 100.0, b->cells.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(b->ev[1], nullptr));
+  HIP_TRY(hipMemcpy(cells_f64_host, b->cells.p, (size_t)n_cells * npix * sizeof(double), hipMemcpyDeviceToHost));
+  return elapsed(b, &b->average_ms);
+}
+
+extern "C" int rpsf_builder_kernel_ms(const rpsf_builder* b, double* patch_ms, double* average_ms) {
+  if (!b) return fail(RPSF_E_BADARG, "null argument");
+  if (patch_ms) *patch_ms = b->patch_ms;
+  if (average_ms) *average_ms = b->average_ms;
+  return RPSF_OK;
+}

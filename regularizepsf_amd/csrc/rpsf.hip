@@ -56,6 +56,9 @@ static int fail(int code, const std::string& msg) {
                   std::string(#expr) + ": " + hipGetErrorString(e_));                                   \
   } while (0)
 
+// the same for the translation units that implement entry points of their own (csrc/builder.hip)
+__attribute__((visibility("hidden"))) int rpsf_detail_fail(int code, const std::string& msg) { return fail(code, msg); }
+
 extern "C" const char* rpsf_last_error(void) { return g_err.c_str(); }
 
 // Development sweeps read their knobs from the environment ONLY in builds made with -DRPSF_DEV_ENV (scripts/, never the product): a stray variable
