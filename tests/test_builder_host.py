@@ -193,6 +193,9 @@ def test_emulated_patch_kernel_flags():
         _, rounded, shift = bld.star_geometry(centre, n)
         patches, flags = bc.emu_patches(frame, n, rounded, shift)
         assert flags.tolist() == [bld.ACCEPTED] and np.isfinite(patches).all()
+        want, want_flags = bc.oracle_patches(frame, n, rounded, shift)  # ... and give what float64 SciPy gives
+        assert want_flags.tolist() == [bld.ACCEPTED]
+        assert np.abs(patches - want).max() <= TOL * np.abs(want).max()
 
 
 def test_emulated_average_kernel_against_numpy():
@@ -213,3 +216,72 @@ def test_emulated_kernels_end_to_end_against_the_reference_cells(name):
         cells = bc.emu_average(stack, index, q, g["offsets"], g["members"])
         for got, want in zip(cells, g[f"cells_{method}"]):
             assert np.abs(got - want).max() <= TOL * np.abs(want).max()
+
+
+# ------------------------------------------------------------------------------------------------ every patch-size path (float64 SciPy oracle)
+# The cases and criteria of tests/test_gpu_builder_sizes.py, shared through tests/builder_cases.py.  The emulator runs the threads one
+# after another and clears its LDS between stars, so this side checks the arithmetic and the index algebra of each size path; barriers,
+# the LDS carve and the launch itself are the GPU side's.
+SIZES = list(bc.SIZE_CASES)
+
+
+def _emulated_stack(name):
+    """Kernel B1 on the emulator over every frame of a size case: (the accepted float32 patches in star order, all flags)."""
+    case = bc.size_case(name)
+    kept, flags = [], []
+    for frame, rounded, shift in zip(case["frames"], case["rounded"], case["shift"]):
+        patches, accepted = bc.emu_patches(frame, case["n"], rounded, shift, *case["thresholds"])
+        kept.append(patches[accepted == 1])
+        flags.append(accepted)
+    return np.concatenate(kept), np.concatenate(flags)
+
+
+@pytest.mark.parametrize("name", SIZES)
+def test_size_cases_are_well_posed(name):
+    case = bc.size_case(name)
+    bc.well_posed(case)
+    assert all(8 <= len(pos) <= 12 for pos in case["stars"])
+    # the star whose corner is k + 0.5 on both axes
+    assert all(np.array_equal(np.abs(corner[-1] - np.rint(corner[-1])), [0.5, 0.5]) for corner in case["corner"])
+    if case["n"] == 4:  # a corner that is an exact integer (shift -0.5) makes a ring pixel equal the centre there: none in this case
+        assert not np.any(np.concatenate(case["shift"]) == -0.5)
+
+
+@pytest.mark.parametrize("name", SIZES)
+def test_emulated_patch_kernel_per_size_against_scipy(name):
+    bc.check_size_patches(name, *_emulated_stack(name))
+
+
+def _emulated_average(case):
+    return lambda method, q: bc.emu_average(case["stack"], bld.AVERAGE_METHODS[method], q, case["offsets"], case["members"])
+
+
+def test_emulated_average_kernel_with_ties_and_percentile_ends():
+    bc.check_b2(bc.tie_case(), _emulated_average(bc.tie_case()))
+
+
+@pytest.mark.parametrize("n", bc.B2_SIZES)
+def test_emulated_average_kernel_per_size(n):
+    bc.check_b2(bc.b2_size_case(n), _emulated_average(bc.b2_size_case(n)))
+
+
+@pytest.mark.parametrize("name", bc.END_TO_END)
+def test_emulated_kernels_frames_to_cells_per_size(name):
+    stack, flags = _emulated_stack(name)
+    assert np.array_equal(flags, np.concatenate(bc.size_case(name)["flags"]))
+    bc.check_end_to_end(name, lambda method, q, offsets, members: bc.emu_average(stack, bld.AVERAGE_METHODS[method], q, offsets, members))
+
+
+def test_emulated_patch_kernel_on_the_growth_frames_and_beyond_float32():
+    """The two remaining inputs of the GPU tests' storage section, arithmetic only."""
+    case = bc.growth_case()
+    bc.well_posed(case)
+    for frame, rounded, shift, want, want_flags in zip(case["frames"], case["rounded"], case["shift"], case["patches"], case["flags"]):
+        patches, flags = bc.emu_patches(frame, case["n"], rounded, shift)
+        assert np.array_equal(flags, want_flags) and want_flags.all()
+        assert np.all(np.abs(patches - want).max(axis=(1, 2)) <= TOL * np.abs(want).max(axis=(1, 2)))
+    bright = bc.near_float32_max_case()
+    kept = bright["patches"][0][0]  # float64 keeps the patch: finite, but its maximum does not fit float32 ...
+    assert np.isfinite(kept).all() and kept.max() > 1.1 * float(np.finfo(np.float32).max) and bright["flags"][0].tolist() == [bld.ACCEPTED]
+    _, flags = bc.emu_patches(bright["frames"][0], 16, bright["rounded"][0], bright["shift"][0])
+    assert flags.tolist() == [bld.REJECTED]  # ... so the kernel, whose stack is float32 and finite, does not
