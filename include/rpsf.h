@@ -107,7 +107,10 @@ enum {
   RPSF_OPT_HOST_BANDS = 5,    /* -1 automatic, else the row bands a single host frame is cut into (0 or 1: none) */
   RPSF_OPT_STREAM_GROUP = 6,  /* 0 automatic, else frames per group of the streamed host path */
   RPSF_OPT_STREAM_DEPTH = 7,  /* 0 automatic, else groups in flight of the streamed host path */
-  RPSF_OPT_DEBUG_ORPHAN = 8   /* testing aid of the direct overlap-add: every value-th workgroup behaves as if placed on a foreign XCD */
+  RPSF_OPT_DEBUG_ORPHAN = 8,  /* testing aid of the direct overlap-add: every value-th workgroup behaves as if placed on a foreign XCD */
+  RPSF_OPT_HEAD_KPREFETCH = 9 /* 0 / 1: persistent launches of a 256-pixel plan - the head summing workgroups touch the transfer kernel of the
+                                 first round's patches before they sum (default 0: measured a loss; ignored by other plans).
+                                 Changes no value of the result. */
 };
 int rpsf_plan_set_option(rpsf_plan* plan, int option, int value);
 int rpsf_plan_sweep_info(const rpsf_plan* plan, int* regions, long* jobs, long* patch_slots, int* slabs_per_phase);

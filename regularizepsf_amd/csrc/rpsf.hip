@@ -188,6 +188,8 @@ struct PatchPath {
   bool prefetch = false;             // persistent launches: head summing workgroups touch the image first (RPSF_PREFETCH)
   DevBuf<uint32_t> d_prefetch_tiles;  // per chunk: lattice tiles in the order the chunk's patches first need them
   uint32_t prefetch_first[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int k_prefetch = 0;                // (measured a loss, DESIGN.md 5.10: off) 256-pixel persistent launches: the head summing workgroups touch the first
+                                     // round's K before they sum (RPSF_OPT_HEAD_KPREFETCH)
   int head_patches = 0;              // (measured neutral, profiles/r03i: off) persistent launches: patches a head summing workgroup computes before it sums (RPSF_HEAD_PATCHES)
   bool fuse_pays = false;            // the second-generation plans (N = 128, 256)
   // Persistent patch workgroups (patch_kernel2_256p; fused launches of the 256-pixel plan): per-XCD slot queues, never reset
@@ -232,7 +234,7 @@ struct PlanStream {
   hipStream_t stream = nullptr;
   bool borrowed_stream = false;  // a view runs on its parent's
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_busy = nullptr;    // end of the last apply (applies on different streams are serialised)
+  hipEvent_t ev_busy = nullptr;    // end of the last apply (applies on different streams are serialised); recorded once the plan has seen a second stream
   ~PlanStream() {
     if (ev_busy) (void)hipEventDestroy(ev_busy);
     for (auto& e : ev)
@@ -267,6 +269,7 @@ struct rpsf_plan : PlanStream {
   int last_host_bands = 0;  // row bands the last single host frame was cut into (rpsf_plan_host_bands)
   hipStream_t last_stream = nullptr;
   bool busy_valid = false;
+  bool multi_stream = false;  // the plan has been applied on more than one stream: applies record ev_busy (launch_apply)
   // the lattice (setup_lattice): read by the planes, the sweep kernel and host_one_frame
   int lat_r0 = 0, lat_c0 = 0, nti = 0, ntj = 0;
   DevBuf<uint8_t> d_cover;
@@ -844,7 +847,7 @@ static int plan_create_impl(rpsf_plan** out, int device, int patch_size, int n_p
     }
     if (parent) {  // tables, packed K and error word are the parent's (owner())
       p->have_k = parent->have_k;
-      p->overlap_mode = parent->overlap_mode, p->patch.stagger_us = parent->patch.stagger_us;
+      p->overlap_mode = parent->overlap_mode, p->patch.stagger_us = parent->patch.stagger_us, p->patch.k_prefetch = parent->patch.k_prefetch;
       return RPSF_OK;
     }
     return dispatch_patch(p->patch.v2, N, [&]<class T>() -> int {
@@ -1074,6 +1077,7 @@ struct PatchLaunch {
   int stagger_ticks, stagger_blocks;
   int sum_first, frame_major, plane_nt;  // fused and persistent
   int rows, head_patches, prefetch;      // persistent: patch workgroups per XCD, ...
+  int k_prefetch;                        // persistent, 256-pixel plan: first-round K prefetch by the head summing workgroups (0 / 1)
   uint32_t xq_base[8], xq_draws[8];      // persistent: where this launch's draws from the slot queue of each XCD start, and how many it makes
   uint32_t sum_queue_base, sum_queue_draws;  // fused and persistent: the same for the tile queue
 };
@@ -1142,6 +1146,7 @@ static PatchLaunch patch_launch_for(const rpsf_plan* p, const float* d_img, cons
   // of its XCD's chunk first (RPSF_HEAD_PATCHES=0: off)
   L.head_patches = p->patch.head_patches;
   L.prefetch = p->patch.prefetch && p->patch.d_prefetch_tiles ? 1 : 0;
+  L.k_prefetch = N256 && !L.head_patches ? p->patch.k_prefetch : 0;
   // persistent workgroups keep the phase they start with: holding the resident ones back by up to 10 us spreads the
   // store bursts of the chip over the patch period (profiles/r02ai, r02ak: -2..3 % from four rounds of patches on; with the
   // plane stores kept in the Infinity Cache, r02av: 0.210 / 0.208 / 0.193 / 0.190 / 0.189 / 0.191 / 0.195 ms at 0 / 5 / 8 / 10 / 12 / 15 / 20 us)
@@ -1207,6 +1212,7 @@ static PatchParams patch_params(const rpsf_plan* p, const PatchLaunch& L, const 
   if (L.form != PatchLaunch::PERSISTENT) return pp;
   pp.persist = L.rows, pp.xq = p->patch.d_xq;
   pp.head_patches = L.head_patches, pp.prefetch = L.prefetch, pp.prefetch_tiles = p->patch.d_prefetch_tiles;
+  pp.k_prefetch = L.k_prefetch, pp.k_patches = o->n_patches;
   for (int x = 0; x < 9; ++x) pp.prefetch_first[x] = p->patch.prefetch_first[x];
   for (int x = 0; x < 8; ++x) pp.xq_base[x] = L.xq_base[x];
   return pp;
@@ -1379,7 +1385,17 @@ static int launch_apply(rpsf_plan* p, const float* d_img, float* d_out, const rp
                      16 * plane_floats_needed(g) < ((size_t)1 << 32);  // the planes are addressed through one 32-bit buffer offset
   const size_t n_tiles = (size_t)p->nti * p->ntj;
   // The plan's scratch (planes, flags) serves one apply at a time: an apply on another stream waits for the last one.
-  if (p->busy_valid && st != p->last_stream) HIP_TRY(hipStreamWaitEvent(st, p->ev_busy, 0));
+  // A plan that has only ever been applied on one stream records nothing behind its launches (stream order is all it needs, and back-to-back
+  // applies then have nothing between them but what the caller puts there).  The first apply that arrives on another stream waits on the host,
+  // once, for what the plan has enqueued so far - device-wide, because the previous stream is the caller's and may be gone by now - and from
+  // then on every apply records the event and an apply on another stream waits for it.
+  if (p->busy_valid && st != p->last_stream) {
+    if (p->multi_stream) HIP_TRY(hipStreamWaitEvent(st, p->ev_busy, 0));
+    else {
+      HIP_TRY(hipDeviceSynchronize());
+      p->multi_stream = true;
+    }
+  }
   if (kind != OV_ATOMIC) {
     const size_t need = plane_floats_needed(g);
     if (need > p->patch.planes_floats || (size_t)b.frames > p->patch.planes_frames) {  // four planes per frame in flight
@@ -1438,7 +1454,7 @@ static int launch_apply(rpsf_plan* p, const float* d_img, float* d_out, const rp
   if (kind == OV_PLANES && !fused) rc = launch_sum(p, d_out, g, st, b);
   if (kind == OV_DIRECT) rc = launch_fixup(p, d_out, g, st, b);
   if (rc != RPSF_OK) return rc;
-  HIP_TRY(hipEventRecord(p->ev_busy, st));
+  if (p->multi_stream) HIP_TRY(hipEventRecord(p->ev_busy, st));
   p->last_stream = st, p->busy_valid = true;
   return RPSF_OK;
 }
@@ -1483,6 +1499,10 @@ extern "C" int rpsf_plan_set_option(rpsf_plan* p, int option, int value) {
     case RPSF_OPT_STREAM_DEPTH:
       if (value < 0 || value > 16) return fail(RPSF_E_BADARG, "RPSF_OPT_STREAM_DEPTH takes 0 (automatic) or 1..16");
       p->stream_depth_opt = value;
+      break;
+    case RPSF_OPT_HEAD_KPREFETCH:
+      if (value != 0 && value != 1) return fail(RPSF_E_BADARG, "RPSF_OPT_HEAD_KPREFETCH takes 0 or 1");
+      p->patch.k_prefetch = p->N == 256 ? value : 0;
       break;
     case RPSF_OPT_DEBUG_ORPHAN:
       if (value < 0) return fail(RPSF_E_BADARG, "RPSF_OPT_DEBUG_ORPHAN takes 0 (off) or a positive modulus");
@@ -2640,6 +2660,9 @@ extern "C" int rpsf_apply_device_timed(rpsf_plan* p, const void* image_dev, void
 
 // `iters` applies back to back between ONE pair of events on the plan's stream: the average apply as the device sees it, with nothing
 // between two launches that a caller's loop would not put there (per-apply event pairs cost a marker packet each: ~8 us of the 184 here).
+// Nothing at all, since launch_apply records its end-of-apply event only for plans that have been applied on more than one stream: that
+// record - no timing, nobody waiting - alone kept consecutive launches 5.8 us apart (kernel trace, profiles/head_kprefetch_ab.log: end of
+// launch i to start of launch i + 1, 5.80 -> 0.00 us; start to start 187.2 -> 182.7 us).
 extern "C" int rpsf_apply_device_loop_ms(rpsf_plan* p, const void* image_dev, void* out_dev, const rpsf_geometry* geom, int iters,
                                          double* ms_per_apply) {
   if (!p || !image_dev || !out_dev || iters <= 0 || !ms_per_apply) return fail(RPSF_E_BADARG, "bad argument");

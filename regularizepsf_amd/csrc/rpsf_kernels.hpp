@@ -296,6 +296,9 @@ struct PatchParams {
   const uint32_t* prefetch_tiles;  // per chunk: the lattice tiles of the image in the order the chunk's patches first need them ...
   uint32_t prefetch_first[9];      // ... chunk x owns entries [prefetch_first[x], prefetch_first[x + 1])
   int head_patches;  // persistent launches: the summing workgroups at the head of the grid compute this many (0 or 1) patches before they turn to summing
+  int k_prefetch;    // persistent launches of the 256-pixel plan: the head summing workgroups first touch the K of the first round's patches
+                     // (rpsf_kernels2.hpp, prefetch_first_round_k)
+  int k_patches;     // ... patches the K allocation behind g / gs holds
 };
 
 template <class C>

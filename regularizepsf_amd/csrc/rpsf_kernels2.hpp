@@ -183,6 +183,60 @@ struct ImagePrefetch {
   }
 };
 
+// K prefetch of the FIRST round by the head summing workgroups of a persistent launch (256-pixel plan, RPSF_OPT_HEAD_KPREFETCH).  The patch
+// workgroups of a launch all ask for their first patch's pair words inside the start-up stagger - the one burst of K that HBM cannot
+// deliver in time (the first round's pair-word step waits 4 us longer than the later ones) - while for the gather and
+// the forward stages before it nobody reads K at all, and the head summing workgroups have nothing to sum for a whole patch period.  Head
+// workgroup h touches the packed K of the first-round slots h / 8, h / 8 + sum_first / 8, ... of chunk h % 8 - the chunk whose patch
+// workgroups share its XCD, so the lines land in that L2 as well as in the memory-side cache: one dword per 128-byte line, word chunk by
+// word chunk (a patch needs chunk 0 first and the others a dependent round trip later each), the side array with chunk 0, in slot order
+// (which workgroup draws which slot is a race, so the stagger's order is not known here).  Not paced: the fabric is idle.  Nobody needs the
+// values - a ring of PF loads per thread stays in flight and the oldest is added to a sink when its register is needed again - and the
+// loads carry no streaming hint (lines loaded with it are not kept in the Infinity Cache).  Only the first round: from the
+// second on the fabric is busy and K would cross it twice (profiles/r03y).  Draws nothing from a queue and counts nothing.
+// OFF BY DEFAULT - measured, DESIGN.md 5.10 / profiles/head_kprefetch_ab.log: the first round's pair-word step does get shorter (9.9 -> 8.4 us),
+// but the launch gets LONGER, 0.182 -> 0.199 ms at 4096^2: with K at hand the workgroups leave the first round as close together as the
+// stagger put them, and every later round pays for it (period 34.0 -> 36.2 us).  Chunk 0 alone is neutral; two chunks already lose.
+template <class C>
+__device__ __forceinline__ void prefetch_first_round_k(const PatchParams& p, int blk) {
+  constexpr int PF = 8;
+  constexpr int CHUNK_FLOATS = C::KCH * C::T * 4;    // one word chunk of one patch: KCH pair words of 16 bytes per thread
+  constexpr int GS_LINES = C::GS_PER_PATCH * 8 / 128;  // 128-byte lines of a patch's side array
+  static_assert(CHUNK_FLOATS == C::T * 32, "one 128-byte line per thread, patch and word chunk");
+  static_assert(C::GS_PER_PATCH * 8 % 128 == 0 && C::T % GS_LINES == 0, "whole lines; whole patches per pass over the side arrays");
+  const int x = blk & 7, e0 = blk >> 3, step = p.sum_first >> 3;
+  // the distinct slots behind queue positions [0, persist) of the chunk (patch_body2's position-to-slot rule), clipped to what the chunk holds
+  int cnt = p.n_frames <= 1 || p.frame_major ? p.persist : (p.persist + p.n_frames - 1) / p.n_frames;
+  cnt = min(cnt, min(p.chunk - p.slot0, p.n_patches - x * p.chunk - p.slot0));
+  const int mine = cnt > e0 ? (cnt - e0 + step - 1) / step : 0;  // this workgroup's share (workgroup-uniform)
+  typedef const int __attribute__((address_space(4))) cint_as4;
+  auto patch_of = [&](int i) RPSF_AI {  // i-th slot of this workgroup -> patch index, or -1 (through the scalar cache: a uniform address)
+    const int seq = x * p.chunk + p.slot0 + e0 + i * step;
+    const int patch = ((const cint_as4*)(const void*)(p.desc + (p.seq_base + seq)))[2];
+    return patch >= 0 && patch < p.k_patches ? patch : -1;  // (never outside the plan's K allocation)
+  };
+  auto touch = [](const float* a) RPSF_AI {
+    return *reinterpret_cast<const volatile float*>(a);  // (plain policy; agent-scope loads measured the same)
+  };
+  float d[PF] = {};
+  float sink = 0.f;
+  const int t = (int)threadIdx.x;
+  for (int i0 = 0; i0 < mine; i0 += C::T / GS_LINES) {  // the side arrays: one line per thread, T / GS_LINES patches per pass
+    const int i = i0 + t / GS_LINES;
+    const int patch = i < mine ? patch_of(i) : -1;
+    if (patch >= 0) sink += touch(reinterpret_cast<const float*>(p.gs + (size_t)patch * C::GS_PER_PATCH) + (t % GS_LINES) * 32);
+  }
+  for (int c = 0; c < C::NCHUNK; ++c)
+    for (int i0 = 0; i0 < mine; i0 += PF)
+      StaticFor<0, PF>::run([&]<int U>() RPSF_AI {
+        const int patch = i0 + U < mine ? patch_of(i0 + U) : -1;  // (workgroup-uniform)
+        sink += d[U], d[U] = 0.f;
+        if (patch >= 0) d[U] = touch(reinterpret_cast<const float*>(p.g + (size_t)patch * C::G_PER_PATCH) + (size_t)c * CHUNK_FLOATS + t * 32);
+      });
+  StaticFor<0, PF>::run([&]<int U>() RPSF_AI { sink += d[U]; });
+  asm volatile("" ::"v"(sink));  // (the loads must happen; their values do not matter)
+}
+
 // HOT: the instantiation the persistent kernels are compiled from - a fused launch on colour planes whose geometry the launcher has
 // checked (hot_geometry, rpsf.hip): no float atomics, no direct mode, no pixel-by-pixel rim paths in the code (they cost the 256-pixel
 // kernel 29 spilled SGPRs and half of its 200 KB).  Everything else runs the one-patch-per-workgroup kernel patch_kernel2.
@@ -270,6 +324,8 @@ __device__ __forceinline__ void patch_body2(const PatchParams& p, REENTER&& reen
     }
     if constexpr (PERSIST && C::T == 512) {
       if (!again && blk < p.sum_first) {  // a head summing workgroup: the image prefetch is its side job
+        // ... and, ahead of it, the first round's K (workgroup-uniform, once per launch; not where the head workgroups compute a patch first)
+        if (p.k_prefetch && p.head_patches == 0) prefetch_first_round_k<C>(p, blk);
         ImagePrefetch<C> prefetch(p, blk, p.prefetch && p.n_frames <= 1);
         sum_tiles_worker<ImagePrefetch<C>&, 8, SUM_KNOWN_FUSED>(p.ts, 0, 1, prefetch);
         prefetch.finish();
