@@ -323,6 +323,37 @@ int rpsf_builder_average(rpsf_builder* builder, int method, double percentile, i
 /* Device time of the last B1 and the last B2 launch, milliseconds (either pointer may be NULL). */
 int rpsf_builder_kernel_ms(const rpsf_builder* builder, double* patch_ms, double* average_ms);
 
+/* find_stars: star positions for the builder, upstream of the star list.  The detector is this library's own, modelled on
+ * sep.Background + sep.extract WITHOUT deblending; it is not sep and its positions differ from sep's for blended or extended sources.
+ * A finder is made for one frame shape and one background box (8 .. 128 pixels, anything else: RPSF_E_UNSUPPORTED; frames of up to
+ * 2^31 - 1 pixels).  A pixel is usable when it is finite and not masked.  Everything is float64 on a frame rounded to float32 once;
+ * two runs on one input agree bit for bit. */
+typedef struct rpsf_stars rpsf_stars;
+int rpsf_stars_create(rpsf_stars** out, int device, int height, int width, int box);
+void rpsf_stars_destroy(rpsf_stars* finder);
+/* Kernel S1: upload the frame (float32, or float64 narrowed once) and the mask (height x width bytes, non-zero = ignore; NULL: none) and
+ * return the RAW background mesh, ceil(height / box) x ceil(width / box) float64 each: per box up to 16 rounds of clipping at
+ * |v - median| <= 3 sd (exact median, NumPy's rule), then level = median if sd == 0 or |mean - median| >= 0.3 sd, else
+ * 2.5 median - 1.5 mean, and rms = sd.  A box without a usable pixel gives NaN in both.  Filling and filtering the mesh is the caller's. */
+int rpsf_stars_background(rpsf_stars* finder, const void* image_host, int image_is_f64, const uint8_t* mask_host_or_null,
+                          double* level_host, double* rms_host);
+/* Kernels S2 - S4 on the frame uploaded last: level_host is the caller's filled and filtered mesh (finite everywhere), threshold_abs the
+ * absolute threshold T.  Residual d = pixel - bilinear surface through the mesh on usable pixels, 0 elsewhere; f = d filtered with
+ * [[1,2,1],[2,4,2],[1,2,1]] / 16 (zeros outside the frame); detected: f > T on a usable pixel; 8-connected components; kept:
+ * min_area <= area <= max_area (max_area < 0: no upper limit) and sum d > 0.  *count receives the number kept.
+ * RPSF_E_STATE before the first rpsf_stars_background. */
+int rpsf_stars_detect(rpsf_stars* finder, const double* level_host, double threshold_abs, long min_area, long max_area, size_t* count);
+/* Detections first .. first + count of the last detect, in raster order of each component's first pixel: count x 4 float64
+ * (row, col, flux, area) with (row, col) = (sum d row, sum d col) / sum d over the component's pixels, d unfiltered. */
+int rpsf_stars_positions(rpsf_stars* finder, size_t first, size_t count, double* out);
+/* Kernel S3 alone on a mask of the finder's shape (non-zero = detected): labels_host (int32) receives for every detected pixel the
+ * smallest linear index row * width + col of its 8-connected component and -1 elsewhere. */
+int rpsf_stars_label(rpsf_stars* finder, const uint8_t* detected_host, int32_t* labels_host);
+/* The tile S2 and S3 work on (either pointer may be NULL). */
+int rpsf_stars_info(const rpsf_stars* finder, int* tile_rows, int* tile_cols);
+/* Device time of the last S1, S2, S3 and S4 launches, milliseconds. */
+int rpsf_stars_kernel_ms(const rpsf_stars* finder, double ms[4]);
+
 /* Host-side helper for the saturation branch of apply (transform.py:135-138): sequential, row-major
  * NaN-ignoring neighbourhood-mean fill of the masked pixels of the float64 padded image (no GPU involved). */
 int rpsf_saturation_fill(double* padded, int rows, int cols, const uint8_t* mask, int neighborhood_width);

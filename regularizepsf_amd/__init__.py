@@ -26,6 +26,7 @@ from regularizepsf_amd.functional import (
 from regularizepsf_amd._native import pinned_empty
 from regularizepsf_amd.builder import ArrayPSFBuilder
 from regularizepsf_amd.psf import ArrayPSF
+from regularizepsf_amd.stars import find_stars
 from regularizepsf_amd.transform import ArrayPSFTransform
 from regularizepsf_amd.util import IndexedCube, calculate_covering
 
@@ -47,6 +48,7 @@ __all__ = [
     "VariedFunctionalPSF",
     "calculate_covering",
     "elliptical_gaussian",
+    "find_stars",
     "moffat",
     "pinned_empty",
     "simple_functional_psf",

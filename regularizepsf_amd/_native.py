@@ -105,6 +105,14 @@ _PROTOTYPES = {
     "rpsf_builder_load_patches": (c_int, [c_void_p, c_size_t, c_void_p]),
     "rpsf_builder_average": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p]),
     "rpsf_builder_kernel_ms": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
+    "rpsf_stars_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int]),
+    "rpsf_stars_destroy": (None, [c_void_p]),
+    "rpsf_stars_background": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "rpsf_stars_detect": (c_int, [c_void_p, c_void_p, c_double, ctypes.c_long, ctypes.c_long, POINTER(c_size_t)]),
+    "rpsf_stars_positions": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p]),
+    "rpsf_stars_label": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "rpsf_stars_info": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "rpsf_stars_kernel_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rpsf_saturation_fill": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
     "rpsf_dev_alloc": (c_int, [c_int, c_size_t, POINTER(c_void_p)]),
     "rpsf_dev_free": (c_int, [c_int, c_void_p]),
