@@ -289,8 +289,8 @@ int rpsf_psf_model_fft_device(int device, int model, int patch_size, int count, 
 
 /* ArrayPSFBuilder.build downstream of the star list (regularizepsf/builder.py:139-265): a builder owns a device stack of float32
  * N x N star patches (background-subtracted, not normalised), filled frame by frame and then averaged per lattice cell.  Star finding
- * (sep, image_processing.py:65-74), the cell membership (builder.py:45-51) and the final per-cell clean-up (builder.py:231-260) stay with
- * the caller.  N from 4 to 128, odd sizes included (anything else: RPSF_E_UNSUPPORTED); `capacity` patches are allocated at once, the
+ * (sep, image_processing.py:65-74) and the cell membership (builder.py:45-51) stay with the caller; the final per-cell clean-up
+ * (builder.py:231-260) is the caller's after rpsf_builder_average and the device's with rpsf_builder_model.  N from 4 to 128, odd sizes included (anything else: RPSF_E_UNSUPPORTED); `capacity` patches are allocated at once, the
  * stack grows by itself beyond that.  INVARIANT: every patch of the stack is finite and has a non-zero centre pixel [N/2][N/2]. */
 typedef struct rpsf_builder rpsf_builder;
 int rpsf_builder_create(rpsf_builder** out, int device, int patch_size, size_t capacity);
@@ -322,6 +322,19 @@ int rpsf_builder_average(rpsf_builder* builder, int method, double percentile, i
                          const int32_t* members_i32, double* cells_f64_host);
 /* Device time of the last B1 and the last B2 launch, milliseconds (either pointer may be NULL). */
 int rpsf_builder_kernel_ms(const rpsf_builder* builder, double* patch_ms, double* average_ms);
+/* The per-cell clean-up of builder.py:238-258, kernel B3, on n_cells (> 0) cells of N x N float64 the caller supplies (every pixel
+ * finite, else RPSF_E_BADARG): background plane fitted to the ring around the non-zero interior and subtracted, everything inside the
+ * region below 0.5 % of the centre dropped, the 4-connected component of the centre kept and dilated by one pixel, unit sum
+ * (DESIGN.md 3.6 has the definition step by step).  out_f64_host: n_cells x N x N float64; flags_u8_host[c] receives
+ * 0: cleaned (an all-zero cell leaves all NaN, as from the reference), 1: the cell is not zero and its ring has fewer than three pixels or
+ * all on one line - out holds the cell as it came, and the caller decides (the reference takes SciPy's minimum-norm fit there). */
+int rpsf_builder_clean(rpsf_builder* builder, int n_cells, const double* cells_f64_host, double* out_f64_host, uint8_t* flags_u8_host);
+/* rpsf_builder_average followed by rpsf_builder_clean with the averaged cells staying on the device: one download, of the cleaned cells
+ * and the flags.  out_f64_host of a cell with flag 1 holds the AVERAGED cell. */
+int rpsf_builder_model(rpsf_builder* builder, int method, double percentile, int n_cells, const int64_t* cell_offsets_i64,
+                       const int32_t* members_i32, double* out_f64_host, uint8_t* flags_u8_host);
+/* Device time of the last B3 launch, milliseconds. */
+int rpsf_builder_clean_ms(const rpsf_builder* builder, double* ms);
 
 /* find_stars: star positions for the builder, upstream of the star list.  The detector is this library's own, modelled on
  * sep.Background + sep.extract WITHOUT deblending; it is not sep and its positions differ from sep's for blended or extended sources.

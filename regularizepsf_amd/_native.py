@@ -105,6 +105,9 @@ _PROTOTYPES = {
     "rpsf_builder_load_patches": (c_int, [c_void_p, c_size_t, c_void_p]),
     "rpsf_builder_average": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p]),
     "rpsf_builder_kernel_ms": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
+    "rpsf_builder_clean": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "rpsf_builder_model": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rpsf_builder_clean_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rpsf_stars_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int]),
     "rpsf_stars_destroy": (None, [c_void_p]),
     "rpsf_stars_background": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

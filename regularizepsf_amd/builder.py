@@ -3,9 +3,10 @@
 What the reference does per star in a Python loop (image_processing.py:95-121: slice the reflect-padded frame, spline-shift the
 patch onto the pixel grid, subtract a background plane, test) and per lattice cell over Python lists (builder.py:53-102:
 ``np.nansum`` / ``np.nanmedian`` / ``np.nanpercentile``) runs in two HIP kernels behind ``rpsf_builder_*`` (include/rpsf.h).
-The host keeps what is bookkeeping: the rounded corners and shift amounts (Python's half-to-even ``round``), the cell
-membership of every patch, and the final per-cell clean-up (builder.py:231-260), which is a few ``scipy.ndimage`` calls on at
-most a few thousand small float64 arrays.
+The host keeps what is bookkeeping: the rounded corners and shift amounts (Python's half-to-even ``round``) and the cell
+membership of every patch.  The final per-cell clean-up (builder.py:231-260) is ``clean_cell`` here, a few ``scipy.ndimage``
+calls per cell, or with ``ArrayPSFBuilder(..., cleanup="device")`` a third kernel, which leaves to ``clean_cell`` only the cells whose
+background fit it flags as degenerate.
 
 The boundary of the feature is the star list: ``build(..., stars=[...])`` takes the ``(row, col)`` positions ``sep.extract``
 returns; without it ``sep`` is imported and called as the reference calls it.
@@ -25,6 +26,8 @@ from regularizepsf_amd.util import IndexedCube, calculate_covering
 
 AVERAGE_METHODS = {"mean": 0, "median": 1, "percentile": 2}
 REJECTED, ACCEPTED, DEGENERATE_RING = 0, 1, 2
+CLEANED, DEGENERATE_CELL = 0, 1  # flags of a cell after the device clean-up
+CLEANUPS = ("host", "device")
 
 
 def _frames(images) -> list[np.ndarray]:
@@ -159,6 +162,16 @@ def clean_cell(cell: np.ndarray) -> np.ndarray:
         return patch / np.nansum(patch)
 
 
+def model_on_device(stack, method: str, percentile: float, offsets: np.ndarray, members: np.ndarray) -> np.ndarray:
+    """The cleaned cells of a filled stack with the averaging and the clean-up both on the device.  The kernel does not restate
+    SciPy's minimum-norm fit for a cell whose ring has fewer than three pixels (or all on one line): it flags the cell and
+    hands back its averaged values, and ``clean_cell`` does that one here - so the result is ``clean_cell``'s for every cell."""
+    values, flags = stack.model(method, percentile, offsets, members)
+    for c in np.flatnonzero(flags == DEGENERATE_CELL):
+        values[c] = clean_cell(values[c])
+    return values
+
+
 class _Stack:
     """A native builder handle: the device stack of accepted float32 patches."""
 
@@ -207,6 +220,33 @@ class _Stack:
                                              n._ptr(members), n._ptr(cells)))
         return cells
 
+    def clean(self, cells: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """Kernel B3 alone on float64 cells of the builder's size: (cleaned cells, flags).  A cell flagged DEGENERATE_CELL comes
+        back as it went in."""
+        n = self._native
+        cells = np.ascontiguousarray(cells, np.float64).reshape(-1, self.psf_size, self.psf_size)
+        out, flags = np.empty_like(cells), np.zeros(len(cells), np.uint8)
+        n.check(n.lib().rpsf_builder_clean(self._handle, len(cells), n._ptr(cells), n._ptr(out), n._ptr(flags)))
+        return out, flags
+
+    def model(self, method: str, percentile: float, offsets: np.ndarray, members: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """``average`` then ``clean`` without the averaged cells leaving the device: (cleaned cells, flags).  A cell flagged
+        DEGENERATE_CELL holds its averaged values."""
+        n = self._native
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        members = np.ascontiguousarray(members, np.int32)
+        out = np.empty((len(offsets) - 1, self.psf_size, self.psf_size), np.float64)
+        flags = np.zeros(len(offsets) - 1, np.uint8)
+        n.check(n.lib().rpsf_builder_model(self._handle, AVERAGE_METHODS[method], float(percentile), len(offsets) - 1, n._ptr(offsets),
+                                           n._ptr(members), n._ptr(out), n._ptr(flags)))
+        return out, flags
+
+    def clean_ms(self) -> float:
+        """Device time of the last clean-up (B3) launch."""
+        ms = ctypes.c_double(0)
+        self._native.check(self._native.lib().rpsf_builder_clean_ms(self._handle, ctypes.byref(ms)))
+        return ms.value
+
     def kernel_ms(self) -> tuple[float, float]:
         """Device time of the last patch (B1) and the last averaging (B2) launch."""
         b1, b2 = ctypes.c_double(0), ctypes.c_double(0)
@@ -228,13 +268,24 @@ class _Stack:
 class ArrayPSFBuilder:
     """A builder that takes a series of images and constructs an ArrayPSF to represent their implicit PSF."""
 
-    def __init__(self, psf_size: int, device: int = 0) -> None:
+    def __init__(self, psf_size: int, device: int = 0, *, cleanup: str = "host") -> None:
+        """``cleanup`` says where ``build`` runs the per-cell clean-up: ``"host"`` is ``clean_cell`` on every cell, ``"device"`` the
+        third kernel, with ``clean_cell`` only on the cells it flags (a degenerate background fit) - the same model within 1e-12.
+        It is an argument of the builder and not of ``build``, whose parameter list stays the reference's plus ``stars``."""
+        if cleanup not in CLEANUPS:
+            msg = f"cleanup must be one of {CLEANUPS}, not {cleanup!r}"
+            raise ValueError(msg)
         self._psf_size = psf_size
         self._device = device
+        self._cleanup = cleanup
 
     @property
     def psf_size(self) -> int:
         return self._psf_size
+
+    @property
+    def cleanup(self) -> str:
+        return self._cleanup
 
     def build(self, images, sep_mask=None, hdu_choice: int | None = 0, num_workers: int | None = None,  # noqa: ARG002
               interpolation_scale: int = 1, star_threshold: int = 3, average_method: str = "median", percentile: float = 50,
@@ -262,6 +313,7 @@ class ArrayPSFBuilder:
         if average_method not in AVERAGE_METHODS:
             msg = f"Unknown method {average_method}."
             raise PSFBuilderError(msg)
+        cleanup = self._cleanup
         frames = _frames(images)
         if stars is None:
             masks = [None] * len(frames) if sep_mask is None else _frames(sep_mask)
@@ -289,7 +341,10 @@ class ArrayPSFBuilder:
             corners = calculate_covering(frames[0].shape, size)
             offsets, members = cell_membership(np.array([k[1:] for k in keys], np.float64).reshape(-1, 2), corners, size)
             method = "median" if (average_method == "percentile" and percentile == 50) else average_method
-            cells = stack.average(method, percentile, offsets, members)
+            if cleanup == "device":
+                cleaned = model_on_device(stack, method, percentile, offsets, members)
+            else:
+                cells = stack.average(method, percentile, offsets, members)
             patches = None
             if return_patches:
                 values = stack.patches().astype(np.float64)
@@ -299,6 +354,6 @@ class ArrayPSFBuilder:
 
         counts = {tuple(corner): int(offsets[c + 1] - offsets[c]) for c, corner in enumerate(corners)}
         coordinates = [(corner[0], corner[1]) for corner in corners]
-        values = np.stack([clean_cell(cell) for cell in cells])
+        values = cleaned if cleanup == "device" else np.stack([clean_cell(cell) for cell in cells])
         psf = ArrayPSF(IndexedCube(coordinates, values))
         return (psf, counts, patches) if return_patches else (psf, counts)

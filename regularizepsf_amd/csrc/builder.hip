@@ -5,11 +5,17 @@
 //                               phases of rpsf_core_builder.hpp separated by barriers; writes the float32 patch to a staging
 //                               slot and one flag byte.  A small copy kernel appends the accepted patches to the stack.
 //   B2  builder_average_kernel  one lane per pixel of a cell, the cell's member list walked in CSR order.
+//   B3  builder_clean_kernel    one workgroup per averaged cell, the driver of rpsf_core_cleanup.hpp: the cell's values in registers,
+//                               byte masks and union-find parents in LDS (N = 128: 96 KiB); writes the cleaned float64 cell and one
+//                               flag byte.
 //
 // INVARIANT: every patch in the stack is finite and has a non-zero centre.  B1 accepts nothing else (a zero or non-finite
 // pixel, or a value outside float32, rejects the patch), rpsf_builder_load_patches refuses anything else - so every sample
 // (double)p / (double)centre B2 sees is finite and the order-preserving key of rpsf_core_builder.hpp is total.
-// No atomics anywhere: flags are plain stores of one value, sums run in list order - two builds of one input agree bit for bit.
+// B2's cells are finite in turn, and rpsf_builder_clean refuses anything else: B3 relies on it.
+// No float atomics anywhere, and the only integer ones are the atomicMin of B3's union-find, whose result (the smallest index of a
+// component) does not depend on their order: flags are plain stores of one value, sums run in a fixed order - two builds of one
+// input agree bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -19,6 +25,7 @@
 
 #include "../../include/rpsf.h"
 #include "rpsf_core_builder.hpp"
+#include "rpsf_core_cleanup.hpp"
 
 using namespace rpsfb;
 
@@ -85,6 +92,26 @@ __global__ __launch_bounds__(256) void builder_average_kernel(const float* stack
 }
 
 namespace {
+struct CleanCtx {
+  rpsfc::Regs mine;
+  template <class F>
+  __device__ __forceinline__ void each(F&& f) {
+    f((int)threadIdx.x);
+    __syncthreads();
+  }
+  __device__ __forceinline__ rpsfc::Regs& regs(int) { return mine; }
+};
+}  // namespace
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void builder_clean_kernel(int N, const double* cells, double* cleaned, uint8_t* flags) {
+  extern __shared__ double builder_lds[];
+  CleanCtx ctx;
+  const size_t at = (size_t)blockIdx.x * N * N;
+  rpsfc::clean_cell(ctx, N, THREADS, cells + at, cleaned + at, flags + blockIdx.x, builder_lds);
+}
+
+namespace {
 template <class T>
 struct Buf {  // a device array that only ever grows
   T* p = nullptr;
@@ -110,11 +137,11 @@ struct rpsf_builder {
   size_t capacity = 0;
   Buf<float> frame, staging;
   Buf<int32_t> corners, source, members;
-  Buf<double> frac, cells;
-  Buf<uint8_t> flags;
+  Buf<double> frac, cells, cleaned;
+  Buf<uint8_t> flags, clean_flags;
   Buf<int64_t> offsets;
   hipEvent_t ev[2] = {nullptr, nullptr};
-  double patch_ms = 0, average_ms = 0;
+  double patch_ms = 0, average_ms = 0, clean_ms = 0;
   ~rpsf_builder() {
     if (stack) (void)hipFree(stack);
     for (auto e : ev)
@@ -161,6 +188,8 @@ extern "C" int rpsf_builder_create(rpsf_builder** out, int device, int patch_siz
     if (patch_size > 64) {
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&builder_patch_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds_bytes(MAX_N)));
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&builder_clean_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)rpsfc::lds_bytes(MAX_N)));
     } else {
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&builder_patch_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds_bytes(64)));
@@ -272,9 +301,10 @@ extern "C" int rpsf_builder_load_patches(rpsf_builder* b, size_t count, const fl
   return RPSF_OK;
 }
 
-extern "C" int rpsf_builder_average(rpsf_builder* b, int method, double percentile, int n_cells, const int64_t* cell_offsets_i64,
-                                    const int32_t* members_i32, double* cells_f64_host) {
-  if (!b || !cell_offsets_i64 || !cells_f64_host) return fail(RPSF_E_BADARG, "null argument");
+// B2 into builder->cells, which stay on the device
+static int average_on_device(rpsf_builder* b, int method, double percentile, int n_cells, const int64_t* cell_offsets_i64,
+                             const int32_t* members_i32) {
+  if (!b || !cell_offsets_i64) return fail(RPSF_E_BADARG, "null argument");
   if (method != RPSF_AVERAGE_MEAN && method != RPSF_AVERAGE_MEDIAN && method != RPSF_AVERAGE_PERCENTILE)
     return fail(RPSF_E_BADARG, "unknown averaging method " + std::to_string(method));
   if (method == RPSF_AVERAGE_PERCENTILE && !(percentile >= 0.0 && percentile <= 100.0))
@@ -300,8 +330,62 @@ extern "C" int rpsf_builder_average(rpsf_builder* b, int method, double percenti
                      b->members.p, b->N, method, percentile / 100.0, b->cells.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(b->ev[1], nullptr));
-  HIP_TRY(hipMemcpy(cells_f64_host, b->cells.p, (size_t)n_cells * npix * sizeof(double), hipMemcpyDeviceToHost));
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_builder_average(rpsf_builder* b, int method, double percentile, int n_cells, const int64_t* cell_offsets_i64,
+                                    const int32_t* members_i32, double* cells_f64_host) {
+  if (!cells_f64_host) return fail(RPSF_E_BADARG, "null argument");
+  if (const int rc = average_on_device(b, method, percentile, n_cells, cell_offsets_i64, members_i32)) return rc;
+  HIP_TRY(hipMemcpy(cells_f64_host, b->cells.p, (size_t)n_cells * b->N * b->N * sizeof(double), hipMemcpyDeviceToHost));
   return elapsed(b, &b->average_ms);
+}
+
+// B3 on builder->cells; the cleaned cells and the flags come back in one download each
+static int clean_on_device(rpsf_builder* b, int n_cells, double* out_f64_host, uint8_t* flags_u8_host) {
+  const size_t npix = (size_t)b->N * b->N;
+  HIP_TRY(b->cleaned.reserve((size_t)n_cells * npix));
+  HIP_TRY(b->clean_flags.reserve((size_t)n_cells));
+  HIP_TRY(hipEventRecord(b->ev[0], nullptr));
+  if (b->N > 64) {
+    hipLaunchKernelGGL(builder_clean_kernel<1024>, dim3(n_cells), dim3(1024), rpsfc::lds_bytes(b->N), nullptr, b->N, b->cells.p,
+                       b->cleaned.p, b->clean_flags.p);
+  } else {
+    hipLaunchKernelGGL(builder_clean_kernel<256>, dim3(n_cells), dim3(256), rpsfc::lds_bytes(b->N), nullptr, b->N, b->cells.p,
+                       b->cleaned.p, b->clean_flags.p);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(b->ev[1], nullptr));
+  HIP_TRY(hipMemcpy(out_f64_host, b->cleaned.p, (size_t)n_cells * npix * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(flags_u8_host, b->clean_flags.p, (size_t)n_cells, hipMemcpyDeviceToHost));
+  return elapsed(b, &b->clean_ms);
+}
+
+extern "C" int rpsf_builder_clean(rpsf_builder* b, int n_cells, const double* cells_f64_host, double* out_f64_host,
+                                  uint8_t* flags_u8_host) {
+  if (!b || !cells_f64_host || !out_f64_host || !flags_u8_host) return fail(RPSF_E_BADARG, "null argument");
+  if (n_cells <= 0) return fail(RPSF_E_BADARG, "n_cells must be positive");
+  const size_t npix = (size_t)b->N * b->N;
+  for (size_t i = 0; i < (size_t)n_cells * npix; ++i)
+    if (!std::isfinite(cells_f64_host[i])) return fail(RPSF_E_BADARG, "cell " + std::to_string(i / npix) + " has a non-finite pixel");
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(b->cells.reserve((size_t)n_cells * npix));
+  HIP_TRY(hipMemcpy(b->cells.p, cells_f64_host, (size_t)n_cells * npix * sizeof(double), hipMemcpyHostToDevice));
+  return clean_on_device(b, n_cells, out_f64_host, flags_u8_host);
+}
+
+extern "C" int rpsf_builder_model(rpsf_builder* b, int method, double percentile, int n_cells, const int64_t* cell_offsets_i64,
+                                  const int32_t* members_i32, double* out_f64_host, uint8_t* flags_u8_host) {
+  if (!out_f64_host || !flags_u8_host) return fail(RPSF_E_BADARG, "null argument");
+  if (const int rc = average_on_device(b, method, percentile, n_cells, cell_offsets_i64, members_i32)) return rc;
+  if (const int rc = elapsed(b, &b->average_ms)) return rc;
+  return clean_on_device(b, n_cells, out_f64_host, flags_u8_host);
+}
+
+extern "C" int rpsf_builder_clean_ms(const rpsf_builder* b, double* ms) {
+  if (!b || !ms) return fail(RPSF_E_BADARG, "null argument");
+  *ms = b->clean_ms;
+  return RPSF_OK;
 }
 
 extern "C" int rpsf_builder_kernel_ms(const rpsf_builder* b, double* patch_ms, double* average_ms) {

@@ -1,5 +1,6 @@
-"""Where the time of ArrayPSFBuilder.build goes (PSF builder): the two kernels, the host stages, and the same
-stages done with NumPy / SciPy on this box's host the way the reference does them.
+"""Where the time of ArrayPSFBuilder.build goes (PSF builder): the three kernels, the host stages, the build with
+the clean-up on the host and on the device, and the same stages done with NumPy / SciPy on this box's host the way the reference
+does them.
 
     python scripts/builder_timing.py [--frames 16] [--size 2048] [--stars 2000] [--n 32] [--host-frames 1] [--host-cells 400]
 
@@ -125,15 +126,34 @@ def main() -> None:
         must = len(members) * n * n * 4 + len(corners) * n * n * 8
         res[f"b2_{method}_GBps"] = must / (ms * 1e-3) / 1e9
     t0 = time.perf_counter()
-    for cell in cells:
-        bld.clean_cell(cell)
+    on_host = [bld.clean_cell(cell) for cell in cells]
     res["cleanup_ms"] = (time.perf_counter() - t0) * 1e3
+    # the clean-up on the device (kernel B3): alone on the cells just averaged, then behind B2 without the cells leaving the device
+    stack.clean(cells)
+    t0 = time.perf_counter()
+    cleaned, flagged = stack.clean(cells)
+    res["clean_call_ms"] = (time.perf_counter() - t0) * 1e3  # with the cells' upload and the download of the result
+    res["clean_kernel_ms"] = stack.clean_ms()
+    res["clean_GBps"] = 2 * len(corners) * n * n * 8 / (res["clean_kernel_ms"] * 1e-3) / 1e9  # every cell read once and written once
+    res["clean_flagged"] = int(flagged.sum())
+    worst = 0.0
+    for got, want, flag in zip(cleaned, on_host, flagged):
+        if not flag and np.isfinite(want).all():
+            worst = max(worst, float(np.abs(got - want).max() / np.abs(want).max()))
+    res["clean_max_rel_err"] = worst
+    stack.model("percentile", 30.0, offsets, members)
+    t0 = time.perf_counter()
+    stack.model("percentile", 30.0, offsets, members)
+    res["model_call_ms"] = (time.perf_counter() - t0) * 1e3  # B2 (percentile) + B3 + one download
     patches = stack.patches()
     stack.close()
 
     t0 = time.perf_counter()
     rp.ArrayPSFBuilder(n).build(frames, stars=stars)
     res["build_ms"] = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    rp.ArrayPSFBuilder(n, cleanup="device").build(frames, stars=stars)
+    res["build_device_ms"] = (time.perf_counter() - t0) * 1e3
 
     # the same stages on the host
     t0 = time.perf_counter()
