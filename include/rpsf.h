@@ -188,6 +188,37 @@ int rpsf_apply_host_saturated(rpsf_plan* plan, const void* image_host, int image
 int rpsf_apply_frames_host_saturated(rpsf_plan* plan, const void* const* images_host, int image_is_f64, int n_frames, int height,
                                      int width, int pad_mode, double threshold, int dilation, int neighborhood_width,
                                      void* const* outs_host, int out_is_f64);
+/* The saturation branch with every step on the device (kernels F1 - F5, csrc/saturation.hip; DESIGN.md 3.8 has the definition):
+ * image_dev is a float32 height x width frame on the plan's device, out_dev receives the float32 height x width result.  The frame is
+ * padded by 2N with pad_mode's index map, thresholded ((double)value > threshold; NaN is not hot), the mask dilated `dilation` >= 1
+ * times with the cross element, the masked pixels filled in row-major order with the float64 nan-mean of [i - w/2, i + w/2) x
+ * [j - w/2, j + w/2) (Python slice rules; later pixels see earlier fills), the padded float32 frame corrected with the geometry
+ * rpsf_apply_host_saturated uses, the raw values restored on the mask and the frame cropped: on a float32 frame the result has the
+ * bits of rpsf_apply_host_saturated's.  Arguments as there, and neighborhood_width / 2 >= 1 (an always-empty window needs no kernel:
+ * RPSF_E_BADARG, use the host route).  Asynchronous on `stream` (NULL: the plan's own) EXCEPT that the call waits for the stream once,
+ * after the labelling, to read the hot, masked and group counts; with nothing hot F2 - F4 do nothing and the padded frame is corrected
+ * as it is.  *n_masked_or_null: masked pixels of the padded frame.
+ * SCRATCH, owned by the plan, allocated at the first call, reused, grown when a larger frame arrives, freed with the plan: per pixel
+ * of the padded (height + 4N) x (width + 4N) frame 4 B (float32 frame) + 3 B (hot / mask / grown mask bytes) + 4 B (labels) = 11 B,
+ * plus the padded float32 output rows (4 B per pixel of height + 4N rows for a generic-size plan, of `height` rows otherwise), 8 B per
+ * 64-pixel row segment, and per MASKED pixel 8 B (float64 fill) + at most 8 B (the list, device and pinned host), 24 B per group. */
+int rpsf_apply_device_saturated(rpsf_plan* plan, const void* image_dev, void* out_dev, int height, int width, int pad_mode,
+                                double threshold, int dilation, int neighborhood_width, void* stream, size_t* n_masked_or_null);
+/* rpsf_apply_host_saturated's contract through the device route: the UNPADDED frame is narrowed to float32 and uploaded through the
+ * plan's staging, rpsf_apply_device_saturated runs, `height` rows come back, and for a float64 frame the masked in-frame pixels, which
+ * the device lists, receive the caller's own float64 values.  A float64 frame is thresholded and filled from its float32 rounding
+ * (what every device path of the library holds): a pixel whose float64 value lies on the other side of the threshold from its float32
+ * rounding is the one place where the two routes can disagree beyond the rounding of the fill's inputs. */
+int rpsf_apply_host_saturated_device(rpsf_plan* plan, const void* image_host, int image_is_f64, int height, int width, int pad_mode,
+                                     double threshold, int dilation, int neighborhood_width, void* out_host, int out_is_f64);
+/* Device time of the last F1 ... F5 launches of the plan, milliseconds (F3's includes the host's one wait; zeros for what did not run). */
+int rpsf_saturation_kernel_ms(rpsf_plan* plan, double ms[5]);
+/* Test entry: F1 - F4 alone on a float32 host frame.  padded_host ((height + 4N) x (width + 4N) float32) receives the filled padded
+ * frame, mask_host (as many bytes) the dilated mask; reverse_groups != 0 makes F4's workgroups take the groups last first (the result
+ * must not depend on it); *n_groups_or_null: independent groups found. */
+int rpsf_saturation_fill_device(rpsf_plan* plan, const float* image_host, int height, int width, int pad_mode, double threshold,
+                                int dilation, int neighborhood_width, int reverse_groups, float* padded_host, uint8_t* mask_host,
+                                int* n_groups_or_null);
 /* Same with image and output already resident on the plan's device; asynchronous on `stream`
  * (a hipStream_t, or NULL for the plan's own stream).  Every pixel of the resident output rows is written
  * (uncovered ones with 0).  image_dev / out_dev must be ordinary device memory of the plan's device

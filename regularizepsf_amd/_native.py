@@ -72,6 +72,10 @@ _PROTOTYPES = {
     "rpsf_apply": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "rpsf_apply_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int]),
     "rpsf_apply_host_saturated": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int]),
+    "rpsf_apply_device_saturated": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, POINTER(c_size_t)]),
+    "rpsf_apply_host_saturated_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int]),
+    "rpsf_saturation_kernel_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rpsf_saturation_fill_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_int)]),
     "rpsf_apply_frames_host_saturated": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int]),
     "rpsf_apply_device": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(Geometry), c_void_p]),
     "rpsf_apply_device_timed": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(Geometry), c_int, c_void_p, c_void_p]),
@@ -348,6 +352,45 @@ class Plan:
                                               float(threshold), int(dilation), int(neighborhood_width), _ptr(out),
                                               int(np.dtype(out_dtype) == np.float64)))
         return out
+
+    def apply_host_saturated_device(self, image: np.ndarray, pad_mode: int, threshold: float, dilation: int, neighborhood_width: int,
+                                    out_dtype=np.float64) -> np.ndarray:
+        """``apply_host_saturated`` with mask, dilation, fill and restore on the GPU (kernels F1 - F5): the unpadded frame goes up as float32,
+        the masked pixels of a float64 frame get the caller's own values back.  Needs ``neighborhood_width // 2 >= 1``."""
+        img = np.asarray(image)
+        if img.dtype not in (np.float32, np.float64) or img.dtype.byteorder == ">":
+            img = img.astype(np.float64)
+        img = np.ascontiguousarray(img)
+        out = np.empty(img.shape, out_dtype)
+        check(lib().rpsf_apply_host_saturated_device(self._handle, _ptr(img), int(img.dtype == np.float64), img.shape[0], img.shape[1],
+                                                     pad_mode, float(threshold), int(dilation), int(neighborhood_width), _ptr(out),
+                                                     int(np.dtype(out_dtype) == np.float64)))
+        return out
+
+    def apply_device_saturated(self, image_ptr: c_void_p, out_ptr: c_void_p, height: int, width: int, pad_mode: int, threshold: float,
+                               dilation: int, neighborhood_width: int, stream: c_void_p | None = None) -> int:
+        """The saturation branch on a float32 frame resident on the plan's device; returns the masked pixels of the padded frame."""
+        n = c_size_t(0)
+        check(lib().rpsf_apply_device_saturated(self._handle, image_ptr, out_ptr, int(height), int(width), pad_mode, float(threshold),
+                                                int(dilation), int(neighborhood_width), stream, ctypes.byref(n)))
+        return n.value
+
+    def saturation_kernel_ms(self) -> np.ndarray:
+        """Device time of the last F1 ... F5 launches, milliseconds."""
+        ms = (c_double * 5)()
+        check(lib().rpsf_saturation_kernel_ms(self._handle, ms))
+        return np.array(ms[:])
+
+    def saturation_fill_device(self, image: np.ndarray, pad_mode: int, threshold: float, dilation: int, neighborhood_width: int,
+                               reverse_groups: bool = False) -> tuple[np.ndarray, np.ndarray, int]:
+        """Test entry: F1 - F4 alone; (filled padded float32 frame, mask, number of independent groups)."""
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        shape = (img.shape[0] + 4 * self.patch_size, img.shape[1] + 4 * self.patch_size)
+        padded, mask, groups = np.empty(shape, np.float32), np.empty(shape, np.uint8), c_int(0)
+        check(lib().rpsf_saturation_fill_device(self._handle, _ptr(img), img.shape[0], img.shape[1], pad_mode, float(threshold), int(dilation),
+                                                int(neighborhood_width), int(bool(reverse_groups)), _ptr(padded), _ptr(mask),
+                                                ctypes.byref(groups)))
+        return padded, mask.astype(bool), groups.value
 
     def apply_frames_host_saturated(self, images, pad_mode: int, threshold: float, dilation: int, neighborhood_width: int,
                                     out_dtype=np.float64) -> np.ndarray:

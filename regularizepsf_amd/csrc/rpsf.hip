@@ -35,6 +35,7 @@
 #define RPSF_HOST_TU 1
 #include "rpsf_device.hpp"
 #include "rpsf_hostpipe.hpp"
+#include "rpsf_saturation.hpp"
 
 RPSF_PLANS_V1(RPSF_DECL_V1)
 RPSF_PLANS_V2(RPSF_DECL_V2)
@@ -133,6 +134,9 @@ struct PipeRelease {
 };
 struct FftPlanRelease {
   void operator()(void* h) const;  // hipfftDestroy (g_hipfft, below)
+};
+struct SatDeviceRelease {
+  void operator()(SatDevice* d) const { rpsf_sat_destroy(d); }
 };
 
 // Host scratch of the saturation branch (rpsf_apply_host_saturated), per staging slot, kept between calls
@@ -248,6 +252,7 @@ struct rpsf_plan : PlanStream {
   DevBuf<int32_t> d_coords;
   DevBuf<float> d_win;  // read by the patch kernels and the sweep kernel; uploaded with the first-generation tables (a view reads its parent's)
   std::unique_ptr<rpsf_host::HostPipe, PipeRelease> pipe;  // host-array entry points: staging slots, copy streams (rpsf_hostpipe.hpp)
+  std::unique_ptr<SatDevice, SatDeviceRelease> sat_dev;  // rpsf_apply_device_saturated: device scratch of the saturation branch (csrc/saturation.hip), made at the first such call
   std::vector<SatScratch> sat;  // rpsf_apply_host_saturated: per staging slot, the 2N-padded float64 frame, its mask and the raw values (host scratch, kept between calls)
   // Views: a plan over a subset of another plan's patches that shares its tables, its packed K (desc.z = the patch's index in the
   // parent), its error word and its stream - the row bands a single large host frame is cut into so that its upload, its patches and
@@ -2365,6 +2370,19 @@ extern "C" int rpsf_device_numa_node(int device, int* node) {
 // A sequence of frames (rpsf_apply_frames_host_saturated - the reference's example corrects a list of frames this way, docs/source/example.ipynb
 // cell 25) alternates between two staging slots: the host steps of frame i + 1 run while the GPU corrects frame i.
 // ------------------------------------------------------------------------------------------------
+// The correction of the 2N-padded frame of an H x W image: rows [r_lo, r_hi) of it are read, rows [o_lo, o_lo + o_rows) written
+static int padded_geometry(const rpsf_plan* p, int H, int W, int* r_lo, int* r_hi, int* o_lo, int* o_rows, rpsf_geometry* g) {
+  const int N = p->N;
+  const long PH = (long)H + 4L * N, PW = (long)W + 4L * N;
+  if (PH * PW >= ((long)1 << 31)) return fail(RPSF_E_UNSUPPORTED, "padded frame too large for this entry point");
+  // rows of the padded frame the patches read, and the geometry of the correction on it (the hipFFT fallback takes whole frames only)
+  *r_lo = p->generic ? 0 : (int)std::max<long>(0, 2L * N + std::min(0, p->corner_min[0]));
+  *r_hi = p->generic ? (int)PH : (int)std::min<long>(PH, 2L * N + p->corner_max[0] + N);
+  *o_lo = p->generic ? 0 : 2 * N, *o_rows = p->generic ? (int)PH : H;  // output rows the device hands back
+  *g = rpsf_geometry{(int)PH, (int)PW, RPSF_PAD_CONSTANT, 0.f, 2 * N, 2 * N, *r_lo, *r_hi - *r_lo, (int)PW, *o_lo, *o_rows, (int)PW};
+  return check_geometry(p, g);
+}
+
 struct SatRun {
   rpsf_plan* p;
   int H, W, N, pad_mode, dilation, width, in_f64, out_f64;
@@ -2377,13 +2395,7 @@ struct SatRun {
   int init(rpsf_plan* plan, int height, int w, int mode, double thr, int dil, int nbw, int image_is_f64, int out_is_f64, int slots) {
     p = plan, H = height, W = w, N = plan->N, pad_mode = mode, dilation = dil, width = nbw, in_f64 = image_is_f64, out_f64 = out_is_f64, threshold = thr;
     PH = (long)H + 4L * N, PW = (long)W + 4L * N;
-    if (PH * PW >= ((long)1 << 31)) return fail(RPSF_E_UNSUPPORTED, "padded frame too large for this entry point");
-    // rows of the padded frame the patches read, and the geometry of the correction on it (the hipFFT fallback takes whole frames only)
-    r_lo = p->generic ? 0 : (int)std::max<long>(0, 2L * N + std::min(0, p->corner_min[0]));
-    r_hi = p->generic ? (int)PH : (int)std::min<long>(PH, 2L * N + p->corner_max[0] + N);
-    o_lo = p->generic ? 0 : 2 * N, o_rows = p->generic ? (int)PH : H;  // output rows the device hands back
-    g = rpsf_geometry{(int)PH, (int)PW, RPSF_PAD_CONSTANT, 0.f, 2 * N, 2 * N, r_lo, r_hi - r_lo, (int)PW, o_lo, o_rows, (int)PW};
-    int rc = check_geometry(p, &g);
+    int rc = padded_geometry(p, H, W, &r_lo, &r_hi, &o_lo, &o_rows, &g);
     if (rc != RPSF_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
     rc = pipe_ensure(p, (size_t)PH * PW, slots);
@@ -2562,6 +2574,143 @@ extern "C" int rpsf_apply_frames_host_saturated(rpsf_plan* p, const void* const*
   if (err == hipSuccess) err = run.finish((n_frames - 1) & 1, outs_host[n_frames - 1]);
   if (err != hipSuccess) return drain_after_error(p, err, "saturated host frames");
   return sweep_check(p);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same branch with every step on the device (csrc/saturation.hip): F1 - F4 build the filled padded frame from the
+// resident H x W frame, the plan corrects it with the geometry above, F5 restores and crops.
+// ------------------------------------------------------------------------------------------------
+struct SatDeviceRun {
+  SatCall call;
+  rpsf_geometry g;
+  int r_lo, r_hi;
+};
+
+static int sat_device_init(rpsf_plan* p, int height, int width, int pad_mode, double threshold, int dilation, int neighborhood_width,
+                           SatDeviceRun* run) {
+  if (neighborhood_width / 2 < 1) return fail(RPSF_E_BADARG, "the device route needs neighborhood_width // 2 >= 1 (an always-empty window: the host route)");
+  int o_lo, o_rows;
+  const int rc = padded_geometry(p, height, width, &run->r_lo, &run->r_hi, &o_lo, &o_rows, &run->g);
+  if (rc != RPSF_OK) return rc;
+  run->call = SatCall{height, width, p->N, pad_mode, dilation, neighborhood_width, threshold, run->r_lo, o_lo, o_rows, false};
+  HIP_TRY(hipSetDevice(p->device));
+  if (!p->sat_dev) p->sat_dev.reset(rpsf_sat_create());
+  return RPSF_OK;
+}
+
+// F1 - F4, the correction, F5; asynchronous on st but for the one wait inside rpsf_sat_fill
+static int sat_device_apply(rpsf_plan* p, const SatDeviceRun& run, const float* image_dev, float* out_dev, hipStream_t st) {
+  float *padded = nullptr, *corrected = nullptr;
+  int rc = rpsf_sat_fill(p->sat_dev.get(), run.call, image_dev, st, &padded, &corrected);
+  if (rc != RPSF_OK) return rc;
+  rc = launch_apply(p, padded + (size_t)run.r_lo * run.g.width, corrected, run.g, st, nullptr);
+  if (rc != RPSF_OK) return rc;
+  return rpsf_sat_restore(p->sat_dev.get(), run.call, image_dev, out_dev, st);
+}
+
+extern "C" int rpsf_apply_device_saturated(rpsf_plan* p, const void* image_dev, void* out_dev, int height, int width, int pad_mode, double threshold,
+                                           int dilation, int neighborhood_width, void* stream, size_t* n_masked_or_null) {
+  int rc = check_saturated_call(p, image_dev, out_dev, height, width, pad_mode, dilation, neighborhood_width);
+  if (rc != RPSF_OK) return rc;
+  SatDeviceRun run;
+  rc = sat_device_init(p, height, width, pad_mode, threshold, dilation, neighborhood_width, &run);
+  if (rc != RPSF_OK) return rc;
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : p->stream;
+  rc = sat_device_apply(p, run, static_cast<const float*>(image_dev), static_cast<float*>(out_dev), st);
+  if (rc != RPSF_OK) return rc;
+  if (n_masked_or_null) {
+    int n_hot, n_mask, n_groups;
+    rpsf_sat_counts(p->sat_dev.get(), &n_hot, &n_mask, &n_groups);
+    *n_masked_or_null = (size_t)n_mask;
+  }
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_apply_host_saturated_device(rpsf_plan* p, const void* image_host, int image_is_f64, int height, int width, int pad_mode,
+                                                double threshold, int dilation, int neighborhood_width, void* out_host, int out_is_f64) {
+  int rc = check_saturated_call(p, image_host, out_host, height, width, pad_mode, dilation, neighborhood_width);
+  if (rc != RPSF_OK) return rc;
+  SatDeviceRun run;
+  rc = sat_device_init(p, height, width, pad_mode, threshold, dilation, neighborhood_width, &run);
+  if (rc != RPSF_OK) return rc;
+  const size_t npix = (size_t)height * width;
+  rc = pipe_ensure(p, npix, 1);
+  if (rc != RPSF_OK) return rc;
+  HostPipe& q = *p->pipe;
+  HostPool& pool = HostPool::get(p->device);
+  const int T = host_parts_for(npix * sizeof(float));
+  pool.run(T, [&](int t) {
+    size_t a, b;
+    rpsf_host::split_range(0, npix, t, T, a, b);
+    rpsf_host::narrow_or_copy(q.h_in[0], image_host, image_is_f64 != 0, a, b);
+  });
+  hipError_t err = hipMemcpyAsync(q.d_in[0], q.h_in[0], npix * sizeof(float), hipMemcpyHostToDevice, p->stream);
+  if (err != hipSuccess) return drain_after_error(p, err, "saturated host frame, device route");
+  rc = sat_device_apply(p, run, q.d_in[0], q.d_out[0], p->stream);
+  if (rc != RPSF_OK) {
+    (void)hipStreamSynchronize(p->stream);
+    return rc;
+  }
+  err = hipMemcpyAsync(q.h_out[0], q.d_out[0], npix * sizeof(float), hipMemcpyDeviceToHost, p->stream);
+  if (err != hipSuccess) return drain_after_error(p, err, "saturated host frame, device route");
+  const int32_t* list = nullptr;
+  size_t n_list = 0;
+  rc = rpsf_sat_list(p->sat_dev.get(), p->stream, &list, &n_list);  // waits for the stream
+  if (rc != RPSF_OK) return rc;
+  if (!list) {
+    err = hipStreamSynchronize(p->stream);
+    if (err != hipSuccess) return drain_after_error(p, err, "saturated host frame, device route");
+  }
+  pool.run(T, [&](int t) {
+    size_t a, b;
+    rpsf_host::split_range(0, npix, t, T, a, b);
+    rpsf_host::widen_or_copy(out_host, out_is_f64 != 0, q.h_out[0], a, b);
+  });
+  if (image_is_f64) {  // the caller's own values on the mask, not their float32 roundings
+    const double* src = static_cast<const double*>(image_host);
+    for (size_t k = 0; k < n_list; ++k) {
+      if (out_is_f64) static_cast<double*>(out_host)[list[k]] = src[list[k]];
+      else static_cast<float*>(out_host)[list[k]] = (float)src[list[k]];
+    }
+  }
+  return sweep_check(p);
+}
+
+extern "C" int rpsf_saturation_kernel_ms(rpsf_plan* p, double ms[5]) {
+  if (!p || !ms) return fail(RPSF_E_BADARG, "null argument");
+  for (int i = 0; i < 5; ++i) ms[i] = 0.0;
+  if (!p->sat_dev) return RPSF_OK;
+  HIP_TRY(hipSetDevice(p->device));
+  return rpsf_sat_kernel_ms(p->sat_dev.get(), ms);
+}
+
+// Test entry: F1 - F4 alone on a float32 host frame; the filled padded frame ((H + 4N) x (W + 4N) float32) and the mask come back
+extern "C" int rpsf_saturation_fill_device(rpsf_plan* p, const float* image_host, int height, int width, int pad_mode, double threshold, int dilation,
+                                           int neighborhood_width, int reverse_groups, float* padded_host, uint8_t* mask_host, int* n_groups_or_null) {
+  if (!p || !image_host || !padded_host || !mask_host) return fail(RPSF_E_BADARG, "null argument");
+  if (height <= 0 || width <= 0) return fail(RPSF_E_BADARG, "image shape must be positive");
+  if (pad_mode < 0 || pad_mode > RPSF_PAD_WRAP) return fail(RPSF_E_BADARG, "unknown pad mode");
+  if (dilation < 1 || neighborhood_width / 2 < 1) return fail(RPSF_E_BADARG, "dilation must be >= 1 and neighborhood_width // 2 >= 1");
+  const long PH = (long)height + 4L * p->N, PW = (long)width + 4L * p->N;
+  if (PH * PW >= ((long)1 << 31)) return fail(RPSF_E_UNSUPPORTED, "padded frame too large for this entry point");
+  HIP_TRY(hipSetDevice(p->device));
+  if (!p->sat_dev) p->sat_dev.reset(rpsf_sat_create());
+  const SatCall call{height, width, p->N, pad_mode, dilation, neighborhood_width, threshold, 0, 0, 1, reverse_groups != 0};
+  DevBuf<float> d_image;
+  HIP_TRY(d_image.upload(image_host, (size_t)height * width));
+  float *padded = nullptr, *corrected = nullptr;
+  int rc = rpsf_sat_fill(p->sat_dev.get(), call, d_image, p->stream, &padded, &corrected);
+  if (rc == RPSF_OK) rc = rpsf_sat_mask(p->sat_dev.get(), call, p->stream, mask_host);  // waits for the stream
+  if (rc != RPSF_OK) {
+    (void)hipStreamSynchronize(p->stream);
+    return rc;
+  }
+  HIP_TRY(hipMemcpy(padded_host, padded, (size_t)PH * PW * sizeof(float), hipMemcpyDeviceToHost));
+  if (n_groups_or_null) {
+    int n_hot, n_mask;
+    rpsf_sat_counts(p->sat_dev.get(), &n_hot, &n_mask, n_groups_or_null);
+  }
+  return RPSF_OK;
 }
 
 // Self-test of the host worker pool (no GPU involved: the CPU test suite calls it): `jobs` jobs of `parts` parts from each of `callers` threads at

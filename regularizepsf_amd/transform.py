@@ -64,9 +64,10 @@ def _kernel_stamp(cube: IndexedCube) -> tuple:
 class ArrayPSFTransform:
     """Transformation from a source PSF to a target PSF that can be applied to images."""
 
-    def __init__(self, transfer_kernel: IndexedCube, device: int = 0) -> None:
+    def __init__(self, transfer_kernel: IndexedCube, device: int = 0, *, saturation: str = "host") -> None:
         self._transfer_kernel = transfer_kernel
         self._device = device
+        self.saturation = saturation
         self._plan: _native.Plan | None = None
         self._plan_stamp: tuple | None = None
         self._corner_bounds: tuple | None = None
@@ -93,15 +94,30 @@ class ArrayPSFTransform:
 
     __hash__ = None
 
+    @property
+    def saturation(self) -> str:
+        """Where ``apply`` does the steps of the saturation branch around the correction (mask, dilation, ordered fill, restore):
+        ``"host"`` (default) as the reference does them, on the float64 frame, or ``"device"``: kernels F1 - F5 on the float32 frame
+        (DESIGN.md 3.8).  Bit-identical on float32 frames; not in the reference's API."""
+        return self._saturation
+
+    @saturation.setter
+    def saturation(self, value: str) -> None:
+        if value not in ("host", "device"):
+            msg = f"saturation must be 'host' or 'device', got {value!r}"
+            raise ValueError(msg)
+        self._saturation = value
+
     # ------------------------------------------------------------------ construct (transform.py:53-83)
     @classmethod
-    def construct(cls, source, target, alpha: float, epsilon: float, device: int = 0) -> "ArrayPSFTransform":
+    def construct(cls, source, target, alpha: float, epsilon: float, device: int = 0, *, saturation: str = "host") -> "ArrayPSFTransform":
         """Build the transform taking ``source`` to ``target``.
 
         ``alpha`` controls the hardness of the transition from amplification to attenuation and
         ``epsilon`` the maximum amplification.  Raises :class:`InvalidCoordinateError` when the two
         models are not sampled at the same coordinates (transform.py:74-76).  The kernel keeps the
         dtype of the PSF spectra (complex64 for float32 PSFs, complex128 for float64 ones).
+        ``saturation`` (keyword only, not in the reference): see the property of that name.
         """
         if np.any(np.array(source.coordinates) != np.array(target.coordinates)):
             msg = "Source PSF coordinates do not match target PSF coordinates."
@@ -137,7 +153,7 @@ class ArrayPSFTransform:
                     kbuf.free()
 
             cube = IndexedCube._deferred(source.coordinates, shape, fetch)
-            out = cls(cube, device=device)
+            out = cls(cube, device=device, saturation=saturation)
             out._plan, out._plan_stamp = plan, _kernel_stamp(cube)
             ref = weakref.ref(out)
 
@@ -156,7 +172,7 @@ class ArrayPSFTransform:
                     and all(isinstance(v, numbers.Integral) for c in source.coordinates for v in c))
         if not resident:
             kernel = _native.build_transfer(s_fft, t_fft, alpha, epsilon, device=device)
-            return cls(IndexedCube(source.coordinates, kernel), device=device)
+            return cls(IndexedCube(source.coordinates, kernel), device=device, saturation=saturation)
         # complex64 spectra and a patch size the kernels support: K is built on the device, packed for K1 from
         # there (no second trip over PCIe at the first apply) and copied back once for the IndexedCube.
         s_fft = np.ascontiguousarray(s_fft, dtype=np.complex64)
@@ -174,7 +190,7 @@ class ArrayPSFTransform:
             for b in bufs:
                 b.free()
         cube = IndexedCube(source.coordinates, kernel)
-        out = cls(cube, device=device)
+        out = cls(cube, device=device, saturation=saturation)
         out._plan, out._plan_stamp = plan, _kernel_stamp(cube)
         return out
 
@@ -307,6 +323,10 @@ class ArrayPSFTransform:
                 and isinstance(neighborhood_width, numbers.Integral) and neighborhood_width >= 0):
             # the saturation branch in one library call: the reference's host steps (pad, mask, dilation, sequential fill, restore) on the
             # plan's own scratch, the correction of the padded frame on the GPU (rpsf_apply_host_saturated)
+            if self._saturation == "device" and neighborhood_width // 2 >= 1:
+                # the same steps on the GPU, on the float32 frame (rpsf_apply_host_saturated_device); an always-empty window stays with the host
+                return plan.apply_host_saturated_device(image, _native.PAD_MODES[pad_mode], saturation_threshold, saturation_dilation,
+                                                        neighborhood_width)
             return plan.apply_host_saturated(image, _native.PAD_MODES[pad_mode], saturation_threshold, saturation_dilation,
                                              neighborhood_width)
 
@@ -388,7 +408,8 @@ class ArrayPSFTransform:
         dtype = np.dtype(out.dtype if out is not None else dtype)
         if (saturation_threshold != math.inf and pad_mode in _native.PAD_MODES and len(frames) > 0 and len(self) > 0
                 and dtype in (np.float32, np.float64) and isinstance(saturation_dilation, numbers.Integral) and saturation_dilation >= 1
-                and isinstance(neighborhood_width, numbers.Integral) and neighborhood_width >= 0):
+                and isinstance(neighborhood_width, numbers.Integral) and neighborhood_width >= 0
+                and not (self._saturation == "device" and neighborhood_width // 2 >= 1)):  # (the device route: the loop over apply, below)
             # the saturation branch for a sequence of frames: the host steps of frame i + 1 (pad, mask, dilation, sequential fill) run while the
             # GPU corrects frame i (rpsf_apply_frames_host_saturated)
             n = self._checked_patch_size()
