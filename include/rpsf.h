@@ -108,9 +108,11 @@ enum {
   RPSF_OPT_STREAM_GROUP = 6,  /* 0 automatic, else frames per group of the streamed host path */
   RPSF_OPT_STREAM_DEPTH = 7,  /* 0 automatic, else groups in flight of the streamed host path */
   RPSF_OPT_DEBUG_ORPHAN = 8,  /* testing aid of the direct overlap-add: every value-th workgroup behaves as if placed on a foreign XCD */
-  RPSF_OPT_HEAD_KPREFETCH = 9 /* 0 / 1: persistent launches of a 256-pixel plan - the head summing workgroups touch the transfer kernel of the
+  RPSF_OPT_HEAD_KPREFETCH = 9, /* 0 / 1: persistent launches of a 256-pixel plan - the head summing workgroups touch the transfer kernel of the
                                  first round's patches before they sum (default 0: measured a loss; ignored by other plans).
                                  Changes no value of the result. */
+  RPSF_OPT_SAT_GROUP = 10     /* 0 automatic (scratch under 1 GiB), else 1..65535 frames per frame-group of the batched device
+                                 saturation route.  Changes no value of the result. */
 };
 int rpsf_plan_set_option(rpsf_plan* plan, int option, int value);
 int rpsf_plan_sweep_info(const rpsf_plan* plan, int* regions, long* jobs, long* patch_slots, int* slabs_per_phase);
@@ -211,7 +213,8 @@ int rpsf_apply_device_saturated(rpsf_plan* plan, const void* image_dev, void* ou
  * rounding is the one place where the two routes can disagree beyond the rounding of the fill's inputs. */
 int rpsf_apply_host_saturated_device(rpsf_plan* plan, const void* image_host, int image_is_f64, int height, int width, int pad_mode,
                                      double threshold, int dilation, int neighborhood_width, void* out_host, int out_is_f64);
-/* Device time of the last F1 ... F5 launches of the plan, milliseconds (F3's includes the host's one wait; zeros for what did not run). */
+/* Device time of the last F1 ... F5 launches of the plan, milliseconds (F3's includes the host's one wait; zeros for what did not run).
+ * After a batch call (rpsf_apply_batch_device_saturated and its kin): F1 ... F5 of the LAST frame-group, all its frames together. */
 int rpsf_saturation_kernel_ms(rpsf_plan* plan, double ms[5]);
 /* Test entry: F1 - F4 alone on a float32 host frame.  padded_host ((height + 4N) x (width + 4N) float32) receives the filled padded
  * frame, mask_host (as many bytes) the dilated mask; reverse_groups != 0 makes F4's workgroups take the groups last first (the result
@@ -219,6 +222,39 @@ int rpsf_saturation_kernel_ms(rpsf_plan* plan, double ms[5]);
 int rpsf_saturation_fill_device(rpsf_plan* plan, const float* image_host, int height, int width, int pad_mode, double threshold,
                                 int dilation, int neighborhood_width, int reverse_groups, float* padded_host, uint8_t* mask_host,
                                 int* n_groups_or_null);
+/* rpsf_apply_device_saturated for n_frames float32 frames of one shape on the plan's device, image_stride floats apart (>= height x
+ * width, any alignment); frame f of the result goes to outs_dev + f x out_stride (>= height x width), the floats between two frames
+ * stay untouched.  Frame by frame the result has the bits of rpsf_apply_device_saturated's.  The batch is cut into frame-groups
+ * (RPSF_OPT_SAT_GROUP; automatic: as many frames as keep the scratch below under 1 GiB).  A frame-group shares every launch of F1 - F3
+ * (the frame is a grid index; labels, roots and counters stay per frame), the host waits for the stream ONCE per frame-group, not per
+ * frame, F4 is one launch of one wave per group over all frames' groups, longest groups first, the correction is the shared-K batch
+ * launch of rpsf_apply_batch_device on the padded frames, F5 one launch.  Argument checks as rpsf_apply_device_saturated
+ * (neighborhood_width / 2 < 1: RPSF_E_BADARG), n_frames < 0: RPSF_E_BADARG, a stride below height x width with n_frames > 1:
+ * RPSF_E_BADARG, n_frames == 0: RPSF_OK and nothing is done (the pointers may then be NULL).  RPSF_E_UNSUPPORTED when a frame-group
+ * holds 2^31 masked pixels or more (cut it smaller).  n_masked_per_frame_or_null: n_frames entries, masked pixels of padded frame f.
+ * SCRATCH per frame of a frame-group: what rpsf_apply_device_saturated lists for one frame (every per-frame array starts on a
+ * multiple of 4 elements), 28 B of counters and offsets, and the batch launch's own 16 B per output pixel; 8 B more per group. */
+int rpsf_apply_batch_device_saturated(rpsf_plan* plan, const void* images_dev, void* outs_dev, int n_frames, size_t image_stride,
+                                      size_t out_stride, int height, int width, int pad_mode, double threshold, int dilation,
+                                      int neighborhood_width, void* stream, size_t* n_masked_per_frame_or_null);
+/* rpsf_apply_host_saturated_device's contract for n_frames host frames of one shape and type, per frame-group: the frames are narrowed
+ * to float32 into the plan's page-locked staging and uploaded, rpsf_apply_batch_device_saturated's route runs, `height` rows per frame
+ * come back, and for float64 input every frame's listed pixels receive the caller's own float64 values.  A frame-group's upload is not
+ * overlapped with the previous group's kernels.  n_frames == 0: RPSF_OK. */
+int rpsf_apply_frames_host_saturated_device(rpsf_plan* plan, const void* const* images_host, int image_is_f64, int n_frames, int height,
+                                            int width, int pad_mode, double threshold, int dilation, int neighborhood_width,
+                                            void* const* outs_host, int out_is_f64);
+/* Of the last batch call of the plan (either entry above, or the test entry below): info[0] frames, info[1] frame-groups (= host waits
+ * before F4), info[2] fill groups over all frames, info[3] masked pixels of the padded frames (saturating at INT_MAX).  Zeros before
+ * the first.  After a batch call rpsf_saturation_kernel_ms reports F1 ... F5 of the LAST frame-group (F4 with its ordering pass). */
+int rpsf_saturation_batch_info(rpsf_plan* plan, int info[4]);
+/* Test entry: F1 - F4 alone on n_frames float32 host frames (contiguous, height x width each), cut into frame-groups as above.
+ * padded_host (n_frames x (height + 4N) x (width + 4N) float32, dense) receives the filled padded frames, masks_host (as many bytes)
+ * the dilated masks, groups_per_frame_or_null[f] the independent groups of frame f.  order: 0 F4's workgroups take the groups longest
+ * first, 1 that order reversed, 2 the group table's own order (frame by frame); the result must not depend on it. */
+int rpsf_saturation_fill_batch_device(rpsf_plan* plan, const float* images_host, int n_frames, int height, int width, int pad_mode,
+                                      double threshold, int dilation, int neighborhood_width, int order, float* padded_host,
+                                      uint8_t* masks_host, int* groups_per_frame_or_null);
 /* Same with image and output already resident on the plan's device; asynchronous on `stream`
  * (a hipStream_t, or NULL for the plan's own stream).  Every pixel of the resident output rows is written
  * (uncovered ones with 0).  image_dev / out_dev must be ordinary device memory of the plan's device

@@ -76,6 +76,12 @@ _PROTOTYPES = {
     "rpsf_apply_host_saturated_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int]),
     "rpsf_saturation_kernel_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rpsf_saturation_fill_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_int)]),
+    "rpsf_apply_batch_device_saturated": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_int, c_int, c_int, c_double, c_int, c_int,
+                                                  c_void_p, POINTER(c_size_t)]),
+    "rpsf_apply_frames_host_saturated_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int]),
+    "rpsf_saturation_batch_info": (c_int, [c_void_p, POINTER(c_int)]),
+    "rpsf_saturation_fill_batch_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                  c_void_p]),
     "rpsf_apply_frames_host_saturated": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int]),
     "rpsf_apply_device": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(Geometry), c_void_p]),
     "rpsf_apply_device_timed": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(Geometry), c_int, c_void_p, c_void_p]),
@@ -256,7 +262,7 @@ class Plan:
         check(lib().rpsf_plan_set_overlap_mode(self._handle, {"auto": 0, "atomic": 1, "planes": 2, "direct": 3, "sweep": 4}[mode]))
 
     OPTIONS = {"persist": 1, "fuse": 2, "k_cached": 3, "plane_nt": 4, "host_bands": 5, "stream_group": 6, "stream_depth": 7, "debug_orphan": 8,
-               "head_kprefetch": 9}
+               "head_kprefetch": 9, "sat_group": 10}
 
     def set_option(self, name: str, value: int) -> None:
         """Pin a launch option of the plan (include/rpsf.h, RPSF_OPT_*): what tests and callers may choose instead of environment variables."""
@@ -391,6 +397,55 @@ class Plan:
                                                 int(neighborhood_width), int(bool(reverse_groups)), _ptr(padded), _ptr(mask),
                                                 ctypes.byref(groups)))
         return padded, mask.astype(bool), groups.value
+
+    def apply_batch_device_saturated(self, images_ptr: c_void_p, outs_ptr: c_void_p, n_frames: int, image_stride: int, out_stride: int,
+                                     height: int, width: int, pad_mode: int, threshold: float, dilation: int, neighborhood_width: int,
+                                     stream: c_void_p | None = None) -> np.ndarray:
+        """The saturation branch on ``n_frames`` resident float32 frames of one shape, ``image_stride`` / ``out_stride`` floats apart: shared
+        launches of F1 - F3, one host wait per frame-group, one F4 launch; returns the masked pixels of every padded frame."""
+        counts = (c_size_t * max(1, int(n_frames)))()
+        check(lib().rpsf_apply_batch_device_saturated(self._handle, images_ptr, outs_ptr, int(n_frames), int(image_stride), int(out_stride),
+                                                      int(height), int(width), pad_mode, float(threshold), int(dilation),
+                                                      int(neighborhood_width), stream, counts))
+        return np.array(counts[: max(0, int(n_frames))], dtype=np.int64)
+
+    def apply_frames_host_saturated_device(self, images, pad_mode: int, threshold: float, dilation: int, neighborhood_width: int,
+                                           out_dtype=np.float64) -> np.ndarray:
+        """``apply_frames_host_saturated`` through the batched device route (kernels F1 - F5 on all frames of a frame-group at once); the
+        masked pixels of float64 frames get the caller's own values back.  Needs ``neighborhood_width // 2 >= 1``."""
+        frames = [np.asarray(im) for im in images]
+        if any(f.ndim != 2 or f.shape != frames[0].shape for f in frames):
+            msg = "frames must be two dimensional and of one shape"
+            raise ValueError(msg)
+        is_f32 = all(f.dtype == np.float32 for f in frames)
+        want = np.float32 if is_f32 else np.float64
+        frames = [np.ascontiguousarray(f if f.dtype == want and f.dtype.byteorder != ">" else f.astype(want)) for f in frames]
+        n, shape = len(frames), (frames[0].shape if frames else (0, 0))
+        out = np.empty((n, *shape), out_dtype)
+        in_ptrs = (c_void_p * max(1, n))(*[f.ctypes.data for f in frames])
+        out_ptrs = (c_void_p * max(1, n))(*[out[i].ctypes.data for i in range(n)])
+        check(lib().rpsf_apply_frames_host_saturated_device(self._handle, in_ptrs, int(not is_f32), n, shape[0], shape[1], pad_mode,
+                                                            float(threshold), int(dilation), int(neighborhood_width), out_ptrs,
+                                                            int(np.dtype(out_dtype) == np.float64)))
+        return out
+
+    def saturation_batch_info(self) -> tuple[int, int, int, int]:
+        """Of the last batch call: (frames, frame-groups = host waits before F4, fill groups over all frames, masked pixels)."""
+        info = (c_int * 4)()
+        check(lib().rpsf_saturation_batch_info(self._handle, info))
+        return tuple(info[:])
+
+    def saturation_fill_batch_device(self, images, pad_mode: int, threshold: float, dilation: int, neighborhood_width: int,
+                                     order: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Test entry: F1 - F4 alone on a stack of frames; (filled padded float32 frames, masks, groups per frame).  ``order``: 0 F4 takes
+        the groups longest first, 1 that order reversed, 2 frame by frame."""
+        stack = np.ascontiguousarray(np.stack([np.asarray(im, dtype=np.float32) for im in images]))
+        n, h, w = stack.shape
+        shape = (n, h + 4 * self.patch_size, w + 4 * self.patch_size)
+        padded, masks, groups = np.empty(shape, np.float32), np.empty(shape, np.uint8), np.zeros(n, np.int32)
+        check(lib().rpsf_saturation_fill_batch_device(self._handle, _ptr(stack), n, h, w, pad_mode, float(threshold), int(dilation),
+                                                      int(neighborhood_width), int(order), _ptr(padded), _ptr(masks), _ptr(groups)))
+        return padded, masks.astype(bool), groups
 
     def apply_frames_host_saturated(self, images, pad_mode: int, threshold: float, dilation: int, neighborhood_width: int,
                                     out_dtype=np.float64) -> np.ndarray:

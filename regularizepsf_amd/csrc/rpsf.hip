@@ -36,6 +36,7 @@
 #include "rpsf_device.hpp"
 #include "rpsf_hostpipe.hpp"
 #include "rpsf_saturation.hpp"
+#include "rpsf_core_saturation_batch.hpp"
 
 RPSF_PLANS_V1(RPSF_DECL_V1)
 RPSF_PLANS_V2(RPSF_DECL_V2)
@@ -271,6 +272,8 @@ struct rpsf_plan : PlanStream {
   int cu_count = 256;
   bool lattice = false;
   int host_bands_opt = -1, stream_group_opt = 0, stream_depth_opt = 0;  // rpsf_plan_set_option; -1 / 0: the library decides
+  int sat_group_opt = 0;            // RPSF_OPT_SAT_GROUP: frames per frame-group of the batched device saturation route (0: by the scratch budget)
+  int sat_batch_info[4] = {};       // rpsf_saturation_batch_info
   int last_host_bands = 0;  // row bands the last single host frame was cut into (rpsf_plan_host_bands)
   hipStream_t last_stream = nullptr;
   bool busy_valid = false;
@@ -1509,6 +1512,10 @@ extern "C" int rpsf_plan_set_option(rpsf_plan* p, int option, int value) {
       if (value != 0 && value != 1) return fail(RPSF_E_BADARG, "RPSF_OPT_HEAD_KPREFETCH takes 0 or 1");
       p->patch.k_prefetch = p->N == 256 ? value : 0;
       break;
+    case RPSF_OPT_SAT_GROUP:
+      if (value < 0 || value > 65535) return fail(RPSF_E_BADARG, "RPSF_OPT_SAT_GROUP takes 0 (automatic) or 1..65535");
+      p->sat_group_opt = value;
+      return RPSF_OK;  // (no launch of the correction depends on it: the band views stay)
     case RPSF_OPT_DEBUG_ORPHAN:
       if (value < 0) return fail(RPSF_E_BADARG, "RPSF_OPT_DEBUG_ORPHAN takes 0 (off) or a positive modulus");
       p->patch.orphan_mod = value;
@@ -2710,6 +2717,210 @@ extern "C" int rpsf_saturation_fill_device(rpsf_plan* p, const float* image_host
     int n_hot, n_mask;
     rpsf_sat_counts(p->sat_dev.get(), &n_hot, &n_mask, n_groups_or_null);
   }
+  return RPSF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The device route for a batch of frames of one shape (csrc/rpsf_core_saturation_batch.hpp, DESIGN.md 3.8 "Frame batches"): cut into
+// frame-groups; per frame-group F1 - F3 with the frame as a grid index, one wait, one F4 launch, the shared-K batch launch on the padded
+// frames, one F5 launch.
+// ------------------------------------------------------------------------------------------------
+struct SatBatchStats {
+  long frames = 0, frame_groups = 0, groups = 0, masked = 0;
+  void store(rpsf_plan* p) const {
+    const long v[4] = {frames, frame_groups, groups, masked};
+    for (int i = 0; i < 4; ++i) p->sat_batch_info[i] = (int)std::min<long>(v[i], 0x7FFFFFFF);
+  }
+};
+
+static int sat_group_frames(const rpsf_plan* p, const SatDeviceRun& run) {
+  if (p->sat_group_opt > 0) return p->sat_group_opt;
+  return rpsfsatb::auto_group_frames((size_t)run.g.height * run.g.width, (size_t)run.call.out_rows * run.g.width);
+}
+
+// one frame-group, resident; asynchronous on st but for the one wait inside rpsf_sat_fill_batch
+static int sat_device_apply_group(rpsf_plan* p, const SatDeviceRun& run, int frames, const float* images_dev, size_t image_stride, float* outs_dev,
+                                  size_t out_stride, hipStream_t st, SatBatchStats* stats, size_t* n_masked_or_null) {
+  float *padded = nullptr, *corrected = nullptr;
+  size_t p_stride = 0, c_stride = 0;
+  SatDevice* sd = p->sat_dev.get();
+  int rc = rpsf_sat_fill_batch(sd, run.call, frames, images_dev, image_stride, rpsfsatb::ORDER_LONGEST_FIRST, st, &padded, &p_stride, &corrected, &c_stride);
+  if (rc != RPSF_OK) return rc;
+  rc = launch_batch(p, padded + (size_t)run.r_lo * run.g.width, corrected, frames, p_stride, c_stride, run.g, st);
+  if (rc != RPSF_OK) return rc;
+  rc = rpsf_sat_restore_batch(sd, run.call, images_dev, image_stride, outs_dev, out_stride, st);
+  if (rc != RPSF_OK) return rc;
+  long groups = 0, masked = 0;
+  rpsf_sat_batch_totals(sd, &groups, &masked);
+  stats->frame_groups += 1, stats->groups += groups, stats->masked += masked;
+  for (int f = 0; n_masked_or_null && f < frames; ++f) {
+    int n_hot, n_mask, n_groups;
+    rpsf_sat_frame_counts(sd, f, &n_hot, &n_mask, &n_groups);
+    n_masked_or_null[f] = (size_t)n_mask;
+  }
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_apply_batch_device_saturated(rpsf_plan* p, const void* images_dev, void* outs_dev, int n_frames, size_t image_stride,
+                                                 size_t out_stride, int height, int width, int pad_mode, double threshold, int dilation,
+                                                 int neighborhood_width, void* stream, size_t* n_masked_per_frame_or_null) {
+  if (p && n_frames == 0) {
+    SatBatchStats().store(p);
+    return RPSF_OK;
+  }
+  int rc = check_saturated_call(p, images_dev, outs_dev, height, width, pad_mode, dilation, neighborhood_width);
+  if (rc != RPSF_OK) return rc;
+  if (n_frames < 0) return fail(RPSF_E_BADARG, "n_frames must not be negative");
+  if (n_frames > 1 && (image_stride < (size_t)height * width || out_stride < (size_t)height * width))
+    return fail(RPSF_E_BADARG, "frame stride smaller than one frame");
+  SatDeviceRun run;
+  rc = sat_device_init(p, height, width, pad_mode, threshold, dilation, neighborhood_width, &run);
+  if (rc != RPSF_OK) return rc;
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : p->stream;
+  const int G = sat_group_frames(p, run);
+  SatBatchStats stats;
+  stats.frames = n_frames;
+  for (int f0 = 0; f0 < n_frames; f0 += G) {
+    rc = sat_device_apply_group(p, run, std::min(G, n_frames - f0), static_cast<const float*>(images_dev) + (size_t)f0 * image_stride, image_stride,
+                                static_cast<float*>(outs_dev) + (size_t)f0 * out_stride, out_stride, st, &stats,
+                                n_masked_per_frame_or_null ? n_masked_per_frame_or_null + f0 : nullptr);
+    if (rc != RPSF_OK) return rc;
+  }
+  stats.store(p);
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_apply_frames_host_saturated_device(rpsf_plan* p, const void* const* images_host, int image_is_f64, int n_frames, int height,
+                                                       int width, int pad_mode, double threshold, int dilation, int neighborhood_width,
+                                                       void* const* outs_host, int out_is_f64) {
+  if (p && n_frames == 0) {
+    SatBatchStats().store(p);
+    return RPSF_OK;
+  }
+  int rc = check_saturated_call(p, images_host, outs_host, height, width, pad_mode, dilation, neighborhood_width);
+  if (rc != RPSF_OK) return rc;
+  if (n_frames < 0) return fail(RPSF_E_BADARG, "n_frames must not be negative");
+  for (int f = 0; f < n_frames; ++f)
+    if (!images_host[f] || !outs_host[f]) return fail(RPSF_E_BADARG, "null frame pointer");
+  SatDeviceRun run;
+  rc = sat_device_init(p, height, width, pad_mode, threshold, dilation, neighborhood_width, &run);
+  if (rc != RPSF_OK) return rc;
+  const size_t npix = (size_t)height * width;
+  const int G = std::min(sat_group_frames(p, run), n_frames);
+  rc = pipe_ensure(p, npix * G, 1);
+  if (rc != RPSF_OK) return rc;
+  HostPipe& q = *p->pipe;
+  HostPool& pool = HostPool::get(p->device);
+  const int T = host_parts_for(npix * G * sizeof(float));
+  SatBatchStats stats;
+  stats.frames = n_frames;
+  for (int f0 = 0; f0 < n_frames; f0 += G) {
+    const int fg = std::min(G, n_frames - f0);
+    const size_t total = npix * fg;
+    pool.run(T, [&](int t) {  // the group's frames laid end to end, cut into T parts
+      size_t a, b;
+      rpsf_host::split_range(0, total, t, T, a, b);
+      while (a < b) {
+        const size_t f = a / npix, lo = a % npix, hi = std::min(npix, lo + (b - a));
+        rpsf_host::narrow_or_copy(q.h_in[0] + f * npix, images_host[f0 + f], image_is_f64 != 0, lo, hi);
+        a += hi - lo;
+      }
+    });
+    hipError_t err = hipMemcpyAsync(q.d_in[0], q.h_in[0], total * sizeof(float), hipMemcpyHostToDevice, p->stream);
+    if (err != hipSuccess) return drain_after_error(p, err, "saturated host frames, device route");
+    rc = sat_device_apply_group(p, run, fg, q.d_in[0], npix, q.d_out[0], npix, p->stream, &stats, nullptr);
+    if (rc != RPSF_OK) {
+      (void)hipStreamSynchronize(p->stream);
+      return rc;
+    }
+    err = hipMemcpyAsync(q.h_out[0], q.d_out[0], total * sizeof(float), hipMemcpyDeviceToHost, p->stream);
+    if (err != hipSuccess) return drain_after_error(p, err, "saturated host frames, device route");
+    const int32_t* list = nullptr;
+    const int *info = nullptr, *counters = nullptr;
+    rc = rpsf_sat_lists_batch(p->sat_dev.get(), p->stream, &list, &info, &counters);  // waits for the stream when there is a list
+    if (rc != RPSF_OK) {
+      (void)hipStreamSynchronize(p->stream);
+      return rc;
+    }
+    if (!list) {
+      err = hipStreamSynchronize(p->stream);
+      if (err != hipSuccess) return drain_after_error(p, err, "saturated host frames, device route");
+    }
+    pool.run(T, [&](int t) {
+      size_t a, b;
+      rpsf_host::split_range(0, total, t, T, a, b);
+      while (a < b) {
+        const size_t f = a / npix, lo = a % npix, hi = std::min(npix, lo + (b - a));
+        rpsf_host::widen_or_copy(outs_host[f0 + f], out_is_f64 != 0, q.h_out[0] + f * npix, lo, hi);
+        a += hi - lo;
+      }
+    });
+    if (image_is_f64 && list) {  // the caller's own values on the mask, not their float32 roundings
+      for (int f = 0; f < fg; ++f) {
+        const double* src = static_cast<const double*>(images_host[f0 + f]);
+        const int32_t* mine = list + info[rpsfsatb::FRAME_INFO * f + rpsfsatb::I_LIST0];
+        const int n = counters[rpsfsatb::FRAME_COUNTERS * f + rpsfsatb::C_HOT] ? counters[rpsfsatb::FRAME_COUNTERS * f + rpsfsatb::C_LIST] : 0;
+        for (int k = 0; k < n; ++k) {
+          if (out_is_f64) static_cast<double*>(outs_host[f0 + f])[mine[k]] = src[mine[k]];
+          else static_cast<float*>(outs_host[f0 + f])[mine[k]] = (float)src[mine[k]];
+        }
+      }
+    }
+  }
+  stats.store(p);
+  return sweep_check(p);
+}
+
+extern "C" int rpsf_saturation_batch_info(rpsf_plan* p, int info[4]) {
+  if (!p || !info) return fail(RPSF_E_BADARG, "null argument");
+  for (int i = 0; i < 4; ++i) info[i] = p->sat_batch_info[i];
+  return RPSF_OK;
+}
+
+// Test entry: F1 - F4 alone on n_frames float32 host frames, frame-group by frame-group
+extern "C" int rpsf_saturation_fill_batch_device(rpsf_plan* p, const float* images_host, int n_frames, int height, int width, int pad_mode,
+                                                 double threshold, int dilation, int neighborhood_width, int order, float* padded_host,
+                                                 uint8_t* masks_host, int* groups_per_frame_or_null) {
+  if (!p || !images_host || !padded_host || !masks_host) return fail(RPSF_E_BADARG, "null argument");
+  if (n_frames < 1) return fail(RPSF_E_BADARG, "n_frames must be positive");
+  if (height <= 0 || width <= 0) return fail(RPSF_E_BADARG, "image shape must be positive");
+  if (pad_mode < 0 || pad_mode > RPSF_PAD_WRAP) return fail(RPSF_E_BADARG, "unknown pad mode");
+  if (dilation < 1 || neighborhood_width / 2 < 1) return fail(RPSF_E_BADARG, "dilation must be >= 1 and neighborhood_width // 2 >= 1");
+  if (order < rpsfsatb::ORDER_LONGEST_FIRST || order > rpsfsatb::ORDER_FRAMES) return fail(RPSF_E_BADARG, "order must be 0, 1 or 2");
+  const long PH = (long)height + 4L * p->N, PW = (long)width + 4L * p->N;
+  if (PH * PW >= ((long)1 << 31)) return fail(RPSF_E_UNSUPPORTED, "padded frame too large for this entry point");
+  HIP_TRY(hipSetDevice(p->device));
+  if (!p->sat_dev) p->sat_dev.reset(rpsf_sat_create());
+  SatDevice* sd = p->sat_dev.get();
+  const SatCall call{height, width, p->N, pad_mode, dilation, neighborhood_width, threshold, 0, 0, 1, false};
+  const size_t npix = (size_t)height * width, np = (size_t)PH * PW;
+  const int G = std::min(n_frames, p->sat_group_opt > 0 ? p->sat_group_opt : rpsfsatb::auto_group_frames(np, (size_t)height * PW));
+  DevBuf<float> d_images;
+  HIP_TRY(d_images.upload(images_host, npix * n_frames));
+  SatBatchStats stats;
+  stats.frames = n_frames;
+  for (int f0 = 0; f0 < n_frames; f0 += G) {
+    const int fg = std::min(G, n_frames - f0);
+    float *padded = nullptr, *corrected = nullptr;
+    size_t p_stride = 0, c_stride = 0;
+    const float* d_first = d_images;
+    int rc = rpsf_sat_fill_batch(sd, call, fg, d_first + (size_t)f0 * npix, npix, order, p->stream, &padded, &p_stride, &corrected, &c_stride);
+    if (rc == RPSF_OK) rc = rpsf_sat_masks_batch(sd, call, p->stream, masks_host + (size_t)f0 * np);  // waits for the stream
+    if (rc != RPSF_OK) {
+      (void)hipStreamSynchronize(p->stream);
+      return rc;
+    }
+    for (int f = 0; f < fg; ++f) {
+      HIP_TRY(hipMemcpy(padded_host + (size_t)(f0 + f) * np, padded + f * p_stride, np * sizeof(float), hipMemcpyDeviceToHost));
+      int n_hot, n_mask, n_groups;
+      rpsf_sat_frame_counts(sd, f, &n_hot, &n_mask, &n_groups);
+      if (groups_per_frame_or_null) groups_per_frame_or_null[f0 + f] = n_groups;
+    }
+    long groups = 0, masked = 0;
+    rpsf_sat_batch_totals(sd, &groups, &masked);
+    stats.frame_groups += 1, stats.groups += groups, stats.masked += masked;
+  }
+  stats.store(p);
   return RPSF_OK;
 }
 

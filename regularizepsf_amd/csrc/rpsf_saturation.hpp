@@ -29,3 +29,20 @@ __attribute__((visibility("hidden"))) int rpsf_sat_list(SatDevice* s, hipStream_
 __attribute__((visibility("hidden"))) int rpsf_sat_mask(SatDevice* s, const SatCall& c, hipStream_t st, uint8_t* mask_host);  // PH x PW bytes (zeros when nothing was hot)
 __attribute__((visibility("hidden"))) int rpsf_sat_counts(SatDevice* s, int* n_hot, int* n_mask, int* n_groups);  // of the last fill
 __attribute__((visibility("hidden"))) int rpsf_sat_kernel_ms(SatDevice* s, double ms[5]);
+
+// ---- a group of `frames` frames of one shape, image_stride floats apart (csrc/rpsf_core_saturation_batch.hpp).  F1 - F4 on `st` with ONE
+// synchronisation of it for all frames; F4 is one launch over every frame's groups in `order_mode` (rpsfsatb::ORDER_*).  *padded: the
+// filled padded frames, *p_stride floats apart; *corrected: room for out_rows x PW float32 per frame, *c_stride apart.
+__attribute__((visibility("hidden"))) int rpsf_sat_fill_batch(SatDevice* s, const SatCall& c, int frames, const float* images_dev, size_t image_stride,
+                                                               int order_mode, hipStream_t st, float** padded, size_t* p_stride, float** corrected,
+                                                               size_t* c_stride);
+// F5 of every frame of the last rpsf_sat_fill_batch, one launch
+__attribute__((visibility("hidden"))) int rpsf_sat_restore_batch(SatDevice* s, const SatCall& c, const float* images_dev, size_t image_stride,
+                                                                  float* outs_dev, size_t out_stride, hipStream_t st);
+// every frame's list to the host, one wait for `st`: frame fr's entries start at info_host[FRAME_INFO * fr + I_LIST0] and number
+// counters_host[FRAME_COUNTERS * fr + C_LIST]; *list_host stays null, and nothing is waited for, when no frame had a masked pixel
+__attribute__((visibility("hidden"))) int rpsf_sat_lists_batch(SatDevice* s, hipStream_t st, const int32_t** list_host, const int** info_host,
+                                                                const int** counters_host);
+__attribute__((visibility("hidden"))) int rpsf_sat_masks_batch(SatDevice* s, const SatCall& c, hipStream_t st, uint8_t* masks_host);  // frames x PH x PW bytes
+__attribute__((visibility("hidden"))) int rpsf_sat_frame_counts(SatDevice* s, int frame, int* n_hot, int* n_mask, int* n_groups);  // of the last frame-group
+__attribute__((visibility("hidden"))) void rpsf_sat_batch_totals(SatDevice* s, long* groups, long* masked);  // of the last frame-group

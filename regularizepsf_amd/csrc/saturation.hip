@@ -8,6 +8,9 @@
 //   F4  sat_fill_kernel                    one wave per group: the sequential nan-mean fill of the group's pixels in raster order
 //   F5  sat_restore_kernel                 raw values on the mask, crop, list of the masked in-frame pixels
 //
+// A group of frames of one shape goes through the same phases with the frame as a grid index (sat_*_batch_kernel, the drivers of
+// rpsf_core_saturation_batch.hpp): F1 - F3 once for all frames, ONE host wait, one F4 launch over all frames' groups, longest first.
+//
 // The phases are the drivers of rpsf_core_saturation.hpp.  Every launch goes to the caller's stream; the host waits for it once, between
 // the root count and the root list, to size the group table.  When nothing is hot every kernel after F1 returns at its first
 // instruction and F4 is not launched.  The only atomics are integer adds / min / max.
@@ -18,10 +21,13 @@
 
 #include "../../include/rpsf.h"
 #include "rpsf_core_saturation.hpp"
+#include "rpsf_core_saturation_batch.hpp"
 #include "rpsf_saturation.hpp"
 
 using namespace rpsfs;
 using namespace rpsfsat;
+using rpsfsatb::Stack;
+using rpsfsatb::Tables;
 
 int rpsf_detail_fail(int code, const std::string& msg);  // rpsf.hip: sets rpsf_last_error of the calling thread
 static int fail(int code, const std::string& msg) { return rpsf_detail_fail(code, msg); }
@@ -103,6 +109,43 @@ __global__ __launch_bounds__(256) void sat_restore_kernel(Padded f, const float*
   f5_restore(global_id(), f, image, mask, corrected, out_row0, out, list, counters + N_LIST);
 }
 
+// ---- the same for a group of frames: blockIdx.y (the labeller's tiles: blockIdx.z) is the frame
+__global__ __launch_bounds__(256) void sat_pad_batch_kernel(Stack s, const float* images, size_t image_stride, double threshold) {
+  rpsfsatb::b1_pad(global_id(), (int)blockIdx.y, s, images, image_stride, threshold);
+}
+__global__ __launch_bounds__(256) void sat_cross_batch_kernel(Stack s, int from, int last) {
+  rpsfsatb::b2_cross(global_id(), (int)blockIdx.y, s, from, last);
+}
+__global__ __launch_bounds__(256) void sat_rows_batch_kernel(Stack s, int reach, int at) { rpsfsatb::b3_rows(global_id(), (int)blockIdx.y, s, reach, at); }
+__global__ __launch_bounds__(256) void sat_cols_batch_kernel(Stack s, int reach, int at) { rpsfsatb::b3_cols(global_id(), (int)blockIdx.y, s, reach, at); }
+__global__ __launch_bounds__(TILE_THREADS) void sat_label_tile_batch_kernel(Stack s, int grown) {
+  GpuCtx ctx;
+  rpsfsatb::b3_tile(ctx, (int)blockIdx.z, s, grown, (int)blockIdx.y, (int)blockIdx.x, reinterpret_cast<int*>(sat_lds));
+}
+__global__ __launch_bounds__(256) void sat_label_seam_batch_kernel(Stack s) { rpsfsatb::b3_seam(global_id(), (int)blockIdx.y, s); }
+__global__ __launch_bounds__(256) void sat_label_flatten_batch_kernel(Stack s) { rpsfsatb::b3_flatten(global_id(), (int)blockIdx.y, s); }
+__global__ __launch_bounds__(256) void sat_count_batch_kernel(Stack s) { rpsfsatb::b3_count(global_id(), (int)blockIdx.y, s); }
+__global__ __launch_bounds__(SCAN_THREADS) void sat_scan_batch_kernel(Stack s) {
+  GpuCtx ctx;
+  rpsfsatb::b3_scan(ctx, (int)blockIdx.x, s, reinterpret_cast<int*>(sat_lds));
+}
+__global__ __launch_bounds__(256) void sat_roots_batch_kernel(Stack s, Tables t) { rpsfsatb::b3_roots(global_id(), (int)blockIdx.y, s, t); }
+__global__ __launch_bounds__(256) void sat_group_init_batch_kernel(Tables t) { rpsfsatb::b3_init(global_id(), (int)blockIdx.y, t); }
+__global__ __launch_bounds__(256) void sat_group_accumulate_batch_kernel(Stack s, Tables t, int at) {
+  rpsfsatb::b3_accumulate(global_id(), (int)blockIdx.y, s, t, at);
+}
+__global__ __launch_bounds__(256) void sat_order_hist_kernel(Tables t) { rpsfsatb::o_hist(global_id(), t); }
+__global__ __launch_bounds__(256) void sat_order_scatter_kernel(Tables t) { rpsfsatb::o_scatter(global_id(), t); }
+__global__ __launch_bounds__(FILL_LANES) void sat_fill_batch_kernel(Stack s, Tables t, int order_mode, int at, int h) {
+  GpuCtx ctx;
+  rpsfsatb::b4_group(ctx, (long)blockIdx.x, order_mode, s, t, at, h, reinterpret_cast<FillLds*>(sat_lds));
+}
+__global__ __launch_bounds__(256) void sat_restore_batch_kernel(Stack s, const int* info, int at, const float* images, size_t image_stride,
+                                                                const float* corrected, size_t c_stride, int out_row0, float* outs,
+                                                                size_t out_stride, int32_t* lists) {
+  rpsfsatb::b5_restore(global_id(), (int)blockIdx.y, s, info, at, images, image_stride, corrected, c_stride, out_row0, outs, out_stride, lists);
+}
+
 namespace {
 template <class T>
 struct Buf {  // a device array that only ever grows
@@ -110,7 +153,10 @@ struct Buf {  // a device array that only ever grows
   size_t cap = 0;
   hipError_t reserve(size_t count) {
     if (count <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
+    if (p) {  // (nothing of an earlier call may still be running on the old array)
+      (void)hipDeviceSynchronize();
+      (void)hipFree(p);
+    }
     p = nullptr, cap = 0;
     const hipError_t e = hipMalloc(&p, count * sizeof(T));
     if (e == hipSuccess) cap = count;
@@ -126,7 +172,10 @@ struct PinnedBuf {  // the same in page-locked host memory
   size_t cap = 0;
   hipError_t reserve(size_t count) {
     if (count <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
+    if (p) {
+      (void)hipDeviceSynchronize();
+      (void)hipHostFree(p);
+    }
     p = nullptr, cap = 0;
     const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), count * sizeof(T), hipHostMallocDefault);
     if (e == hipSuccess) cap = count;
@@ -153,6 +202,12 @@ struct SatDevice {
   enum { E_START, E_F1, E_F2, E_F3, E_F4, E_F5A, E_F5B, N_EVENTS };
   hipEvent_t ev[N_EVENTS] = {};
   bool timed = false, restored = false;
+  // a group of frames (rpsf_sat_fill_batch): the arrays above hold `b_frames` frames b_stride apart, counters and tables are these
+  Buf<int> b_counters, b_info, b_gframe, b_order;  // FRAME_COUNTERS per frame + SHARED_COUNTERS; FRAME_INFO per frame; per group
+  PinnedBuf<int> h_b_counters, h_b_info;
+  int b_frames = 0, b_at = 0;
+  size_t b_stride = 0, b_cstride = 0, b_nseg = 0;
+  long b_groups = 0, b_masked = 0, b_listed = 0;
   ~SatDevice() {
     for (auto e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -287,3 +342,146 @@ int rpsf_sat_counts(SatDevice* s, int* n_hot, int* n_mask, int* n_groups) {
   *n_hot = s->n_hot, *n_mask = s->n_mask, *n_groups = s->n_groups;
   return RPSF_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ a group of frames
+namespace {
+Stack stack_of(const SatDevice* s, const SatCall& c) {
+  Stack k;
+  k.f = Padded{c.H, c.W, c.N, c.H + 4 * c.N, c.W + 4 * c.N, c.pad_mode};
+  k.stride = s->b_stride, k.nseg = s->b_nseg;
+  k.padded = s->padded.p, k.labels = s->labels.p, k.segcnt = s->segcnt.p, k.segoff = s->segoff.p, k.counters = s->b_counters.p;
+  for (int i = 0; i < 3; ++i) k.bytes[i] = s->bytes[i].p;
+  return k;
+}
+}  // namespace
+
+int rpsf_sat_fill_batch(SatDevice* s, const SatCall& c, int frames, const float* images_dev, size_t image_stride, int order_mode, hipStream_t st,
+                        float** padded, size_t* p_stride, float** corrected, size_t* c_stride) {
+  using namespace rpsfsatb;
+  if (frames < 1 || frames > MAX_GROUP_FRAMES) return fail(RPSF_E_BADARG, "saturation: frames per frame-group out of range");
+  const int PH = c.H + 4 * c.N, PW = c.W + 4 * c.N, h = c.width / 2;
+  const long npix = (long)PH * PW, nseg = (long)PH * segs_per_row(PW);
+  const size_t F = (size_t)frames, stride = frame_stride((size_t)npix), cstride = frame_stride((size_t)c.out_rows * PW);
+  const size_t n_counters = F * FRAME_COUNTERS + SHARED_COUNTERS;
+  s->timed = s->restored = false;
+  s->b_frames = 0, s->b_groups = s->b_masked = s->b_listed = 0;
+  for (auto& e : s->ev)
+    if (!e) HIP_TRY(hipEventCreate(&e));
+  HIP_TRY(s->padded.reserve(F * stride));
+  HIP_TRY(s->corrected.reserve(F * cstride));
+  for (auto& b : s->bytes) HIP_TRY(b.reserve(F * stride));
+  HIP_TRY(s->labels.reserve(F * stride));
+  HIP_TRY(s->segcnt.reserve(F * (size_t)nseg));
+  HIP_TRY(s->segoff.reserve(F * (size_t)nseg));
+  HIP_TRY(s->b_counters.reserve(n_counters));
+  HIP_TRY(s->h_b_counters.reserve(F * FRAME_COUNTERS));
+  HIP_TRY(s->b_info.reserve(F * FRAME_INFO));
+  HIP_TRY(s->h_b_info.reserve(F * FRAME_INFO));
+  s->b_stride = stride, s->b_cstride = cstride, s->b_nseg = (size_t)nseg;
+  *padded = s->padded.p, *p_stride = stride, *corrected = s->corrected.p, *c_stride = cstride;
+  const Stack k = stack_of(s, c);
+  const unsigned fy = (unsigned)frames;
+  const dim3 quads(blocks_for((npix + 3) / 4), fy), pixels(blocks_for(npix), fy), segs(blocks_for(nseg), fy);
+
+  HIP_TRY(hipMemsetAsync(s->b_counters.p, 0, n_counters * sizeof(int), st));
+  HIP_TRY(hipEventRecord(s->ev[SatDevice::E_START], st));
+  hipLaunchKernelGGL(sat_pad_batch_kernel, quads, dim3(256), 0, st, k, images_dev, image_stride, c.threshold);
+  HIP_TRY(hipEventRecord(s->ev[SatDevice::E_F1], st));
+  int at = 0;
+  for (int pass = 0; pass < c.dilation; ++pass, at ^= 1)
+    hipLaunchKernelGGL(sat_cross_batch_kernel, quads, dim3(256), 0, st, k, at, pass == c.dilation - 1);
+  HIP_TRY(hipEventRecord(s->ev[SatDevice::E_F2], st));
+  int grown = at;
+  if (const int reach = box_reach(h); reach > 0) {
+    hipLaunchKernelGGL(sat_rows_batch_kernel, pixels, dim3(256), 0, st, k, reach, at);
+    hipLaunchKernelGGL(sat_cols_batch_kernel, pixels, dim3(256), 0, st, k, reach, at);
+    grown = 2;
+  }
+  const dim3 tiles((PW + TILE_C - 1) / TILE_C, (PH + TILE_R - 1) / TILE_R, fy);
+  hipLaunchKernelGGL(sat_label_tile_batch_kernel, tiles, dim3(TILE_THREADS), TILE_R * TILE_C * sizeof(int), st, k, grown);
+  hipLaunchKernelGGL(sat_label_seam_batch_kernel, dim3(blocks_for((long)tiles.x * tiles.y * SEAM_SLOTS), fy), dim3(256), 0, st, k);
+  hipLaunchKernelGGL(sat_label_flatten_batch_kernel, pixels, dim3(256), 0, st, k);
+  hipLaunchKernelGGL(sat_count_batch_kernel, segs, dim3(256), 0, st, k);
+  hipLaunchKernelGGL(sat_scan_batch_kernel, dim3(fy), dim3(SCAN_THREADS), (SCAN_THREADS + 32) * sizeof(int), st, k);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(s->h_b_counters.p, s->b_counters.p, F * FRAME_COUNTERS * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));  // the one wait of the frame-group
+  if (!plan_tables(s->h_b_counters.p, frames, (size_t)c.H * c.W, s->h_b_info.p, &s->b_groups, &s->b_masked, &s->b_listed))
+    return fail(RPSF_E_UNSUPPORTED, "saturation: hot pixels without a group, or 2^31 masked pixels in one frame-group (cut it with RPSF_OPT_SAT_GROUP)");
+  s->b_frames = frames, s->b_at = at;
+  HIP_TRY(hipMemcpyAsync(s->b_info.p, s->h_b_info.p, F * FRAME_INFO * sizeof(int), hipMemcpyHostToDevice, st));
+  if (s->b_groups == 0) return RPSF_OK;  // nothing hot in any frame
+  const size_t n = (size_t)s->b_groups;
+  HIP_TRY(s->roots.reserve(n));
+  HIP_TRY(s->stats.reserve(GROUP_STATS * n));
+  HIP_TRY(s->b_gframe.reserve(n));
+  HIP_TRY(s->b_order.reserve(n));
+  HIP_TRY(s->fills.reserve((size_t)s->b_masked));
+  HIP_TRY(s->list.reserve((size_t)s->b_listed));
+  HIP_TRY(s->h_list.reserve((size_t)s->b_listed));
+  int most = 0;  // groups of one frame
+  for (int fr = 0; fr < frames; ++fr) most = std::max(most, s->h_b_info.p[FRAME_INFO * fr + I_GROUPS]);
+  const Tables t{s->b_info.p, s->roots.p, s->stats.p, s->b_gframe.p, s->b_order.p, s->b_counters.p + F * FRAME_COUNTERS, s->fills.p, s->b_groups};
+  hipLaunchKernelGGL(sat_roots_batch_kernel, segs, dim3(256), 0, st, k, t);
+  hipLaunchKernelGGL(sat_group_init_batch_kernel, dim3(blocks_for(most), fy), dim3(256), 0, st, t);
+  hipLaunchKernelGGL(sat_group_accumulate_batch_kernel, pixels, dim3(256), 0, st, k, t, at);
+  HIP_TRY(hipEventRecord(s->ev[SatDevice::E_F3], st));
+  if (order_mode != ORDER_FRAMES) {
+    hipLaunchKernelGGL(sat_order_hist_kernel, dim3(blocks_for(s->b_groups)), dim3(256), 0, st, t);
+    hipLaunchKernelGGL(sat_order_scatter_kernel, dim3(blocks_for(s->b_groups)), dim3(256), 0, st, t);
+  }
+  hipLaunchKernelGGL(sat_fill_batch_kernel, dim3((unsigned)n), dim3(FILL_LANES), sizeof(FillLds), st, k, t, order_mode, at, h);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(s->ev[SatDevice::E_F4], st));
+  s->timed = true;
+  return RPSF_OK;
+}
+
+int rpsf_sat_restore_batch(SatDevice* s, const SatCall& c, const float* images_dev, size_t image_stride, float* outs_dev, size_t out_stride,
+                           hipStream_t st) {
+  if (s->b_frames < 1) return fail(RPSF_E_STATE, "saturation: no filled frame-group to restore");
+  const Stack k = stack_of(s, c);
+  HIP_TRY(hipEventRecord(s->ev[SatDevice::E_F5A], st));
+  hipLaunchKernelGGL(sat_restore_batch_kernel, dim3(blocks_for((long)c.H * c.W), (unsigned)s->b_frames), dim3(256), 0, st, k, s->b_info.p, s->b_at,
+                     images_dev, image_stride, s->corrected.p, s->b_cstride, c.out_row0, outs_dev, out_stride, s->list.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(s->ev[SatDevice::E_F5B], st));
+  s->restored = true;
+  return RPSF_OK;
+}
+
+int rpsf_sat_lists_batch(SatDevice* s, hipStream_t st, const int32_t** list_host, const int** info_host, const int** counters_host) {
+  using namespace rpsfsatb;
+  *list_host = nullptr, *info_host = s->h_b_info.p, *counters_host = s->h_b_counters.p;
+  if (s->b_listed == 0) return RPSF_OK;
+  HIP_TRY(hipMemcpyAsync(s->h_b_counters.p, s->b_counters.p, (size_t)s->b_frames * FRAME_COUNTERS * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(s->h_list.p, s->list.p, (size_t)s->b_listed * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int fr = 0; fr < s->b_frames; ++fr) {
+    const long n = s->h_b_counters.p[FRAME_COUNTERS * fr + C_LIST];
+    const long room = (fr + 1 < s->b_frames ? s->h_b_info.p[FRAME_INFO * (fr + 1) + I_LIST0] : s->b_listed) - s->h_b_info.p[FRAME_INFO * fr + I_LIST0];
+    if (n < 0 || n > room) return fail(RPSF_E_HIP, "saturation: a list of masked pixels is longer than its mask (internal error)");
+  }
+  *list_host = s->h_list.p;
+  return RPSF_OK;
+}
+
+int rpsf_sat_masks_batch(SatDevice* s, const SatCall& c, hipStream_t st, uint8_t* masks_host) {
+  const size_t np = (size_t)(c.H + 4 * c.N) * (c.W + 4 * c.N);
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int fr = 0; fr < s->b_frames; ++fr) {
+    uint8_t* dst = masks_host + fr * np;
+    if (s->h_b_counters.p[rpsfsatb::FRAME_COUNTERS * fr + rpsfsatb::C_HOT] == 0) std::fill(dst, dst + np, (uint8_t)0);
+    else HIP_TRY(hipMemcpy(dst, s->bytes[s->b_at].p + fr * s->b_stride, np, hipMemcpyDeviceToHost));
+  }
+  return RPSF_OK;
+}
+
+int rpsf_sat_frame_counts(SatDevice* s, int fr, int* n_hot, int* n_mask, int* n_groups) {
+  const int* c = s->h_b_counters.p + rpsfsatb::FRAME_COUNTERS * fr;
+  const bool hot = c[rpsfsatb::C_HOT] != 0;
+  *n_hot = c[rpsfsatb::C_HOT], *n_mask = hot ? c[rpsfsatb::C_MASK] : 0, *n_groups = hot ? c[rpsfsatb::C_GROUPS] : 0;
+  return RPSF_OK;
+}
+
+void rpsf_sat_batch_totals(SatDevice* s, long* groups, long* masked) { *groups = s->b_groups, *masked = s->b_masked; }

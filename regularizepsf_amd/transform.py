@@ -383,6 +383,9 @@ class ArrayPSFTransform:
         float64, on three streams and a persistent pool of host threads (``rpsf_apply_frames_host``).  Frames that already
         live on the GPU should use ``_native.Plan.apply_batch_device``.  ``dtype`` is the result dtype (the reference
         returns float64; ``np.float32`` skips the widening); ``out`` an existing C-contiguous stack to fill.
+        With a finite ``saturation_threshold`` and ``saturation="device"``, float32 / float64 frames go through the batched device route
+        (``rpsf_apply_frames_host_saturated_device``: the frames of a frame-group share the launches of kernels F1 - F3, the host waits for
+        the device once and one launch fills every frame's groups), again bit-identical to the loop.
         Extension of the reference API - there is no ``apply_batch`` upstream.
         """
         with self._lock:
@@ -406,10 +409,26 @@ class ArrayPSFTransform:
                 msg = "images must be a sequence of two dimensional arrays of one shape"
                 raise ValueError(msg)
         dtype = np.dtype(out.dtype if out is not None else dtype)
+        if (self._saturation == "device" and isinstance(saturation_threshold, numbers.Real) and math.isfinite(saturation_threshold)
+                and pad_mode in _native.PAD_MODES and len(frames) > 0 and len(self) > 0 and dtype in (np.float32, np.float64)
+                and isinstance(saturation_dilation, numbers.Integral) and saturation_dilation >= 1
+                and isinstance(neighborhood_width, numbers.Integral) and neighborhood_width // 2 >= 1
+                and all(f.dtype in (np.float32, np.float64) for f in ([stack] if stack is not None else frames))):
+            # the device route for all frames of a frame-group at once: shared launches of F1 - F3, one host wait, one F4 launch, the shared-K
+            # batch launch on the padded frames (rpsf_apply_frames_host_saturated_device); bit-identical to the loop over apply
+            n = self._checked_patch_size()
+            plan = self._device_plan()
+            self._check_corners(n, *shape)
+            res = plan.apply_frames_host_saturated_device(frames, _native.PAD_MODES[pad_mode], saturation_threshold, saturation_dilation,
+                                                          neighborhood_width, out_dtype=dtype)
+            if out is not None:
+                out[...] = res
+                return out
+            return res
         if (saturation_threshold != math.inf and pad_mode in _native.PAD_MODES and len(frames) > 0 and len(self) > 0
                 and dtype in (np.float32, np.float64) and isinstance(saturation_dilation, numbers.Integral) and saturation_dilation >= 1
                 and isinstance(neighborhood_width, numbers.Integral) and neighborhood_width >= 0
-                and not (self._saturation == "device" and neighborhood_width // 2 >= 1)):  # (the device route: the loop over apply, below)
+                and not (self._saturation == "device" and neighborhood_width // 2 >= 1)):  # (the device route's other frames - integer frames, a threshold that is not finite: the loop over apply, below)
             # the saturation branch for a sequence of frames: the host steps of frame i + 1 (pad, mask, dilation, sequential fill) run while the
             # GPU corrects frame i (rpsf_apply_frames_host_saturated)
             n = self._checked_patch_size()
