@@ -154,7 +154,13 @@ int rpsf_plan_transfer_bytes(const rpsf_plan* plan, size_t* bytes);
  * (height, width).  origin_* is added to every patch corner (used when the caller hands over an
  * already padded image).  image_row0/image_rows and out_row0/out_rows describe which rows of the
  * full image / full output are resident at the device pointers (row-band sharding); for a whole
- * image they are 0 and height. */
+ * image they are 0 and height.
+ * ld_image / ld_out are the row strides in floats (>= width, any value); the pointers and the frame strides of a batch need the
+ * alignment of a float and no more.  The library chooses 16-byte, 8-byte or pixel-wise accesses per call from these numbers; on
+ * every overlap-add mode but the atomics the result has the same bits whichever it chooses.  Of the output, columns [0, width) of
+ * the resident rows are written and nothing else: not the floats between two rows, before the pointer, behind the last row or
+ * between the frames of a batch (tests/test_gpu_geometry.py).  A call that is refused (RPSF_E_BADARG for a geometry outside these
+ * bounds, RPSF_E_UNSUPPORTED for a row window on a plan of the hipFFT fallback) has written nothing. */
 typedef struct rpsf_geometry {
   int height, width;
   int pad_mode;
