@@ -915,7 +915,9 @@ __global__ __launch_bounds__(256) void fixup_kernel(FixParams p) {
 // regularizepsf_amd/functional.py; the reference evaluates a Python callable per patch on the host,
 // regularizepsf/psf.py:65-70,159-165).  One workgroup per patch; element [i][j] of a patch is the model at row = j, col = i:
 // the reference hands np.meshgrid(arange, arange) - 'xy' indexing - to the model as (row, col).  Evaluated in float64 from
-// float64 parameters, stored as float32 (what the spectrum kernel K3 takes).  normalize: every patch is scaled to unit sum.
+// float64 parameters, stored as float32 (what the spectrum kernel K3 takes): one rounding per sample, and a sample below 2**-126 stays a
+// float32 denormal - the conversion does not flush (measured and asserted in tests/test_gpu_functional.py).  normalize: every patch is
+// scaled to unit sum, the sum taken in float64.
 enum PsfModel : int { MODEL_ELLIPTICAL_GAUSSIAN = 0, MODEL_MOFFAT = 1 };
 constexpr int RPSF_MODEL_PARAMS_DEV = 8;
 __device__ __forceinline__ double psf_model_value(int model, const double* __restrict__ q, double row, double col) {

@@ -1,5 +1,6 @@
 """Functional PSF models: the reference's API and checks (regularizepsf/psf.py:25-189, mirrored from its tests/test_psf.py:93-237)
-on the host, and - on the GPU - the built-in device models rasterised by kernel K6 against the same formulas in NumPy."""
+on the host, and - on the GPU - the built-in device models rasterised by kernel K6 against the same formulas in NumPy, at 2e-7 of a
+cube's peak: the global bar.  tests/test_gpu_functional.py holds K6 to one float32 rounding per sample beside it."""
 
 import numpy as np
 import pytest

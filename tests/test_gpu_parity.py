@@ -965,6 +965,59 @@ def test_sweep_kernel_batches_and_row_windows(n):
         check(single.astype(np.float64), orc.apply_transfer(images[f], coords, k, pad_mode="reflect"))
 
 
+@pytest.mark.parametrize(("n", "patches"), [(16, 33489), (32, 8464), (64, 2209)])
+def test_k_installed_in_two_upload_rounds_at_the_sweep_sizes(n, patches):
+    """rpsf_plan_set_transfer uploads K 64 MiB at a time and packs every round at its offset: pack_kernel3 into d_k3 (what the sweep kernel
+    reads) and the first-generation packer into d_g / d_gs (what 'planes' reads).  A covering of a 1456 x 1456 frame is just over one round at
+    N = 16, 32 and 64.  Plan A takes K from the host (two rounds), plan B from one device buffer (one call, first = 0): the same bits from both
+    under either kernel, and the oracle's result - over the whole frame, and on their own over the output rows whose patches all went up in
+    the second round.  The corners are the covering's, ordered by row: in the covering's own order (four sub-lattices one after the other) no
+    pixel has all of its four patches in the last round."""
+    from regularizepsf_amd import _native
+
+    shape = (1456, 1456)
+    rng = np.random.default_rng(1456 + n)
+    coords = sorted(tuple(int(v) for v in c) for c in rp.calculate_covering(shape, n))
+    per_round = (64 << 20) // (n * n * 8)
+    assert len(coords) == patches > per_round and patches <= 2 * per_round
+    k = np.empty((patches, n, n), np.complex64)
+    k.real = rng.standard_normal(k.shape, np.float32)
+    k.imag = rng.standard_normal(k.shape, np.float32)
+    image = orc.starfield(*shape, n).astype(np.float32)
+    pad = _native.PAD_MODES["symmetric"]
+    # rows of the output that only second-round patches reach
+    first_round_end = max(r + n for r, _ in coords[:per_round])
+    rows = slice(first_round_end, shape[0])
+    assert shape[0] - first_round_end >= n // 2 and all(r + n <= first_round_end or i >= per_round for i, (r, _) in enumerate(coords))
+
+    a, b = _native.Plan(n, coords), _native.Plan(n, coords)
+    a.set_transfer(k)
+    d_k = _native.DeviceBuffer(k.nbytes).upload(k)
+    try:
+        b.set_transfer_device(d_k.ptr)
+    finally:
+        d_k.free()
+    assert a.sweep_info()["regions"] > 0 and b.sweep_info()["regions"] > 0  # automatic = the sweep kernel
+    out_a, out_b = a.apply(image, pad), b.apply(image, pad)
+    ref = orc.apply_transfer(image, coords, k, workers=-1)
+    for name, out in (("host route, two rounds", out_a), ("device route, one call", out_b)):
+        whole = rel_errors(out.astype(np.float64), ref)
+        second = rel_errors(out[rows].astype(np.float64), ref[rows])
+        print(f"K-ROUNDS | N={n} | {patches} patches, {per_round} per round | sweep | {name} | whole frame {whole[0]:.2e} | "
+              f"rows {rows.start}..{shape[0] - 1} (second round only) {second[0]:.2e}")
+        assert second[0] <= TOL and second[1] <= TOL, (name, "the rows of the second round", second)
+        assert whole[0] <= TOL and whole[1] <= TOL, (name, whole)
+    assert np.array_equal(out_a, out_b), "sweep kernel: K in two rounds differs from K in one call"
+    a.set_overlap_mode("planes")
+    b.set_overlap_mode("planes")
+    planes_a, planes_b = a.apply(image, pad), b.apply(image, pad)
+    whole, second = rel_errors(planes_a.astype(np.float64), ref), rel_errors(planes_a[rows].astype(np.float64), ref[rows])
+    print(f"K-ROUNDS | N={n} | planes (first-generation kernel) | host route, two rounds | whole frame {whole[0]:.2e} | second-round rows {second[0]:.2e}")
+    assert second[0] <= TOL and second[1] <= TOL, ("planes, the rows of the second round", second)
+    assert whole[0] <= TOL and whole[1] <= TOL, ("planes", whole)
+    assert np.array_equal(planes_a, planes_b), "planes: K in two rounds differs from K in one call"
+
+
 def test_one_transform_from_two_threads():
     """ArrayPSFTransform.apply may be called from several threads on ONE transform (the reference is plain NumPy and
     allows it); the device plan is not re-entrant, so the calls take turns."""
