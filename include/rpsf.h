@@ -205,26 +205,31 @@ int rpsf_apply_frames_host_saturated(rpsf_plan* plan, const void* const* images_
  * bits of rpsf_apply_host_saturated's.  Arguments as there, and neighborhood_width / 2 >= 1 (an always-empty window needs no kernel:
  * RPSF_E_BADARG, use the host route).  Asynchronous on `stream` (NULL: the plan's own) EXCEPT that the call waits for the stream once,
  * after the labelling, to read the hot, masked and group counts; with nothing hot F2 - F4 do nothing and the padded frame is corrected
- * as it is.  *n_masked_or_null: masked pixels of the padded frame.
- * SCRATCH, owned by the plan, allocated at the first call, reused, grown when a larger frame arrives, freed with the plan: per pixel
+ * as it is.  *n_masked_or_null: masked pixels of the padded frame.  The frame is a frame-group of one on the route of
+ * rpsf_apply_batch_device_saturated (there is one driver), with F4's workgroups in the group table's own order, the ascending order of
+ * the groups' first pixels: no ordering pass runs.  rpsf_saturation_batch_info is left as it was.
+ * SCRATCH, owned by the plan, shared with the batch entry points, allocated at the first call, reused, grown when a larger frame arrives, freed with the plan: per pixel
  * of the padded (height + 4N) x (width + 4N) frame 4 B (float32 frame) + 3 B (hot / mask / grown mask bytes) + 4 B (labels) = 11 B,
  * plus the padded float32 output rows (4 B per pixel of height + 4N rows for a generic-size plan, of `height` rows otherwise), 8 B per
  * 64-pixel row segment, and per MASKED pixel 8 B (float64 fill) + at most 8 B (the list, device and pinned host), 24 B per group. */
 int rpsf_apply_device_saturated(rpsf_plan* plan, const void* image_dev, void* out_dev, int height, int width, int pad_mode,
                                 double threshold, int dilation, int neighborhood_width, void* stream, size_t* n_masked_or_null);
-/* rpsf_apply_host_saturated's contract through the device route: the UNPADDED frame is narrowed to float32 and uploaded through the
- * plan's staging, rpsf_apply_device_saturated runs, `height` rows come back, and for a float64 frame the masked in-frame pixels, which
+/* rpsf_apply_host_saturated's contract through the device route (rpsf_apply_frames_host_saturated_device's steps for one frame, in
+ * the group table's own order, the batch info left as it was): the UNPADDED frame is narrowed to float32 and uploaded through the
+ * plan's staging, rpsf_apply_device_saturated's route runs, `height` rows come back, and for a float64 frame the masked in-frame pixels, which
  * the device lists, receive the caller's own float64 values.  A float64 frame is thresholded and filled from its float32 rounding
  * (what every device path of the library holds): a pixel whose float64 value lies on the other side of the threshold from its float32
  * rounding is the one place where the two routes can disagree beyond the rounding of the fill's inputs. */
 int rpsf_apply_host_saturated_device(rpsf_plan* plan, const void* image_host, int image_is_f64, int height, int width, int pad_mode,
                                      double threshold, int dilation, int neighborhood_width, void* out_host, int out_is_f64);
-/* Device time of the last F1 ... F5 launches of the plan, milliseconds (F3's includes the host's one wait; zeros for what did not run).
- * After a batch call (rpsf_apply_batch_device_saturated and its kin): F1 ... F5 of the LAST frame-group, all its frames together. */
+/* Device time of the last F1 ... F5 launches of the plan, milliseconds (F3's includes the host's one wait; zeros for what did not run):
+ * of the LAST frame-group, all its frames together - after a single-frame call that frame, after a batch call
+ * (rpsf_apply_batch_device_saturated and its kin) the batch's last frame-group. */
 int rpsf_saturation_kernel_ms(rpsf_plan* plan, double ms[5]);
 /* Test entry: F1 - F4 alone on a float32 host frame.  padded_host ((height + 4N) x (width + 4N) float32) receives the filled padded
- * frame, mask_host (as many bytes) the dilated mask; reverse_groups != 0 makes F4's workgroups take the groups last first (the result
- * must not depend on it); *n_groups_or_null: independent groups found. */
+ * frame, mask_host (as many bytes) the dilated mask; *n_groups_or_null: independent groups found.  rpsf_saturation_fill_batch_device
+ * for one frame with order 2, and with reverse_groups != 0 order 1: F4's workgroups take the groups shortest first instead of in the
+ * table's own order (the result must not depend on it).  Leaves rpsf_saturation_batch_info as it was. */
 int rpsf_saturation_fill_device(rpsf_plan* plan, const float* image_host, int height, int width, int pad_mode, double threshold,
                                 int dilation, int neighborhood_width, int reverse_groups, float* padded_host, uint8_t* mask_host,
                                 int* n_groups_or_null);
@@ -234,7 +239,8 @@ int rpsf_saturation_fill_device(rpsf_plan* plan, const float* image_host, int he
  * (RPSF_OPT_SAT_GROUP; automatic: as many frames as keep the scratch below under 1 GiB).  A frame-group shares every launch of F1 - F3
  * (the frame is a grid index; labels, roots and counters stay per frame), the host waits for the stream ONCE per frame-group, not per
  * frame, F4 is one launch of one wave per group over all frames' groups, longest groups first, the correction is the shared-K batch
- * launch of rpsf_apply_batch_device on the padded frames, F5 one launch.  Argument checks as rpsf_apply_device_saturated
+ * launch of rpsf_apply_batch_device on the padded frames, F5 one launch; n_frames == 1 takes the same steps, ordering pass included.
+ * Argument checks as rpsf_apply_device_saturated
  * (neighborhood_width / 2 < 1: RPSF_E_BADARG), n_frames < 0: RPSF_E_BADARG, a stride below height x width with n_frames > 1:
  * RPSF_E_BADARG, n_frames == 0: RPSF_OK and nothing is done (the pointers may then be NULL).  RPSF_E_UNSUPPORTED when a frame-group
  * holds 2^31 masked pixels or more (cut it smaller).  n_masked_per_frame_or_null: n_frames entries, masked pixels of padded frame f.
@@ -250,7 +256,7 @@ int rpsf_apply_batch_device_saturated(rpsf_plan* plan, const void* images_dev, v
 int rpsf_apply_frames_host_saturated_device(rpsf_plan* plan, const void* const* images_host, int image_is_f64, int n_frames, int height,
                                             int width, int pad_mode, double threshold, int dilation, int neighborhood_width,
                                             void* const* outs_host, int out_is_f64);
-/* Of the last batch call of the plan (either entry above, or the test entry below): info[0] frames, info[1] frame-groups (= host waits
+/* Of the last batch call of the plan (either entry above, or the test entry below; a single-frame call changes nothing): info[0] frames, info[1] frame-groups (= host waits
  * before F4), info[2] fill groups over all frames, info[3] masked pixels of the padded frames (saturating at INT_MAX).  Zeros before
  * the first.  After a batch call rpsf_saturation_kernel_ms reports F1 ... F5 of the LAST frame-group (F4 with its ordering pass). */
 int rpsf_saturation_batch_info(rpsf_plan* plan, int info[4]);

@@ -23,20 +23,11 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rpsf.h"
 #include "rpsf_core_builder.hpp"
 #include "rpsf_core_cleanup.hpp"
+#include "rpsf_side_unit.hpp"
 
 using namespace rpsfb;
-
-int rpsf_detail_fail(int code, const std::string& msg);  // rpsf.hip: sets rpsf_last_error of the calling thread
-static int fail(int code, const std::string& msg) { return rpsf_detail_fail(code, msg); }
-#define HIP_TRY(expr)                                                                                               \
-  do {                                                                                                              \
-    hipError_t e_ = (expr);                                                                                         \
-    if (e_ != hipSuccess)                                                                                           \
-      return fail(e_ == hipErrorOutOfMemory ? RPSF_E_NOMEM : RPSF_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 struct B1Params {
   const float* image;
@@ -110,25 +101,6 @@ __global__ __launch_bounds__(THREADS) void builder_clean_kernel(int N, const dou
   const size_t at = (size_t)blockIdx.x * N * N;
   rpsfc::clean_cell(ctx, N, THREADS, cells + at, cleaned + at, flags + blockIdx.x, builder_lds);
 }
-
-namespace {
-template <class T>
-struct Buf {  // a device array that only ever grows
-  T* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t count) {
-    if (count <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr, cap = 0;
-    const hipError_t e = hipMalloc(&p, count * sizeof(T));
-    if (e == hipSuccess) cap = count;
-    return e;
-  }
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-};
-}  // namespace
 
 struct rpsf_builder {
   int device = 0, N = 0;

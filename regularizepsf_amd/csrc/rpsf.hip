@@ -1648,9 +1648,9 @@ extern "C" int rpsf_apply_device(rpsf_plan* p, const void* image_dev, void* out_
 
 
 // Frames per launch group: the colour planes take 16 bytes per output pixel per frame in flight; keep
-// them under a quarter of the device memory.
+// them under a quarter of the device memory.  (One frame is one group: nothing is asked of the device.)
 static int batch_group_frames(const rpsf_plan* p, const rpsf_geometry& g, int n_frames) {
-  if (p->generic || overlap_kind(p) == OV_ATOMIC || overlap_kind(p) == OV_SWEEP) return n_frames;
+  if (n_frames == 1 || p->generic || overlap_kind(p) == OV_ATOMIC || overlap_kind(p) == OV_SWEEP) return n_frames;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) total_b = (size_t)64 << 30;
   const size_t per_frame = 16 * plane_floats_needed(g);
@@ -2584,8 +2584,10 @@ extern "C" int rpsf_apply_frames_host_saturated(rpsf_plan* p, const void* const*
 }
 
 // ------------------------------------------------------------------------------------------------
-// The same branch with every step on the device (csrc/saturation.hip): F1 - F4 build the filled padded frame from the
-// resident H x W frame, the plan corrects it with the geometry above, F5 restores and crops.
+// The same branch with every step on the device (csrc/saturation.hip, csrc/rpsf_core_saturation_batch.hpp): frames of one
+// shape are cut into frame-groups; per frame-group F1 - F3 with the frame as a grid index build the filled padded frames from the
+// resident H x W frames, one wait, one F4 launch, the shared-K batch launch corrects the padded frames with the geometry above, one F5
+// launch restores and crops.  A single frame is a frame-group of one whose F4 takes the groups in the table's own order.
 // ------------------------------------------------------------------------------------------------
 struct SatDeviceRun {
   SatCall call;
@@ -2599,132 +2601,13 @@ static int sat_device_init(rpsf_plan* p, int height, int width, int pad_mode, do
   int o_lo, o_rows;
   const int rc = padded_geometry(p, height, width, &run->r_lo, &run->r_hi, &o_lo, &o_rows, &run->g);
   if (rc != RPSF_OK) return rc;
-  run->call = SatCall{height, width, p->N, pad_mode, dilation, neighborhood_width, threshold, run->r_lo, o_lo, o_rows, false};
+  run->call = SatCall{height, width, p->N, pad_mode, dilation, neighborhood_width, threshold, run->r_lo, o_lo, o_rows};
   HIP_TRY(hipSetDevice(p->device));
   if (!p->sat_dev) p->sat_dev.reset(rpsf_sat_create());
   return RPSF_OK;
 }
 
-// F1 - F4, the correction, F5; asynchronous on st but for the one wait inside rpsf_sat_fill
-static int sat_device_apply(rpsf_plan* p, const SatDeviceRun& run, const float* image_dev, float* out_dev, hipStream_t st) {
-  float *padded = nullptr, *corrected = nullptr;
-  int rc = rpsf_sat_fill(p->sat_dev.get(), run.call, image_dev, st, &padded, &corrected);
-  if (rc != RPSF_OK) return rc;
-  rc = launch_apply(p, padded + (size_t)run.r_lo * run.g.width, corrected, run.g, st, nullptr);
-  if (rc != RPSF_OK) return rc;
-  return rpsf_sat_restore(p->sat_dev.get(), run.call, image_dev, out_dev, st);
-}
-
-extern "C" int rpsf_apply_device_saturated(rpsf_plan* p, const void* image_dev, void* out_dev, int height, int width, int pad_mode, double threshold,
-                                           int dilation, int neighborhood_width, void* stream, size_t* n_masked_or_null) {
-  int rc = check_saturated_call(p, image_dev, out_dev, height, width, pad_mode, dilation, neighborhood_width);
-  if (rc != RPSF_OK) return rc;
-  SatDeviceRun run;
-  rc = sat_device_init(p, height, width, pad_mode, threshold, dilation, neighborhood_width, &run);
-  if (rc != RPSF_OK) return rc;
-  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : p->stream;
-  rc = sat_device_apply(p, run, static_cast<const float*>(image_dev), static_cast<float*>(out_dev), st);
-  if (rc != RPSF_OK) return rc;
-  if (n_masked_or_null) {
-    int n_hot, n_mask, n_groups;
-    rpsf_sat_counts(p->sat_dev.get(), &n_hot, &n_mask, &n_groups);
-    *n_masked_or_null = (size_t)n_mask;
-  }
-  return RPSF_OK;
-}
-
-extern "C" int rpsf_apply_host_saturated_device(rpsf_plan* p, const void* image_host, int image_is_f64, int height, int width, int pad_mode,
-                                                double threshold, int dilation, int neighborhood_width, void* out_host, int out_is_f64) {
-  int rc = check_saturated_call(p, image_host, out_host, height, width, pad_mode, dilation, neighborhood_width);
-  if (rc != RPSF_OK) return rc;
-  SatDeviceRun run;
-  rc = sat_device_init(p, height, width, pad_mode, threshold, dilation, neighborhood_width, &run);
-  if (rc != RPSF_OK) return rc;
-  const size_t npix = (size_t)height * width;
-  rc = pipe_ensure(p, npix, 1);
-  if (rc != RPSF_OK) return rc;
-  HostPipe& q = *p->pipe;
-  HostPool& pool = HostPool::get(p->device);
-  const int T = host_parts_for(npix * sizeof(float));
-  pool.run(T, [&](int t) {
-    size_t a, b;
-    rpsf_host::split_range(0, npix, t, T, a, b);
-    rpsf_host::narrow_or_copy(q.h_in[0], image_host, image_is_f64 != 0, a, b);
-  });
-  hipError_t err = hipMemcpyAsync(q.d_in[0], q.h_in[0], npix * sizeof(float), hipMemcpyHostToDevice, p->stream);
-  if (err != hipSuccess) return drain_after_error(p, err, "saturated host frame, device route");
-  rc = sat_device_apply(p, run, q.d_in[0], q.d_out[0], p->stream);
-  if (rc != RPSF_OK) {
-    (void)hipStreamSynchronize(p->stream);
-    return rc;
-  }
-  err = hipMemcpyAsync(q.h_out[0], q.d_out[0], npix * sizeof(float), hipMemcpyDeviceToHost, p->stream);
-  if (err != hipSuccess) return drain_after_error(p, err, "saturated host frame, device route");
-  const int32_t* list = nullptr;
-  size_t n_list = 0;
-  rc = rpsf_sat_list(p->sat_dev.get(), p->stream, &list, &n_list);  // waits for the stream
-  if (rc != RPSF_OK) return rc;
-  if (!list) {
-    err = hipStreamSynchronize(p->stream);
-    if (err != hipSuccess) return drain_after_error(p, err, "saturated host frame, device route");
-  }
-  pool.run(T, [&](int t) {
-    size_t a, b;
-    rpsf_host::split_range(0, npix, t, T, a, b);
-    rpsf_host::widen_or_copy(out_host, out_is_f64 != 0, q.h_out[0], a, b);
-  });
-  if (image_is_f64) {  // the caller's own values on the mask, not their float32 roundings
-    const double* src = static_cast<const double*>(image_host);
-    for (size_t k = 0; k < n_list; ++k) {
-      if (out_is_f64) static_cast<double*>(out_host)[list[k]] = src[list[k]];
-      else static_cast<float*>(out_host)[list[k]] = (float)src[list[k]];
-    }
-  }
-  return sweep_check(p);
-}
-
-extern "C" int rpsf_saturation_kernel_ms(rpsf_plan* p, double ms[5]) {
-  if (!p || !ms) return fail(RPSF_E_BADARG, "null argument");
-  for (int i = 0; i < 5; ++i) ms[i] = 0.0;
-  if (!p->sat_dev) return RPSF_OK;
-  HIP_TRY(hipSetDevice(p->device));
-  return rpsf_sat_kernel_ms(p->sat_dev.get(), ms);
-}
-
-// Test entry: F1 - F4 alone on a float32 host frame; the filled padded frame ((H + 4N) x (W + 4N) float32) and the mask come back
-extern "C" int rpsf_saturation_fill_device(rpsf_plan* p, const float* image_host, int height, int width, int pad_mode, double threshold, int dilation,
-                                           int neighborhood_width, int reverse_groups, float* padded_host, uint8_t* mask_host, int* n_groups_or_null) {
-  if (!p || !image_host || !padded_host || !mask_host) return fail(RPSF_E_BADARG, "null argument");
-  if (height <= 0 || width <= 0) return fail(RPSF_E_BADARG, "image shape must be positive");
-  if (pad_mode < 0 || pad_mode > RPSF_PAD_WRAP) return fail(RPSF_E_BADARG, "unknown pad mode");
-  if (dilation < 1 || neighborhood_width / 2 < 1) return fail(RPSF_E_BADARG, "dilation must be >= 1 and neighborhood_width // 2 >= 1");
-  const long PH = (long)height + 4L * p->N, PW = (long)width + 4L * p->N;
-  if (PH * PW >= ((long)1 << 31)) return fail(RPSF_E_UNSUPPORTED, "padded frame too large for this entry point");
-  HIP_TRY(hipSetDevice(p->device));
-  if (!p->sat_dev) p->sat_dev.reset(rpsf_sat_create());
-  const SatCall call{height, width, p->N, pad_mode, dilation, neighborhood_width, threshold, 0, 0, 1, reverse_groups != 0};
-  DevBuf<float> d_image;
-  HIP_TRY(d_image.upload(image_host, (size_t)height * width));
-  float *padded = nullptr, *corrected = nullptr;
-  int rc = rpsf_sat_fill(p->sat_dev.get(), call, d_image, p->stream, &padded, &corrected);
-  if (rc == RPSF_OK) rc = rpsf_sat_mask(p->sat_dev.get(), call, p->stream, mask_host);  // waits for the stream
-  if (rc != RPSF_OK) {
-    (void)hipStreamSynchronize(p->stream);
-    return rc;
-  }
-  HIP_TRY(hipMemcpy(padded_host, padded, (size_t)PH * PW * sizeof(float), hipMemcpyDeviceToHost));
-  if (n_groups_or_null) {
-    int n_hot, n_mask;
-    rpsf_sat_counts(p->sat_dev.get(), &n_hot, &n_mask, n_groups_or_null);
-  }
-  return RPSF_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The device route for a batch of frames of one shape (csrc/rpsf_core_saturation_batch.hpp, DESIGN.md 3.8 "Frame batches"): cut into
-// frame-groups; per frame-group F1 - F3 with the frame as a grid index, one wait, one F4 launch, the shared-K batch launch on the padded
-// frames, one F5 launch.
-// ------------------------------------------------------------------------------------------------
+// What rpsf_saturation_batch_info reports: the frames entry points store it, a single-frame call keeps its own and stores nothing
 struct SatBatchStats {
   long frames = 0, frame_groups = 0, groups = 0, masked = 0;
   void store(rpsf_plan* p) const {
@@ -2740,11 +2623,11 @@ static int sat_group_frames(const rpsf_plan* p, const SatDeviceRun& run) {
 
 // one frame-group, resident; asynchronous on st but for the one wait inside rpsf_sat_fill_batch
 static int sat_device_apply_group(rpsf_plan* p, const SatDeviceRun& run, int frames, const float* images_dev, size_t image_stride, float* outs_dev,
-                                  size_t out_stride, hipStream_t st, SatBatchStats* stats, size_t* n_masked_or_null) {
+                                  size_t out_stride, int order, hipStream_t st, SatBatchStats* stats, size_t* n_masked_or_null) {
   float *padded = nullptr, *corrected = nullptr;
   size_t p_stride = 0, c_stride = 0;
   SatDevice* sd = p->sat_dev.get();
-  int rc = rpsf_sat_fill_batch(sd, run.call, frames, images_dev, image_stride, rpsfsatb::ORDER_LONGEST_FIRST, st, &padded, &p_stride, &corrected, &c_stride);
+  int rc = rpsf_sat_fill_batch(sd, run.call, frames, images_dev, image_stride, order, st, &padded, &p_stride, &corrected, &c_stride);
   if (rc != RPSF_OK) return rc;
   rc = launch_batch(p, padded + (size_t)run.r_lo * run.g.width, corrected, frames, p_stride, c_stride, run.g, st);
   if (rc != RPSF_OK) return rc;
@@ -2759,6 +2642,94 @@ static int sat_device_apply_group(rpsf_plan* p, const SatDeviceRun& run, int fra
     n_masked_or_null[f] = (size_t)n_mask;
   }
   return RPSF_OK;
+}
+
+// one frame-group of host arrays through the plan's staging slot 0 (room for `frames` frames: pipe_ensure): staged as float32, uploaded,
+// sat_device_apply_group, downloaded, widened; T: parts of the host pool's copies
+static int sat_host_group(rpsf_plan* p, const SatDeviceRun& run, int frames, const void* const* images_host, int image_is_f64, void* const* outs_host,
+                          int out_is_f64, int order, int T, SatBatchStats* stats) {
+  const size_t npix = (size_t)run.call.H * run.call.W, total = npix * frames;
+  HostPipe& q = *p->pipe;
+  HostPool& pool = HostPool::get(p->device);
+  pool.run(T, [&](int t) {  // the group's frames laid end to end, cut into T parts
+    size_t a, b;
+    rpsf_host::split_range(0, total, t, T, a, b);
+    while (a < b) {
+      const size_t f = a / npix, lo = a % npix, hi = std::min(npix, lo + (b - a));
+      rpsf_host::narrow_or_copy(q.h_in[0] + f * npix, images_host[f], image_is_f64 != 0, lo, hi);
+      a += hi - lo;
+    }
+  });
+  hipError_t err = hipMemcpyAsync(q.d_in[0], q.h_in[0], total * sizeof(float), hipMemcpyHostToDevice, p->stream);
+  if (err != hipSuccess) return drain_after_error(p, err, "saturated host frames, device route");
+  int rc = sat_device_apply_group(p, run, frames, q.d_in[0], npix, q.d_out[0], npix, order, p->stream, stats, nullptr);
+  if (rc != RPSF_OK) {
+    (void)hipStreamSynchronize(p->stream);
+    return rc;
+  }
+  err = hipMemcpyAsync(q.h_out[0], q.d_out[0], total * sizeof(float), hipMemcpyDeviceToHost, p->stream);
+  if (err != hipSuccess) return drain_after_error(p, err, "saturated host frames, device route");
+  const int32_t* list = nullptr;
+  const int *info = nullptr, *counters = nullptr;
+  rc = rpsf_sat_lists_batch(p->sat_dev.get(), p->stream, &list, &info, &counters);  // waits for the stream when there is a list
+  if (rc != RPSF_OK) {
+    (void)hipStreamSynchronize(p->stream);
+    return rc;
+  }
+  if (!list) {
+    err = hipStreamSynchronize(p->stream);
+    if (err != hipSuccess) return drain_after_error(p, err, "saturated host frames, device route");
+  }
+  pool.run(T, [&](int t) {
+    size_t a, b;
+    rpsf_host::split_range(0, total, t, T, a, b);
+    while (a < b) {
+      const size_t f = a / npix, lo = a % npix, hi = std::min(npix, lo + (b - a));
+      rpsf_host::widen_or_copy(outs_host[f], out_is_f64 != 0, q.h_out[0] + f * npix, lo, hi);
+      a += hi - lo;
+    }
+  });
+  if (image_is_f64 && list) {  // the caller's own values on the mask, not their float32 roundings
+    for (int f = 0; f < frames; ++f) {
+      const double* src = static_cast<const double*>(images_host[f]);
+      const int32_t* mine = list + info[rpsfsatb::FRAME_INFO * f + rpsfsatb::I_LIST0];
+      const int n = counters[rpsfsatb::FRAME_COUNTERS * f + rpsfsatb::C_HOT] ? counters[rpsfsatb::FRAME_COUNTERS * f + rpsfsatb::C_LIST] : 0;
+      for (int k = 0; k < n; ++k) {
+        if (out_is_f64) static_cast<double*>(outs_host[f])[mine[k]] = src[mine[k]];
+        else static_cast<float*>(outs_host[f])[mine[k]] = (float)src[mine[k]];
+      }
+    }
+  }
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_apply_device_saturated(rpsf_plan* p, const void* image_dev, void* out_dev, int height, int width, int pad_mode, double threshold,
+                                           int dilation, int neighborhood_width, void* stream, size_t* n_masked_or_null) {
+  int rc = check_saturated_call(p, image_dev, out_dev, height, width, pad_mode, dilation, neighborhood_width);
+  if (rc != RPSF_OK) return rc;
+  SatDeviceRun run;
+  rc = sat_device_init(p, height, width, pad_mode, threshold, dilation, neighborhood_width, &run);
+  if (rc != RPSF_OK) return rc;
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : p->stream;
+  const size_t npix = (size_t)height * width;
+  SatBatchStats stats;
+  return sat_device_apply_group(p, run, 1, static_cast<const float*>(image_dev), npix, static_cast<float*>(out_dev), npix, rpsfsatb::ORDER_FRAMES, st,
+                                &stats, n_masked_or_null);
+}
+
+extern "C" int rpsf_apply_host_saturated_device(rpsf_plan* p, const void* image_host, int image_is_f64, int height, int width, int pad_mode,
+                                                double threshold, int dilation, int neighborhood_width, void* out_host, int out_is_f64) {
+  int rc = check_saturated_call(p, image_host, out_host, height, width, pad_mode, dilation, neighborhood_width);
+  if (rc != RPSF_OK) return rc;
+  SatDeviceRun run;
+  rc = sat_device_init(p, height, width, pad_mode, threshold, dilation, neighborhood_width, &run);
+  if (rc != RPSF_OK) return rc;
+  const size_t npix = (size_t)height * width;
+  rc = pipe_ensure(p, npix, 1);
+  if (rc != RPSF_OK) return rc;
+  SatBatchStats stats;
+  rc = sat_host_group(p, run, 1, &image_host, image_is_f64, &out_host, out_is_f64, rpsfsatb::ORDER_FRAMES, host_parts_for(npix * sizeof(float)), &stats);
+  return rc != RPSF_OK ? rc : sweep_check(p);
 }
 
 extern "C" int rpsf_apply_batch_device_saturated(rpsf_plan* p, const void* images_dev, void* outs_dev, int n_frames, size_t image_stride,
@@ -2782,7 +2753,7 @@ extern "C" int rpsf_apply_batch_device_saturated(rpsf_plan* p, const void* image
   stats.frames = n_frames;
   for (int f0 = 0; f0 < n_frames; f0 += G) {
     rc = sat_device_apply_group(p, run, std::min(G, n_frames - f0), static_cast<const float*>(images_dev) + (size_t)f0 * image_stride, image_stride,
-                                static_cast<float*>(outs_dev) + (size_t)f0 * out_stride, out_stride, st, &stats,
+                                static_cast<float*>(outs_dev) + (size_t)f0 * out_stride, out_stride, rpsfsatb::ORDER_LONGEST_FIRST, st, &stats,
                                 n_masked_per_frame_or_null ? n_masked_per_frame_or_null + f0 : nullptr);
     if (rc != RPSF_OK) return rc;
   }
@@ -2809,66 +2780,24 @@ extern "C" int rpsf_apply_frames_host_saturated_device(rpsf_plan* p, const void*
   const int G = std::min(sat_group_frames(p, run), n_frames);
   rc = pipe_ensure(p, npix * G, 1);
   if (rc != RPSF_OK) return rc;
-  HostPipe& q = *p->pipe;
-  HostPool& pool = HostPool::get(p->device);
   const int T = host_parts_for(npix * G * sizeof(float));
   SatBatchStats stats;
   stats.frames = n_frames;
   for (int f0 = 0; f0 < n_frames; f0 += G) {
-    const int fg = std::min(G, n_frames - f0);
-    const size_t total = npix * fg;
-    pool.run(T, [&](int t) {  // the group's frames laid end to end, cut into T parts
-      size_t a, b;
-      rpsf_host::split_range(0, total, t, T, a, b);
-      while (a < b) {
-        const size_t f = a / npix, lo = a % npix, hi = std::min(npix, lo + (b - a));
-        rpsf_host::narrow_or_copy(q.h_in[0] + f * npix, images_host[f0 + f], image_is_f64 != 0, lo, hi);
-        a += hi - lo;
-      }
-    });
-    hipError_t err = hipMemcpyAsync(q.d_in[0], q.h_in[0], total * sizeof(float), hipMemcpyHostToDevice, p->stream);
-    if (err != hipSuccess) return drain_after_error(p, err, "saturated host frames, device route");
-    rc = sat_device_apply_group(p, run, fg, q.d_in[0], npix, q.d_out[0], npix, p->stream, &stats, nullptr);
-    if (rc != RPSF_OK) {
-      (void)hipStreamSynchronize(p->stream);
-      return rc;
-    }
-    err = hipMemcpyAsync(q.h_out[0], q.d_out[0], total * sizeof(float), hipMemcpyDeviceToHost, p->stream);
-    if (err != hipSuccess) return drain_after_error(p, err, "saturated host frames, device route");
-    const int32_t* list = nullptr;
-    const int *info = nullptr, *counters = nullptr;
-    rc = rpsf_sat_lists_batch(p->sat_dev.get(), p->stream, &list, &info, &counters);  // waits for the stream when there is a list
-    if (rc != RPSF_OK) {
-      (void)hipStreamSynchronize(p->stream);
-      return rc;
-    }
-    if (!list) {
-      err = hipStreamSynchronize(p->stream);
-      if (err != hipSuccess) return drain_after_error(p, err, "saturated host frames, device route");
-    }
-    pool.run(T, [&](int t) {
-      size_t a, b;
-      rpsf_host::split_range(0, total, t, T, a, b);
-      while (a < b) {
-        const size_t f = a / npix, lo = a % npix, hi = std::min(npix, lo + (b - a));
-        rpsf_host::widen_or_copy(outs_host[f0 + f], out_is_f64 != 0, q.h_out[0] + f * npix, lo, hi);
-        a += hi - lo;
-      }
-    });
-    if (image_is_f64 && list) {  // the caller's own values on the mask, not their float32 roundings
-      for (int f = 0; f < fg; ++f) {
-        const double* src = static_cast<const double*>(images_host[f0 + f]);
-        const int32_t* mine = list + info[rpsfsatb::FRAME_INFO * f + rpsfsatb::I_LIST0];
-        const int n = counters[rpsfsatb::FRAME_COUNTERS * f + rpsfsatb::C_HOT] ? counters[rpsfsatb::FRAME_COUNTERS * f + rpsfsatb::C_LIST] : 0;
-        for (int k = 0; k < n; ++k) {
-          if (out_is_f64) static_cast<double*>(outs_host[f0 + f])[mine[k]] = src[mine[k]];
-          else static_cast<float*>(outs_host[f0 + f])[mine[k]] = (float)src[mine[k]];
-        }
-      }
-    }
+    rc = sat_host_group(p, run, std::min(G, n_frames - f0), images_host + f0, image_is_f64, outs_host + f0, out_is_f64, rpsfsatb::ORDER_LONGEST_FIRST, T,
+                        &stats);
+    if (rc != RPSF_OK) return rc;
   }
   stats.store(p);
   return sweep_check(p);
+}
+
+extern "C" int rpsf_saturation_kernel_ms(rpsf_plan* p, double ms[5]) {
+  if (!p || !ms) return fail(RPSF_E_BADARG, "null argument");
+  for (int i = 0; i < 5; ++i) ms[i] = 0.0;
+  if (!p->sat_dev) return RPSF_OK;
+  HIP_TRY(hipSetDevice(p->device));
+  return rpsf_sat_kernel_ms(p->sat_dev.get(), ms);
 }
 
 extern "C" int rpsf_saturation_batch_info(rpsf_plan* p, int info[4]) {
@@ -2877,10 +2806,11 @@ extern "C" int rpsf_saturation_batch_info(rpsf_plan* p, int info[4]) {
   return RPSF_OK;
 }
 
-// Test entry: F1 - F4 alone on n_frames float32 host frames, frame-group by frame-group
-extern "C" int rpsf_saturation_fill_batch_device(rpsf_plan* p, const float* images_host, int n_frames, int height, int width, int pad_mode,
-                                                 double threshold, int dilation, int neighborhood_width, int order, float* padded_host,
-                                                 uint8_t* masks_host, int* groups_per_frame_or_null) {
+// The test entries: F1 - F4 alone on n_frames float32 host frames, frame-group by frame-group; the filled padded frames
+// ((H + 4N) x (W + 4N) float32 each) and the masks come back
+static int sat_fill_frames(rpsf_plan* p, const float* images_host, int n_frames, int height, int width, int pad_mode, double threshold, int dilation,
+                           int neighborhood_width, int order, float* padded_host, uint8_t* masks_host, int* groups_per_frame_or_null,
+                           SatBatchStats* stats) {
   if (!p || !images_host || !padded_host || !masks_host) return fail(RPSF_E_BADARG, "null argument");
   if (n_frames < 1) return fail(RPSF_E_BADARG, "n_frames must be positive");
   if (height <= 0 || width <= 0) return fail(RPSF_E_BADARG, "image shape must be positive");
@@ -2892,13 +2822,12 @@ extern "C" int rpsf_saturation_fill_batch_device(rpsf_plan* p, const float* imag
   HIP_TRY(hipSetDevice(p->device));
   if (!p->sat_dev) p->sat_dev.reset(rpsf_sat_create());
   SatDevice* sd = p->sat_dev.get();
-  const SatCall call{height, width, p->N, pad_mode, dilation, neighborhood_width, threshold, 0, 0, 1, false};
+  const SatCall call{height, width, p->N, pad_mode, dilation, neighborhood_width, threshold, 0, 0, 1};
   const size_t npix = (size_t)height * width, np = (size_t)PH * PW;
   const int G = std::min(n_frames, p->sat_group_opt > 0 ? p->sat_group_opt : rpsfsatb::auto_group_frames(np, (size_t)height * PW));
   DevBuf<float> d_images;
   HIP_TRY(d_images.upload(images_host, npix * n_frames));
-  SatBatchStats stats;
-  stats.frames = n_frames;
+  stats->frames = n_frames;
   for (int f0 = 0; f0 < n_frames; f0 += G) {
     const int fg = std::min(G, n_frames - f0);
     float *padded = nullptr, *corrected = nullptr;
@@ -2918,10 +2847,27 @@ extern "C" int rpsf_saturation_fill_batch_device(rpsf_plan* p, const float* imag
     }
     long groups = 0, masked = 0;
     rpsf_sat_batch_totals(sd, &groups, &masked);
-    stats.frame_groups += 1, stats.groups += groups, stats.masked += masked;
+    stats->frame_groups += 1, stats->groups += groups, stats->masked += masked;
   }
-  stats.store(p);
   return RPSF_OK;
+}
+
+// one frame; reverse_groups: F4's workgroups take the groups in the reverse of the batch's order instead of the table's own
+extern "C" int rpsf_saturation_fill_device(rpsf_plan* p, const float* image_host, int height, int width, int pad_mode, double threshold, int dilation,
+                                           int neighborhood_width, int reverse_groups, float* padded_host, uint8_t* mask_host, int* n_groups_or_null) {
+  SatBatchStats stats;
+  return sat_fill_frames(p, image_host, 1, height, width, pad_mode, threshold, dilation, neighborhood_width,
+                         reverse_groups ? rpsfsatb::ORDER_REVERSED : rpsfsatb::ORDER_FRAMES, padded_host, mask_host, n_groups_or_null, &stats);
+}
+
+extern "C" int rpsf_saturation_fill_batch_device(rpsf_plan* p, const float* images_host, int n_frames, int height, int width, int pad_mode,
+                                                 double threshold, int dilation, int neighborhood_width, int order, float* padded_host,
+                                                 uint8_t* masks_host, int* groups_per_frame_or_null) {
+  SatBatchStats stats;
+  const int rc = sat_fill_frames(p, images_host, n_frames, height, width, pad_mode, threshold, dilation, neighborhood_width, order, padded_host,
+                                 masks_host, groups_per_frame_or_null, &stats);
+  if (rc == RPSF_OK) stats.store(p);
+  return rc;
 }
 
 // Self-test of the host worker pool (no GPU involved: the CPU test suite calls it): `jobs` jobs of `parts` parts from each of `callers` threads at

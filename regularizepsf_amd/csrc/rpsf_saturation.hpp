@@ -1,36 +1,25 @@
 // rpsf_saturation.hpp - what csrc/rpsf.hip sees of csrc/saturation.hip: the device scratch of a plan's saturation branch and the two
-// halves of the route around the correction of the padded frame (which is the plan's own launch, rpsf.hip).
+// halves of the route around the correction of the padded frames (which is the plan's own launch, rpsf.hip).  The unit of work is the
+// frame-group: `frames` frames of one shape; a single frame is a frame-group of one.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
 
-struct SatDevice;  // scratch, events and counters; owned by the plan, made at the first call, grown when a larger frame arrives
+struct SatDevice;  // scratch, events and counters; owned by the plan, made at the first call, grown when a larger frame-group arrives
 
 struct SatCall {
   int H, W, N, pad_mode, dilation, width;
   double threshold;
   int in_row0, out_row0, out_rows;  // rows of the padded frame the correction reads from / writes (SatRun::init's geometry)
-  bool reverse_groups;              // testing aid: F4's workgroups take the groups last first
 };
 
 __attribute__((visibility("hidden"))) SatDevice* rpsf_sat_create();
 __attribute__((visibility("hidden"))) void rpsf_sat_destroy(SatDevice* s);  // (the plan's device is current)
-// F1 - F4 on `st`, one synchronisation of it in between (hot count, group count, masked count).  *padded: the filled padded frame
-// (PH x PW float32), *corrected: room for out_rows x PW float32.
-__attribute__((visibility("hidden"))) int rpsf_sat_fill(SatDevice* s, const SatCall& c, const float* image_dev, hipStream_t st, float** padded,
-                                                         float** corrected);
-// F5 on `st`: raw values on the mask, crop into out_dev (H x W), the list of masked in-frame pixels
-__attribute__((visibility("hidden"))) int rpsf_sat_restore(SatDevice* s, const SatCall& c, const float* image_dev, float* out_dev, hipStream_t st);
-// copies the list of F5 (row * W + col of every masked in-frame pixel, in no particular order) to the host and waits for `st`;
-// *list_host stays null, and nothing is waited for, when nothing was hot
-__attribute__((visibility("hidden"))) int rpsf_sat_list(SatDevice* s, hipStream_t st, const int32_t** list_host, size_t* count);
-__attribute__((visibility("hidden"))) int rpsf_sat_mask(SatDevice* s, const SatCall& c, hipStream_t st, uint8_t* mask_host);  // PH x PW bytes (zeros when nothing was hot)
-__attribute__((visibility("hidden"))) int rpsf_sat_counts(SatDevice* s, int* n_hot, int* n_mask, int* n_groups);  // of the last fill
-__attribute__((visibility("hidden"))) int rpsf_sat_kernel_ms(SatDevice* s, double ms[5]);
+__attribute__((visibility("hidden"))) int rpsf_sat_kernel_ms(SatDevice* s, double ms[5]);  // F1 ... F5 of the last frame-group, device time
 
-// ---- a group of `frames` frames of one shape, image_stride floats apart (csrc/rpsf_core_saturation_batch.hpp).  F1 - F4 on `st` with ONE
+// `frames` frames of one shape, image_stride floats apart (csrc/rpsf_core_saturation_batch.hpp).  F1 - F4 on `st` with ONE
 // synchronisation of it for all frames; F4 is one launch over every frame's groups in `order_mode` (rpsfsatb::ORDER_*).  *padded: the
 // filled padded frames, *p_stride floats apart; *corrected: room for out_rows x PW float32 per frame, *c_stride apart.
 __attribute__((visibility("hidden"))) int rpsf_sat_fill_batch(SatDevice* s, const SatCall& c, int frames, const float* images_dev, size_t image_stride,

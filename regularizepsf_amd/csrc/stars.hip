@@ -17,30 +17,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rpsf.h"
 #include "rpsf_core_stars.hpp"
+#include "rpsf_side_unit.hpp"
 
 using namespace rpsfs;
-
-int rpsf_detail_fail(int code, const std::string& msg);  // rpsf.hip: sets rpsf_last_error of the calling thread
-static int fail(int code, const std::string& msg) { return rpsf_detail_fail(code, msg); }
-#define HIP_TRY(expr)                                                                                               \
-  do {                                                                                                              \
-    hipError_t e_ = (expr);                                                                                         \
-    if (e_ != hipSuccess)                                                                                           \
-      return fail(e_ == hipErrorOutOfMemory ? RPSF_E_NOMEM : RPSF_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-namespace {
-struct GpuCtx {
-  template <class F>
-  __device__ __forceinline__ void each(F&& f) {
-    f((int)threadIdx.x);
-    __syncthreads();
-  }
-};
-__device__ __forceinline__ long global_id() { return (long)blockIdx.x * blockDim.x + threadIdx.x; }
-}  // namespace
 
 extern __shared__ __attribute__((aligned(16))) char stars_lds[];
 
@@ -82,26 +62,6 @@ __global__ __launch_bounds__(WALK_THREADS) void stars_walk_kernel(Frame fr, cons
   s4_walk(ctx, fr, L, labels, roots, stats, count, min_area, max_area, (long)blockIdx.x * WALK_WAVES, reinterpret_cast<double*>(stars_lds),
           moments);
 }
-
-namespace {
-template <class T>
-struct Buf {  // a device array that only ever grows
-  T* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t count) {
-    if (count <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr, cap = 0;
-    const hipError_t e = hipMalloc(&p, count * sizeof(T));
-    if (e == hipSuccess) cap = count;
-    return e;
-  }
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-};
-unsigned blocks_for(long threads) { return (unsigned)((threads + 255) / 256); }
-}  // namespace
 
 struct rpsf_stars {
   int device = 0, H = 0, W = 0, box = 0, nby = 0, nbx = 0;

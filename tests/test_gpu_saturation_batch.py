@@ -1,7 +1,8 @@
-"""The batched device saturation route on the GPU (csrc/saturation.hip's batch drivers, csrc/rpsf_core_saturation_batch.hpp; DESIGN.md
+"""The device saturation route for batches of frames on the GPU (csrc/saturation.hip, csrc/rpsf_core_saturation_batch.hpp; DESIGN.md
 3.8 "Frame batches").
 
-A batch shares launches, never data: every frame must come out with the bits the single-frame entry gives it.  The stacks of
+A batch shares launches, never data: every frame must come out with the bits the single-frame entry gives it (a frame-group of one on
+the same driver, so the comparisons that decide are the independent ones).  The stacks of
 tests/saturation_batch_cases.py are held against ``saturation_cases.reference_fill`` per frame and against the CPU emulator; the whole
 route against ``rpsf_apply_device_saturated`` on a fresh plan, against ``saturation="host"`` and against the loop over ``apply``.
 """
@@ -277,3 +278,35 @@ def test_one_frame_no_frame_and_bad_arguments():
     finally:
         buf.free()
         out.free()
+
+
+# ------------------------------------------------------------------------------------------------ 11: a single frame is a frame-group of one
+@pytest.mark.parametrize("name", sorted(sc.CASES))
+def test_the_single_frame_entry_is_a_frame_group_of_one_in_table_order(name):
+    _, n, _, pad_mode, (dilation, width) = sc.CASES[name]
+    mode = _native.PAD_MODES[pad_mode]
+    plan = _native.Plan(n, [(0, 0)])
+    single, mask, groups = plan.saturation_fill_device(sc.frame(name), mode, sc.THRESHOLD, dilation, width)
+    padded, masks, per_frame = plan.saturation_fill_batch_device([sc.frame(name)], mode, sc.THRESHOLD, dilation, width, order=bc.ORDER_FRAMES)
+    assert np.array_equal(masks[0].astype(bool), mask) and list(per_frame) == [groups]
+    sc.assert_same_bits(np.ascontiguousarray(padded[0]), single, f"{name}: a batch of one in table order")
+    backward, backward_mask, backward_groups = plan.saturation_fill_device(sc.frame(name), mode, sc.THRESHOLD, dilation, width, reverse_groups=True)
+    assert np.array_equal(backward_mask, mask) and backward_groups == groups
+    sc.assert_same_bits(backward, single, f"{name}: groups taken last first")
+
+
+def test_single_frame_calls_leave_the_batch_info_as_it_was():
+    n, shape = 16, (40, 48)
+    coords, k = orc.synthetic_transfer(*shape, n, alpha=1.0, epsilon=0.1)
+    frames, _ = _three_frames(n, shape)
+    t = rp.ArrayPSFTransform(rp.IndexedCube(coords, k), saturation="device")
+    plan = t._device_plan()
+    _resident_batch(plan, frames, "symmetric", 1, 7)
+    info = plan.saturation_batch_info()
+    assert info[:2] == (3, 1) and info[2] > 0 and info[3] > 20
+    plan.saturation_fill_device(frames[0], _native.PAD_MODES["symmetric"], THRESHOLD, 1, 7)
+    assert plan.saturation_batch_info() == info, "saturation_fill_device"
+    _resident_single(plan, frames[2], "symmetric", 1, 7)
+    assert plan.saturation_batch_info() == info, "apply_device_saturated"
+    t.apply(frames[0], saturation_threshold=THRESHOLD, saturation_dilation=1, neighborhood_width=7)
+    assert t._device_plan() is plan and plan.saturation_batch_info() == info, 'apply(..., saturation="device")'

@@ -57,6 +57,19 @@ def test_the_order_in_which_f4_takes_the_groups_changes_no_bit():
         bc.check_same_results(bc.run_stack(RUN, "order", order=order), longest_first, f"order {order}")
 
 
+@pytest.mark.parametrize("name", sorted(sc.CASES))
+def test_a_frame_group_of_one_is_the_single_frame_emulator_bit_for_bit_in_every_order(name):
+    """The device route has one driver, and a single frame is a frame-group of one: the batch drivers must give such a group what the
+    per-thread functions give the frame when they are driven directly (tests/emu/emu_saturation.cpp)."""
+    _, n, _, pad_mode, (dilation, width) = sc.CASES[name]
+    want, want_mask, want_groups = sc.emu_fill(sc.frame(name), n, pad_mode, dilation, width)
+    for order in (bc.ORDER_LONGEST_FIRST, bc.ORDER_REVERSED, bc.ORDER_FRAMES):
+        padded, masks, groups, info = bc.emu_fill_batch([sc.frame(name)], n, pad_mode, dilation, width, order=order)
+        assert padded.shape == (1, *want.shape) and np.array_equal(padded[0].view(np.uint32), want.view(np.uint32)), (name, order)
+        assert np.array_equal(masks[0], want_mask), (name, order)
+        assert list(groups) == [want_groups] and info[:3] == (1, 1, want_groups), (name, order)
+
+
 def test_restore_gives_every_frame_its_own_values_crop_and_list():
     name = "kinds_edge"
     _, n, (h, w), pad_mode, (dilation, width) = bc.STACKS[name]
