@@ -1,5 +1,7 @@
 // rpsf.hip - host side of librpsf_hip.so: plans, launches and the C ABI of include/rpsf.h; the RCCL and
-// hipFFT loaders.  The device code is in rpsf_kernels.hpp (kernels) and rpsf_core.hpp (per-thread phases).
+// hipFFT loaders.  The device code is in rpsf_kernels.hpp (kernels) and rpsf_core.hpp (per-thread phases).  What follows from a corner
+// list and a frame geometry alone - lattice tables, processing order, row bands, the geometry predicates of the launch forms - is plain
+// C++ in rpsf_lattice.hpp (as the job lists of the sweep kernel are in rpsf_plan3.hpp): this file uploads what those return.
 //
 // Kernels (rpsf_kernels.hpp):
 //   patch_kernel<C>        K1: fused gather+pad+window -> 2-D DFT -> x folded K -> inverse DFT -> window ->
@@ -35,6 +37,7 @@
 #define RPSF_HOST_TU 1
 #include "rpsf_device.hpp"
 #include "rpsf_hostpipe.hpp"
+#include "rpsf_lattice.hpp"
 #include "rpsf_saturation.hpp"
 #include "rpsf_core_saturation_batch.hpp"
 
@@ -85,13 +88,7 @@ static int dispatch_v3(int N, F&& f) {
     default: return fail(RPSF_E_UNSUPPORTED, "no third-generation plan for this patch size");
   }
 }
-static bool has_v3(int N) { return N == 64 || N == 32 || N == 16; }
-
-// Patches one workgroup of the patch kernels processes (first generation: 64-thread workgroups shared by several small patches), and
-// the patches per XCD chunk that follow from it: an eighth of the plan's, in whole workgroups.  The processing order, the prefetch
-// lists and the fused tile order are cut by it (setup_lattice) and the kernels index by it (PatchParams::chunk).
-static constexpr int patch_teams(int N) { return N * N / 2 / 64 >= 64 ? 1 : 64 / (N * N / 2 / 64); }
-static int chunk_patches(int n_patches, int teams) { return ((n_patches + 7) / 8 + teams - 1) / teams * teams; }
+static bool has_v3(int N) { return sweep_patch_size(N); }
 
 // Python's slice arithmetic for [start, stop) over a length-n axis (a negative bound wraps once): the window rule of the saturation fill
 static void py_slice(long start, long stop, long n, long* lo, long* hi) {
@@ -302,19 +299,6 @@ static const rpsf_plan* owner(const rpsf_plan* p) { return p->parent ? p->parent
 enum OverlapKind { OV_ATOMIC = 0, OV_PLANES = 1, OV_DIRECT = 2, OV_SWEEP = 3 };
 static OverlapKind overlap_kind(const rpsf_plan* p);
 
-static uint64_t morton2(uint32_t a, uint32_t b) {
-  auto spread = [](uint64_t x) {
-    x &= 0xffffffffull;
-    x = (x | (x << 16)) & 0x0000ffff0000ffffull;
-    x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
-    x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
-    x = (x | (x << 2)) & 0x3333333333333333ull;
-    x = (x | (x << 1)) & 0x5555555555555555ull;
-    return x;
-  };
-  return (spread(a) << 1) | spread(b);
-}
-
 // Regions and job lists of the sweep kernel for `target_regions` workgroups (rpsf_plan3.hpp); replaces the plan's previous lists
 static int build_sweep_lists(rpsf_plan* p, int target_regions) {
   const int nli = p->nti - 1, nlj = p->ntj - 1;
@@ -345,211 +329,46 @@ static int build_sweep_lists(rpsf_plan* p, int target_regions) {
   return RPSF_OK;
 }
 
-// Regular lattice test + colour classes + tile tables + processing order (host, at plan creation)
+// Regular lattice test + colour classes + tile tables + processing order (rpsf_lattice.hpp), uploaded at plan creation
 static int setup_lattice(rpsf_plan* p) {
-  const int n = p->n_patches, half = p->N / 2;
-  int r0 = p->h_coords[0], c0 = p->h_coords[1], r1 = r0, c1 = c0;
-  for (int i = 0; i < n; ++i) {
-    r0 = std::min(r0, p->h_coords[2 * i]), r1 = std::max(r1, p->h_coords[2 * i]);
-    c0 = std::min(c0, p->h_coords[2 * i + 1]), c1 = std::max(c1, p->h_coords[2 * i + 1]);
-  }
-  bool ok = true;
-  for (int i = 0; i < n && ok; ++i)
-    ok = (p->h_coords[2 * i] - r0) % half == 0 && (p->h_coords[2 * i + 1] - c0) % half == 0;
-  int nti = 0, ntj = 0;
-  if (ok) {
-    nti = (r1 - r0) / half + 2, ntj = (c1 - c0) / half + 2;
-    if ((size_t)nti * ntj >= ((size_t)1 << 24)) ok = false;
-  }
-  std::vector<uint8_t> cls(n, 0);
-  std::vector<int32_t> cell;  // lattice cell -> patch (or -1)
-  const int nli = nti - 1, nlj = ntj - 1;
-  const int par_i = ok && p->parent && p->parent->lattice ? ((r0 - p->parent->lat_r0) / half) & 1 : 0;
-  const int par_j = ok && p->parent && p->parent->lattice ? ((c0 - p->parent->lat_c0) / half) & 1 : 0;
-  if (ok) {
-    cell.assign((size_t)nli * nlj, -1);
-    for (int i = 0; i < n && ok; ++i) {
-      const int li = (p->h_coords[2 * i] - r0) / half, lj = (p->h_coords[2 * i + 1] - c0) / half;
-      if (cell[(size_t)li * nlj + lj] >= 0) ok = false;  // duplicate corner: two patches in one plane cell
-      cell[(size_t)li * nlj + lj] = i;
-      // (a view takes its colours from the parent's lattice: the planes are summed in colour order, so a band's pixels then come out
-      // bit-identical to the whole-frame apply's)
-      cls[i] = (uint8_t)((((li + par_i) & 1) << 1) | ((lj + par_j) & 1));
-    }
-  }
-  p->lattice = ok;
-  const int chunk = chunk_patches(n, patch_teams(p->N));
-  p->patch.direct_ok = ok && patch_teams(p->N) == 1;
-  // ---- processing order: 8 chunks, one per XCD (workgroups b and b + 8 share one) ----
-  p->h_order.resize(n);
-  if (ok) {
-    // Column strips walked boustrophedon, cut into 8 equal runs: compact regions, so that the four patches over a
-    // tile mostly run on one XCD (they read the same pixels through one L2, and the tile can be accumulated there).
-    int strips = nlj >= 8 ? std::max(4, nlj / 8) : 1;  // strips about 8 patches wide (4096^2: 4 as before; 8192^2: 8, -1.2 % against 4)
-    if (const char* e = dev_env("RPSF_STRIPS")) strips = std::max(1, std::min(nlj, std::atoi(e)));  // development sweeps
-    int k = 0;
-    bool meet = true;  // (4096^2 / 256: 0.1877 vs 0.1900 ms with alternating strip directions; RPSF_ORDER_MEET=0 selects those)
-    if (const char* e = dev_env("RPSF_ORDER_MEET")) meet = std::atoi(e) != 0;
-    for (int s2 = 0; s2 < strips; ++s2) {
-      const int ja = (int)((long)nlj * s2 / strips), jb = (int)((long)nlj * (s2 + 1) / strips);
-      if (meet) {
-        // the upper half of every strip top-down, the lower half bottom-up: the two XCDs of a strip meet in the middle at the end, and
-        // neighbouring strips walk the same rows at the same time, so the tiles on region borders do not wait a whole launch for
-        // their last contributor (their planes would long have left the Infinity Cache)
-        const int mid = (nli + 1) / 2;
-        for (int li = 0; li < mid; ++li)
-          for (int lj = ja; lj < jb; ++lj)
-            if (cell[(size_t)li * nlj + lj] >= 0) p->h_order[k++] = cell[(size_t)li * nlj + lj];
-        for (int li = nli - 1; li >= mid; --li)
-          for (int lj = ja; lj < jb; ++lj)
-            if (cell[(size_t)li * nlj + lj] >= 0) p->h_order[k++] = cell[(size_t)li * nlj + lj];
-        continue;
-      }
-      for (int step = 0; step < nli; ++step) {
-        const int li = (s2 & 1) ? nli - 1 - step : step;
-        for (int lj = ja; lj < jb; ++lj)
-          if (cell[(size_t)li * nlj + lj] >= 0) p->h_order[k++] = cell[(size_t)li * nlj + lj];
-      }
-    }
-    // Inside a chunk the patches on the rim of the lattice go first.  They hang over the image edge and take the slower
-    // padded gather / cropped store path (+50 % per patch at N = 256); dispatched first, they are the long jobs of a
-    // longest-job-first list schedule: a CU that drew one simply takes one patch fewer later on, instead of a late rim
-    // patch stretching the last round.  (Round 1: N = 256 215 -> 207 us, 2048^2 / N = 128 67 -> 58 us.)
-    if (!dev_env("RPSF_NO_RIM_FIRST")) {
-      auto rim = [&](int32_t i) {
-        const int r = p->h_coords[2 * i], c = p->h_coords[2 * i + 1];
-        return r == r0 || r == r1 || c == c0 || c == c1;
-      };
-      // ... until the rim patches got their 16-byte paths: they are now the cheaper ones (half or a quarter of the stores).  With one
-      // patch per CU (N = 256) they go LAST, so that the patches of the partial last round are the short ones (4096^2: -1 %,
-      // profiles/r02av); with four workgroups per CU (N = 128) first is still the better order (2048^2: 0.0685 vs 0.0705 ms).
-      bool rim_last = p->N == 256;
-      if (const char* e = dev_env("RPSF_RIM_LAST")) rim_last = std::atoi(e) != 0;
-      for (int x = 0; x < 8; ++x) {
-        const int lo = std::min(n, x * chunk), hi = std::min(n, lo + chunk);
-        if (rim_last)
-          std::stable_partition(p->h_order.begin() + lo, p->h_order.begin() + hi, [&](int32_t i) { return !rim(i); });
-        else
-          std::stable_partition(p->h_order.begin() + lo, p->h_order.begin() + hi, rim);
-      }
-    }
-  } else {
-    std::vector<std::pair<uint64_t, int32_t>> keyed(n);
-    for (int i = 0; i < n; ++i)
-      keyed[i] = {morton2((uint32_t)((p->h_coords[2 * i] - r0) / half), (uint32_t)((p->h_coords[2 * i + 1] - c0) / half)), i};
-    std::sort(keyed.begin(), keyed.end());
-    for (int i = 0; i < n; ++i) p->h_order[i] = keyed[i].second;
-  }
-  {
-    std::vector<int4> desc(n);
-    for (int s2 = 0; s2 < n; ++s2) {
-      int i = p->h_order[s2];
-      desc[s2] = make_int4(p->h_coords[2 * i], p->h_coords[2 * i + 1], p->k_index.empty() ? i : p->k_index[i], ok ? cls[i] : 0);
-    }
-    HIP_TRY(p->d_desc.upload(desc.data(), n));
-  }
-  if (!ok) return RPSF_OK;
-  p->lat_r0 = r0, p->lat_c0 = c0, p->nti = nti, p->ntj = ntj;
+  LatticeKnobs knobs;  // development sweeps
+  if (const char* e = dev_env("RPSF_STRIPS")) knobs.strips = std::max(1, std::atoi(e));
+  if (const char* e = dev_env("RPSF_ORDER_MEET")) knobs.meet = std::atoi(e) != 0;
+  if (dev_env("RPSF_NO_RIM_FIRST")) knobs.rim_first = false;
+  if (const char* e = dev_env("RPSF_RIM_LAST")) knobs.rim_last = std::atoi(e) != 0;
+  const LatticeParent parent = p->parent ? LatticeParent{p->parent->lat_r0, p->parent->lat_c0, p->parent->lattice} : LatticeParent{};
+  LatticeTables t = lattice_build(p->N, p->n_patches, p->h_coords.data(), p->k_index.empty() ? nullptr : p->k_index.data(), p->patch.v2,
+                                  p->parent ? &parent : nullptr, knobs);
+  const size_t n = (size_t)p->n_patches;
+  p->lattice = t.lattice, p->patch.direct_ok = t.direct_ok;
+  p->h_order = std::move(t.order);
+  static_assert(sizeof(PatchDesc) == sizeof(int4) && sizeof(QuadWords) == sizeof(uint4), "uploaded as they are");
+  HIP_TRY(p->d_desc.upload(reinterpret_cast<const int4*>(t.desc.data()), n));
+  if (!t.lattice) return RPSF_OK;
+  p->lat_r0 = t.r0, p->lat_c0 = t.c0, p->nti = t.nti, p->ntj = t.ntj;
   // ---- third generation: regions and job lists (rpsf_plan3.hpp) when every lattice cell has its patch ----
-  if (has_v3(p->N) && nli >= 2 && nlj >= 2 && (size_t)nli * nlj == (size_t)n) {
-    p->sweep.slot.resize((size_t)nli * nlj);
-    for (size_t c = 0; c < p->sweep.slot.size(); ++c) p->sweep.slot[c] = p->k_index.empty() ? cell[c] : p->k_index[cell[c]];
-    p->sweep.par_j = par_j;
+  if (!t.sweep_slot.empty()) {
+    p->sweep.slot = std::move(t.sweep_slot);
+    p->sweep.par_j = t.par_j;
     const int rc3 = build_sweep_lists(p, std::max(8, p->cu_count));
     if (rc3 != RPSF_OK) return rc3;
   }
-  // ---- tiles: coverage, owner chunk, ranks ----
-  std::vector<int> chunk_of(n), seq_of(n);
-  for (int s2 = 0; s2 < n; ++s2) chunk_of[p->h_order[s2]] = s2 / chunk, seq_of[p->h_order[s2]] = s2;
-  std::vector<uint8_t> cover((size_t)nti * ntj, 0), tile_info((size_t)nti * ntj, 0);
-  std::vector<uint32_t> quad_of((size_t)n * 4, quad_word(QUAD_NONE, 0, 0));
-  for (int ti = 0; ti < nti; ++ti)
-    for (int tj = 0; tj < ntj; ++tj) {
-      int who[4], nwho = 0;  // contributors by colour
-      for (int a2 = 0; a2 < 2; ++a2)
-        for (int b2 = 0; b2 < 2; ++b2) {
-          const int li = ti - a2, lj = tj - b2;
-          if (li < 0 || lj < 0 || li >= nli || lj >= nlj) continue;
-          const int i = cell[(size_t)li * nlj + lj];
-          if (i >= 0) who[nwho++] = i;
-        }
-      std::sort(who, who + nwho, [&](int a2, int b2) { return seq_of[a2] < seq_of[b2]; });  // accumulation order = processing order
-      const size_t tile = (size_t)ti * ntj + tj;
-      int owner = -1, best = 0;
-      for (int k = 0; k < nwho; ++k) {
-        cover[tile] |= (uint8_t)(1u << cls[who[k]]);
-        int cnt = 0;
-        for (int m = 0; m < nwho; ++m) cnt += chunk_of[who[m]] == chunk_of[who[k]];
-        if (cnt > best) best = cnt, owner = chunk_of[who[k]];  // ties: the chunk of the earliest contributor
-      }
-      int rank = 0;
-      uint8_t side = 0;
-      for (int k = 0; k < nwho; ++k) {
-        const int i = who[k];
-        const int li = (p->h_coords[2 * i] - r0) / half, lj = (p->h_coords[2 * i + 1] - c0) / half;
-        const int q = 2 * (ti - li) + (tj - lj);
-        if (p->patch.direct_ok && chunk_of[i] == owner) {
-          quad_of[(size_t)i * 4 + q] = quad_word(QUAD_DIRECT, (uint32_t)rank++, (uint32_t)tile);
-        } else {
-          quad_of[(size_t)i * 4 + q] = quad_word(QUAD_SIDE, 0, (uint32_t)tile);
-          side |= (uint8_t)(1u << cls[i]);
-        }
-      }
-      tile_info[tile] = (uint8_t)(side | (nwho ? 16 : 0));
-    }
-  HIP_TRY(p->d_cover.upload(cover.data(), cover.size()));
-  if (p->patch.v2) {  // fused plane sum: tile order (by the slot of the last contributor: the dispatch order inside a chunk) and counters
-    std::vector<std::pair<int, uint32_t>> keyed;
-    for (int ti = 0; ti < nti; ++ti)
-      for (int tj = 0; tj < ntj; ++tj) {
-        int last = -1;
-        for (int a2 = 0; a2 < 2; ++a2)
-          for (int b2 = 0; b2 < 2; ++b2) {
-            const int li = ti - a2, lj = tj - b2;
-            if (li < 0 || lj < 0 || li >= nli || lj >= nlj) continue;
-            const int i = cell[(size_t)li * nlj + lj];
-            if (i >= 0) last = std::max(last, seq_of[i] % chunk);
-          }
-        keyed.push_back({last, (uint32_t)(ti * ntj + tj)});
-      }
-    std::stable_sort(keyed.begin(), keyed.end(), [](const auto& a2, const auto& b2) { return a2.first < b2.first; });
-    std::vector<uint32_t> order(keyed.size());
-    for (size_t i = 0; i < keyed.size(); ++i) order[i] = keyed[i].second;
-    HIP_TRY(p->patch.d_sum_order.upload(order.data(), order.size()));
-    HIP_TRY(p->patch.d_tile_done.alloc(order.size()));
-    HIP_TRY(hipMemset(p->patch.d_tile_done, 0, order.size() * sizeof(uint32_t)));
+  HIP_TRY(p->d_cover.upload(t.cover.data(), t.cover.size()));
+  if (p->patch.v2) {  // fused plane sum: tile order and counters
+    HIP_TRY(p->patch.d_sum_order.upload(t.sum_order.data(), t.sum_order.size()));
+    HIP_TRY(p->patch.d_tile_done.alloc(t.sum_order.size()));
+    HIP_TRY(hipMemset(p->patch.d_tile_done, 0, t.sum_order.size() * sizeof(uint32_t)));
     HIP_TRY(p->patch.d_sum_queue.alloc(1));
     HIP_TRY(hipMemset(p->patch.d_sum_queue, 0, sizeof(uint32_t)));
     HIP_TRY(p->patch.d_xq.alloc(8 * 32));
     HIP_TRY(hipMemset(p->patch.d_xq, 0, 8 * 32 * sizeof(uint32_t)));
-    {  // image prefetch lists: for every chunk, each lattice tile once, in the order the chunk's slots first touch it
-      std::vector<uint32_t> tiles;
-      for (int x = 0; x < 8; ++x) {
-        p->patch.prefetch_first[x] = (uint32_t)tiles.size();
-        std::vector<char> seen((size_t)nti * ntj, 0);
-        for (int s2 = std::min(n, x * chunk); s2 < std::min(n, (x + 1) * chunk); ++s2) {
-          const int i = p->h_order[s2];
-          const int li = (p->h_coords[2 * i] - r0) / half, lj = (p->h_coords[2 * i + 1] - c0) / half;
-          for (int q = 0; q < 4; ++q) {
-            const size_t tile = (size_t)(li + (q >> 1)) * ntj + (lj + (q & 1));
-            if (!seen[tile]) seen[tile] = 1, tiles.push_back((uint32_t)tile);
-          }
-        }
-      }
-
-      p->patch.prefetch_first[8] = (uint32_t)tiles.size();
-      HIP_TRY(p->patch.d_prefetch_tiles.alloc(std::max<size_t>(1, tiles.size())));
-      HIP_TRY(hipMemcpy(p->patch.d_prefetch_tiles, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
+    std::copy_n(t.prefetch_first, 9, p->patch.prefetch_first);
+    HIP_TRY(p->patch.d_prefetch_tiles.alloc(std::max<size_t>(1, t.prefetch_tiles.size())));
+    HIP_TRY(hipMemcpy(p->patch.d_prefetch_tiles, t.prefetch_tiles.data(), t.prefetch_tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
   if (p->patch.direct_ok) {
-    std::vector<uint4> quads(n);
-    for (int s2 = 0; s2 < n; ++s2) {
-      const uint32_t* q = &quad_of[(size_t)p->h_order[s2] * 4];
-      quads[s2] = make_uint4(q[0], q[1], q[2], q[3]);
-    }
-    HIP_TRY(p->patch.d_quads.upload(quads.data(), n));
-    HIP_TRY(p->patch.d_tile_info.upload(tile_info.data(), tile_info.size()));
+    HIP_TRY(p->patch.d_quads.upload(reinterpret_cast<const uint4*>(t.quads.data()), n));
+    HIP_TRY(p->patch.d_tile_info.upload(t.tile_info.data(), t.tile_info.size()));
     HIP_TRY(p->patch.d_chunk_xcc.alloc(8));
     HIP_TRY(hipMemset(p->patch.d_chunk_xcc, 0, 8 * sizeof(uint32_t)));
   }
@@ -578,7 +397,7 @@ struct PatchPlan {
   static constexpr int WG = L::WG, TEAMS = WG / C::T;  // (Launch<C>::TEAMS; the second generation has one patch per workgroup)
   static constexpr size_t LDS_BYTES = L::LDS_BYTES;
   static constexpr size_t PACK_PER_PATCH = C::G_PER_PATCH + (Gen2 ? C::GS_PER_PATCH : 0);  // elements one thread each of the pack kernels writes
-  static_assert(TEAMS == patch_teams(C::N), "setup_lattice cuts the chunks by patch_teams()");
+  static_assert(TEAMS == patch_teams(C::N), "lattice_build cuts the chunks by patch_teams()");
   // (functions, not members: only the generation's own templates are instantiated for C)
   static constexpr auto kernel() { if constexpr (Gen2) return &patch_kernel2<C>; else return &patch_kernel<C>; }
   static constexpr auto pack() { if constexpr (Gen2) return &pack_kernel2<C>; else return &pack_kernel<C>; }
@@ -1016,12 +835,9 @@ struct Batch {
   size_t im_stride = 0, out_stride = 0;
 };
 
-// Whether the lattice tiles cover the resident output window.  The plane sums, the direct mode's fix-up and the sweep kernel write lattice tiles
-// only: pixels of the window that no tile covers are written by nobody (the reference leaves them zero), so the window is cleared first.
+// Whether the plan's lattice tiles cover the resident output window (rpsf_lattice.hpp): where they do not, the window is cleared first
 static bool lattice_covers_window(const rpsf_plan* p, const rpsf_geometry& g) {
-  const int half = p->N / 2;
-  const long r0 = (long)p->lat_r0 + g.origin_row, c0 = (long)p->lat_c0 + g.origin_col;
-  return r0 <= g.out_row0 && r0 + (long)p->nti * half >= (long)g.out_row0 + g.out_rows && c0 <= 0 && c0 + (long)p->ntj * half >= g.width;
+  return lattice_covers_window(p->N, p->lat_r0, p->lat_c0, p->nti, p->ntj, g);
 }
 
 // Zeroes the resident output window of every frame
@@ -1060,16 +876,10 @@ static int sum_first_for(const rpsf_plan* p, int frames) {
   return work >= 2048 ? 32 : work >= 1024 ? 16 : work >= 512 ? 8 : 0;
 }
 
-// What the persistent kernels are compiled for (patch_body2's HOT instantiation has no pixel-by-pixel rim paths): every 16-byte unit
-// of a patch - four pixels of one row starting at a column that is a multiple of 4 - maps under np.pad's index map to four consecutive
-// image columns (ascending or descending) or to the fill.  True for 'constant', 'symmetric' and 'wrap' when the width is a multiple of
-// 4 (no unit straddles an image edge or a reflection); 'reflect' and 'edge' tear units apart.  Other launches take patch_kernel2.
-// (self-contained: the patch columns themselves - lattice origin + origin_col - and the plane stride are checked here too, not left to the
-// `fused` predicate of launch_apply, so that relaxing that one can never hand the HOT kernels a unit they have no path for)
+// What the persistent kernels are compiled for (hot_geometry, rpsf_lattice.hpp), for this plan, image and frame stride
 static bool hot_geometry(const rpsf_plan* p, const float* d_img, const rpsf_geometry& g, size_t im_stride) {
-  return (g.pad_mode == RPSF_PAD_CONSTANT || g.pad_mode == RPSF_PAD_SYMMETRIC || g.pad_mode == RPSF_PAD_WRAP) && g.width % 4 == 0 &&
-         g.ld_image % 4 == 0 && g.origin_col % 4 == 0 && im_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(d_img) & 15) == 0 &&
-         p->lattice && ((long)p->lat_c0 + g.origin_col) % 4 == 0 && p->patch.planes_floats % 4 == 0;
+  const bool aligned16 = im_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(d_img) & 15) == 0 && p->patch.planes_floats % 4 == 0;
+  return hot_geometry(g, p->lattice, p->lat_c0, aligned16);
 }
 
 // What the patch launch of one apply is: decided by patch_launch_for from the plan as it stands, committed by launch_apply (the queue positions the
@@ -1288,7 +1098,6 @@ static OverlapKind overlap_kind(const rpsf_plan* p) {
     default: return p->sweep.ok ? OV_SWEEP : p->lattice ? OV_PLANES : OV_ATOMIC;  // direct stays opt-in until it beats the planes
   }
 }
-static size_t plane_floats_needed(const rpsf_geometry& g) { return ((size_t)g.out_rows * g.width + 3) & ~(size_t)3; }
 
 static int launch_apply_generic(rpsf_plan* p, const float* d_img, float* d_out, const rpsf_geometry& g, hipStream_t st,
                                 hipEvent_t ev_k0, hipEvent_t ev_k1, Batch b) {
@@ -1387,10 +1196,9 @@ static int launch_apply(rpsf_plan* p, const float* d_img, float* d_out, const rp
   if (kind == OV_DIRECT && (size_t)g.out_rows * g.ld_out * sizeof(float) >= ((size_t)1 << 32))
     return fail(RPSF_E_UNSUPPORTED, "direct overlap-add addresses the output through a 32-bit buffer offset: frame too large");
   if (patch_launch_too_large(p, b.frames)) return fail(RPSF_E_BADARG, "batch too large for one launch");
-  // Fused plane sum: one frame, every plane line written whole by one store instruction (see sum_tile)
-  const bool fused = kind == OV_PLANES && p->patch.v2 && p->patch.fuse_pays && p->patch.d_tile_done && !p->patch.no_fuse && b.frames <= 255 && g.width % 32 == 0 &&
-                     g.ld_out % 4 == 0 && ((long)p->lat_c0 + g.origin_col) % 32 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0 &&
-                     16 * plane_floats_needed(g) < ((size_t)1 << 32);  // the planes are addressed through one 32-bit buffer offset
+  // Fused plane sum: what the plan must have, and the geometry the summing workgroups are written for (fused_geometry, rpsf_lattice.hpp)
+  const bool fused = kind == OV_PLANES && p->patch.v2 && p->patch.fuse_pays && p->patch.d_tile_done && !p->patch.no_fuse && b.frames <= 255 &&
+                     fused_geometry(g, p->lat_c0, (reinterpret_cast<uintptr_t>(d_out) & 15) == 0);
   const size_t n_tiles = (size_t)p->nti * p->ntj;
   // The plan's scratch (planes, flags) serves one apply at a time: an apply on another stream waits for the last one.
   // A plan that has only ever been applied on one stream records nothing behind its launches (stream order is all it needs, and back-to-back
@@ -1833,40 +1641,17 @@ static int ensure_bands(rpsf_plan* p, const rpsf_geometry& g, int want) {
   drop_bands(p);
   p->bands_h = g.height, p->bands_w = g.width, p->bands_mode = g.pad_mode, p->bands_want = want;  // (remembered also when the answer is "no bands")
   if (p->generic || p->parent || !p->lattice || (overlap_kind(p) != OV_PLANES && overlap_kind(p) != OV_SWEEP) || g.pad_mode == RPSF_PAD_WRAP || want < 2) return 0;
-  const int N = p->N, H = g.height;
-  std::vector<int> rows;
-  for (int i = 0; i < p->n_patches; ++i) rows.push_back(p->h_coords[2 * i]);
-  std::sort(rows.begin(), rows.end());
-  rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
-  const int L = (int)rows.size();
-  const int B = std::min({want, (int)HostPipe::MAX_BANDS, L / 2});  // at least two lattice rows per band (it runs a third: the one above)
-  if (B < 2) return 0;
-  std::vector<int> cut(B + 1);
-  // (equal bands: a first band of two lattice rows - an earlier first download - bought nothing, profiles/r06y_host_frame_knobs.log)
-  for (int b = 0; b < B; ++b) cut[b] = b == 0 ? 0 : std::min(H, std::max(0, rows[(size_t)L * b / B]));
-  cut[B] = H;
-  for (int b = 0; b < B; ++b)
-    if (cut[b + 1] <= cut[b]) return 0;
+  RowBands cuts;
+  const int B = row_bands(p->N, p->n_patches, p->h_coords.data(), g.height, want, (int)HostPipe::MAX_BANDS, cuts);
   std::vector<std::unique_ptr<rpsf_plan>> bands;
-  std::vector<int> in_rows;
   for (int b = 0; b < B; ++b) {
-    std::vector<int32_t> idx, coords;
-    int in_hi = 0;
-    for (int i = 0; i < p->n_patches; ++i) {
-      const int r = p->h_coords[2 * i];
-      if (r < cut[b + 1] && r + N > cut[b]) {
-        idx.push_back(i), coords.push_back(r), coords.push_back(p->h_coords[2 * i + 1]);
-        in_hi = std::max(in_hi, std::min(H, r + N));
-      }
-    }
+    std::vector<int32_t> coords;
+    for (const int32_t i : cuts.patches[b]) coords.push_back(p->h_coords[2 * i]), coords.push_back(p->h_coords[2 * i + 1]);
     rpsf_plan* view = nullptr;
-    // (every np.pad mode but 'wrap' maps a row beyond the image edge to a row within the patch's own reach, so rows [0, in_hi) suffice)
-    const int rc = idx.empty() ? fail(RPSF_E_STATE, "empty row band") :
-                                 plan_create_impl(&view, p->device, N, (int)idx.size(), coords.data(), p, idx.data());
-    if (rc != RPSF_OK) return 0;
-    bands.emplace_back(view), in_rows.push_back(std::max(in_hi, cut[b + 1]));
+    if (plan_create_impl(&view, p->device, p->N, (int)cuts.patches[b].size(), coords.data(), p, cuts.patches[b].data()) != RPSF_OK) return 0;
+    bands.emplace_back(view);
   }
-  p->bands = std::move(bands), p->band_rows = cut, p->band_in_rows = in_rows;
+  if (B) p->bands = std::move(bands), p->band_rows = std::move(cuts.cut), p->band_in_rows = std::move(cuts.in_rows);
   return B;
 }
 

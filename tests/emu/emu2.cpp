@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../regularizepsf_amd/csrc/rpsf_core2.hpp"
+#include "../../regularizepsf_amd/csrc/rpsf_lattice.hpp"
 
 using namespace rpsf;
 
@@ -49,7 +50,12 @@ static int emu2_apply_t(int n_patches, const int32_t* coords, int H, int W, int 
   auto pstore1 = [](float* p, float v) { *p = v; };
   std::vector<int> maps(2 * N);
   cf* park = lds.data() + C::BUF_UNITS;
-  std::vector<uint8_t> touched;  // direct mode: which quadrant tiles of the output have been initialised (by N/2 tiles from the first corner)
+  // colour planes and direct mode: colours and tile indices are the library's (rpsf_lattice.hpp; the caller passes a lattice)
+  const LatticeTables lat = lattice_build(N, n_patches, coords, nullptr, true, nullptr);
+  if (direct && !lat.lattice) return -2;
+  std::vector<int> slot_of(n_patches);
+  for (int s = 0; s < n_patches; ++s) slot_of[lat.order[s]] = s;
+  std::vector<uint8_t> touched((size_t)lat.nti * lat.ntj, 0);  // direct mode: which lattice tiles of the output have been initialised
   for (int p = 0; p < n_patches; ++p) {
     const cf* kf = reinterpret_cast<const cf*>(kfull) + (size_t)p * N * N;
     for (int t = 0; t < T; ++t)
@@ -107,18 +113,14 @@ static int emu2_apply_t(int n_patches, const int32_t* coords, int H, int W, int 
     for (int t = 0; t < T; ++t) stage1h<C, 1, true>(t, R(t), tw.data());
     if (!direct) {
       for (int t = 0; t < T; ++t) store_patch2<C>(t, R(t), ov, ov, 0, pr, pc, win.data(), nullptr, add, load4, load1, pstore4, pstore1);
-    } else if (direct == 2) {  // the plane of the patch's lattice parity (the caller passes a lattice with corners at multiples of N/2)
-      const int half = N / 2, plane = 2 * (((pr + 8 * N) / half) & 1) + (((pc + 8 * N) / half) & 1);
+    } else if (direct == 2) {  // the plane of the patch's colour
+      const int plane = lat.desc[slot_of[p]].colour;
       for (int t = 0; t < T; ++t) store_patch2<C>(t, R(t), pv, pv, plane, pr, pc, win.data(), nullptr, add, load4, load1, pstore4, pstore1);
     } else {
-      // direct stores, sequential: the first patch over a tile stores, later ones accumulate (the flags' job on the GPU);
-      // tiles are indexed from the first patch corner (the caller passes a lattice)
-      const int half = N / 2, r0 = coords[0] - 4 * N, c0 = coords[1] - 4 * N, ntj = (W + 8 * N) / half + 2;
-      if (touched.empty()) touched.assign((size_t)((H + 8 * N) / half + 2) * ntj, 0);
+      // direct stores, sequential: the first patch over a tile stores, later ones accumulate (the flags' job on the GPU)
       uint32_t qw[4];
       for (int q = 0; q < 4; ++q) {
-        const int ti = (pr - r0) / half + (q >> 1), tj = (pc - c0) / half + (q & 1);
-        uint8_t& seen = touched[(size_t)ti * ntj + tj];
+        uint8_t& seen = touched[quad_tile(lat.quads[slot_of[p]].q[q])];
         qw[q] = quad_word(QUAD_DIRECT, 0, 0) | (seen ? QUAD_ACC : 0u);
         seen = 1;
       }

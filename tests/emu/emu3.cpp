@@ -1,4 +1,4 @@
-// CPU lane emulator for rpsf_core3.hpp + rpsf_plan3.hpp (test infrastructure, never shipped in the product path).
+// CPU lane emulator for rpsf_core3.hpp + rpsf_plan3.hpp + rpsf_lattice.hpp (test infrastructure, never shipped in the product path).
 // Runs the per-lane phases of the third-generation (sweep) kernel lane by lane, with a phase boundary wherever the wave
 // exchanges data through LDS, over the very job lists the library builds - so the index algebra (transposes, packed-K
 // format, ring addressing, store / add / flush rules, dependency lists) is checked against the oracle without a GPU.
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../regularizepsf_amd/csrc/rpsf_core3.hpp"
+#include "../../regularizepsf_amd/csrc/rpsf_lattice.hpp"
 #include "../../regularizepsf_amd/csrc/rpsf_plan3.hpp"
 
 using namespace rpsf;
@@ -19,23 +20,12 @@ template <class C>
 static int emu3_apply_t(int n_patches, const int32_t* coords, int Himg, int Wimg, int pad_mode, float pad_value, const float* img,
                         const float* kfull, float* out, int target_regions, unsigned order_seed, int aligned, int64_t* stats) {
   constexpr int N = C::N, H = C::H;
-  // ---- lattice (as setup_lattice in rpsf.hip) ----
-  int r0 = coords[0], c0 = coords[1], r1 = r0, c1 = c0;
-  for (int i = 0; i < n_patches; ++i) {
-    r0 = std::min(r0, coords[2 * i]), r1 = std::max(r1, coords[2 * i]);
-    c0 = std::min(c0, coords[2 * i + 1]), c1 = std::max(c1, coords[2 * i + 1]);
-  }
-  const int nli = (r1 - r0) / H + 1, nlj = (c1 - c0) / H + 1;
-  if ((long)nli * nlj != n_patches) return -2;
-  std::vector<int32_t> cell((size_t)nli * nlj, -1);
-  for (int i = 0; i < n_patches; ++i) {
-    if ((coords[2 * i] - r0) % H || (coords[2 * i + 1] - c0) % H) return -2;
-    cell[(size_t)((coords[2 * i] - r0) / H) * nlj + (coords[2 * i + 1] - c0) / H] = i;
-  }
-  for (int32_t x : cell)
-    if (x < 0) return -2;
+  // ---- lattice: the library's own (rpsf_lattice.hpp); the sweep kernel needs every cell filled ----
+  const LatticeTables lat = lattice_build(N, n_patches, coords, nullptr, false, nullptr);
+  const int r0 = lat.r0, c0 = lat.c0, nli = lat.nti - 1, nlj = lat.ntj - 1;
+  if (!lat.lattice || (long)nli * nlj != n_patches) return -2;
   Plan3 plan;
-  if (!plan3_build(N, C::KSMAX, C::WAVES, nli, nlj, cell.data(), 0, target_regions, plan)) return -3;
+  if (!plan3_build(N, C::KSMAX, C::WAVES, nli, nlj, lat.cell.data(), lat.par_j, target_regions, plan)) return -3;
   if (stats) stats[0] = (int64_t)plan.regions.size(), stats[1] = (int64_t)plan.jobs.size(), stats[2] = plan.patch_slots, stats[3] = plan.ks;
   // ---- packed K ----
   std::vector<float> k3((size_t)n_patches * C::K_FLOATS);

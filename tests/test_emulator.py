@@ -51,11 +51,12 @@ def test_emulated_kernel_matches_reference_golden(emu, case):
 EMU2_SRC = ROOT / "tests" / "emu" / "emu2.cpp"
 EMU2_LIB = ROOT / "tests" / "emu" / "libemu2.so"
 CORE2 = ROOT / "regularizepsf_amd" / "csrc" / "rpsf_core2.hpp"
+LATTICE = ROOT / "regularizepsf_amd" / "csrc" / "rpsf_lattice.hpp"
 
 
 @pytest.fixture(scope="module")
 def emu2():
-    if not EMU2_LIB.exists() or EMU2_LIB.stat().st_mtime < max(EMU2_SRC.stat().st_mtime, CORE.stat().st_mtime, CORE2.stat().st_mtime):
+    if not EMU2_LIB.exists() or EMU2_LIB.stat().st_mtime < max(EMU2_SRC.stat().st_mtime, CORE.stat().st_mtime, CORE2.stat().st_mtime, LATTICE.stat().st_mtime):
         clang = "/opt/rocm/lib/llvm/bin/clang++"
         if not pathlib.Path(clang).exists():
             clang = shutil.which("clang++")
@@ -148,7 +149,7 @@ def test_slot_table_keeps_the_gid_indexed_exchange_free_of_bank_conflicts(emu2, 
 # ---- third generation (N = 16, 32, 64): the sweep kernel's per-lane phases and its job lists ----------------------------------
 EMU3_SRC = ROOT / "tests" / "emu" / "emu3.cpp"
 EMU3_LIB = ROOT / "tests" / "emu" / "libemu3.so"
-CORE3 = [ROOT / "regularizepsf_amd" / "csrc" / n for n in ("rpsf_core.hpp", "rpsf_core3.hpp", "rpsf_plan3.hpp")]
+CORE3 = [ROOT / "regularizepsf_amd" / "csrc" / n for n in ("rpsf_core.hpp", "rpsf_core3.hpp", "rpsf_plan3.hpp", "rpsf_lattice.hpp")]
 
 
 @pytest.fixture(scope="module")
