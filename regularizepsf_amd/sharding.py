@@ -124,6 +124,10 @@ def make_band_plans(coordinates, patch_size: int, height: int, world: int, pad_m
     first = [int(lattice_rows[cuts[g]]) for g in range(world)]
     last = [int(lattice_rows[cuts[g + 1] - 1]) for g in range(world)]
     own0 = [0] + [min(max(first[g], 0), height) for g in range(1, world)] + [height]
+    if any(own0[g + 1] <= own0[g] for g in range(world)):
+        # (a covering's first lattice row lies at -N/2: a band of that row alone ends where the image begins)
+        msg = "a band would own no output rows; use fewer ranks"
+        raise ValueError(msg)
     plans = []
     if seam == "recompute":
         for g in range(world):
