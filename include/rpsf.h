@@ -331,6 +331,56 @@ int rpsf_apply_batch_device(rpsf_plan* plan, const void* images_dev, void* outs_
 int rpsf_apply_batch_device_timed(rpsf_plan* plan, const void* images_dev, void* outs_dev, int n_frames,
                                   size_t image_stride, size_t out_stride, const rpsf_geometry* geom, int iters,
                                   float* total_ms, float* kernel_ms);
+/* DEVICE-ARRAY VIEWS: what regularizepsf_amd.DeviceArray - or any object with __cuda_array_interface__ - hands to apply and apply_batch
+ * (the reference takes NumPy arrays only, transform.py:85-117; this is the device-resident counterpart of its np.asarray / astype).
+ * A view is rows x cols elements of `dtype` in ordinary device memory of the plan's device, element (r, c) at
+ * data + r * row_stride + c * col_stride BYTES.  Strides are positive; a pointer or a stride that is no multiple of the item size is
+ * served, byte by byte.  An OUTPUT view is float32, float64 or float16.  Bad arguments (null view, null data of a non-empty view, a
+ * non-positive stride, rows or cols < 0, an unknown dtype, an output dtype outside the three) return RPSF_E_BADARG and write nothing; an
+ * empty view (rows or cols == 0) returns RPSF_OK and does nothing. */
+#define RPSF_DTYPE_FLOAT32 0
+#define RPSF_DTYPE_FLOAT64 1
+#define RPSF_DTYPE_FLOAT16 2
+#define RPSF_DTYPE_UINT8 3
+#define RPSF_DTYPE_INT16 4
+#define RPSF_DTYPE_UINT16 5
+#define RPSF_DTYPE_INT32 6
+typedef struct rpsf_view {
+  void* data;
+  int dtype;
+  int rows, cols;
+  int64_t row_stride, col_stride; /* bytes */
+} rpsf_view;
+/* What an apply did with its views, a bit set: */
+#define RPSF_ROUTE_C1 1        /* the input went through conversion kernel C1 (gather and convert to a dense float32 frame) */
+#define RPSF_ROUTE_C2 2        /* the output went through conversion kernel C2 (convert and scatter from a dense float32 frame) */
+#define RPSF_ROUTE_SATURATED 4 /* the saturation route ran (rpsf_apply_device_saturated / rpsf_apply_batch_device_saturated) */
+#define RPSF_ROUTE_STAGED 8    /* a batch: the frames were gathered into the plan's staging stack */
+/* ZERO COPY: a side is taken as it is - no kernel added, no byte copied, the view goes straight into rpsf_apply_device (a stack of such
+ * planes with one frame stride that is a multiple of 4 bytes into rpsf_apply_batch_device) - when it is float32 with col_stride == 4, a
+ * row_stride that is a positive multiple of 4, at least 4 * cols and at most INT_MAX floats, and a 4-byte aligned pointer: what
+ * rpsf_geometry's ld_image / ld_out promise.  Every other side goes through C1 / C2 (csrc/convert.hip) and a dense float32 frame in
+ * STAGING owned by the plan: 4 B per pixel (rounded up to 4 pixels per frame) per frame of the call for each side that needs it, allocated
+ * at the first such call, grown when a larger call arrives, freed with the plan.  The saturation entry points take dense frames, so on
+ * that route a pitched float32 side is staged as well.
+ * rpsf_view_route: *route = the RPSF_ROUTE_C1 / _C2 bits a plain (threshold = +inf) single-frame apply of these views sets; pure, no GPU. */
+int rpsf_view_route(const rpsf_view* image, const rpsf_view* out, int* route);
+/* C1 or C2 alone on `device`, asynchronous on `stream` (NULL: the null stream): dst a dense float32 view (row_stride == 4 * cols) -> C1 from
+ * any src; else src a dense float32 view and dst float32 / float64 / float16 -> C2; anything else, or two shapes: RPSF_E_BADARG. */
+int rpsf_convert_view(int device, const rpsf_view* src, const rpsf_view* dst, void* stream);
+/* ArrayPSFTransform.apply on views (whole-image geometry): threshold == +inf is rpsf_apply_device's correction (pad_value: constant mode),
+ * anything else rpsf_apply_device_saturated's route with its preconditions (dilation >= 1, neighborhood_width / 2 >= 1) and its one wait.
+ * Integers convert as (float)(double)v, float64 by the C cast, float16 output rounds to nearest even.  image and out have one shape.
+ * Everything is enqueued on `stream` (NULL: the plan's own); a call on another stream than the last one that used the staging waits
+ * for that one on the device.  *route_or_null receives the RPSF_ROUTE_* bits. */
+int rpsf_apply_view(rpsf_plan* plan, const rpsf_view* image, const rpsf_view* out, int pad_mode, float pad_value, double threshold,
+                    int dilation, int neighborhood_width, void* stream, int* route_or_null);
+/* The same for n_frames frames of one shape, images[f] -> outs[f], with the shared-K batch launch (rpsf_apply_batch_device /
+ * rpsf_apply_batch_device_saturated): frame by frame the bits of rpsf_apply_view.  A side whose views are zero copy (saturation: dense),
+ * of one row stride and evenly spaced by a positive multiple of 4 bytes is taken as it is; any other side is gathered into / scattered
+ * from one staging stack (RPSF_ROUTE_STAGED with RPSF_ROUTE_C1 for the input).  n_frames == 0: RPSF_OK; < 0: RPSF_E_BADARG. */
+int rpsf_apply_batch_view(rpsf_plan* plan, const rpsf_view* images, const rpsf_view* outs, int n_frames, int pad_mode, float pad_value,
+                          double threshold, int dilation, int neighborhood_width, void* stream, int* route_or_null);
 /* The plan's own stream (hipStream_t), for callers that enqueue follow-up work such as the seam exchange. */
 void* rpsf_plan_stream(rpsf_plan* plan);
 
@@ -481,6 +531,9 @@ void* rpsf_comm_stream(rpsf_comm* comm);
 int rpsf_comm_ranks(rpsf_comm* comm, int* ranks);
 /* Make `waiter` (a hipStream_t) wait for everything enqueued on `signaller` so far. */
 int rpsf_stream_wait(int device, void* waiter, void* signaller);
+/* Block the calling thread until everything enqueued on `stream` (a hipStream_t of `device`) has finished: what DeviceArray.to_host waits
+ * with for the one stream its array was last written on, instead of for the whole device. */
+int rpsf_stream_synchronize(int device, void* stream);
 /* Events (hipEvent_t without timing) for dependencies that span steps: record on one stream now, make another stream wait for
  * it later (the sharded step's double-buffered seam rows). */
 int rpsf_event_create(int device, void** event);

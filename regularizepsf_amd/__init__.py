@@ -25,6 +25,7 @@ from regularizepsf_amd.functional import (
 )
 from regularizepsf_amd._native import pinned_empty
 from regularizepsf_amd.builder import ArrayPSFBuilder
+from regularizepsf_amd.device_array import DeviceArray, device_empty, to_device
 from regularizepsf_amd.psf import ArrayPSF
 from regularizepsf_amd.stars import find_stars
 from regularizepsf_amd.transform import ArrayPSFTransform
@@ -36,6 +37,7 @@ __all__ = [
     "ArrayPSF",
     "ArrayPSFBuilder",
     "ArrayPSFTransform",
+    "DeviceArray",
     "FunctionParameterMismatchError",
     "IncorrectShapeError",
     "IndexedCube",
@@ -47,10 +49,12 @@ __all__ = [
     "SimpleFunctionalPSF",
     "VariedFunctionalPSF",
     "calculate_covering",
+    "device_empty",
     "elliptical_gaussian",
     "find_stars",
     "moffat",
     "pinned_empty",
     "simple_functional_psf",
+    "to_device",
     "varied_functional_psf",
 ]

@@ -47,7 +47,24 @@ class Geometry(ctypes.Structure):
         return cls(height, width, pad_mode, pad_value, 0, 0, 0, height, width, 0, height, width)
 
 
+class View(ctypes.Structure):
+    """rpsf_view of include/rpsf.h: rows x cols elements of ``dtype`` (DTYPES), byte strides."""
+
+    _fields_ = [("data", c_void_p), ("dtype", c_int), ("rows", c_int), ("cols", c_int),
+                ("row_stride", ctypes.c_int64), ("col_stride", ctypes.c_int64)]
+
+
+#: RPSF_DTYPE_* of include/rpsf.h by NumPy dtype string
+DTYPES = {"<f4": 0, "<f8": 1, "<f2": 2, "|u1": 3, "<i2": 4, "<u2": 5, "<i4": 6}
+ROUTE_C1, ROUTE_C2, ROUTE_SATURATED, ROUTE_STAGED = 1, 2, 4, 8
+
+_VIEW_APPLY = [c_int, c_float, c_double, c_int, c_int, c_void_p, POINTER(c_int)]  # pad_mode ... route_or_null
+
 _PROTOTYPES = {
+    "rpsf_view_route": (c_int, [POINTER(View), POINTER(View), POINTER(c_int)]),
+    "rpsf_convert_view": (c_int, [c_int, POINTER(View), POINTER(View), c_void_p]),
+    "rpsf_apply_view": (c_int, [c_void_p, POINTER(View), POINTER(View), *_VIEW_APPLY]),
+    "rpsf_apply_batch_view": (c_int, [c_void_p, POINTER(View), POINTER(View), c_int, *_VIEW_APPLY]),
     "rpsf_last_error": (c_char_p, []),
     "rpsf_device_count": (c_int, [POINTER(c_int)]),
     "rpsf_device_info": (c_int, [c_int, POINTER(c_int), c_char_p, c_size_t]),
@@ -140,6 +157,7 @@ _PROTOTYPES = {
     "rpsf_comm_stream": (c_void_p, [c_void_p]),
     "rpsf_comm_ranks": (c_int, [c_void_p, POINTER(ctypes.c_int)]),
     "rpsf_stream_wait": (c_int, [c_int, c_void_p, c_void_p]),
+    "rpsf_stream_synchronize": (c_int, [c_int, c_void_p]),
     "rpsf_event_create": (c_int, [c_int, POINTER(c_void_p)]),
     "rpsf_event_record": (c_int, [c_void_p, c_void_p]),
     "rpsf_stream_wait_event": (c_int, [c_void_p, c_void_p]),
@@ -556,6 +574,26 @@ class Plan:
                                                   ctypes.byref(geometry), iters, _ptr(total), _ptr(kern)))
         return total, kern
 
+    def apply_view(self, image: View, out: View, pad_mode: int, threshold: float = float("inf"), dilation: int = 1,
+                   neighborhood_width: int = 7, stream: c_void_p | None = None, pad_value: float = 0.0) -> int:
+        """rpsf_apply_view: device-resident views of any supported dtype and strides in and out; returns the RPSF_ROUTE_* bits."""
+        route = c_int(0)
+        check(lib().rpsf_apply_view(self._handle, ctypes.byref(image), ctypes.byref(out), pad_mode, pad_value, float(threshold), int(dilation),
+                                    int(neighborhood_width), stream, ctypes.byref(route)))
+        return route.value
+
+    def apply_batch_view(self, images, outs, pad_mode: int, threshold: float = float("inf"), dilation: int = 1,
+                         neighborhood_width: int = 7, stream: c_void_p | None = None, pad_value: float = 0.0) -> int:
+        """rpsf_apply_batch_view on two equally long sequences of views (one shape); returns the RPSF_ROUTE_* bits."""
+        n = len(images)
+        if len(outs) != n:
+            msg = "as many out views as image views"
+            raise ValueError(msg)
+        route = c_int(0)
+        check(lib().rpsf_apply_batch_view(self._handle, (View * max(1, n))(*images), (View * max(1, n))(*outs), n, pad_mode, pad_value,
+                                          float(threshold), int(dilation), int(neighborhood_width), stream, ctypes.byref(route)))
+        return route.value
+
     def synchronize(self) -> None:
         check(lib().rpsf_device_synchronize(self.device))
 
@@ -569,6 +607,18 @@ class Plan:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+def view_route(image: View, out: View) -> int:
+    """The RPSF_ROUTE_C1 / _C2 bits a plain apply of these views would set (the zero-copy predicate; needs no GPU)."""
+    route = c_int(-1)
+    check(lib().rpsf_view_route(ctypes.byref(image), ctypes.byref(out), ctypes.byref(route)))
+    return route.value
+
+
+def convert_view(src: View, dst: View, device: int = 0, stream: c_void_p | None = None) -> None:
+    """Kernel C1 (dst a dense float32 view) or C2 (src one) alone, asynchronous on ``stream`` (None: the null stream)."""
+    check(lib().rpsf_convert_view(device, ctypes.byref(src), ctypes.byref(dst), stream))
 
 
 def build_transfer(source_fft: np.ndarray, target_fft: np.ndarray, alpha: float, epsilon: float, device: int = 0) -> np.ndarray:
@@ -717,6 +767,11 @@ def add_rows(accum_ptr: c_void_p, src_ptr: c_void_p, count: int, device: int = 0
 def stream_wait(waiter: c_void_p, signaller: c_void_p, device: int = 0) -> None:
     """Work enqueued on ``waiter`` from now on starts after everything enqueued on ``signaller`` so far."""
     check(lib().rpsf_stream_wait(device, waiter, signaller))
+
+
+def stream_synchronize(stream: c_void_p, device: int = 0) -> None:
+    """Wait on the host for everything enqueued on ``stream`` so far."""
+    check(lib().rpsf_stream_synchronize(device, stream))
 
 
 def cu_masks(compute_units: int, carve: int, layout: str | None = None) -> tuple[np.ndarray, np.ndarray]:

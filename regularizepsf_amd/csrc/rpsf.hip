@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -40,6 +41,8 @@
 #include "rpsf_lattice.hpp"
 #include "rpsf_saturation.hpp"
 #include "rpsf_core_saturation_batch.hpp"
+#include "rpsf_convert.hpp"
+#include "rpsf_core_convert.hpp"
 
 RPSF_PLANS_V1(RPSF_DECL_V1)
 RPSF_PLANS_V2(RPSF_DECL_V2)
@@ -271,6 +274,13 @@ struct rpsf_plan : PlanStream {
   int host_bands_opt = -1, stream_group_opt = 0, stream_depth_opt = 0;  // rpsf_plan_set_option; -1 / 0: the library decides
   int sat_group_opt = 0;            // RPSF_OPT_SAT_GROUP: frames per frame-group of the batched device saturation route (0: by the scratch budget)
   int sat_batch_info[4] = {};       // rpsf_saturation_batch_info
+  // rpsf_apply_view / rpsf_apply_batch_view: dense float32 staging of the sides that are not zero copy (4 B per pixel per frame of the call and side,
+  // frames rounded up to 4 pixels; made at the first such call, grown on demand), and the end of the last call that used it
+  DevBuf<float> d_view_in, d_view_out;
+  size_t view_in_floats = 0, view_out_floats = 0;
+  hipEvent_t ev_view = nullptr;
+  hipStream_t view_stream = nullptr;
+  bool view_busy = false;
   int last_host_bands = 0;  // row bands the last single host frame was cut into (rpsf_plan_host_bands)
   hipStream_t last_stream = nullptr;
   bool busy_valid = false;
@@ -289,6 +299,7 @@ struct rpsf_plan : PlanStream {
   ~rpsf_plan() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
+    if (ev_view) (void)hipEventDestroy(ev_view);
     bands.clear();
   }
 };
@@ -2577,6 +2588,125 @@ extern "C" int rpsf_apply_frames_host_saturated_device(rpsf_plan* p, const void*
   return sweep_check(p);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Device-array views (include/rpsf.h, rpsf_view): a side that is what rpsf_geometry describes goes into the launch as it is, any other
+// through the plan's staging and kernel C1 / C2 (csrc/convert.hip; predicate and checks: csrc/rpsf_core_convert.hpp)
+// ------------------------------------------------------------------------------------------------
+// One side of a call: `n` views of one shape.  direct: every view zero copy (dense, for the saturation route), one row stride, evenly
+// spaced by a positive multiple of 4 bytes that holds a frame.  uniform: one dtype, one pair of strides, evenly spaced - one C1 / C2 launch.
+struct ViewSide {
+  bool direct = true, uniform = true;
+  int64_t frame_bytes = 0;
+};
+static ViewSide view_side(const rpsf_view* v, int n, bool need_dense) {
+  ViewSide s;
+  s.frame_bytes = n > 1 ? static_cast<char*>(v[1].data) - static_cast<char*>(v[0].data) : 0;
+  for (int f = 0; f < n; ++f) {
+    if (!(need_dense ? rpsfconv::dense_f32(v[f]) : rpsfconv::zero_copy(v[f]))) s.direct = false;
+    if (v[f].dtype != v[0].dtype || v[f].row_stride != v[0].row_stride || v[f].col_stride != v[0].col_stride ||
+        static_cast<char*>(v[f].data) - static_cast<char*>(v[0].data) != (int64_t)f * s.frame_bytes)
+      s.direct = s.uniform = false;
+  }
+  if (n > 1 && (s.frame_bytes <= 0 || s.frame_bytes % 4 || s.frame_bytes < (int64_t)(v[0].rows - 1) * v[0].row_stride + 4 * (int64_t)v[0].cols))
+    s.direct = false;
+  return s;
+}
+
+static int view_staging(DevBuf<float>& buf, size_t& cap, size_t floats) {
+  if (floats <= cap) return RPSF_OK;
+  HIP_TRY(hipDeviceSynchronize());  // earlier calls, on whatever stream, may still use the old staging
+  cap = 0;
+  HIP_TRY(buf.alloc(floats));
+  cap = floats;
+  return RPSF_OK;
+}
+
+static int apply_views(rpsf_plan* p, const rpsf_view* images, const rpsf_view* outs, int n, int pad_mode, float pad_value, double threshold, int dilation,
+                       int neighborhood_width, void* stream, int* route_or_null, bool batch) {
+  if (route_or_null) *route_or_null = 0;
+  if (!p) return fail(RPSF_E_BADARG, "null plan");
+  if (n < 0) return fail(RPSF_E_BADARG, "n_frames must not be negative");
+  if (n == 0) return RPSF_OK;
+  if (!images || !outs) return fail(RPSF_E_BADARG, "null argument");
+  bool empty = false;
+  for (int f = 0; f < n; ++f) {
+    bool e_in, e_out;
+    if (const char* why = rpsfconv::view_problem(images + f, false, &e_in)) return fail(RPSF_E_BADARG, std::string("image: ") + why);
+    if (const char* why = rpsfconv::view_problem(outs + f, true, &e_out)) return fail(RPSF_E_BADARG, std::string("out: ") + why);
+    if (images[f].rows != images[0].rows || images[f].cols != images[0].cols || outs[f].rows != images[0].rows || outs[f].cols != images[0].cols)
+      return fail(RPSF_E_BADARG, "every image and every out view must have one shape");
+    empty = e_in;
+  }
+  if (empty) return RPSF_OK;
+  if (pad_mode < 0 || pad_mode > RPSF_PAD_WRAP) return fail(RPSF_E_BADARG, "unknown pad mode");
+  if (!p->have_k) return fail(RPSF_E_STATE, "no transfer kernel installed (call rpsf_plan_set_transfer first)");
+  const int H = images[0].rows, W = images[0].cols;
+  const bool saturated = !(threshold == std::numeric_limits<double>::infinity());
+  const ViewSide in = view_side(images, n, saturated), out = view_side(outs, n, saturated);
+  rpsf_geometry g{H, W, pad_mode, pad_value, 0, 0, 0, H, in.direct ? (int)(images[0].row_stride / 4) : W, 0, H, out.direct ? (int)(outs[0].row_stride / 4) : W};
+  SatDeviceRun run;
+  int rc;
+  if (saturated) {
+    if (dilation < 1 || neighborhood_width < 0) return fail(RPSF_E_BADARG, "dilation must be >= 1 and the neighbourhood width >= 0 (other values: the NumPy route)");
+    rc = sat_device_init(p, H, W, pad_mode, threshold, dilation, neighborhood_width, &run);
+  } else {
+    rc = check_geometry(p, &g);
+  }
+  if (rc != RPSF_OK) return rc;
+  HIP_TRY(hipSetDevice(p->device));
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : p->stream;
+  const size_t npix = (size_t)H * W, stage_stride = (npix + 3) / 4 * 4;  // (every staged frame starts on 16 bytes)
+  const bool staged = !in.direct || !out.direct;
+  if (!in.direct && (rc = view_staging(p->d_view_in, p->view_in_floats, stage_stride * n)) != RPSF_OK) return rc;
+  if (!out.direct && (rc = view_staging(p->d_view_out, p->view_out_floats, stage_stride * n)) != RPSF_OK) return rc;
+  if (staged) {  // the staging serves one call at a time: a call on another stream waits, on the device, for the last one that used it
+    if (!p->ev_view) HIP_TRY(hipEventCreateWithFlags(&p->ev_view, hipEventDisableTiming));
+    if (p->view_busy && st != p->view_stream) HIP_TRY(hipStreamWaitEvent(st, p->ev_view, 0));
+  }
+  const float* d_in = static_cast<const float*>(images[0].data);
+  float* d_out = static_cast<float*>(outs[0].data);
+  size_t in_stride = (size_t)(in.frame_bytes / 4), out_stride = (size_t)(out.frame_bytes / 4);
+  if (!in.direct) {
+    if (in.uniform) rc = rpsf_conv_gather(images[0], n, in.frame_bytes, p->d_view_in, (int64_t)stage_stride, st);
+    for (int f = 0; !in.uniform && f < n && rc == RPSF_OK; ++f) rc = rpsf_conv_gather(images[f], 1, 0, p->d_view_in + f * stage_stride, 0, st);
+    if (rc != RPSF_OK) return rc;
+    d_in = p->d_view_in, in_stride = stage_stride;
+  }
+  if (!out.direct) d_out = p->d_view_out, out_stride = stage_stride;
+  if (!saturated) {
+    rc = launch_batch(p, d_in, d_out, n, in_stride, out_stride, g, st);
+  } else {
+    const int G = batch ? sat_group_frames(p, run) : 1;
+    SatBatchStats stats;
+    stats.frames = n;
+    for (int f0 = 0; f0 < n && rc == RPSF_OK; f0 += G)
+      rc = sat_device_apply_group(p, run, std::min(G, n - f0), d_in + (size_t)f0 * in_stride, in_stride, d_out + (size_t)f0 * out_stride, out_stride,
+                                  batch ? rpsfsatb::ORDER_LONGEST_FIRST : rpsfsatb::ORDER_FRAMES, st, &stats, nullptr);
+    if (batch && rc == RPSF_OK) stats.store(p);
+  }
+  if (rc == RPSF_OK && !out.direct) {
+    if (out.uniform) rc = rpsf_conv_scatter(p->d_view_out, (int64_t)stage_stride, outs[0], n, out.frame_bytes, st);
+    for (int f = 0; !out.uniform && f < n && rc == RPSF_OK; ++f) rc = rpsf_conv_scatter(p->d_view_out + f * stage_stride, 0, outs[f], 1, 0, st);
+  }
+  if (staged) {
+    HIP_TRY(hipEventRecord(p->ev_view, st));
+    p->view_stream = st, p->view_busy = true;
+  }
+  if (rc == RPSF_OK && route_or_null)
+    *route_or_null = (in.direct ? 0 : RPSF_ROUTE_C1 | (batch ? RPSF_ROUTE_STAGED : 0)) | (out.direct ? 0 : RPSF_ROUTE_C2) | (saturated ? RPSF_ROUTE_SATURATED : 0);
+  return rc;
+}
+
+extern "C" int rpsf_apply_view(rpsf_plan* p, const rpsf_view* image, const rpsf_view* out, int pad_mode, float pad_value, double threshold, int dilation,
+                               int neighborhood_width, void* stream, int* route_or_null) {
+  return apply_views(p, image, out, 1, pad_mode, pad_value, threshold, dilation, neighborhood_width, stream, route_or_null, false);
+}
+
+extern "C" int rpsf_apply_batch_view(rpsf_plan* p, const rpsf_view* images, const rpsf_view* outs, int n_frames, int pad_mode, float pad_value,
+                                     double threshold, int dilation, int neighborhood_width, void* stream, int* route_or_null) {
+  return apply_views(p, images, outs, n_frames, pad_mode, pad_value, threshold, dilation, neighborhood_width, stream, route_or_null, true);
+}
+
 extern "C" int rpsf_saturation_kernel_ms(rpsf_plan* p, double ms[5]) {
   if (!p || !ms) return fail(RPSF_E_BADARG, "null argument");
   for (int i = 0; i < 5; ++i) ms[i] = 0.0;
@@ -3111,6 +3241,12 @@ extern "C" int rpsf_stream_wait(int device, void* waiter, void* signaller) {
   if (e == hipSuccess) e = hipStreamWaitEvent(reinterpret_cast<hipStream_t>(waiter), ev, 0);
   (void)hipEventDestroy(ev);  // released once the recorded work has completed
   if (e != hipSuccess) return fail(RPSF_E_HIP, hipGetErrorString(e));
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stream_synchronize(int device, void* stream) {
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
   return RPSF_OK;
 }
 

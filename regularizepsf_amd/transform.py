@@ -17,7 +17,7 @@ import weakref
 
 import numpy as np
 
-from regularizepsf_amd import _native
+from regularizepsf_amd import _native, device_array
 from regularizepsf_amd.exceptions import InvalidCoordinateError
 from regularizepsf_amd.util import IndexedCube
 
@@ -71,6 +71,7 @@ class ArrayPSFTransform:
         self._plan: _native.Plan | None = None
         self._plan_stamp: tuple | None = None
         self._corner_bounds: tuple | None = None
+        self.last_route = 0  # RPSF_ROUTE_* bits of the last apply / apply_batch on device arrays (include/rpsf.h)
         # one device plan (staging buffers, colour planes, one stream) per transform: calls from several threads take turns
         self._lock = threading.RLock()
 
@@ -280,7 +281,7 @@ class ArrayPSFTransform:
     # ------------------------------------------------------------------ apply (transform.py:85-177)
     def apply(self, image: np.ndarray, workers: int | None = None, pad_mode: str = "symmetric",
               saturation_threshold: float = math.inf, saturation_dilation: int = 1,
-              neighborhood_width: int = 7, *, out: np.ndarray | None = None) -> np.ndarray:
+              neighborhood_width: int = 7, *, out: np.ndarray | None = None, stream=None) -> np.ndarray:
         """Apply the transform to an image and return the corrected image (float64, same shape).
 
         Parameters follow the reference: ``pad_mode`` is any ``np.pad`` mode; pixels brighter than
@@ -291,8 +292,33 @@ class ArrayPSFTransform:
         ``out`` (keyword only, not in the reference): a C-contiguous float64 or float32 array of the image's shape to write the result
         into and return - a caller's loop that reuses one result array spares every call the first touch of two megabytes of fresh pages
         per 512 x 512 frame, which costs anything between 10 and 200 us on a busy host (`scripts/notebook_factors.py`).
+
+        DEVICE FRAMES (not in the reference): ``image`` may be a :class:`~regularizepsf_amd.DeviceArray`, or any object with
+        ``__cuda_array_interface__``, on the transform's device - float32, float64, float16, uint8, int16, uint16 or int32, at any
+        positive strides.  The result is then a ``DeviceArray`` and nothing crosses PCIe.  ITS DTYPE IS ``out``'s IF ``out`` IS GIVEN, ELSE
+        FLOAT32 - not the float64 of the host route: the kernels compute in float32, and widening a resident frame would only double its
+        bytes.  ``out`` may be a float32, float64 or float16 device array (or protocol object) of the image's shape at any positive strides;
+        it is returned itself when it is a ``DeviceArray``, wrapped in one otherwise.  A float32 side whose rows are contiguous
+        (any row pitch, any offset) is read or written in place; every other side goes through a conversion kernel and staging owned by
+        the plan.  Integer and float64 frames enter as ``(float)(double)v``, so the result is that of the host route on
+        ``image.astype(np.float32)``.  A finite ``saturation_threshold`` runs the saturation kernels on the device whatever
+        ``saturation=`` says.
+        ``stream=None`` is the safe mode: the call waits for the device before it launches (whoever produced ``image`` is unknown) and for
+        its own stream before it returns.  ``stream=`` an integer stream handle, or an object with a ``cuda_stream`` attribute, is the
+        asynchronous mode: everything is enqueued on that stream, behind the stream the input says it was last written on (an event),
+        the call does not wait on the host (the saturation route does once, for its counts) and the result carries the stream until
+        ``to_host`` has waited for it.
+        What the device routes do not cover comes down, runs the host route above and goes back up, cast to the result dtype:
+        ``np.pad`` modes the kernels do not evaluate (anything but constant, symmetric, reflect, edge, wrap) and the corner cases of the
+        saturation arguments (a threshold that is not finite, ``saturation_dilation < 1`` or not integral, ``neighborhood_width // 2 < 1``).
         """
         del workers
+        if device_array.is_device_array(image):
+            with self._lock:
+                return self._apply_device_locked(image, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, out, stream)
+        if stream is not None:
+            msg = "stream= goes with device arrays; a NumPy frame is corrected when the call returns"
+            raise ValueError(msg)
         with self._lock:
             result = self._apply_locked(image, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, out)
         if out is not None and result is not out:  # (the branches that build their result on the host)
@@ -353,6 +379,111 @@ class ArrayPSFTransform:
         corrected[mask] = raw[mask]
         return corrected[2 * n : height + 2 * n, 2 * n : width + 2 * n]
 
+    # ------------------------------------------------------------------ device frames
+    def _device_route(self, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width) -> bool:
+        """Whether rpsf_apply_view / rpsf_apply_batch_view cover these arguments (else: down, the host route, up)."""
+        if pad_mode not in _native.PAD_MODES or not isinstance(saturation_threshold, numbers.Real):
+            return False
+        if saturation_threshold == math.inf:
+            return True
+        return (math.isfinite(saturation_threshold) and isinstance(saturation_dilation, numbers.Integral) and saturation_dilation >= 1
+                and isinstance(neighborhood_width, numbers.Integral) and neighborhood_width // 2 >= 1)
+
+    def _enter_stream(self, stream, inputs, outputs):
+        """Order a device call behind what is pending on its arrays; returns (handle or None, c_void_p or None)."""
+        handle = device_array.stream_handle(stream)
+        if handle is None:  # the safe mode: nobody knows what produced the input, or on which stream
+            _native.check(_native.lib().rpsf_device_synchronize(self._device))
+            for a in (*inputs, *outputs):
+                a._pending.stream = None
+            return None, None
+        s = _native.c_void_p(handle)
+        for pending in {a._pending.stream for a in (*inputs, *outputs)} - {None, handle}:
+            _native.stream_wait(s, _native.c_void_p(pending), self._device)
+        return handle, s
+
+    def _leave_stream(self, plan, handle, outputs) -> None:
+        if handle is None:
+            _native.stream_synchronize(plan.stream, self._device)
+        for a in outputs:
+            a._pending.stream = handle
+
+    def _device_out(self, out, shape, dtype) -> "device_array.DeviceArray":
+        if out is None:
+            return device_array.device_empty(shape, dtype, self._device)
+        out = device_array.as_device_array(out, self._device, writeable=True, what="out")
+        if out.dtype not in device_array.RESULT_DTYPES:
+            msg = f"out must be float32, float64 or float16, got {out.dtype}"
+            raise ValueError(msg)
+        if out.shape != tuple(shape):
+            msg = "out must have the image's shape"
+            raise ValueError(msg)
+        return out
+
+    def _apply_device_locked(self, image, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, out, stream):
+        image = device_array.as_device_array(image, self._device)
+        if image.ndim != 2:
+            msg = f"image must be two dimensional, got shape {image.shape}"
+            raise ValueError(msg)
+        if len(self) == 0:
+            msg = "need at least one array to stack"
+            raise ValueError(msg)
+        n = self._checked_patch_size()
+        plan = self._device_plan()
+        self._check_corners(n, *image.shape)
+        result = self._device_out(out, image.shape, np.float32)
+        if not self._device_route(pad_mode, saturation_threshold, saturation_dilation, neighborhood_width):
+            host = self._apply_locked(image.to_host(), pad_mode, saturation_threshold, saturation_dilation, neighborhood_width)
+            result._assign(host.astype(result.dtype))
+            return result
+        handle, s = self._enter_stream(stream, (image,), (result,))
+        self.last_route = plan.apply_view(image._view2d(), result._view2d(), _native.PAD_MODES[pad_mode], saturation_threshold,
+                                          saturation_dilation, neighborhood_width, s)
+        self._leave_stream(plan, handle, (result,))
+        return result
+
+    def _apply_batch_device_locked(self, images, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, dtype, out, stream):
+        if device_array.is_device_array(images):
+            stack = device_array.as_device_array(images, self._device, what="images")
+            if stack.ndim != 3:
+                msg = f"images must have shape (frames, H, W), got {stack.shape}"
+                raise ValueError(msg)
+            frames, shape = [stack[i] for i in range(stack.shape[0])], stack.shape[1:]
+        else:
+            frames = [device_array.as_device_array(im, self._device, what="images") for im in images]
+            shape = frames[0].shape if frames else (0, 0)
+            if any(f.ndim != 2 or f.shape != shape for f in frames):
+                msg = "images must be a sequence of two dimensional arrays of one shape"
+                raise ValueError(msg)
+        dtype = np.dtype(dtype)
+        if out is not None:
+            out = device_array.as_device_array(out, self._device, writeable=True, what="out")
+            dtype = out.dtype
+            if out.shape != (len(frames), *shape):
+                msg = "out must have shape (frames, H, W)"
+                raise ValueError(msg)
+        covered = (dtype in device_array.RESULT_DTYPES and len(frames) > 0
+                   and self._device_route(pad_mode, saturation_threshold, saturation_dilation, neighborhood_width))
+        if not covered:  # down, the host route, up: the host route's result, whatever it is for these arguments
+            host = self._apply_batch_locked([f.to_host() for f in frames], None, pad_mode, saturation_threshold, saturation_dilation,
+                                            neighborhood_width, dtype if dtype in device_array.RESULT_DTYPES else np.float64, None)
+            if out is None:
+                return device_array.to_device(host.astype(dtype if dtype in device_array.DTYPES else np.float64, copy=False), self._device)
+            out._assign(host)
+            return out
+        if len(self) == 0:
+            msg = "need at least one array to stack"
+            raise ValueError(msg)
+        n = self._checked_patch_size()
+        plan = self._device_plan()
+        self._check_corners(n, *shape)
+        result = out if out is not None else device_array.device_empty((len(frames), *shape), dtype, self._device)
+        handle, s = self._enter_stream(stream, frames, (result,))
+        self.last_route = plan.apply_batch_view([f._view2d() for f in frames], [result[i]._view2d() for i in range(len(frames))],
+                                                _native.PAD_MODES[pad_mode], saturation_threshold, saturation_dilation, neighborhood_width, s)
+        self._leave_stream(plan, handle, (result,))
+        return result
+
     def _apply_prepadded(self, padded: np.ndarray, shift: int) -> np.ndarray:
         """Run K1 on an image the host already padded by ``shift`` on every side (constant mode, shifted corners)."""
         plan = self._device_plan()
@@ -374,20 +505,38 @@ class ArrayPSFTransform:
 
     def apply_batch(self, images, workers: int | None = None, pad_mode: str = "symmetric",
                     saturation_threshold: float = math.inf, saturation_dilation: int = 1,
-                    neighborhood_width: int = 7, dtype: type = np.float64, out: np.ndarray | None = None) -> np.ndarray:
+                    neighborhood_width: int = 7, dtype: type = np.float64, out: np.ndarray | None = None, stream=None) -> np.ndarray:
         """Apply the transform to a stack ``(frames, H, W)`` or a sequence of equally shaped images; returns a stack.
 
         Equivalent to ``np.stack([self.apply(im, ...) for im in images])`` - the loop a user of the reference writes
         (docs/source/example.ipynb over transform.py:85-177) - and bit-identical to it, but streamed: while one group
         of frames is corrected, the next one crosses PCIe to the device and the previous one comes back and is widened to
         float64, on three streams and a persistent pool of host threads (``rpsf_apply_frames_host``).  Frames that already
-        live on the GPU should use ``_native.Plan.apply_batch_device``.  ``dtype`` is the result dtype (the reference
+        live on the GPU are passed as they are: a 3-D :class:`~regularizepsf_amd.DeviceArray` (or object with
+        ``__cuda_array_interface__``) or a sequence of 2-D ones, with ``out=`` a 3-D one and ``stream=`` as in :meth:`apply`; the result is
+        a ``DeviceArray`` of ``dtype`` (float32, float64 or float16 on the device routes) and each frame has the bits of :meth:`apply` on it.
+        Mixing host and device frames in one sequence raises ``ValueError``.  ``dtype`` is the result dtype (the reference
         returns float64; ``np.float32`` skips the widening); ``out`` an existing C-contiguous stack to fill.
         With a finite ``saturation_threshold`` and ``saturation="device"``, float32 / float64 frames go through the batched device route
         (``rpsf_apply_frames_host_saturated_device``: the frames of a frame-group share the launches of kernels F1 - F3, the host waits for
         the device once and one launch fills every frame's groups), again bit-identical to the loop.
         Extension of the reference API - there is no ``apply_batch`` upstream.
         """
+        on_device = device_array.is_device_array(images)
+        if not on_device and not isinstance(images, np.ndarray):
+            images = list(images)
+            kinds = {device_array.is_device_array(im) for im in images}
+            if len(kinds) == 2:
+                msg = "images mixes host and device frames"
+                raise ValueError(msg)
+            on_device = kinds == {True}
+        if on_device:
+            with self._lock:
+                return self._apply_batch_device_locked(images, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width,
+                                                       dtype, out, stream)
+        if stream is not None:
+            msg = "stream= goes with device arrays; NumPy frames are corrected when the call returns"
+            raise ValueError(msg)
         with self._lock:
             return self._apply_batch_locked(images, workers, pad_mode, saturation_threshold, saturation_dilation,
                                             neighborhood_width, dtype, out)
