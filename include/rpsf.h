@@ -465,6 +465,31 @@ int rpsf_builder_model(rpsf_builder* builder, int method, double percentile, int
 /* Device time of the last B3 launch, milliseconds. */
 int rpsf_builder_clean_ms(const rpsf_builder* builder, double* ms);
 
+/* interpolation_scale = s of the reference builder.  _scale_image (image_processing.py:49-59), kernels U1 / U2: the
+ * height x width frame (float32 or float64, not narrowed before the solve; both at least 4, else RPSF_E_BADARG - the cubic spline needs
+ * four points) resampled with the not-a-knot interpolating cubic spline - RectBivariateSpline's defaults on integer knots - one pass per
+ * axis, float64 throughout, onto (1 + (height - 1) s) x (1 + (width - 1) s) samples; sample [i s][j s] is pixel [i][j] itself.
+ * scale >= 1, scale == 1 copies.  out_f64_host: the scaled frame, float64.  Two runs of one input agree bit for bit. */
+int rpsf_scale_image(int device, const void* image_host, int image_is_f64, int height, int width, int scale, double* out_f64_host);
+/* Device time of the calling thread's last upscale, milliseconds (either pointer may be NULL, not both): U1, the axis-0 pass, and U2, the
+ * axis-1 pass with its two transposes. */
+int rpsf_scale_kernel_ms(double* u1_ms, double* u2_ms);
+/* A builder for interpolation_scale = scale: its stack holds P x P patches, P = patch_size * scale (B1 and B2 run at P), its cells and
+ * its model are patch_size x patch_size (B3 runs at patch_size).  patch_size or P outside 4..128: RPSF_E_UNSUPPORTED; scale < 1:
+ * RPSF_E_BADARG; scale == 1 is rpsf_builder_create.  On such a builder rpsf_builder_patches and rpsf_builder_load_patches move P x P
+ * patches, rpsf_builder_average delivers patch_size x patch_size cells (B2, then the block mean B4), rpsf_builder_model the same cells
+ * cleaned (B2, B4, B3), and rpsf_builder_clean takes patch_size x patch_size cells. */
+int rpsf_builder_create_scaled(rpsf_builder** out, int device, int patch_size, int scale, size_t capacity);
+/* rpsf_builder_add_frame for the UNSCALED frame of a scaled builder (`scale` must be the builder's): the frame is uploaded as it is,
+ * upscaled on the device as by rpsf_scale_image, rounded to float32 once into the buffer B1 reads, and B1 runs with the scaled height
+ * and width - no scaled frame crosses PCIe.  corners_i32 and frac_f64 are in scaled-frame pixels, computed with P. */
+int rpsf_builder_add_frame_scaled(rpsf_builder* builder, const void* image_host, int image_is_f64, int height, int width, int scale,
+                                  int n_stars, const int32_t* corners_i32, const double* frac_f64, double saturation_threshold,
+                                  double star_minimum, double star_maximum, uint8_t* accepted_u8_host);
+/* downscale_local_mean (builder.py:234-235), kernel B4 alone: n_cells (> 0) cells of P x P float64 the caller supplies -> cells of
+ * patch_size x patch_size, each pixel the sum of its scale x scale block in row-major order, in float64, divided by scale * scale. */
+int rpsf_builder_downscale(rpsf_builder* builder, int n_cells, const double* cells_f64_host, double* out_f64_host);
+
 /* find_stars: star positions for the builder, upstream of the star list.  The detector is this library's own, modelled on
  * sep.Background + sep.extract WITHOUT deblending; it is not sep and its positions differ from sep's for blended or extended sources.
  * A finder is made for one frame shape and one background box (8 .. 128 pixels, anything else: RPSF_E_UNSUPPORTED; frames of up to

@@ -24,7 +24,7 @@ from regularizepsf_amd.functional import (
     varied_functional_psf,
 )
 from regularizepsf_amd._native import pinned_empty
-from regularizepsf_amd.builder import ArrayPSFBuilder
+from regularizepsf_amd.builder import ArrayPSFBuilder, scale_image
 from regularizepsf_amd.device_array import DeviceArray, device_empty, to_device
 from regularizepsf_amd.psf import ArrayPSF
 from regularizepsf_amd.stars import find_stars
@@ -54,6 +54,7 @@ __all__ = [
     "find_stars",
     "moffat",
     "pinned_empty",
+    "scale_image",
     "simple_functional_psf",
     "to_device",
     "varied_functional_psf",

@@ -135,6 +135,12 @@ _PROTOTYPES = {
     "rpsf_builder_clean": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "rpsf_builder_model": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rpsf_builder_clean_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rpsf_scale_image": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "rpsf_scale_kernel_ms": (c_int, [POINTER(c_double), POINTER(c_double)]),
+    "rpsf_builder_create_scaled": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_size_t]),
+    "rpsf_builder_add_frame_scaled": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double,
+                                              c_double, c_void_p]),
+    "rpsf_builder_downscale": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "rpsf_stars_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int]),
     "rpsf_stars_destroy": (None, [c_void_p]),
     "rpsf_stars_background": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

@@ -6,7 +6,9 @@ patch onto the pixel grid, subtract a background plane, test) and per lattice ce
 The host keeps what is bookkeeping: the rounded corners and shift amounts (Python's half-to-even ``round``) and the cell
 membership of every patch.  The final per-cell clean-up (builder.py:231-260) is ``clean_cell`` here, a few ``scipy.ndimage``
 calls per cell, or with ``ArrayPSFBuilder(..., cleanup="device")`` a third kernel, which leaves to ``clean_cell`` only the cells whose
-background fit it flags as degenerate.
+background fit it flags as degenerate.  ``interpolation_scale`` (image_processing.py:49-59, builder.py:225-235) is opt-in with
+``ArrayPSFBuilder(..., interpolation="device")``: every frame is upscaled on the device (``scale_image`` is the same resampling as a
+function of its own), the patches are cut at ``N * s`` pixels and every averaged cell is brought back to ``N x N`` by a block mean.
 
 The boundary of the feature is the star list: ``build(..., stars=[...])`` takes the ``(row, col)`` positions ``sep.extract``
 returns; without it ``sep`` is imported and called as the reference calls it.
@@ -28,6 +30,8 @@ AVERAGE_METHODS = {"mean": 0, "median": 1, "percentile": 2}
 REJECTED, ACCEPTED, DEGENERATE_RING = 0, 1, 2
 CLEANED, DEGENERATE_CELL = 0, 1  # flags of a cell after the device clean-up
 CLEANUPS = ("host", "device")
+INTERPOLATIONS = ("off", "device")
+MAX_PATCH = 128  # the largest patch the kernels cut: psf_size * interpolation_scale may not exceed it
 
 
 def _frames(images) -> list[np.ndarray]:
@@ -82,6 +86,54 @@ def _find_stars(frame: np.ndarray, star_threshold: float, star_mask) -> np.ndarr
     except Exception:  # noqa: BLE001  (the reference treats any failure as "no stars")
         return np.zeros((0, 2))
     return np.stack([np.asarray(found["y"], np.float64), np.asarray(found["x"], np.float64)], axis=-1)
+
+
+def _scale(interpolation_scale) -> int:
+    """``interpolation_scale`` as a Python int: an integer (of any integer type, or a float that is one) of at least 1."""
+    try:
+        scale = int(interpolation_scale)
+        ok = scale == interpolation_scale and scale >= 1 and not isinstance(interpolation_scale, bool)
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        msg = f"interpolation_scale must be an integer of at least 1, not {interpolation_scale!r}"
+        raise ValueError(msg)
+    return scale
+
+
+def scaled_shape(shape: tuple[int, int], interpolation_scale: int) -> tuple[int, int]:
+    """The shape ``_scale_image`` gives a frame (image_processing.py:53-58)."""
+    return 1 + (shape[0] - 1) * interpolation_scale, 1 + (shape[1] - 1) * interpolation_scale
+
+
+def _scale_frame(frame: np.ndarray, scale: int, device: int) -> np.ndarray:
+    from regularizepsf_amd import _native as n
+
+    if min(frame.shape) < 4:
+        msg = f"interpolation_scale needs frames of at least 4 x 4 pixels (the cubic spline takes four points), not {frame.shape}"
+        raise ValueError(msg)
+    if frame.dtype != np.float32:
+        frame = frame.astype(np.float64, copy=False)
+    frame = np.ascontiguousarray(frame)
+    out = np.empty(scaled_shape(frame.shape, scale), np.float64)
+    n.check(n.lib().rpsf_scale_image(device, n._ptr(frame), int(frame.dtype == np.float64), frame.shape[0], frame.shape[1], scale, n._ptr(out)))
+    return out
+
+
+def scale_image(images, interpolation_scale: int, *, device: int = 0):
+    """``_scale_image`` of the reference (image_processing.py:49-59) on the GPU: every frame resampled with the interpolating cubic
+    spline ``RectBivariateSpline(arange(H), arange(W), frame)`` onto ``1 + (H - 1) s`` by ``1 + (W - 1) s`` samples, in float64.
+
+    ``images`` is one 2-D frame, a 3-D stack or a list of frames; the result has the same form and is float64 (float32 frames are
+    widened exactly, anything else is taken as float64).  ``find_stars(scale_image(frames, s))`` gives the ``stars=`` of
+    ``ArrayPSFBuilder(..., interpolation="device").build(frames, interpolation_scale=s)``: positions in scaled-frame pixels.
+    """
+    scale = _scale(interpolation_scale)
+    frames = _frames(images)
+    out = [_scale_frame(frame, scale, device) for frame in frames]
+    if isinstance(images, np.ndarray):
+        return out[0] if images.ndim == 2 else np.stack(out)
+    return out
 
 
 def star_geometry(positions: np.ndarray, psf_size: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -175,12 +227,19 @@ def model_on_device(stack, method: str, percentile: float, offsets: np.ndarray, 
 class _Stack:
     """A native builder handle: the device stack of accepted float32 patches."""
 
-    def __init__(self, psf_size: int, device: int, capacity: int) -> None:
+    def __init__(self, psf_size: int, device: int, capacity: int, scale: int = 1) -> None:
+        """``scale`` > 1: a scaled builder - ``add_frame`` takes the unscaled frame and upscales it on the device, the stack holds
+        patches of ``patch_size = psf_size * scale``, the cells of ``average`` and ``model`` are ``psf_size`` wide."""
         from regularizepsf_amd import _native
 
-        self._native, self.psf_size = _native, int(psf_size)
+        self._native, self.psf_size, self.scale = _native, int(psf_size), int(scale)
+        self.patch_size = self.psf_size * self.scale
         self._handle = ctypes.c_void_p()
-        _native.check(_native.lib().rpsf_builder_create(ctypes.byref(self._handle), device, self.psf_size, max(1, int(capacity))))
+        if self.scale == 1:
+            _native.check(_native.lib().rpsf_builder_create(ctypes.byref(self._handle), device, self.psf_size, max(1, int(capacity))))
+        else:
+            _native.check(_native.lib().rpsf_builder_create_scaled(ctypes.byref(self._handle), device, self.psf_size, self.scale,
+                                                                   max(1, int(capacity))))
 
     def add_frame(self, frame: np.ndarray, rounded: np.ndarray, shift: np.ndarray, saturation_threshold: float, star_minimum: float,
                   star_maximum: float) -> np.ndarray:
@@ -191,13 +250,19 @@ class _Stack:
         corners = np.ascontiguousarray(rounded, np.int32).reshape(-1, 2)
         frac = np.ascontiguousarray(shift, np.float64).reshape(-1, 2)
         flags = np.zeros(len(corners), np.uint8)
-        n.check(n.lib().rpsf_builder_add_frame(self._handle, n._ptr(frame), int(frame.dtype == np.float64), frame.shape[0], frame.shape[1],
-                                               len(corners), n._ptr(corners), n._ptr(frac), float(saturation_threshold),
-                                               float(star_minimum), float(star_maximum), n._ptr(flags)))
+        if self.scale == 1:
+            n.check(n.lib().rpsf_builder_add_frame(self._handle, n._ptr(frame), int(frame.dtype == np.float64), frame.shape[0],
+                                                   frame.shape[1], len(corners), n._ptr(corners), n._ptr(frac),
+                                                   float(saturation_threshold), float(star_minimum), float(star_maximum), n._ptr(flags)))
+        else:
+            n.check(n.lib().rpsf_builder_add_frame_scaled(self._handle, n._ptr(frame), int(frame.dtype == np.float64), frame.shape[0],
+                                                          frame.shape[1], self.scale, len(corners), n._ptr(corners), n._ptr(frac),
+                                                          float(saturation_threshold), float(star_minimum), float(star_maximum),
+                                                          n._ptr(flags)))
         return flags
 
     def load(self, patches: np.ndarray) -> None:
-        p = np.ascontiguousarray(patches, np.float32).reshape(-1, self.psf_size, self.psf_size)
+        p = np.ascontiguousarray(patches, np.float32).reshape(-1, self.patch_size, self.patch_size)
         self._native.check(self._native.lib().rpsf_builder_load_patches(self._handle, len(p), self._native._ptr(p)))
 
     def __len__(self) -> int:
@@ -207,7 +272,7 @@ class _Stack:
 
     def patches(self, first: int = 0, count: int | None = None) -> np.ndarray:
         count = len(self) - first if count is None else count
-        out = np.empty((count, self.psf_size, self.psf_size), np.float32)
+        out = np.empty((count, self.patch_size, self.patch_size), np.float32)
         self._native.check(self._native.lib().rpsf_builder_patches(self._handle, first, count, self._native._ptr(out)))
         return out
 
@@ -219,6 +284,14 @@ class _Stack:
         n.check(n.lib().rpsf_builder_average(self._handle, AVERAGE_METHODS[method], float(percentile), len(offsets) - 1, n._ptr(offsets),
                                              n._ptr(members), n._ptr(cells)))
         return cells
+
+    def downscale(self, cells: np.ndarray) -> np.ndarray:
+        """Kernel B4 alone on float64 cells of ``patch_size``: their block means, cells of ``psf_size``."""
+        n = self._native
+        cells = np.ascontiguousarray(cells, np.float64).reshape(-1, self.patch_size, self.patch_size)
+        out = np.empty((len(cells), self.psf_size, self.psf_size), np.float64)
+        n.check(n.lib().rpsf_builder_downscale(self._handle, len(cells), n._ptr(cells), n._ptr(out)))
+        return out
 
     def clean(self, cells: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
         """Kernel B3 alone on float64 cells of the builder's size: (cleaned cells, flags).  A cell flagged DEGENERATE_CELL comes
@@ -268,13 +341,21 @@ class _Stack:
 class ArrayPSFBuilder:
     """A builder that takes a series of images and constructs an ArrayPSF to represent their implicit PSF."""
 
-    def __init__(self, psf_size: int, device: int = 0, *, cleanup: str = "host") -> None:
-        """``cleanup`` says where ``build`` runs the per-cell clean-up: ``"host"`` is ``clean_cell`` on every cell, ``"device"`` the
+    def __init__(self, psf_size: int, device: int = 0, *, interpolation: str = "off", cleanup: str = "host") -> None:
+        """``interpolation`` says what ``build`` does with ``interpolation_scale != 1``: ``"off"`` refuses it, ``"device"`` upscales
+        every frame on the GPU, cuts the patches at ``psf_size * interpolation_scale`` pixels and block-averages every cell back to
+        ``psf_size`` before the clean-up, as the reference does.  With ``interpolation_scale == 1`` the two settings are the same build.
+
+        ``cleanup`` says where ``build`` runs the per-cell clean-up: ``"host"`` is ``clean_cell`` on every cell, ``"device"`` the
         third kernel, with ``clean_cell`` only on the cells it flags (a degenerate background fit) - the same model within 1e-12.
         It is an argument of the builder and not of ``build``, whose parameter list stays the reference's plus ``stars``."""
         if cleanup not in CLEANUPS:
             msg = f"cleanup must be one of {CLEANUPS}, not {cleanup!r}"
             raise ValueError(msg)
+        if interpolation not in INTERPOLATIONS:
+            msg = f"interpolation must be one of {INTERPOLATIONS}, not {interpolation!r}"
+            raise ValueError(msg)
+        self._interpolation = interpolation
         self._psf_size = psf_size
         self._device = device
         self._cleanup = cleanup
@@ -286,6 +367,10 @@ class ArrayPSFBuilder:
     @property
     def cleanup(self) -> str:
         return self._cleanup
+
+    @property
+    def interpolation(self) -> str:
+        return self._interpolation
 
     def build(self, images, sep_mask=None, hdu_choice: int | None = 0, num_workers: int | None = None,  # noqa: ARG002
               interpolation_scale: int = 1, star_threshold: int = 3, average_method: str = "median", percentile: float = 50,
@@ -299,10 +384,21 @@ class ArrayPSFBuilder:
         ``(row, col)`` star positions per frame - the ``y``, ``x`` columns of ``sep.extract`` - which skips star finding.
         ``patches`` maps ``(frame, row - N / 2, col - N / 2)`` to the float64 copy of the float32 patch kept on the device
         (background-subtracted, not normalised); ``counts`` maps every corner of the covering to its number of stars.
+
+        ``interpolation_scale = s > 1`` needs ``ArrayPSFBuilder(..., interpolation="device")``.  Then ``stars`` are positions in the
+        SCALED frame (what ``sep.extract`` returns on it: ``find_stars(scale_image(frames, s))``), the patches are ``N s`` wide with
+        keys ``(frame, row - N s / 2, col - N s / 2)``, and the covering is the reference's: cells of ``N s`` pixels over
+        ``(Hs s, Ws s)`` with ``Hs = 1 + (H - 1) s`` (builder.py:225 multiplies the shape that is already scaled once more).
         """
         size = self._psf_size
-        if interpolation_scale != 1:
-            msg = "interpolation_scale != 1 is not implemented (the reference resamples with scikit-image, which this package does not depend on)"
+        scale = _scale(interpolation_scale)
+        if scale != 1 and self._interpolation == "off":
+            msg = ('interpolation_scale != 1 is opt-in: construct the builder with ArrayPSFBuilder(..., interpolation="device") to resample '
+                   "the frames on the GPU")
+            raise NotImplementedError(msg)
+        patch = size * scale  # the size patches are cut, shifted and averaged at
+        if scale != 1 and patch > MAX_PATCH:
+            msg = f"psf_size * interpolation_scale = {patch} is not implemented: the patch kernels stop at {MAX_PATCH} pixels"
             raise NotImplementedError(msg)
         if image_mask is not None:
             msg = "image_mask is not implemented (the reference spline-shifts the boolean mask; what that yields is defined by SciPy's cast only)"
@@ -315,31 +411,40 @@ class ArrayPSFBuilder:
             raise PSFBuilderError(msg)
         cleanup = self._cleanup
         frames = _frames(images)
+        if scale != 1 and min(frames[0].shape) < 4:
+            msg = f"interpolation_scale needs frames of at least 4 x 4 pixels (the cubic spline takes four points), not {frames[0].shape}"
+            raise ValueError(msg)
         if stars is None:
             masks = [None] * len(frames) if sep_mask is None else _frames(sep_mask)
-            stars = [_find_stars(frame, star_threshold, mask) for frame, mask in zip(frames, masks)]
+            seen = frames if scale == 1 else [_scale_frame(frame, scale, self._device) for frame in frames]  # sep sees the scaled frame
+            stars = [_find_stars(frame, star_threshold, mask) for frame, mask in zip(seen, masks)]
         elif len(stars) != len(frames):
             msg = f"stars has {len(stars)} entries for {len(frames)} frames"
             raise ValueError(msg)
 
-        stack = _Stack(size, self._device, sum(len(np.asarray(s).reshape(-1, 2)) for s in stars))
+        capacity = sum(len(np.asarray(s).reshape(-1, 2)) for s in stars)
+        stack = _Stack(size, self._device, capacity) if scale == 1 else _Stack(size, self._device, capacity, scale)
         try:
             keys: dict[tuple[int, float, float], int] = {}  # patch key -> index into the device stack, in insertion order
             for i, (frame, positions) in enumerate(zip(frames, stars)):
-                corner, rounded, shift = star_geometry(positions, size)
+                corner, rounded, shift = star_geometry(positions, patch)
                 # equal keys of one frame: dict.update keeps the first position and the last value - the same patch either way
                 _, first = np.unique(corner, axis=0, return_index=True)
                 first.sort()
                 flags = stack.add_frame(frame, rounded[first], shift[first], saturation_threshold, star_minimum, star_maximum)
                 if np.any(flags == DEGENERATE_RING):
-                    bad = corner[first][flags == DEGENERATE_RING][0] + size / 2
+                    bad = corner[first][flags == DEGENERATE_RING][0] + patch / 2
                     msg = (f"Frame {i}: the patch of the star at {tuple(float(v) for v in bad)} has fewer than three border pixels below "
                            "its centre (or all on one line), so no background plane can be fitted.")
                     raise PSFBuilderError(msg)
                 for row, col in corner[first][flags == ACCEPTED].tolist():
                     keys[(i, row, col)] = len(keys)
-            corners = calculate_covering(frames[0].shape, size)
-            offsets, members = cell_membership(np.array([k[1:] for k in keys], np.float64).reshape(-1, 2), corners, size)
+            if scale == 1:
+                corners = calculate_covering(frames[0].shape, size)
+            else:  # builder.py:225-227 as it stands: the scaled shape times the scale
+                scaled = scaled_shape(frames[0].shape, scale)
+                corners = calculate_covering((scaled[0] * scale, scaled[1] * scale), patch)
+            offsets, members = cell_membership(np.array([k[1:] for k in keys], np.float64).reshape(-1, 2), corners, patch)
             method = "median" if (average_method == "percentile" and percentile == 50) else average_method
             if cleanup == "device":
                 cleaned = model_on_device(stack, method, percentile, offsets, members)

@@ -8,6 +8,8 @@
 //   B3  builder_clean_kernel    one workgroup per averaged cell, the driver of rpsf_core_cleanup.hpp: the cell's values in registers,
 //                               byte masks and union-find parents in LDS (N = 128: 96 KiB); writes the cleaned float64 cell and one
 //                               flag byte.
+//   A scaled builder (rpsf_builder_create_scaled, interpolation_scale = s of the reference) runs B1 and B2 at P = N s on frames that
+//   csrc/scale.hip upscales on the device, brings every averaged P x P cell back to N x N with its kernel B4, and runs B3 at N.
 //
 // INVARIANT: every patch in the stack is finite and has a non-zero centre.  B1 accepts nothing else (a zero or non-finite
 // pixel, or a value outside float32, rejects the patch), rpsf_builder_load_patches refuses anything else - so every sample
@@ -25,6 +27,7 @@
 
 #include "rpsf_core_builder.hpp"
 #include "rpsf_core_cleanup.hpp"
+#include "rpsf_scale.hpp"
 #include "rpsf_side_unit.hpp"
 
 using namespace rpsfb;
@@ -103,7 +106,10 @@ __global__ __launch_bounds__(THREADS) void builder_clean_kernel(int N, const dou
 }
 
 struct rpsf_builder {
-  int device = 0, N = 0;
+  int device = 0, N = 0;  // N: the size of the patches in the stack (B1, B2)
+  int model = 0, scale = 1;  // model: the size of a cell of the model (B3); N = model * scale
+  rpsf_scale_scratch* upscale = nullptr;
+  Buf<double> small;  // scaled builder: the averaged cells after B4, model x model
   size_t count = 0;
   float* stack = nullptr;
   size_t capacity = 0;
@@ -116,6 +122,7 @@ struct rpsf_builder {
   double patch_ms = 0, average_ms = 0, clean_ms = 0;
   ~rpsf_builder() {
     if (stack) (void)hipFree(stack);
+    rpsf_detail_scale_scratch_free(upscale);
     for (auto e : ev)
       if (e) (void)hipEventDestroy(e);
   }
@@ -148,24 +155,33 @@ static int elapsed(rpsf_builder* b, double* ms) {
   return RPSF_OK;
 }
 
-extern "C" int rpsf_builder_create(rpsf_builder** out, int device, int patch_size, size_t capacity) {
+// B1 and B2 at patch_size * scale, B3 at patch_size
+static int create(rpsf_builder** out, int device, int patch_size, int scale, size_t capacity) {
   if (!out) return fail(RPSF_E_BADARG, "null argument");
   if (patch_size < MIN_N || patch_size > MAX_N)
     return fail(RPSF_E_UNSUPPORTED, "builder patch size " + std::to_string(patch_size) + " is outside 4..128");
+  if (scale < 1) return fail(RPSF_E_BADARG, "scale must be at least 1");
+  if (scale > MAX_N / patch_size)
+    return fail(RPSF_E_UNSUPPORTED, "builder patch size " + std::to_string(patch_size) + " times scale " + std::to_string(scale) +
+                                        " is outside 4..128");
+  const int P = patch_size * scale;
   HIP_TRY(hipSetDevice(device));
   rpsf_builder* b = new rpsf_builder;
-  b->device = device, b->N = patch_size;
+  b->device = device, b->N = P, b->model = patch_size, b->scale = scale;
   auto made = [&]() -> int {
     for (auto& e : b->ev) HIP_TRY(hipEventCreate(&e));
-    if (patch_size > 64) {
+    if (scale > 1) b->upscale = rpsf_detail_scale_scratch_new();
+    // the two kernels take their sizes apart on a scaled builder: B1's LDS follows P, B3's the model's size
+    if (P > 64) {
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&builder_patch_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds_bytes(MAX_N)));
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&builder_clean_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)rpsfc::lds_bytes(MAX_N)));
     } else {
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&builder_patch_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds_bytes(64)));
     }
+    if (patch_size > 64)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&builder_clean_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)rpsfc::lds_bytes(MAX_N)));
     return grow_stack(b, capacity ? capacity : 1);
   }();
   if (made != RPSF_OK) {
@@ -176,11 +192,35 @@ extern "C" int rpsf_builder_create(rpsf_builder** out, int device, int patch_siz
   return RPSF_OK;
 }
 
+extern "C" int rpsf_builder_create(rpsf_builder** out, int device, int patch_size, size_t capacity) {
+  return create(out, device, patch_size, 1, capacity);
+}
+
+extern "C" int rpsf_builder_create_scaled(rpsf_builder** out, int device, int patch_size, int scale, size_t capacity) {
+  return create(out, device, patch_size, scale, capacity);
+}
+
 extern "C" void rpsf_builder_destroy(rpsf_builder* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   delete b;
 }
+
+// the star list of a frame of height x width, checked before anything is uploaded
+static int check_stars(const rpsf_builder* b, int height, int width, int n_stars, const int32_t* corners_i32, const double* frac_f64) {
+  const int N = b->N;
+  for (int i = 0; i < 2 * n_stars; ++i) {
+    // the reference's corner is round(position - N / 2) of a position inside the frame; anything within one frame of it is gathered
+    // through the mirror map, anything farther is a caller's mistake
+    const long limit = i % 2 ? width : height;
+    if (corners_i32[i] < -N - limit || corners_i32[i] > 2 * limit) return fail(RPSF_E_BADARG, "a star's corner lies far outside the frame");
+    if (!(std::fabs(frac_f64[i]) <= 2.0)) return fail(RPSF_E_BADARG, "a shift amount is not within two pixels");
+  }
+  return RPSF_OK;
+}
+
+static int patches_of_frame(rpsf_builder* b, int height, int width, int n_stars, const int32_t* corners_i32, const double* frac_f64,
+                            double saturation_threshold, double star_minimum, double star_maximum, uint8_t* accepted_u8_host);
 
 extern "C" int rpsf_builder_add_frame(rpsf_builder* b, const void* image_host, int image_is_f64, int height, int width, int n_stars,
                                       const int32_t* corners_i32, const double* frac_f64, double saturation_threshold,
@@ -190,15 +230,8 @@ extern "C" int rpsf_builder_add_frame(rpsf_builder* b, const void* image_host, i
   if (n_stars < 0) return fail(RPSF_E_BADARG, "n_stars is negative");
   if (n_stars == 0) return RPSF_OK;
   if (!corners_i32 || !frac_f64 || !accepted_u8_host) return fail(RPSF_E_BADARG, "null argument");
-  const int N = b->N;
-  const size_t npix = (size_t)N * N, fpix = (size_t)height * width;
-  for (int i = 0; i < 2 * n_stars; ++i) {
-    // the reference's corner is round(position - N / 2) of a position inside the frame; anything within one frame of it is gathered
-    // through the mirror map, anything farther is a caller's mistake
-    const long limit = i % 2 ? width : height;
-    if (corners_i32[i] < -N - limit || corners_i32[i] > 2 * limit) return fail(RPSF_E_BADARG, "a star's corner lies far outside the frame");
-    if (!(std::fabs(frac_f64[i]) <= 2.0)) return fail(RPSF_E_BADARG, "a shift amount is not within two pixels");
-  }
+  if (const int rc = check_stars(b, height, width, n_stars, corners_i32, frac_f64)) return rc;
+  const size_t fpix = (size_t)height * width;
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(b->frame.reserve(fpix));
   if (image_is_f64) {  // the frame crosses PCIe once, as float32 - what every apply path of the library uploads
@@ -209,6 +242,40 @@ extern "C" int rpsf_builder_add_frame(rpsf_builder* b, const void* image_host, i
   } else {
     HIP_TRY(hipMemcpy(b->frame.p, image_host, fpix * sizeof(float), hipMemcpyHostToDevice));
   }
+  return patches_of_frame(b, height, width, n_stars, corners_i32, frac_f64, saturation_threshold, star_minimum, star_maximum,
+                          accepted_u8_host);
+}
+
+extern "C" int rpsf_builder_add_frame_scaled(rpsf_builder* b, const void* image_host, int image_is_f64, int height, int width, int scale,
+                                             int n_stars, const int32_t* corners_i32, const double* frac_f64,
+                                             double saturation_threshold, double star_minimum, double star_maximum,
+                                             uint8_t* accepted_u8_host) {
+  if (!b || !image_host) return fail(RPSF_E_BADARG, "null argument");
+  if (scale != b->scale) return fail(RPSF_E_BADARG, "scale " + std::to_string(scale) + " is not the builder's " + std::to_string(b->scale));
+  if (scale == 1)
+    return rpsf_builder_add_frame(b, image_host, image_is_f64, height, width, n_stars, corners_i32, frac_f64, saturation_threshold,
+                                  star_minimum, star_maximum, accepted_u8_host);
+  if (height < 4 || width < 4) return fail(RPSF_E_BADARG, "the spline of the upscale needs at least 4 x 4 pixels");
+  if (n_stars < 0) return fail(RPSF_E_BADARG, "n_stars is negative");
+  if (n_stars == 0) return RPSF_OK;
+  if (!corners_i32 || !frac_f64 || !accepted_u8_host) return fail(RPSF_E_BADARG, "null argument");
+  const long hs = 1 + (long)(height - 1) * scale, ws = 1 + (long)(width - 1) * scale;
+  if (hs > (1L << 30) || ws > (1L << 30)) return fail(RPSF_E_UNSUPPORTED, "the scaled frame is too large");
+  if (const int rc = check_stars(b, (int)hs, (int)ws, n_stars, corners_i32, frac_f64)) return rc;
+  HIP_TRY(hipSetDevice(b->device));
+  // the frame crosses PCIe once, unscaled and in its own type; the scaled frame is born in the buffer B1 reads
+  if (const int rc = rpsf_detail_scale_upload(b->upscale, image_host, image_is_f64, height, width)) return rc;
+  HIP_TRY(b->frame.reserve((size_t)hs * ws));
+  if (const int rc = rpsf_detail_scale_run(b->upscale, image_is_f64, height, width, scale, b->frame.p, 1)) return rc;
+  return patches_of_frame(b, (int)hs, (int)ws, n_stars, corners_i32, frac_f64, saturation_threshold, star_minimum, star_maximum,
+                          accepted_u8_host);
+}
+
+// B1 on builder->frame (height x width float32, on the device) and the append of what it accepts
+static int patches_of_frame(rpsf_builder* b, int height, int width, int n_stars, const int32_t* corners_i32, const double* frac_f64,
+                            double saturation_threshold, double star_minimum, double star_maximum, uint8_t* accepted_u8_host) {
+  const int N = b->N;
+  const size_t npix = (size_t)N * N;
   HIP_TRY(b->corners.reserve(2 * (size_t)n_stars));
   HIP_TRY(b->frac.reserve(2 * (size_t)n_stars));
   HIP_TRY(b->flags.reserve(n_stars));
@@ -302,6 +369,26 @@ static int average_on_device(rpsf_builder* b, int method, double percentile, int
                      b->members.p, b->N, method, percentile / 100.0, b->cells.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(b->ev[1], nullptr));
+  if (b->scale > 1) {  // B4: the reference's downscale_local_mean of every averaged cell (builder.py:234-235)
+    HIP_TRY(b->small.reserve((size_t)n_cells * b->model * b->model));
+    if (const int rc = rpsf_detail_downscale(b->cells.p, n_cells, b->model, b->scale, b->small.p)) return rc;
+  }
+  return RPSF_OK;
+}
+
+// the averaged cells at the model's size, on the device: B2's own, or B4's on a scaled builder
+static double* model_cells(rpsf_builder* b) { return b->scale > 1 ? b->small.p : b->cells.p; }
+
+extern "C" int rpsf_builder_downscale(rpsf_builder* b, int n_cells, const double* cells_f64_host, double* out_f64_host) {
+  if (!b || !cells_f64_host || !out_f64_host) return fail(RPSF_E_BADARG, "null argument");
+  if (n_cells <= 0) return fail(RPSF_E_BADARG, "n_cells must be positive");
+  const size_t big = (size_t)n_cells * b->N * b->N, little = (size_t)n_cells * b->model * b->model;
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(b->cells.reserve(big));
+  HIP_TRY(b->small.reserve(little));
+  HIP_TRY(hipMemcpy(b->cells.p, cells_f64_host, big * sizeof(double), hipMemcpyHostToDevice));
+  if (const int rc = rpsf_detail_downscale(b->cells.p, n_cells, b->model, b->scale, b->small.p)) return rc;
+  HIP_TRY(hipMemcpy(out_f64_host, b->small.p, little * sizeof(double), hipMemcpyDeviceToHost));
   return RPSF_OK;
 }
 
@@ -309,22 +396,24 @@ extern "C" int rpsf_builder_average(rpsf_builder* b, int method, double percenti
                                     const int32_t* members_i32, double* cells_f64_host) {
   if (!cells_f64_host) return fail(RPSF_E_BADARG, "null argument");
   if (const int rc = average_on_device(b, method, percentile, n_cells, cell_offsets_i64, members_i32)) return rc;
-  HIP_TRY(hipMemcpy(cells_f64_host, b->cells.p, (size_t)n_cells * b->N * b->N * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(cells_f64_host, model_cells(b), (size_t)n_cells * b->model * b->model * sizeof(double), hipMemcpyDeviceToHost));
   return elapsed(b, &b->average_ms);
 }
 
 // B3 on builder->cells; the cleaned cells and the flags come back in one download each
 static int clean_on_device(rpsf_builder* b, int n_cells, double* out_f64_host, uint8_t* flags_u8_host) {
-  const size_t npix = (size_t)b->N * b->N;
+  const int N = b->model;
+  const size_t npix = (size_t)N * N;
+  const double* cells = model_cells(b);
   HIP_TRY(b->cleaned.reserve((size_t)n_cells * npix));
   HIP_TRY(b->clean_flags.reserve((size_t)n_cells));
   HIP_TRY(hipEventRecord(b->ev[0], nullptr));
-  if (b->N > 64) {
-    hipLaunchKernelGGL(builder_clean_kernel<1024>, dim3(n_cells), dim3(1024), rpsfc::lds_bytes(b->N), nullptr, b->N, b->cells.p,
-                       b->cleaned.p, b->clean_flags.p);
+  if (N > 64) {
+    hipLaunchKernelGGL(builder_clean_kernel<1024>, dim3(n_cells), dim3(1024), rpsfc::lds_bytes(N), nullptr, N, cells, b->cleaned.p,
+                       b->clean_flags.p);
   } else {
-    hipLaunchKernelGGL(builder_clean_kernel<256>, dim3(n_cells), dim3(256), rpsfc::lds_bytes(b->N), nullptr, b->N, b->cells.p,
-                       b->cleaned.p, b->clean_flags.p);
+    hipLaunchKernelGGL(builder_clean_kernel<256>, dim3(n_cells), dim3(256), rpsfc::lds_bytes(N), nullptr, N, cells, b->cleaned.p,
+                       b->clean_flags.p);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(b->ev[1], nullptr));
@@ -337,12 +426,13 @@ extern "C" int rpsf_builder_clean(rpsf_builder* b, int n_cells, const double* ce
                                   uint8_t* flags_u8_host) {
   if (!b || !cells_f64_host || !out_f64_host || !flags_u8_host) return fail(RPSF_E_BADARG, "null argument");
   if (n_cells <= 0) return fail(RPSF_E_BADARG, "n_cells must be positive");
-  const size_t npix = (size_t)b->N * b->N;
+  const size_t npix = (size_t)b->model * b->model;
   for (size_t i = 0; i < (size_t)n_cells * npix; ++i)
     if (!std::isfinite(cells_f64_host[i])) return fail(RPSF_E_BADARG, "cell " + std::to_string(i / npix) + " has a non-finite pixel");
   HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(b->cells.reserve((size_t)n_cells * npix));
-  HIP_TRY(hipMemcpy(b->cells.p, cells_f64_host, (size_t)n_cells * npix * sizeof(double), hipMemcpyHostToDevice));
+  Buf<double>& cells = b->scale > 1 ? b->small : b->cells;
+  HIP_TRY(cells.reserve((size_t)n_cells * npix));
+  HIP_TRY(hipMemcpy(cells.p, cells_f64_host, (size_t)n_cells * npix * sizeof(double), hipMemcpyHostToDevice));
   return clean_on_device(b, n_cells, out_f64_host, flags_u8_host);
 }
 
