@@ -521,6 +521,45 @@ int rpsf_stars_info(const rpsf_stars* finder, int* tile_rows, int* tile_cols);
 /* Device time of the last S1, S2, S3 and S4 launches, milliseconds. */
 int rpsf_stars_kernel_ms(const rpsf_stars* finder, double ms[4]);
 
+/* THE FUSED ROUTE: a frame is uploaded at most once, the stars are found and the builder's patches cut from that one
+ * float32 frame on the device, and the background mesh never leaves the device.  The results are bit for bit those of
+ * rpsf_stars_background, the host filter of the mesh (regularizepsf_amd.stars.filter_mesh), rpsf_stars_detect and rpsf_builder_add_frame.
+ *
+ * Kernel S1b, after S1 and on the device: valid = both raw meshes finite at the node; the invalid nodes take the median of the valid ones
+ * (NumPy's rule), a 3 x 3 median with the indices clamped at the edges runs over both filled meshes, global_rms is the median of the
+ * filtered rms.  No valid node at all sets a flag on the device and the frame has no stars.
+ *
+ * rpsf_stars_background_view: `image` is a device view of the finder's shape on the finder's device (any dtype and strides of rpsf_view;
+ * a dense float32 view is copied device to device, anything else converted by kernel C1) and is only read; the mask is a host array as
+ * for rpsf_stars_background.  Then S1 and S1b; nothing is downloaded.  _host: the same after the one upload of a host frame (float32, or
+ * float64 narrowed once).  _scaled: the UNSCALED height x width host frame is uploaded in its own type, upscaled on the device as by
+ * rpsf_scale_image and rounded to float32 once into the frame buffer of a finder made for the scaled shape
+ * (1 + (height - 1) scale) x (1 + (width - 1) scale) (anything else: RPSF_E_BADARG; scale >= 2); the mask has the scaled shape. */
+int rpsf_stars_background_view(rpsf_stars* finder, const rpsf_view* image, const uint8_t* mask_host_or_null);
+int rpsf_stars_background_host(rpsf_stars* finder, const void* image_host, int image_is_f64, const uint8_t* mask_host_or_null);
+int rpsf_stars_background_scaled(rpsf_stars* finder, const void* image_host, int image_is_f64, int height, int width, int scale,
+                                 const uint8_t* mask_host_or_null);
+/* Kernel S1b alone on raw meshes of the finder's mesh shape that the caller supplies (NaN and infinities mark invalid nodes):
+ * *none = 1 when no node is valid - then *T = +inf and nothing else is written; else the filtered meshes, *global_rms and
+ * *T = threshold * global_rms, the multiply done on the device. */
+int rpsf_stars_filter_mesh(rpsf_stars* finder, const double* level_host, const double* rms_host, double threshold, double* level_out,
+                           double* rms_out, double* global_rms, double* T, int* none);
+/* Kernels S2 - S4 of rpsf_stars_detect on the frame and the filtered mesh a rpsf_stars_background_view / _host / _scaled left on the device,
+ * with T = threshold * global_rms computed and read there; *count = 0 when no box had a usable pixel.  RPSF_E_STATE before such a call.
+ * rpsf_stars_positions delivers the detections as after rpsf_stars_detect. */
+int rpsf_stars_detect_device(rpsf_stars* finder, double threshold, long min_area, long max_area, size_t* count);
+/* The finder's frame on its device: height x width dense float32, valid until the next frame is given to the finder or it is destroyed
+ * (height and width may be NULL).  RPSF_E_STATE before a frame was uploaded. */
+int rpsf_stars_frame(rpsf_stars* finder, const float** frame_dev, int* height, int* width);
+/* Device time of the last S1b, milliseconds. */
+int rpsf_stars_mesh_ms(const rpsf_stars* finder, double* ms);
+/* rpsf_builder_add_frame on a dense float32 frame that is already on the builder's device - a finder's (rpsf_stars_frame) or the caller's
+ * own; it is only read, nothing is uploaded but the star list.  On a scaled builder the frame is the SCALED one and height and width are
+ * its. */
+int rpsf_builder_add_frame_device(rpsf_builder* builder, const float* frame_dev, int height, int width, int n_stars,
+                                  const int32_t* corners_i32, const double* frac_f64, double saturation_threshold, double star_minimum,
+                                  double star_maximum, uint8_t* accepted_u8_host);
+
 /* Host-side helper for the saturation branch of apply (transform.py:135-138): sequential, row-major
  * NaN-ignoring neighbourhood-mean fill of the masked pixels of the float64 padded image (no GPU involved). */
 int rpsf_saturation_fill(double* padded, int rows, int cols, const uint8_t* mask, int neighborhood_width);

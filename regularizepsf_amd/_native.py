@@ -149,6 +149,16 @@ _PROTOTYPES = {
     "rpsf_stars_label": (c_int, [c_void_p, c_void_p, c_void_p]),
     "rpsf_stars_info": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
     "rpsf_stars_kernel_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rpsf_stars_background_view": (c_int, [c_void_p, POINTER(View), c_void_p]),
+    "rpsf_stars_background_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "rpsf_stars_background_scaled": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "rpsf_stars_filter_mesh": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, POINTER(c_double), POINTER(c_double),
+                                       POINTER(c_int)]),
+    "rpsf_stars_detect_device": (c_int, [c_void_p, c_double, ctypes.c_long, ctypes.c_long, POINTER(c_size_t)]),
+    "rpsf_stars_frame": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int)]),
+    "rpsf_stars_mesh_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rpsf_builder_add_frame_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double, c_double,
+                                              c_void_p]),
     "rpsf_saturation_fill": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
     "rpsf_dev_alloc": (c_int, [c_int, c_size_t, POINTER(c_void_p)]),
     "rpsf_dev_free": (c_int, [c_int, c_void_p]),

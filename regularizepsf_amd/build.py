@@ -16,7 +16,7 @@ import sys
 PKG = pathlib.Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 SOURCES = [CSRC / n for n in ("rpsf.hip", "k1_256.hip", "k1_128.hip", "k1_small.hip", "k2_256.hip", "k2_256p.hip", "k2_128.hip", "k2_128p.hip", "k2_128pc.hip", "k2_128pcs.hip", "k3_16.hip", "k3_32.hip", "k3_64.hip", "builder.hip", "stars.hip", "saturation.hip", "convert.hip", "scale.hip")]
-HEADERS = [CSRC / n for n in ("rpsf_core.hpp", "rpsf_core2.hpp", "rpsf_core3.hpp", "rpsf_plan3.hpp", "rpsf_lattice.hpp", "rpsf_kernels.hpp", "rpsf_kernels2.hpp", "rpsf_kernels3.hpp", "rpsf_device.hpp", "rpsf_hostpipe.hpp", "rpsf_core_builder.hpp", "rpsf_core_cleanup.hpp", "rpsf_core_stars.hpp", "rpsf_core_saturation.hpp", "rpsf_core_saturation_batch.hpp", "rpsf_saturation.hpp", "rpsf_side_unit.hpp", "rpsf_convert.hpp", "rpsf_core_convert.hpp", "rpsf_scale.hpp", "rpsf_core_scale.hpp")] + [
+HEADERS = [CSRC / n for n in ("rpsf_core.hpp", "rpsf_core2.hpp", "rpsf_core3.hpp", "rpsf_plan3.hpp", "rpsf_lattice.hpp", "rpsf_kernels.hpp", "rpsf_kernels2.hpp", "rpsf_kernels3.hpp", "rpsf_device.hpp", "rpsf_hostpipe.hpp", "rpsf_core_builder.hpp", "rpsf_core_cleanup.hpp", "rpsf_core_stars.hpp", "rpsf_core_stars_mesh.hpp", "rpsf_core_saturation.hpp", "rpsf_core_saturation_batch.hpp", "rpsf_saturation.hpp", "rpsf_side_unit.hpp", "rpsf_convert.hpp", "rpsf_core_convert.hpp", "rpsf_scale.hpp", "rpsf_core_scale.hpp")] + [
     PKG.parent / "include" / "rpsf.h"]
 TARGET = PKG / "librpsf_hip.so"
 OBJDIR = PKG / "build"

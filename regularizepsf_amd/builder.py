@@ -11,7 +11,9 @@ background fit it flags as degenerate.  ``interpolation_scale`` (image_processin
 function of its own), the patches are cut at ``N * s`` pixels and every averaged cell is brought back to ``N x N`` by a block mean.
 
 The boundary of the feature is the star list: ``build(..., stars=[...])`` takes the ``(row, col)`` positions ``sep.extract``
-returns; without it ``sep`` is imported and called as the reference calls it.
+returns; without it ``sep`` is imported and called as the reference calls it - or, with ``ArrayPSFBuilder(..., finder="device")``,
+this package's own detector (``regularizepsf_amd.stars``) finds them on the fused route of DESIGN.md 3.11: every frame is uploaded at
+most once (not at all when it is a ``DeviceArray``), the stars are found and the patches cut from that one float32 frame on the device.
 """
 
 from __future__ import annotations
@@ -31,6 +33,8 @@ REJECTED, ACCEPTED, DEGENERATE_RING = 0, 1, 2
 CLEANED, DEGENERATE_CELL = 0, 1  # flags of a cell after the device clean-up
 CLEANUPS = ("host", "device")
 INTERPOLATIONS = ("off", "device")
+FINDERS = ("sep", "device")
+FINDER_OPTIONS = {"box": 64, "min_area": 5, "max_area": None}  # find_stars's defaults
 MAX_PATCH = 128  # the largest patch the kernels cut: psf_size * interpolation_scale may not exceed it
 
 
@@ -71,6 +75,77 @@ def _frames(images) -> list[np.ndarray]:
         msg = "No frames to build a PSF model from"
         raise PSFBuilderError(msg)
     return frames
+
+
+def _device_frames(images, device: int) -> list | None:
+    """Frames that live on the GPU as a list of 2-D ``DeviceArray`` s on ``device`` - a 2-D or 3-D ``DeviceArray`` (or object with
+    ``__cuda_array_interface__``) or a list of 2-D ones; None when ``images`` holds no device array at all (``_frames`` takes it then)."""
+    from regularizepsf_amd.device_array import as_device_array, is_device_array
+
+    if is_device_array(images):
+        array = as_device_array(images, device, what="images")
+        if array.ndim == 3:
+            frames = [array[i] for i in range(array.shape[0])]
+        elif array.ndim == 2:
+            frames = [array]
+        else:
+            msg = "Image data array must be 3D"
+            raise IncorrectShapeError(msg)
+    elif isinstance(images, (list, tuple)) and any(is_device_array(f) for f in images):
+        if not all(is_device_array(f) for f in images):
+            msg = "`images` mixes host and device frames: pass all frames as NumPy arrays or all as device arrays"
+            raise TypeError(msg)
+        frames = [as_device_array(f, device, what="images") for f in images]
+    else:
+        return None
+    shape = None
+    for frame in frames:
+        if frame.ndim != 2:
+            msg = "Every frame must be a two-dimensional array"
+            raise IncorrectShapeError(msg)
+        if shape is None:
+            shape = frame.shape
+        elif shape != frame.shape:
+            msg = ("Images must all be the same shape."
+                   f"Found both {shape} and {frame.shape}.")
+            raise PSFBuilderError(msg)
+    if not frames or 0 in shape:
+        msg = "No frames to build a PSF model from"
+        raise PSFBuilderError(msg)
+    return frames
+
+
+def _dense_f32(frame):
+    """A device frame as a dense float32 ``DeviceArray``: itself when it is one, else a copy through kernel C1 (``(float)(double)v`` for
+    integers, the C cast for float64 - what the host route does to the same values)."""
+    from regularizepsf_amd import _native
+    from regularizepsf_amd.device_array import device_empty
+
+    frame.synchronize()  # the builder's launches are on the null stream
+    if frame.dtype == np.float32 and frame.c_contiguous and frame.ptr % 4 == 0:
+        return frame
+    dense = device_empty(frame.shape, np.float32, frame.device)
+    _native.convert_view(frame._view2d(), dense._view2d(), frame.device)
+    return dense
+
+
+def _finder_options(finder: str, options) -> dict:
+    """``finder_options`` of the constructor with find_stars's defaults and range checks."""
+    from regularizepsf_amd.stars import MAX_BOX, MIN_BOX
+
+    if options is None:
+        return dict(FINDER_OPTIONS)
+    if finder != "device":
+        msg = 'finder_options may only be given with finder="device"'
+        raise ValueError(msg)
+    if not isinstance(options, dict) or set(options) - set(FINDER_OPTIONS):
+        msg = f"finder_options is a dict with any of {tuple(FINDER_OPTIONS)}, not {options!r}"
+        raise ValueError(msg)
+    merged = {**FINDER_OPTIONS, **options}
+    if not MIN_BOX <= int(merged["box"]) <= MAX_BOX:
+        msg = f"box must lie in {MIN_BOX} ... {MAX_BOX}, got {merged['box']}"
+        raise ValueError(msg)
+    return merged
 
 
 def _find_stars(frame: np.ndarray, star_threshold: float, star_mask) -> np.ndarray:
@@ -129,6 +204,9 @@ def scale_image(images, interpolation_scale: int, *, device: int = 0):
     ``ArrayPSFBuilder(..., interpolation="device").build(frames, interpolation_scale=s)``: positions in scaled-frame pixels.
     """
     scale = _scale(interpolation_scale)
+    if _device_frames(images, device) is not None:
+        msg = "scale_image takes host frames: resampling device frames is not supported, bring them to the host (to_host)"
+        raise TypeError(msg)
     frames = _frames(images)
     out = [_scale_frame(frame, scale, device) for frame in frames]
     if isinstance(images, np.ndarray):
@@ -261,6 +339,19 @@ class _Stack:
                                                           n._ptr(flags)))
         return flags
 
+    def add_frame_device(self, frame_ptr: int, shape: tuple[int, int], rounded: np.ndarray, shift: np.ndarray, saturation_threshold: float,
+                         star_minimum: float, star_maximum: float) -> np.ndarray:
+        """``add_frame`` on a dense float32 frame of ``shape`` at ``frame_ptr`` on the builder's device (a scaled builder: the scaled
+        frame); nothing but the star list is uploaded."""
+        n = self._native
+        corners = np.ascontiguousarray(rounded, np.int32).reshape(-1, 2)
+        frac = np.ascontiguousarray(shift, np.float64).reshape(-1, 2)
+        flags = np.zeros(len(corners), np.uint8)
+        n.check(n.lib().rpsf_builder_add_frame_device(self._handle, ctypes.c_void_p(frame_ptr), int(shape[0]), int(shape[1]), len(corners),
+                                                      n._ptr(corners), n._ptr(frac), float(saturation_threshold), float(star_minimum),
+                                                      float(star_maximum), n._ptr(flags)))
+        return flags
+
     def load(self, patches: np.ndarray) -> None:
         p = np.ascontiguousarray(patches, np.float32).reshape(-1, self.patch_size, self.patch_size)
         self._native.check(self._native.lib().rpsf_builder_load_patches(self._handle, len(p), self._native._ptr(p)))
@@ -341,14 +432,27 @@ class _Stack:
 class ArrayPSFBuilder:
     """A builder that takes a series of images and constructs an ArrayPSF to represent their implicit PSF."""
 
-    def __init__(self, psf_size: int, device: int = 0, *, interpolation: str = "off", cleanup: str = "host") -> None:
+    def __init__(self, psf_size: int, device: int = 0, *, finder: str = "sep", finder_options: dict | None = None,
+                 interpolation: str = "off", cleanup: str = "host") -> None:
         """``interpolation`` says what ``build`` does with ``interpolation_scale != 1``: ``"off"`` refuses it, ``"device"`` upscales
         every frame on the GPU, cuts the patches at ``psf_size * interpolation_scale`` pixels and block-averages every cell back to
         ``psf_size`` before the clean-up, as the reference does.  With ``interpolation_scale == 1`` the two settings are the same build.
 
         ``cleanup`` says where ``build`` runs the per-cell clean-up: ``"host"`` is ``clean_cell`` on every cell, ``"device"`` the
         third kernel, with ``clean_cell`` only on the cells it flags (a degenerate background fit) - the same model within 1e-12.
-        It is an argument of the builder and not of ``build``, whose parameter list stays the reference's plus ``stars``."""
+        It is an argument of the builder and not of ``build``, whose parameter list stays the reference's plus ``stars``.
+
+        ``finder`` says who finds the stars when ``build`` gets no ``stars``: ``"sep"`` imports ``sep`` as the reference does,
+        ``"device"`` is this package's detector (``find_stars``; it is not ``sep``) on the fused route: per frame one upload at most, the
+        background mesh filtered on the device, the patches cut from the frame the stars were found in - bit for bit
+        ``build(frames, stars=find_stars(frames, star_threshold, sep_mask, **finder_options))``.  ``finder_options``: a dict with any of
+        ``box``, ``min_area``, ``max_area`` (``find_stars``'s defaults), only with ``finder="device"``."""
+        if finder not in FINDERS:
+            msg = f"finder must be one of {FINDERS}, not {finder!r}"
+            raise ValueError(msg)
+        self._finder_options = _finder_options(finder, finder_options)
+        self._finder = finder
+        self._found_stars: list[np.ndarray] | None = None
         if cleanup not in CLEANUPS:
             msg = f"cleanup must be one of {CLEANUPS}, not {cleanup!r}"
             raise ValueError(msg)
@@ -372,6 +476,16 @@ class ArrayPSFBuilder:
     def interpolation(self) -> str:
         return self._interpolation
 
+    @property
+    def finder(self) -> str:
+        return self._finder
+
+    @property
+    def found_stars(self) -> list[np.ndarray] | None:
+        """After a build that found the stars itself with ``finder="device"``: the ``(k, 2)`` float64 ``(row, col)`` arrays it used, one
+        per frame, in scaled-frame pixels when ``interpolation_scale > 1``.  None before a build and after a build with ``stars=``."""
+        return self._found_stars
+
     def build(self, images, sep_mask=None, hdu_choice: int | None = 0, num_workers: int | None = None,  # noqa: ARG002
               interpolation_scale: int = 1, star_threshold: int = 3, average_method: str = "median", percentile: float = 50,
               saturation_threshold: float = np.inf, image_mask: np.ndarray | None = None, star_minimum: float = 0,
@@ -384,6 +498,14 @@ class ArrayPSFBuilder:
         ``(row, col)`` star positions per frame - the ``y``, ``x`` columns of ``sep.extract`` - which skips star finding.
         ``patches`` maps ``(frame, row - N / 2, col - N / 2)`` to the float64 copy of the float32 patch kept on the device
         (background-subtracted, not normalised); ``counts`` maps every corner of the covering to its number of stars.
+
+        ``images`` may also live on the builder's device: a 2-D or 3-D ``DeviceArray`` or a list of 2-D ``DeviceArray`` s / objects with
+        ``__cuda_array_interface__`` (dtypes and strides as for ``apply``; ``interpolation_scale`` must be 1).  They are read where they
+        lie and give what the host call gives on the same values.  ``sep_mask`` is always a host array.
+
+        Without ``stars`` and with ``ArrayPSFBuilder(..., finder="device")`` the stars are found on the device, with ``star_threshold`` in
+        units of the global background rms and ``sep_mask`` as ``find_stars``'s mask (one 2-D boolean array or one per frame, True =
+        ignore); ``found_stars`` holds them afterwards.
 
         ``interpolation_scale = s > 1`` needs ``ArrayPSFBuilder(..., interpolation="device")``.  Then ``stars`` are positions in the
         SCALED frame (what ``sep.extract`` returns on it: ``find_stars(scale_image(frames, s))``), the patches are ``N s`` wide with
@@ -410,11 +532,31 @@ class ArrayPSFBuilder:
             msg = f"Unknown method {average_method}."
             raise PSFBuilderError(msg)
         cleanup = self._cleanup
-        frames = _frames(images)
+        self._found_stars = None
+        frames = _device_frames(images, self._device)
+        on_device = frames is not None
+        if on_device and scale != 1:
+            msg = "interpolation_scale != 1 takes host frames: resampling device frames is not supported, bring them to the host (to_host)"
+            raise TypeError(msg)
+        if not on_device:
+            frames = _frames(images)
         if scale != 1 and min(frames[0].shape) < 4:
             msg = f"interpolation_scale needs frames of at least 4 x 4 pixels (the cubic spline takes four points), not {frames[0].shape}"
             raise ValueError(msg)
-        if stars is None:
+        seen_shape = tuple(frames[0].shape) if scale == 1 else scaled_shape(frames[0].shape, scale)  # of the frame the patches are cut from
+        fused = stars is None and self._finder == "device"
+        finder = None
+        if fused:
+            from regularizepsf_amd import stars as star_finder
+
+            options = self._finder_options
+            masks = star_finder._masks(sep_mask, frames, seen_shape)
+            finder = star_finder._Finder(seen_shape, options["box"], self._device)
+            stars = [None] * len(frames)
+        elif stars is None:
+            if on_device:
+                msg = 'Star finding with `sep` takes host frames: construct the builder with ArrayPSFBuilder(..., finder="device") or pass stars='
+                raise TypeError(msg)
             masks = [None] * len(frames) if sep_mask is None else _frames(sep_mask)
             seen = frames if scale == 1 else [_scale_frame(frame, scale, self._device) for frame in frames]  # sep sees the scaled frame
             stars = [_find_stars(frame, star_threshold, mask) for frame, mask in zip(seen, masks)]
@@ -422,16 +564,34 @@ class ArrayPSFBuilder:
             msg = f"stars has {len(stars)} entries for {len(frames)} frames"
             raise ValueError(msg)
 
-        capacity = sum(len(np.asarray(s).reshape(-1, 2)) for s in stars)
-        stack = _Stack(size, self._device, capacity) if scale == 1 else _Stack(size, self._device, capacity, scale)
+        capacity = 1 if fused else sum(len(np.asarray(s).reshape(-1, 2)) for s in stars)  # (the stack grows by itself)
+        stack = None
         try:
+            stack = _Stack(size, self._device, capacity) if scale == 1 else _Stack(size, self._device, capacity, scale)
+            found: list[np.ndarray] = []
             keys: dict[tuple[int, float, float], int] = {}  # patch key -> index into the device stack, in insertion order
             for i, (frame, positions) in enumerate(zip(frames, stars)):
+                if fused:  # S1, S1b, S2 - S4 on the one device copy of the frame; B1 below cuts from the same
+                    if scale == 1:
+                        finder.background_device(frame, masks[i])
+                    else:
+                        finder.background_scaled(frame, scale, masks[i])
+                    rows = finder.detect_device(float(star_threshold), int(options["min_area"]), options["max_area"])
+                    positions = np.ascontiguousarray(rows[:, :2])
+                    found.append(positions)
                 corner, rounded, shift = star_geometry(positions, patch)
                 # equal keys of one frame: dict.update keeps the first position and the last value - the same patch either way
                 _, first = np.unique(corner, axis=0, return_index=True)
                 first.sort()
-                flags = stack.add_frame(frame, rounded[first], shift[first], saturation_threshold, star_minimum, star_maximum)
+                if fused:
+                    flags = stack.add_frame_device(finder.frame_ptr(), seen_shape, rounded[first], shift[first], saturation_threshold,
+                                                   star_minimum, star_maximum) if len(first) else np.zeros(0, np.uint8)
+                elif on_device:
+                    dense = _dense_f32(frame)  # (kept alive until B1 has run: add_frame_device waits for it)
+                    flags = stack.add_frame_device(dense.ptr, seen_shape, rounded[first], shift[first], saturation_threshold, star_minimum,
+                                                   star_maximum)
+                else:
+                    flags = stack.add_frame(frame, rounded[first], shift[first], saturation_threshold, star_minimum, star_maximum)
                 if np.any(flags == DEGENERATE_RING):
                     bad = corner[first][flags == DEGENERATE_RING][0] + patch / 2
                     msg = (f"Frame {i}: the patch of the star at {tuple(float(v) for v in bad)} has fewer than three border pixels below "
@@ -455,7 +615,12 @@ class ArrayPSFBuilder:
                 values = stack.patches().astype(np.float64)
                 patches = {key: values[index] for key, index in keys.items()}
         finally:
-            stack.close()
+            if stack is not None:
+                stack.close()
+            if finder is not None:
+                finder.close()
+        if fused:
+            self._found_stars = found
 
         counts = {tuple(corner): int(offsets[c + 1] - offsets[c]) for c, corner in enumerate(corners)}
         coordinates = [(corner[0], corner[1]) for corner in corners]

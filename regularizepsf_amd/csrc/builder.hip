@@ -8,6 +8,7 @@
 //   B3  builder_clean_kernel    one workgroup per averaged cell, the driver of rpsf_core_cleanup.hpp: the cell's values in registers,
 //                               byte masks and union-find parents in LDS (N = 128: 96 KiB); writes the cleaned float64 cell and one
 //                               flag byte.
+//   rpsf_builder_add_frame_device runs B1 on a dense float32 frame that is already on the device (a finder's, DESIGN.md 3.11, or the caller's).
 //   A scaled builder (rpsf_builder_create_scaled, interpolation_scale = s of the reference) runs B1 and B2 at P = N s on frames that
 //   csrc/scale.hip upscales on the device, brings every averaged P x P cell back to N x N with its kernel B4, and runs B3 at N.
 //
@@ -219,8 +220,9 @@ static int check_stars(const rpsf_builder* b, int height, int width, int n_stars
   return RPSF_OK;
 }
 
-static int patches_of_frame(rpsf_builder* b, int height, int width, int n_stars, const int32_t* corners_i32, const double* frac_f64,
-                            double saturation_threshold, double star_minimum, double star_maximum, uint8_t* accepted_u8_host);
+static int patches_of_frame(rpsf_builder* b, const float* frame_dev, int height, int width, int n_stars, const int32_t* corners_i32,
+                            const double* frac_f64, double saturation_threshold, double star_minimum, double star_maximum,
+                            uint8_t* accepted_u8_host);
 
 extern "C" int rpsf_builder_add_frame(rpsf_builder* b, const void* image_host, int image_is_f64, int height, int width, int n_stars,
                                       const int32_t* corners_i32, const double* frac_f64, double saturation_threshold,
@@ -242,7 +244,7 @@ extern "C" int rpsf_builder_add_frame(rpsf_builder* b, const void* image_host, i
   } else {
     HIP_TRY(hipMemcpy(b->frame.p, image_host, fpix * sizeof(float), hipMemcpyHostToDevice));
   }
-  return patches_of_frame(b, height, width, n_stars, corners_i32, frac_f64, saturation_threshold, star_minimum, star_maximum,
+  return patches_of_frame(b, b->frame.p, height, width, n_stars, corners_i32, frac_f64, saturation_threshold, star_minimum, star_maximum,
                           accepted_u8_host);
 }
 
@@ -267,13 +269,29 @@ extern "C" int rpsf_builder_add_frame_scaled(rpsf_builder* b, const void* image_
   if (const int rc = rpsf_detail_scale_upload(b->upscale, image_host, image_is_f64, height, width)) return rc;
   HIP_TRY(b->frame.reserve((size_t)hs * ws));
   if (const int rc = rpsf_detail_scale_run(b->upscale, image_is_f64, height, width, scale, b->frame.p, 1)) return rc;
-  return patches_of_frame(b, (int)hs, (int)ws, n_stars, corners_i32, frac_f64, saturation_threshold, star_minimum, star_maximum,
+  return patches_of_frame(b, b->frame.p, (int)hs, (int)ws, n_stars, corners_i32, frac_f64, saturation_threshold, star_minimum, star_maximum,
                           accepted_u8_host);
 }
 
-// B1 on builder->frame (height x width float32, on the device) and the append of what it accepts
-static int patches_of_frame(rpsf_builder* b, int height, int width, int n_stars, const int32_t* corners_i32, const double* frac_f64,
-                            double saturation_threshold, double star_minimum, double star_maximum, uint8_t* accepted_u8_host) {
+extern "C" int rpsf_builder_add_frame_device(rpsf_builder* b, const float* frame_dev, int height, int width, int n_stars,
+                                             const int32_t* corners_i32, const double* frac_f64, double saturation_threshold,
+                                             double star_minimum, double star_maximum, uint8_t* accepted_u8_host) {
+  if (!b || !frame_dev) return fail(RPSF_E_BADARG, "null argument");
+  if (height < 2 || width < 2) return fail(RPSF_E_BADARG, "a frame needs at least 2 x 2 pixels");
+  if (n_stars < 0) return fail(RPSF_E_BADARG, "n_stars is negative");
+  if (n_stars == 0) return RPSF_OK;
+  if (!corners_i32 || !frac_f64 || !accepted_u8_host) return fail(RPSF_E_BADARG, "null argument");
+  if (const int rc = check_stars(b, height, width, n_stars, corners_i32, frac_f64)) return rc;
+  HIP_TRY(hipSetDevice(b->device));
+  // the frame is read where it lies - a finder's frame buffer or the caller's own array; on a scaled builder it is the scaled frame
+  return patches_of_frame(b, frame_dev, height, width, n_stars, corners_i32, frac_f64, saturation_threshold, star_minimum, star_maximum,
+                          accepted_u8_host);
+}
+
+// B1 on frame_dev (height x width float32, dense, on the builder's device) and the append of what it accepts
+static int patches_of_frame(rpsf_builder* b, const float* frame_dev, int height, int width, int n_stars, const int32_t* corners_i32,
+                            const double* frac_f64, double saturation_threshold, double star_minimum, double star_maximum,
+                            uint8_t* accepted_u8_host) {
   const int N = b->N;
   const size_t npix = (size_t)N * N;
   HIP_TRY(b->corners.reserve(2 * (size_t)n_stars));
@@ -282,7 +300,7 @@ static int patches_of_frame(rpsf_builder* b, int height, int width, int n_stars,
   HIP_TRY(b->staging.reserve((size_t)n_stars * npix));
   HIP_TRY(hipMemcpy(b->corners.p, corners_i32, 2 * (size_t)n_stars * sizeof(int32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->frac.p, frac_f64, 2 * (size_t)n_stars * sizeof(double), hipMemcpyHostToDevice));
-  const B1Params q{b->frame.p, height, width, N, b->corners.p, b->frac.p, saturation_threshold, star_minimum, star_maximum,
+  const B1Params q{frame_dev, height, width, N, b->corners.p, b->frac.p, saturation_threshold, star_minimum, star_maximum,
                    b->staging.p, b->flags.p};
   HIP_TRY(hipEventRecord(b->ev[0], nullptr));
   if (N > 64) {

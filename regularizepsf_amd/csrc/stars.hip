@@ -2,6 +2,8 @@
 // modelled on sep.Background + sep.extract without deblending; it is NOT sep.
 //
 //   S1  stars_mesh_kernel      one workgroup per background box: sigma-clipped level and rms (exact median, fixed-order sums)
+//   S1b stars_mesh_filter_kernel   the mesh filled and 3 x 3 median filtered on the device, global rms and T with it (the drivers of
+//                              rpsf_core_stars_mesh.hpp): one workgroup, or above rpsfm::MANY_NODES nodes the stars_mesh_many_* launches
 //   S2  stars_detect_kernel    one workgroup per 32 x 32 tile: residual against the bilinear background surface (mesh window and
 //                              the tile with a one-pixel halo in LDS), 3 x 3 filter, test against T -> one mask byte per pixel
 //   S3  stars_label_*          union-find per tile in LDS, integer atomicMin across tile seams, flatten:
@@ -17,7 +19,11 @@
 #include <string>
 #include <vector>
 
+#include "rpsf_convert.hpp"
+#include "rpsf_core_convert.hpp"
 #include "rpsf_core_stars.hpp"
+#include "rpsf_core_stars_mesh.hpp"
+#include "rpsf_scale.hpp"
 #include "rpsf_side_unit.hpp"
 
 using namespace rpsfs;
@@ -32,6 +38,39 @@ __global__ __launch_bounds__(TILE_THREADS) void stars_detect_kernel(Frame fr, co
   GpuCtx ctx;
   s2_tile(ctx, fr, L, T, (int)blockIdx.y, (int)blockIdx.x, stars_lds, det);
 }
+// S2 with T read from device memory, where S1b left it
+__global__ __launch_bounds__(TILE_THREADS) void stars_detect_device_kernel(Frame fr, const double* L, const double* T, uint8_t* det) {
+  GpuCtx ctx;
+  s2_tile(ctx, fr, L, T[0], (int)blockIdx.y, (int)blockIdx.x, stars_lds, det);
+}
+__global__ __launch_bounds__(rpsfm::S1B_THREADS) void stars_mesh_filter_kernel(int nby, int nbx, double* level, double* rms, double* level_f,
+                                                                               double* rms_f, double* out, int* none) {
+  GpuCtx ctx;
+  rpsfm::s1b_mesh(ctx, nby, nbx, level, rms, level_f, rms_f, out, none, stars_lds);
+}
+__global__ __launch_bounds__(rpsfm::S1B_THREADS) void stars_mesh_many_count_kernel(rpsfm::Source src, const rpsfm::Sel* state, int step,
+                                                                                   rpsfm::Total* acc) {
+  GpuCtx ctx;
+  rpsfm::many_count(ctx, (int)blockIdx.x, (int)gridDim.x, src, state, step, acc, stars_lds);
+}
+__global__ __launch_bounds__(64) void stars_mesh_many_step_kernel(rpsfm::Sel* state, rpsfm::Total* acc, int step) {
+  if (global_id() == 0) rpsfm::many_step(state, acc, step);
+}
+__global__ __launch_bounds__(256) void stars_mesh_many_fill_kernel(long n, double* level, double* rms, const rpsfm::Sel* valid) {
+  rpsfm::many_fill(global_id(), n, level, rms, valid);
+}
+__global__ __launch_bounds__(256) void stars_mesh_many_filter_kernel(int nby, int nbx, const double* level, const double* rms, double* level_f,
+                                                                     double* rms_f) {
+  rpsfm::many_filter(global_id(), nby, nbx, level, rms, level_f, rms_f);
+}
+__global__ __launch_bounds__(64) void stars_mesh_many_finish_kernel(const rpsfm::Sel* valid, const rpsfm::Sel* all, double* out, int* none) {
+  if (global_id() == 0) rpsfm::many_finish(valid, all, out, none);
+}
+// T = threshold * global_rms: one float64 multiply, one plain store
+__global__ __launch_bounds__(64) void stars_threshold_kernel(double threshold, const int* none, double* out) {
+  if (global_id() == 0) out[rpsfm::OUT_T] = rpsfm::threshold_of(threshold, out[rpsfm::OUT_GLOBAL_RMS], none[0]);
+}
+
 __global__ __launch_bounds__(TILE_THREADS) void stars_label_tile_kernel(const uint8_t* det, int H, int W, int32_t* labels) {
   GpuCtx ctx;
   s3_tile(ctx, det, H, W, (int)blockIdx.y, (int)blockIdx.x, reinterpret_cast<int*>(stars_lds), labels);
@@ -66,7 +105,14 @@ __global__ __launch_bounds__(WALK_THREADS) void stars_walk_kernel(Frame fr, cons
 struct rpsf_stars {
   int device = 0, H = 0, W = 0, box = 0, nby = 0, nbx = 0;
   bool have_frame = false;
+  bool have_mesh = false;  // S1b ran on the frame: level_f, mesh_out and none hold its results
   Buf<float> frame;
+  Buf<double> level_f, rms_f, mesh_out;  // S1b: the filtered meshes; mesh_out[0] = global rms, [1] = T
+  Buf<int> none;                         // S1b: 1 when no box of the frame has a usable pixel
+  Buf<rpsfm::Sel> mesh_state;            // S1b on many workgroups: the two selections
+  Buf<rpsfm::Total> mesh_acc;
+  rpsf_scale_scratch* upscale = nullptr;  // rpsf_stars_background_scaled
+  double mesh_ms = 0;
   Buf<uint8_t> mask, det;
   Buf<int32_t> labels;
   Buf<double> level, rms, moments;
@@ -78,6 +124,7 @@ struct rpsf_stars {
   long nseg() const { return (long)H * segs_per_row(W); }
   Frame view() const { return Frame{frame.p, mask.p, H, W, box, nby, nbx}; }
   ~rpsf_stars() {
+    rpsf_detail_scale_scratch_free(upscale);
     for (auto e : ev)
       if (e) (void)hipEventDestroy(e);
   }
@@ -128,6 +175,14 @@ extern "C" int rpsf_stars_create(rpsf_stars** out, int device, int height, int w
     HIP_TRY(s->segcnt.reserve((size_t)s->nseg()));
     HIP_TRY(s->segoff.reserve((size_t)s->nseg()));
     HIP_TRY(s->total.reserve(1));
+    HIP_TRY(s->level_f.reserve(nmesh));
+    HIP_TRY(s->rms_f.reserve(nmesh));
+    HIP_TRY(s->mesh_out.reserve(2));
+    HIP_TRY(s->none.reserve(1));
+    if ((long)nmesh > rpsfm::MANY_NODES) {
+      HIP_TRY(s->mesh_state.reserve(2));
+      HIP_TRY(s->mesh_acc.reserve(1));
+    }
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&stars_mesh_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)s1_lds_bytes(MAX_BOX)));  // 70 KiB at box = 128
     return RPSF_OK;
@@ -146,13 +201,10 @@ extern "C" void rpsf_stars_destroy(rpsf_stars* s) {
   delete s;
 }
 
-extern "C" int rpsf_stars_background(rpsf_stars* s, const void* image_host, int image_is_f64, const uint8_t* mask_host_or_null,
-                                     double* level_host, double* rms_host) {
-  if (!s || !image_host || !level_host || !rms_host) return fail(RPSF_E_BADARG, "null argument");
-  const size_t npix = (size_t)s->npix(), nmesh = (size_t)s->nby * s->nbx;
-  HIP_TRY(hipSetDevice(s->device));
-  s->have_frame = false;
-  if (image_is_f64) {  // the frame crosses PCIe once, as float32 - what every other path of the library uploads
+// the frame crosses PCIe once, as float32 - what every other path of the library uploads
+static int upload_frame(rpsf_stars* s, const void* image_host, int image_is_f64) {
+  const size_t npix = (size_t)s->npix();
+  if (image_is_f64) {
     std::vector<float> narrow(npix);
     const double* src = static_cast<const double*>(image_host);
     for (size_t i = 0; i < npix; ++i) narrow[i] = (float)src[i];
@@ -160,6 +212,11 @@ extern "C" int rpsf_stars_background(rpsf_stars* s, const void* image_host, int 
   } else {
     HIP_TRY(hipMemcpy(s->frame.p, image_host, npix * sizeof(float), hipMemcpyHostToDevice));
   }
+  return RPSF_OK;
+}
+
+static int upload_mask(rpsf_stars* s, const uint8_t* mask_host_or_null) {
+  const size_t npix = (size_t)s->npix();
   if (mask_host_or_null) {
     std::vector<uint8_t> flags(npix);
     for (size_t i = 0; i < npix; ++i) flags[i] = mask_host_or_null[i] != 0;
@@ -167,17 +224,34 @@ extern "C" int rpsf_stars_background(rpsf_stars* s, const void* image_host, int 
   } else {
     HIP_TRY(hipMemset(s->mask.p, 0, npix));
   }
+  return RPSF_OK;
+}
+
+// S1 on the finder's frame and mask into s->level / s->rms
+static int mesh_on_device(rpsf_stars* s) {
   s->ms[0] = 0;
-  if (const int rc = timed(s, &s->ms[0], [&] {
-        hipLaunchKernelGGL(stars_mesh_kernel, dim3(s->nbx, s->nby), dim3(S1_THREADS), s1_lds_bytes(s->box), nullptr, s->view(), s->level.p,
-                           s->rms.p);
-      }))
-    return rc;
+  return timed(s, &s->ms[0], [&] {
+    hipLaunchKernelGGL(stars_mesh_kernel, dim3(s->nbx, s->nby), dim3(S1_THREADS), s1_lds_bytes(s->box), nullptr, s->view(), s->level.p,
+                       s->rms.p);
+  });
+}
+
+extern "C" int rpsf_stars_background(rpsf_stars* s, const void* image_host, int image_is_f64, const uint8_t* mask_host_or_null,
+                                     double* level_host, double* rms_host) {
+  if (!s || !image_host || !level_host || !rms_host) return fail(RPSF_E_BADARG, "null argument");
+  const size_t nmesh = (size_t)s->nby * s->nbx;
+  HIP_TRY(hipSetDevice(s->device));
+  s->have_frame = s->have_mesh = false;
+  if (const int rc = upload_frame(s, image_host, image_is_f64)) return rc;
+  if (const int rc = upload_mask(s, mask_host_or_null)) return rc;
+  if (const int rc = mesh_on_device(s)) return rc;
   HIP_TRY(hipMemcpy(level_host, s->level.p, nmesh * sizeof(double), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(rms_host, s->rms.p, nmesh * sizeof(double), hipMemcpyDeviceToHost));
   s->have_frame = true;
   return RPSF_OK;
 }
+
+static int detect_on_device(rpsf_stars* s, const double* L, const double* T_dev, double T, long min_area, long max_area, size_t* count);
 
 extern "C" int rpsf_stars_detect(rpsf_stars* s, const double* level_host, double threshold_abs, long min_area, long max_area,
                                  size_t* count) {
@@ -188,13 +262,22 @@ extern "C" int rpsf_stars_detect(rpsf_stars* s, const double* level_host, double
     if (!std::isfinite(level_host[i])) return fail(RPSF_E_BADARG, "the background mesh has a non-finite node");
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipMemcpy(s->level.p, level_host, nmesh * sizeof(double), hipMemcpyHostToDevice));
+  s->have_mesh = false;  // S1b's filled mesh is gone
+  return detect_on_device(s, s->level.p, nullptr, threshold_abs, min_area, max_area, count);
+}
+
+// S2 - S4 on the finder's frame with the filtered mesh L (on the device) and the threshold T_dev[0] (on the device) or, T_dev null, T
+static int detect_on_device(rpsf_stars* s, const double* L, const double* T_dev, double T, long min_area, long max_area, size_t* count) {
   s->found.clear();
   *count = 0;
   s->ms[1] = s->ms[2] = s->ms[3] = 0;
   const dim3 tiles((s->W + TILE_C - 1) / TILE_C, (s->H + TILE_R - 1) / TILE_R);
   if (const int rc = timed(s, &s->ms[1], [&] {
-        hipLaunchKernelGGL(stars_detect_kernel, tiles, dim3(TILE_THREADS), s2_lds_bytes(), nullptr, s->view(), s->level.p, threshold_abs,
-                           s->det.p);
+        if (T_dev) {
+          hipLaunchKernelGGL(stars_detect_device_kernel, tiles, dim3(TILE_THREADS), s2_lds_bytes(), nullptr, s->view(), L, T_dev, s->det.p);
+        } else {
+          hipLaunchKernelGGL(stars_detect_kernel, tiles, dim3(TILE_THREADS), s2_lds_bytes(), nullptr, s->view(), L, T, s->det.p);
+        }
       }))
     return rc;
   if (const int rc = timed(s, &s->ms[2], [&] { launch_label(s); })) return rc;
@@ -218,7 +301,7 @@ extern "C" int rpsf_stars_detect(rpsf_stars* s, const double* level_host, double
         hipLaunchKernelGGL(stars_accumulate_kernel, dim3(blocks_for(s->npix())), dim3(256), 0, nullptr, s->npix(), s->W, s->labels.p,
                            s->roots.p, n, s->stats.p);
         hipLaunchKernelGGL(stars_walk_kernel, dim3((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS), s4_walk_lds_bytes(),
-                           nullptr, s->view(), s->level.p, s->labels.p, s->roots.p, s->stats.p, n, min_area, max_area, s->moments.p);
+                           nullptr, s->view(), L, s->labels.p, s->roots.p, s->stats.p, n, min_area, max_area, s->moments.p);
       }))
     return rc;
   std::vector<double> m(4 * (size_t)n);
@@ -263,5 +346,136 @@ extern "C" int rpsf_stars_info(const rpsf_stars* s, int* tile_rows, int* tile_co
 extern "C" int rpsf_stars_kernel_ms(const rpsf_stars* s, double ms[4]) {
   if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
   for (int i = 0; i < 4; ++i) ms[i] = s->ms[i];
+  return RPSF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the fused route
+// one exact selection on many workgroups: a counting launch and a one-thread step launch per pass
+static void launch_select_many(rpsf_stars* s, const rpsfm::Source& src, rpsfm::Sel* state) {
+  const dim3 grid(rpsfm::many_workgroups(src.n));
+  hipLaunchKernelGGL(stars_mesh_many_step_kernel, dim3(1), dim3(64), 0, nullptr, state, s->mesh_acc.p, -1);
+  for (int step = 0; step < rpsfm::STEPS; ++step) {
+    hipLaunchKernelGGL(stars_mesh_many_count_kernel, grid, dim3(rpsfm::S1B_THREADS), rpsfm::s1b_lds_bytes(), nullptr, src, state, step,
+                       s->mesh_acc.p);
+    hipLaunchKernelGGL(stars_mesh_many_step_kernel, dim3(1), dim3(64), 0, nullptr, state, s->mesh_acc.p, step);
+  }
+}
+
+// S1b on s->level / s->rms (filled in place) into s->level_f / s->rms_f, s->mesh_out[0] and s->none; nothing comes back to the host
+static int filter_mesh_on_device(rpsf_stars* s) {
+  const long n = (long)s->nby * s->nbx;
+  s->mesh_ms = 0;
+  return timed(s, &s->mesh_ms, [&] {
+    if (n <= rpsfm::MANY_NODES) {
+      hipLaunchKernelGGL(stars_mesh_filter_kernel, dim3(1), dim3(rpsfm::S1B_THREADS), rpsfm::s1b_lds_bytes(), nullptr, s->nby, s->nbx,
+                         s->level.p, s->rms.p, s->level_f.p, s->rms_f.p, s->mesh_out.p, s->none.p);
+      return;
+    }
+    launch_select_many(s, rpsfm::Source{s->level.p, s->rms.p, n, 1}, s->mesh_state.p);
+    hipLaunchKernelGGL(stars_mesh_many_fill_kernel, dim3(blocks_for(n)), dim3(256), 0, nullptr, n, s->level.p, s->rms.p, s->mesh_state.p);
+    hipLaunchKernelGGL(stars_mesh_many_filter_kernel, dim3(blocks_for(n)), dim3(256), 0, nullptr, s->nby, s->nbx, s->level.p, s->rms.p,
+                       s->level_f.p, s->rms_f.p);
+    launch_select_many(s, rpsfm::Source{s->rms_f.p, s->rms_f.p, n, 0}, s->mesh_state.p + 1);
+    hipLaunchKernelGGL(stars_mesh_many_finish_kernel, dim3(1), dim3(64), 0, nullptr, s->mesh_state.p, s->mesh_state.p + 1, s->mesh_out.p,
+                       s->none.p);
+  });
+}
+
+// the tail every fused background entry shares: the frame is in s->frame (enqueued on the null stream); mask, S1, S1b
+static int background_on_device(rpsf_stars* s, const uint8_t* mask_host_or_null) {
+  if (const int rc = upload_mask(s, mask_host_or_null)) return rc;
+  if (const int rc = mesh_on_device(s)) return rc;
+  if (const int rc = filter_mesh_on_device(s)) return rc;
+  s->have_frame = s->have_mesh = true;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_background_view(rpsf_stars* s, const rpsf_view* image, const uint8_t* mask_host_or_null) {
+  if (!s || !image) return fail(RPSF_E_BADARG, "null argument");
+  bool empty = false;
+  if (const char* why = rpsfconv::view_problem(image, false, &empty)) return fail(RPSF_E_BADARG, std::string("image: ") + why);
+  if (image->rows != s->H || image->cols != s->W)
+    return fail(RPSF_E_BADARG, "the view is " + std::to_string(image->rows) + " x " + std::to_string(image->cols) + ", the finder's frame " +
+                                   std::to_string(s->H) + " x " + std::to_string(s->W));
+  HIP_TRY(hipSetDevice(s->device));
+  s->have_frame = s->have_mesh = false;
+  if (rpsfconv::dense_f32(*image)) {  // the same bits, device to device; the caller's array is only ever read
+    HIP_TRY(hipMemcpyAsync(s->frame.p, image->data, (size_t)s->npix() * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+  } else if (const int rc = rpsf_conv_gather(*image, 1, 0, s->frame.p, 0, nullptr)) {  // C1
+    return rc;
+  }
+  return background_on_device(s, mask_host_or_null);
+}
+
+extern "C" int rpsf_stars_background_host(rpsf_stars* s, const void* image_host, int image_is_f64, const uint8_t* mask_host_or_null) {
+  if (!s || !image_host) return fail(RPSF_E_BADARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  s->have_frame = s->have_mesh = false;
+  if (const int rc = upload_frame(s, image_host, image_is_f64)) return rc;
+  return background_on_device(s, mask_host_or_null);
+}
+
+extern "C" int rpsf_stars_background_scaled(rpsf_stars* s, const void* image_host, int image_is_f64, int height, int width, int scale,
+                                            const uint8_t* mask_host_or_null) {
+  if (!s || !image_host) return fail(RPSF_E_BADARG, "null argument");
+  if (scale < 2) return fail(RPSF_E_BADARG, "scale must be at least 2 here (scale 1: rpsf_stars_background_host)");
+  if (height < 4 || width < 4) return fail(RPSF_E_BADARG, "the spline of the upscale needs at least 4 x 4 pixels");
+  const long hs = 1 + (long)(height - 1) * scale, ws = 1 + (long)(width - 1) * scale;
+  if (hs != s->H || ws != s->W)
+    return fail(RPSF_E_BADARG, "the scaled frame is " + std::to_string(hs) + " x " + std::to_string(ws) + ", the finder's frame " +
+                                   std::to_string(s->H) + " x " + std::to_string(s->W));
+  HIP_TRY(hipSetDevice(s->device));
+  s->have_frame = s->have_mesh = false;
+  if (!s->upscale) s->upscale = rpsf_detail_scale_scratch_new();
+  // the unscaled frame crosses PCIe once, in its own type; U1 / U2 leave the scaled one, rounded to float32 once, where S1 reads it
+  if (const int rc = rpsf_detail_scale_upload(s->upscale, image_host, image_is_f64, height, width)) return rc;
+  if (const int rc = rpsf_detail_scale_run(s->upscale, image_is_f64, height, width, scale, s->frame.p, 1)) return rc;
+  return background_on_device(s, mask_host_or_null);
+}
+
+extern "C" int rpsf_stars_filter_mesh(rpsf_stars* s, const double* level_host, const double* rms_host, double threshold, double* level_out,
+                                      double* rms_out, double* global_rms, double* T, int* none) {
+  if (!s || !level_host || !rms_host || !level_out || !rms_out || !global_rms || !T || !none) return fail(RPSF_E_BADARG, "null argument");
+  const size_t nmesh = (size_t)s->nby * s->nbx;
+  HIP_TRY(hipSetDevice(s->device));
+  s->have_mesh = false;  // the meshes are the caller's, not the frame's
+  HIP_TRY(hipMemcpy(s->level.p, level_host, nmesh * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->rms.p, rms_host, nmesh * sizeof(double), hipMemcpyHostToDevice));
+  if (const int rc = filter_mesh_on_device(s)) return rc;
+  hipLaunchKernelGGL(stars_threshold_kernel, dim3(1), dim3(64), 0, nullptr, threshold, s->none.p, s->mesh_out.p);
+  HIP_TRY(hipGetLastError());
+  double out[2] = {0, 0};
+  HIP_TRY(hipMemcpy(none, s->none.p, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, s->mesh_out.p, sizeof out, hipMemcpyDeviceToHost));
+  *T = out[rpsfm::OUT_T];
+  if (*none) return RPSF_OK;  // no usable box: nothing else was written
+  *global_rms = out[rpsfm::OUT_GLOBAL_RMS];
+  HIP_TRY(hipMemcpy(level_out, s->level_f.p, nmesh * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(rms_out, s->rms_f.p, nmesh * sizeof(double), hipMemcpyDeviceToHost));
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_detect_device(rpsf_stars* s, double threshold, long min_area, long max_area, size_t* count) {
+  if (!s || !count) return fail(RPSF_E_BADARG, "null argument");
+  if (!s->have_mesh) return fail(RPSF_E_STATE, "rpsf_stars_detect_device before a rpsf_stars_background_view / _host / _scaled of the frame");
+  HIP_TRY(hipSetDevice(s->device));
+  hipLaunchKernelGGL(stars_threshold_kernel, dim3(1), dim3(64), 0, nullptr, threshold, s->none.p, s->mesh_out.p);
+  HIP_TRY(hipGetLastError());
+  // no usable box: T = +inf, nothing is detected, *count stays 0
+  return detect_on_device(s, s->level_f.p, s->mesh_out.p + rpsfm::OUT_T, 0.0, min_area, max_area, count);
+}
+
+extern "C" int rpsf_stars_frame(rpsf_stars* s, const float** frame_dev, int* height, int* width) {
+  if (!s || !frame_dev) return fail(RPSF_E_BADARG, "null argument");
+  if (!s->have_frame) return fail(RPSF_E_STATE, "rpsf_stars_frame before a frame was uploaded");
+  *frame_dev = s->frame.p;
+  if (height) *height = s->H;
+  if (width) *width = s->W;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_mesh_ms(const rpsf_stars* s, double* ms) {
+  if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
+  *ms = s->mesh_ms;
   return RPSF_OK;
 }

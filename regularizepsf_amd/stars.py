@@ -9,8 +9,11 @@ estimate, and the background surface is bilinear where ``sep``'s is bicubic.  Po
 extended sources.  Isolated stars on a smooth background - what a PSF model is built from - come out at their centroids.
 
 Four kernel groups behind ``rpsf_stars_*`` (include/rpsf.h) do the work on whole frames: the mesh (S1), detection (S2),
-labelling (S3) and moments (S4).  The host keeps the bookkeeping: filling and median-filtering the mesh (a few thousand
-numbers) between S1 and S2.
+labelling (S3) and moments (S4).  For host frames the host keeps the bookkeeping: filling and median-filtering the mesh (a few
+thousand numbers, ``filter_mesh``) between S1 and S2.  Device frames (``DeviceArray`` or anything with
+``__cuda_array_interface__``) take the fused route of DESIGN.md 3.11, which ``ArrayPSFBuilder(..., finder="device")`` takes for
+every frame: the frame is read where it lies, kernel S1b does ``filter_mesh``'s work on the device - the same bits - and nothing but
+the positions comes back.
 """
 
 from __future__ import annotations
@@ -19,7 +22,8 @@ import ctypes
 
 import numpy as np
 
-from regularizepsf_amd.builder import _frames
+from regularizepsf_amd.builder import _device_frames, _frames
+from regularizepsf_amd.device_array import is_device_array
 from regularizepsf_amd.exceptions import IncorrectShapeError
 
 MIN_BOX, MAX_BOX = 8, 128
@@ -58,6 +62,69 @@ class _Finder:
         out = np.empty((count.value, 4))
         n.check(n.lib().rpsf_stars_positions(self._handle, 0, count.value, n._ptr(out)))
         return out
+
+    def background_device(self, frame, mask: np.ndarray | None) -> None:
+        """The fused route's S1 and S1b: ``frame`` is a host array (uploaded once) or a 2-D ``DeviceArray`` (read where it lies); the
+        meshes stay on the device."""
+        n = self._native
+        flags = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        flags_ptr = None if flags is None else n._ptr(flags)
+        if isinstance(frame, np.ndarray):
+            if frame.dtype != np.float32:
+                frame = frame.astype(np.float64, copy=False)
+            frame = np.ascontiguousarray(frame)
+            n.check(n.lib().rpsf_stars_background_host(self._handle, n._ptr(frame), int(frame.dtype == np.float64), flags_ptr))
+        else:
+            frame.synchronize()  # the finder's launches are on the null stream
+            view = frame._view2d()
+            n.check(n.lib().rpsf_stars_background_view(self._handle, ctypes.byref(view), flags_ptr))
+
+    def background_scaled(self, frame: np.ndarray, scale: int, mask: np.ndarray | None) -> None:
+        """The same for a finder of the scaled shape: the unscaled host frame is uploaded once and upscaled on the device."""
+        n = self._native
+        if frame.dtype != np.float32:
+            frame = frame.astype(np.float64, copy=False)
+        frame = np.ascontiguousarray(frame)
+        flags = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        n.check(n.lib().rpsf_stars_background_scaled(self._handle, n._ptr(frame), int(frame.dtype == np.float64), frame.shape[0],
+                                                     frame.shape[1], int(scale), None if flags is None else n._ptr(flags)))
+
+    def detect_device(self, threshold: float, min_area: int, max_area: int | None) -> np.ndarray:
+        """Detections of the frame given to ``background_device`` / ``background_scaled`` last, the threshold in units of the global
+        rms S1b left on the device: (k, 4) rows of (row, col, flux, area)."""
+        n = self._native
+        count = ctypes.c_size_t(0)
+        n.check(n.lib().rpsf_stars_detect_device(self._handle, float(threshold), int(min_area), -1 if max_area is None else int(max_area),
+                                                 ctypes.byref(count)))
+        out = np.empty((count.value, 4))
+        n.check(n.lib().rpsf_stars_positions(self._handle, 0, count.value, n._ptr(out)))
+        return out
+
+    def filter_mesh(self, level: np.ndarray, rms: np.ndarray, threshold: float):
+        """S1b alone on raw meshes of the finder's mesh shape: (level, rms, global rms, T, none); with ``none`` = 1 (no valid node) only
+        T (+inf) means anything."""
+        n = self._native
+        level, rms = np.ascontiguousarray(level, np.float64), np.ascontiguousarray(rms, np.float64)
+        if level.shape != self.mesh_shape or rms.shape != self.mesh_shape:
+            msg = f"the meshes must have the finder's mesh shape {self.mesh_shape}"
+            raise IncorrectShapeError(msg)
+        level_f, rms_f = np.empty(self.mesh_shape), np.empty(self.mesh_shape)
+        global_rms, T, none = ctypes.c_double(np.nan), ctypes.c_double(np.nan), ctypes.c_int(-1)
+        n.check(n.lib().rpsf_stars_filter_mesh(self._handle, n._ptr(level), n._ptr(rms), float(threshold), n._ptr(level_f), n._ptr(rms_f),
+                                               ctypes.byref(global_rms), ctypes.byref(T), ctypes.byref(none)))
+        return level_f, rms_f, global_rms.value, T.value, none.value
+
+    def frame_ptr(self) -> int:
+        """The finder's float32 frame on the device (valid until the next frame or ``close``)."""
+        ptr = ctypes.c_void_p()
+        self._native.check(self._native.lib().rpsf_stars_frame(self._handle, ctypes.byref(ptr), None, None))
+        return ptr.value
+
+    def mesh_ms(self) -> float:
+        """Device time of the last S1b."""
+        ms = ctypes.c_double(0)
+        self._native.check(self._native.lib().rpsf_stars_mesh_ms(self._handle, ctypes.byref(ms)))
+        return ms.value
 
     def label(self, detected: np.ndarray) -> np.ndarray:
         """S3 alone: per detected pixel the smallest linear index of its 8-connected component, -1 elsewhere."""
@@ -114,10 +181,20 @@ def frame_stars(finder, frame: np.ndarray, mask: np.ndarray | None, threshold: f
     return finder.detect(level, threshold * global_rms, min_area, max_area)
 
 
-def _masks(mask, frames: list[np.ndarray]) -> list[np.ndarray | None]:
+def frame_stars_device(finder, frame, mask: np.ndarray | None, threshold: float, min_area: int, max_area: int | None) -> np.ndarray:
+    """``frame_stars`` on the fused route: ``frame`` is a host array or a 2-D ``DeviceArray``; the mesh never leaves the device."""
+    finder.background_device(frame, mask)
+    return finder.detect_device(threshold, min_area, max_area)
+
+
+def _masks(mask, frames: list, shape: tuple[int, int] | None = None) -> list[np.ndarray | None]:
+    """One host mask (or None) per frame; ``shape``: what a mask must have when that is not the frames' (the scaled frames')."""
     if mask is None:
         return [None] * len(frames)
-    shape = frames[0].shape
+    if is_device_array(mask) or (isinstance(mask, (list, tuple)) and any(is_device_array(m) for m in mask)):
+        msg = "masks are host arrays: a mask on the device is not supported, bring it to the host (to_host)"
+        raise TypeError(msg)
+    shape = tuple(frames[0].shape) if shape is None else shape
     if isinstance(mask, np.ndarray) and mask.ndim == 2:
         masks = [mask] * len(frames)
     else:
@@ -137,7 +214,9 @@ def find_stars(images, threshold: float = 3.0, mask=None, *, box: int = 64, min_
     """Star positions per frame, in the form ``ArrayPSFBuilder.build(..., stars=...)`` takes: a list of ``(k, 2)`` float64
     arrays of ``(row, col)``, one per frame; a frame without detections gives shape ``(0, 2)``.
 
-    ``images``: what ``build`` takes (a 3-D array, a list of 2-D arrays, a generator, or one 2-D array).  ``threshold``: in units
+    ``images``: what ``build`` takes (a 3-D array, a list of 2-D arrays, a generator, or one 2-D array), or frames that live on
+    ``device``: a 2-D or 3-D ``DeviceArray`` or a list of 2-D ``DeviceArray`` s / objects with ``__cuda_array_interface__``, of the dtypes
+    and strides ``apply`` takes - they are read where they lie, and the result is the host call's on the same values.  ``threshold``: in units
     of the frame's global background rms.  ``mask``: None, one 2-D boolean array for all frames or one per frame (True = ignore).
     ``box``: the background box in pixels, 8 ... 128.  A component is kept when ``min_area <= area <= max_area`` (None: no
     upper limit) and its background-subtracted flux is positive.  Not ``sep``: see the module docstring.
@@ -145,11 +224,14 @@ def find_stars(images, threshold: float = 3.0, mask=None, *, box: int = 64, min_
     if not MIN_BOX <= int(box) <= MAX_BOX:
         msg = f"box must lie in {MIN_BOX} ... {MAX_BOX}, got {box}"
         raise ValueError(msg)
-    frames = _frames(images)
+    frames = _device_frames(images, device)
+    one_frame = frame_stars_device
+    if frames is None:
+        frames, one_frame = _frames(images), frame_stars
     masks = _masks(mask, frames)
     finder = _Finder(frames[0].shape, box, device)
     try:
-        return [np.ascontiguousarray(frame_stars(finder, frame, m, float(threshold), int(min_area), max_area)[:, :2])
+        return [np.ascontiguousarray(one_frame(finder, frame, m, float(threshold), int(min_area), max_area)[:, :2])
                 for frame, m in zip(frames, masks)]
     finally:
         finder.close()
