@@ -1,7 +1,10 @@
 """Build librpsf_hip.so in-tree with hipcc for gfx950:  python -m regularizepsf_amd.build [--force] [-DRPSF_STAMPS ...]
 
-The library is several translation units (csrc/rpsf.hip: host side + plan-independent kernels; csrc/k1_*.hip,
-k2_*.hip: the patch kernels of one group of plans each; csrc/builder.hip: the PSF builder, kernels and entry points; csrc/stars.hip: the star finder, likewise; csrc/saturation.hip: the saturation branch of apply on the device, one route for frame-groups of one frame or many; csrc/convert.hip: the conversion kernels of the device-array views; csrc/scale.hip: the frame upscale and the block mean of the builder's interpolation_scale; the last five share csrc/rpsf_side_unit.hpp) compiled in parallel and linked into one shared object.
+The library is several translation units (csrc/rpsf.hip: the plan, its launch path and option setters, with the plain kernels of that path;
+csrc/rpsf_host.hip: the host-array pipelines; csrc/rpsf_saturated.hip: the saturation drivers and the device-array view entry points;
+csrc/rpsf_construct.hip: transfer-kernel build, PSF spectra and models; csrc/rpsf_shard.hip: device memory, RCCL, streams, events and the seam add
+of the sharded step; the first four share csrc/rpsf_plan.hpp; csrc/k1_*.hip,
+k2_*.hip, k3_*.hip: the patch kernels of one group of plans each; csrc/builder.hip: the PSF builder, kernels and entry points; csrc/stars.hip: the star finder, likewise; csrc/saturation.hip: the saturation branch of apply on the device, one route for frame-groups of one frame or many; csrc/convert.hip: the conversion kernels of the device-array views; csrc/scale.hip: the frame upscale and the block mean of the builder's interpolation_scale; the last five share csrc/rpsf_side_unit.hpp) compiled in parallel and linked into one shared object.
 """
 
 from __future__ import annotations
@@ -15,9 +18,8 @@ import sys
 
 PKG = pathlib.Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
-SOURCES = [CSRC / n for n in ("rpsf.hip", "k1_256.hip", "k1_128.hip", "k1_small.hip", "k2_256.hip", "k2_256p.hip", "k2_128.hip", "k2_128p.hip", "k2_128pc.hip", "k2_128pcs.hip", "k3_16.hip", "k3_32.hip", "k3_64.hip", "builder.hip", "stars.hip", "saturation.hip", "convert.hip", "scale.hip")]
-HEADERS = [CSRC / n for n in ("rpsf_core.hpp", "rpsf_core2.hpp", "rpsf_core3.hpp", "rpsf_plan3.hpp", "rpsf_lattice.hpp", "rpsf_kernels.hpp", "rpsf_kernels2.hpp", "rpsf_kernels3.hpp", "rpsf_device.hpp", "rpsf_hostpipe.hpp", "rpsf_core_builder.hpp", "rpsf_core_cleanup.hpp", "rpsf_core_stars.hpp", "rpsf_core_stars_mesh.hpp", "rpsf_core_saturation.hpp", "rpsf_core_saturation_batch.hpp", "rpsf_saturation.hpp", "rpsf_side_unit.hpp", "rpsf_convert.hpp", "rpsf_core_convert.hpp", "rpsf_scale.hpp", "rpsf_core_scale.hpp")] + [
-    PKG.parent / "include" / "rpsf.h"]
+SOURCES = [CSRC / n for n in ("rpsf.hip", "rpsf_host.hip", "rpsf_saturated.hip", "rpsf_construct.hip", "rpsf_shard.hip", "k1_256.hip", "k1_128.hip", "k1_small.hip", "k2_256.hip", "k2_256p.hip", "k2_128.hip", "k2_128p.hip", "k2_128pc.hip", "k2_128pcs.hip", "k3_16.hip", "k3_32.hip", "k3_64.hip", "builder.hip", "stars.hip", "saturation.hip", "convert.hip", "scale.hip")]
+HEADERS = sorted(CSRC.glob("*.hpp")) + [PKG.parent / "include" / "rpsf.h"]  # (every header there is: none can be forgotten)
 TARGET = PKG / "librpsf_hip.so"
 OBJDIR = PKG / "build"
 FLAGS = ["--offload-arch=gfx950", "-std=c++20", "-O3", "-fno-slp-vectorize", "-munsafe-fp-atomics", "-fPIC"]
@@ -141,7 +143,7 @@ def build(force: bool = False, verbose: bool = True, defines: tuple[str, ...] = 
         subprocess.run(cmd, check=True)
         return obj
 
-    workers = max(1, min(len(SOURCES), (os.cpu_count() or 2)))
+    workers = max(1, min(len(SOURCES), int(os.environ.get("MAX_JOBS", 16))))
     with concurrent.futures.ThreadPoolExecutor(workers) as pool:
         objs = list(pool.map(compile_one, SOURCES))
     check_reentry_contract(next(o for o in objs if o.stem == "k2_256p"), "patch_kernel2_256p")

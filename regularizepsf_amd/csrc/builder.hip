@@ -236,14 +236,7 @@ extern "C" int rpsf_builder_add_frame(rpsf_builder* b, const void* image_host, i
   const size_t fpix = (size_t)height * width;
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(b->frame.reserve(fpix));
-  if (image_is_f64) {  // the frame crosses PCIe once, as float32 - what every apply path of the library uploads
-    std::vector<float> narrow(fpix);
-    const double* src = static_cast<const double*>(image_host);
-    for (size_t i = 0; i < fpix; ++i) narrow[i] = (float)src[i];
-    HIP_TRY(hipMemcpy(b->frame.p, narrow.data(), fpix * sizeof(float), hipMemcpyHostToDevice));
-  } else {
-    HIP_TRY(hipMemcpy(b->frame.p, image_host, fpix * sizeof(float), hipMemcpyHostToDevice));
-  }
+  if (const int rc = upload_frame_f32(b->frame.p, image_host, image_is_f64, fpix)) return rc;
   return patches_of_frame(b, b->frame.p, height, width, n_stars, corners_i32, frac_f64, saturation_threshold, star_minimum, star_maximum,
                           accepted_u8_host);
 }

@@ -1,4 +1,4 @@
-// rpsf_convert.hpp - what csrc/rpsf.hip sees of csrc/convert.hip: the launches of the two conversion kernels around the plan's own apply
+// rpsf_convert.hpp - what csrc/rpsf_saturated.hip sees of csrc/convert.hip: the launches of the two conversion kernels around the plan's own apply
 // (rpsf_apply_view, rpsf_apply_batch_view).  `frames` views of v's shape, dtype and strides, frame_stride bytes apart, against dense
 // float32 frames dense_frame_stride floats apart; one launch, asynchronous on `st`.
 #pragma once

@@ -3,7 +3,7 @@
 // and streams of the three-stream pipeline (H2D of group f + 1 || patch launch of group f || D2H + widening of group f - 1).
 // What a caller of the reference writes is `[transform.apply(image) for image in images]` (regularizepsf/transform.py:85-177
 // called in a loop): every frame crosses PCIe twice, which costs several times the kernel, so the copies of neighbouring
-// frames have to overlap each other and the kernel.  Host-only code, included by rpsf.hip.
+// frames have to overlap each other and the kernel.  Host-only code, included through rpsf_plan.hpp (the plan owns a HostPipe; rpsf_host.hip and rpsf_saturated.hip drive it).
 #pragma once
 
 #include <atomic>

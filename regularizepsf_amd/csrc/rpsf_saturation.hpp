@@ -1,5 +1,5 @@
-// rpsf_saturation.hpp - what csrc/rpsf.hip sees of csrc/saturation.hip: the device scratch of a plan's saturation branch and the two
-// halves of the route around the correction of the padded frames (which is the plan's own launch, rpsf.hip).  The unit of work is the
+// rpsf_saturation.hpp - what csrc/rpsf_saturated.hip sees of csrc/saturation.hip: the device scratch of a plan's saturation branch (owned by the
+// plan, rpsf_plan.hpp) and the two halves of the route around the correction of the padded frames (which is the plan's own launch, rpsf.hip).  The unit of work is the
 // frame-group: `frames` frames of one shape; a single frame is a frame-group of one.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // saturation.hip - the saturation branch of ArrayPSFTransform.apply on the device: what SatRun::prepare / finish of
-// rpsf.hip do on the host, for a frame-group: float32 frames of one shape that are already on the GPU.  A single frame is a
+// rpsf_saturated.hip do on the host, for a frame-group: float32 frames of one shape that are already on the GPU.  A single frame is a
 // frame-group of one.  The frame is a grid index (blockIdx.y; the labeller's tiles: blockIdx.z).
 //
 //   F1  sat_pad_batch_kernel                  2N-padded float32 frames and one hot byte per pixel (value > threshold), hot counts

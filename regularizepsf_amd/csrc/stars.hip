@@ -201,20 +201,6 @@ extern "C" void rpsf_stars_destroy(rpsf_stars* s) {
   delete s;
 }
 
-// the frame crosses PCIe once, as float32 - what every other path of the library uploads
-static int upload_frame(rpsf_stars* s, const void* image_host, int image_is_f64) {
-  const size_t npix = (size_t)s->npix();
-  if (image_is_f64) {
-    std::vector<float> narrow(npix);
-    const double* src = static_cast<const double*>(image_host);
-    for (size_t i = 0; i < npix; ++i) narrow[i] = (float)src[i];
-    HIP_TRY(hipMemcpy(s->frame.p, narrow.data(), npix * sizeof(float), hipMemcpyHostToDevice));
-  } else {
-    HIP_TRY(hipMemcpy(s->frame.p, image_host, npix * sizeof(float), hipMemcpyHostToDevice));
-  }
-  return RPSF_OK;
-}
-
 static int upload_mask(rpsf_stars* s, const uint8_t* mask_host_or_null) {
   const size_t npix = (size_t)s->npix();
   if (mask_host_or_null) {
@@ -242,7 +228,7 @@ extern "C" int rpsf_stars_background(rpsf_stars* s, const void* image_host, int 
   const size_t nmesh = (size_t)s->nby * s->nbx;
   HIP_TRY(hipSetDevice(s->device));
   s->have_frame = s->have_mesh = false;
-  if (const int rc = upload_frame(s, image_host, image_is_f64)) return rc;
+  if (const int rc = upload_frame_f32(s->frame.p, image_host, image_is_f64, (size_t)s->npix())) return rc;
   if (const int rc = upload_mask(s, mask_host_or_null)) return rc;
   if (const int rc = mesh_on_device(s)) return rc;
   HIP_TRY(hipMemcpy(level_host, s->level.p, nmesh * sizeof(double), hipMemcpyDeviceToHost));
@@ -411,7 +397,7 @@ extern "C" int rpsf_stars_background_host(rpsf_stars* s, const void* image_host,
   if (!s || !image_host) return fail(RPSF_E_BADARG, "null argument");
   HIP_TRY(hipSetDevice(s->device));
   s->have_frame = s->have_mesh = false;
-  if (const int rc = upload_frame(s, image_host, image_is_f64)) return rc;
+  if (const int rc = upload_frame_f32(s->frame.p, image_host, image_is_f64, (size_t)s->npix())) return rc;
   return background_on_device(s, mask_host_or_null);
 }
 

@@ -114,8 +114,12 @@ def test_development_switches_still_compile(tmp_path):
         "k2_128p.hip": ["-DRPSF_STAMPS", "-DRPSF2_ABL_NOBAR_MASK=20"],
         "k2_128pcs.hip": ["-DRPSF2_SKEL_PRESUM"],  # the round-6 timing skeleton of a lattice-row pre-sum
         "k3_32.hip": ["-DRPSF3_ABL_ONE_K", "-DRPSF3_ABL_ONE_SLAB", "-DRPSF3_ABL_NO_FLUSH", "-DRPSF3_ABL_NO_COLUMN_FFTS", "-DRPSF3_ABL_NO_WAIT", "-DRPSF3_ABL_FORCE_ERR", "-DRPSF3_DIRECT_GATHER", "-DRPSF3_STAMPS"],  # the sweep kernel's ablations (5.8)
-        "rpsf.hip": ["-DRPSF_DEV_ENV"],  # the environment knobs of the development sweeps
     }
+    # the environment knobs of the development sweeps: every unit that reads one (dev_env, csrc/rpsf_plan.hpp)
+    readers = sorted(p.name for p in hip_build.CSRC.glob("*.hip") if "dev_env(" in p.read_text())
+    assert "rpsf.hip" in readers and "rpsf_host.hip" in readers, readers
+    for source in readers:
+        sets[source] = sets.get(source, []) + ["-DRPSF_DEV_ENV"]
     for source, defines in sets.items():
         out = tmp_path / (source + ".o")
         done = subprocess.run([hipcc, *hip_build.FLAGS, *defines, "-c", str(hip_build.CSRC / source), "-o", str(out)],
@@ -141,12 +145,26 @@ def test_the_shipped_library_reads_two_environment_variables():
     header = (ROOT / "include" / "rpsf.h").read_text()
     assert all(name in header for name in reads)
     # the one other getenv of the sources is dev_env's own, under the define the product build never sets
-    host = (hip_build.CSRC / "rpsf.hip").read_text()
-    assert host.count("std::getenv(") == 1 and "#if defined(RPSF_DEV_ENV)\n  return std::getenv(name);" in host
+    texts = {p.name: p.read_text() for p in sorted(hip_build.CSRC.glob("*")) if p.is_file()}
+    bare = {name: text.count("std::getenv(") - text.count('std::getenv("') for name, text in texts.items()}
+    assert {name: n for name, n in bare.items() if n} == {"rpsf_plan.hpp": 1}, bare
+    assert "#if defined(RPSF_DEV_ENV)\n  return std::getenv(name);" in texts["rpsf_plan.hpp"]
+    assert sum(text.count("std::getenv(") for text in texts.values()) == 3
     assert "RPSF_DEV_ENV" not in " ".join(hip_build.FLAGS)
     binary = (ROOT / "regularizepsf_amd" / "librpsf_hip.so").read_bytes()
     for knob in (b"RPSF_STRIPS", b"RPSF_SUM_FIRST", b"RPSF_V1\0", b"RPSF_NO_PERSIST", b"RPSF_K_CACHED", b"RPSF_STREAM_GROUP"):
         assert knob not in binary, knob
+
+
+def test_every_source_and_header_is_in_the_build_lists():
+    """A unit that build.SOURCES forgets shows only as an undefined symbol when the library is loaded, and a header that build.HEADERS
+    forgets gives a stale build: every *.hip of csrc/ is compiled and every *.hpp is watched."""
+    from regularizepsf_amd import build as hip_build
+
+    assert set(hip_build.CSRC.glob("*.hip")) == set(hip_build.SOURCES)
+    assert len(hip_build.SOURCES) == len(set(hip_build.SOURCES))
+    assert set(hip_build.CSRC.glob("*.hpp")) <= set(hip_build.HEADERS)
+    assert ROOT / "include" / "rpsf.h" in hip_build.HEADERS
 
 
 @pytest.mark.parametrize("threads", ["1", "3", "16"])
