@@ -491,7 +491,9 @@ int rpsf_builder_add_frame_scaled(rpsf_builder* builder, const void* image_host,
 int rpsf_builder_downscale(rpsf_builder* builder, int n_cells, const double* cells_f64_host, double* out_f64_host);
 
 /* find_stars: star positions for the builder, upstream of the star list.  The detector is this library's own, modelled on
- * sep.Background + sep.extract WITHOUT deblending; it is not sep and its positions differ from sep's for blended or extended sources.
+ * sep.Background + sep.extract; it is not sep and its positions differ from sep's for blended or extended sources.  Deblending is an
+ * option (rpsf_stars_set_deblend, off by default): one watershed level on the filtered residual with a significance test per basin - not
+ * sep's multi-threshold tree.  Without it touching stars come out as one detection at their common centroid.
  * A finder is made for one frame shape and one background box (8 .. 128 pixels, anything else: RPSF_E_UNSUPPORTED; frames of up to
  * 2^31 - 1 pixels).  A pixel is usable when it is finite and not masked.  Everything is float64 on a frame rounded to float32 once;
  * two runs on one input agree bit for bit. */
@@ -553,6 +555,31 @@ int rpsf_stars_detect_device(rpsf_stars* finder, double threshold, long min_area
 int rpsf_stars_frame(rpsf_stars* finder, const float** frame_dev, int* height, int* width);
 /* Device time of the last S1b, milliseconds. */
 int rpsf_stars_mesh_ms(const rpsf_stars* finder, double* ms);
+
+/* THE DEBLEND OPTION.  rpsf_stars_set_deblend configures the finder: with on != 0 every following
+ * rpsf_stars_detect / rpsf_stars_detect_device splits blended components, with on == 0 (the state of a new finder) nothing of it runs and
+ * every result is bit for bit what it was.  contrast outside [0, 1], prominence < 0 or a non-finite value: RPSF_E_BADARG.
+ *   D1  on detected pixels p is above q when f(p) > f(q), or f(p) == f(q) and index(p) < index(q) (index = row * width + col); up(p) is
+ *       the highest of p and its detected 8-neighbours, peak(p) the fixed point of following up; equal peaks form a basin.
+ *   D2  per basin: area, sum of d (fixed order), saddle = max of min(f(p), f(q)) over 8-adjacent pairs with q in another basin.
+ *   D3  a basin is significant when area >= min_area, flux >= contrast * F (F: the component's sum of d as S4 computes it) and
+ *       f(peak) - saddle >= prominence * T.
+ *   D4  a component with at most one significant basin is one object, its row bit for bit the undeblended one; otherwise one object
+ *       per significant basin, every pixel of an insignificant basin joining the significant peak of its component at the smallest
+ *       (drow)^2 + (dcol)^2, ties to the smaller index.  Rows as for components, kept by the same area and flux rule, in raster order
+ *       of each object's first pixel. */
+int rpsf_stars_set_deblend(rpsf_stars* finder, int on, double contrast, double prominence);
+/* D1 alone on the caller's f (float64) and mask (non-zero = detected) of the finder's shape: peak_host (int32) receives for every
+ * detected pixel the linear index of its basin's peak and -1 elsewhere.  The counterpart of rpsf_stars_label.  f is expected to be free of
+ * NaN on detected pixels (a NaN compares with nothing, so D1's order is not total there; the walks end all the same, because every step
+ * needs f to rise or the index to fall). */
+int rpsf_stars_basins(rpsf_stars* finder, const double* f_host, const uint8_t* detected_host, int32_t* peak_host);
+/* Of the last detect: the number of components, of basins and of components that were split (any pointer may be NULL); basins and
+ * split_components are 0 when the option was off. */
+int rpsf_stars_deblend_info(const rpsf_stars* finder, size_t* components, size_t* basins, size_t* split_components);
+/* Device time of the last D1 - D4 (or of the last rpsf_stars_basins), milliseconds; 0 when the option was off. */
+int rpsf_stars_deblend_ms(const rpsf_stars* finder, double* ms);
+
 /* rpsf_builder_add_frame on a dense float32 frame that is already on the builder's device - a finder's (rpsf_stars_frame) or the caller's
  * own; it is only read, nothing is uploaded but the star list.  On a scaled builder the frame is the SCALED one and height and width are
  * its. */

@@ -157,6 +157,10 @@ _PROTOTYPES = {
     "rpsf_stars_detect_device": (c_int, [c_void_p, c_double, ctypes.c_long, ctypes.c_long, POINTER(c_size_t)]),
     "rpsf_stars_frame": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int)]),
     "rpsf_stars_mesh_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rpsf_stars_set_deblend": (c_int, [c_void_p, c_int, c_double, c_double]),
+    "rpsf_stars_basins": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rpsf_stars_deblend_info": (c_int, [c_void_p, POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t)]),
+    "rpsf_stars_deblend_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rpsf_builder_add_frame_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double, c_double,
                                               c_void_p]),
     "rpsf_saturation_fill": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),

@@ -34,7 +34,8 @@ CLEANED, DEGENERATE_CELL = 0, 1  # flags of a cell after the device clean-up
 CLEANUPS = ("host", "device")
 INTERPOLATIONS = ("off", "device")
 FINDERS = ("sep", "device")
-FINDER_OPTIONS = {"box": 64, "min_area": 5, "max_area": None}  # find_stars's defaults
+FINDER_OPTIONS = {"box": 64, "min_area": 5, "max_area": None,
+                  "deblend": False, "deblend_contrast": 0.005, "deblend_prominence": 1.0}  # find_stars's defaults
 MAX_PATCH = 128  # the largest patch the kernels cut: psf_size * interpolation_scale may not exceed it
 
 
@@ -131,7 +132,7 @@ def _dense_f32(frame):
 
 def _finder_options(finder: str, options) -> dict:
     """``finder_options`` of the constructor with find_stars's defaults and range checks."""
-    from regularizepsf_amd.stars import MAX_BOX, MIN_BOX
+    from regularizepsf_amd.stars import MAX_BOX, MIN_BOX, deblend_options
 
     if options is None:
         return dict(FINDER_OPTIONS)
@@ -145,6 +146,8 @@ def _finder_options(finder: str, options) -> dict:
     if not MIN_BOX <= int(merged["box"]) <= MAX_BOX:
         msg = f"box must lie in {MIN_BOX} ... {MAX_BOX}, got {merged['box']}"
         raise ValueError(msg)
+    merged["deblend"], merged["deblend_contrast"], merged["deblend_prominence"] = deblend_options(
+        merged["deblend"], merged["deblend_contrast"], merged["deblend_prominence"])
     return merged
 
 
@@ -446,7 +449,8 @@ class ArrayPSFBuilder:
         ``"device"`` is this package's detector (``find_stars``; it is not ``sep``) on the fused route: per frame one upload at most, the
         background mesh filtered on the device, the patches cut from the frame the stars were found in - bit for bit
         ``build(frames, stars=find_stars(frames, star_threshold, sep_mask, **finder_options))``.  ``finder_options``: a dict with any of
-        ``box``, ``min_area``, ``max_area`` (``find_stars``'s defaults), only with ``finder="device"``."""
+        ``box``, ``min_area``, ``max_area``, ``deblend``, ``deblend_contrast``, ``deblend_prominence`` (``find_stars``'s defaults), only with
+        ``finder="device"``."""
         if finder not in FINDERS:
             msg = f"finder must be one of {FINDERS}, not {finder!r}"
             raise ValueError(msg)
@@ -552,6 +556,8 @@ class ArrayPSFBuilder:
             options = self._finder_options
             masks = star_finder._masks(sep_mask, frames, seen_shape)
             finder = star_finder._Finder(seen_shape, options["box"], self._device)
+            if options["deblend"]:
+                finder.set_deblend(True, options["deblend_contrast"], options["deblend_prominence"])
             stars = [None] * len(frames)
         elif stars is None:
             if on_device:

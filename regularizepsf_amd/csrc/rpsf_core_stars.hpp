@@ -235,9 +235,10 @@ RPSFS_HD double s2_filter(const double* dl, int hr, int hc) {
   return ((h[0] + 2.0 * h[1]) + h[2]) / 16.0;
 }
 
-// Tile (ty, tx): det[p] = 1 where the filtered residual exceeds T on a usable pixel.  `L` is the whole filtered mesh.
+// Tile (ty, tx): det[p] = 1 where the filtered residual exceeds T on a usable pixel.  `L` is the whole filtered mesh.  `fout`, when given,
+// takes the filtered residual of every pixel: the bits the threshold saw, for the deblend option (rpsf_core_stars_deblend.hpp).
 template <class Ctx>
-RPSFS_HD void s2_tile(Ctx& ctx, const Frame& fr, const double* L, double T, int ty, int tx, void* lds, uint8_t* det) {
+RPSFS_HD void s2_tile(Ctx& ctx, const Frame& fr, const double* L, double T, int ty, int tx, void* lds, uint8_t* det, double* fout = nullptr) {
   double* dl = static_cast<double*>(lds);
   double* mw = dl + HALO_N;
   const int r0 = ty * TILE_R, c0 = tx * TILE_C;
@@ -265,7 +266,9 @@ RPSFS_HD void s2_tile(Ctx& ctx, const Frame& fr, const double* L, double T, int 
       const int lr = p / TILE_C, lc = p % TILE_C, r = r0 + lr, c = c0 + lc;
       if (r >= fr.H || c >= fr.W) continue;
       const size_t g = (size_t)r * fr.W + c;
-      det[g] = (s2_filter(dl, lr + 1, lc + 1) > T && usable(fr.img, fr.mask, g)) ? 1 : 0;
+      const double f = s2_filter(dl, lr + 1, lc + 1);
+      det[g] = (f > T && usable(fr.img, fr.mask, g)) ? 1 : 0;
+      if (fout) fout[g] = f;
     }
   });
 }

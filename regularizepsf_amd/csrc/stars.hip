@@ -11,6 +11,10 @@
 //   S4  stars_count/scan/roots the roots in index order; stars_init/accumulate: area and bounding box by integer atomics;
 //       stars_walk_kernel      one wave per component of an accepted area: float64 moments over its bounding box, fixed tree
 //
+//   D1 - D4 deblend_*         the deblend option (rpsf_stars_set_deblend; off by default, and then none of this runs): S2 also stores
+//                              the filtered residual; ascent to the peaks, basins, significance, ownership, moments per object
+//                              (the drivers of rpsf_core_stars_deblend.hpp)
+//
 // The phases are the drivers of rpsf_core_stars.hpp.  Launches follow one another on the null stream; no workgroup ever waits for
 // another one, and the only atomics are integer min / max / add - labels and moments are the same on every run.
 #include <hip/hip_runtime.h>
@@ -22,6 +26,7 @@
 #include "rpsf_convert.hpp"
 #include "rpsf_core_convert.hpp"
 #include "rpsf_core_stars.hpp"
+#include "rpsf_core_stars_deblend.hpp"
 #include "rpsf_core_stars_mesh.hpp"
 #include "rpsf_scale.hpp"
 #include "rpsf_side_unit.hpp"
@@ -102,6 +107,52 @@ __global__ __launch_bounds__(WALK_THREADS) void stars_walk_kernel(Frame fr, cons
           moments);
 }
 
+// ------------------------------------------------------------------------------------------------ the deblend option
+// S2 that also stores the filtered residual; T from device memory when T_dev is given
+__global__ __launch_bounds__(TILE_THREADS) void stars_detect_f_kernel(Frame fr, const double* L, const double* T_dev, double T, uint8_t* det,
+                                                                      double* f) {
+  GpuCtx ctx;
+  s2_tile(ctx, fr, L, T_dev ? T_dev[0] : T, (int)blockIdx.y, (int)blockIdx.x, stars_lds, det, f);
+}
+__global__ __launch_bounds__(256) void deblend_up_kernel(int H, int W, const double* f, const uint8_t* det, int32_t* up) {
+  rpsfd::d1_up(global_id(), H, W, f, det, up);
+}
+__global__ __launch_bounds__(256) void deblend_peak_kernel(long npix, const int32_t* up, int32_t* peak) {
+  rpsfd::d1_peak(global_id(), npix, up, peak);
+}
+__global__ __launch_bounds__(256) void deblend_init_kernel(long nb, int W, const int* peaks, int* bstats, uint64_t* saddle) {
+  rpsfd::d2_init(global_id(), nb, W, peaks, bstats, saddle);
+}
+__global__ __launch_bounds__(256) void deblend_accumulate_kernel(int H, int W, const double* f, const int32_t* peak, const int* peaks, long nb,
+                                                                 int* bstats, uint64_t* saddle) {
+  rpsfd::d2_accumulate(global_id(), H, W, f, peak, peaks, nb, bstats, saddle);
+}
+__global__ __launch_bounds__(256) void deblend_want_kernel(long nb, const uint64_t* saddle, uint8_t* want) {
+  rpsfd::d2_want(global_id(), nb, saddle, want);
+}
+__global__ __launch_bounds__(WALK_THREADS) void deblend_walk_kernel(Frame fr, const double* L, const int32_t* labels, rpsfd::Objects o,
+                                                                    double* out) {
+  GpuCtx ctx;
+  rpsfd::d_walk(ctx, fr, L, labels, o, (long)blockIdx.x * WALK_WAVES, reinterpret_cast<double*>(stars_lds), out);
+}
+__global__ __launch_bounds__(256) void deblend_significant_kernel(long nb, int W, const double* f, const int32_t* labels, const int* roots,
+                                                                  long count, const double* moments, const int* peaks, const int* bstats,
+                                                                  const uint64_t* saddle, const double* bflux, rpsfd::Significance s,
+                                                                  const double* T_dev, int* bcomp, uint8_t* sig, int* nsig, int* ostats) {
+  if (T_dev) s.T = T_dev[0];
+  rpsfd::d3_significant(global_id(), nb, W, f, labels, roots, count, moments, peaks, bstats, saddle, bflux, s, bcomp, sig, nsig, ostats);
+}
+__global__ __launch_bounds__(rpsfd::OWN_THREADS) void deblend_own_kernel(int W, const int32_t* labels, const int* roots, const int* stats,
+                                                                         const int32_t* peak, const int* peaks, long nb, const int* bcomp,
+                                                                         const uint8_t* sig, const int* nsig, int32_t* owner, int* ostats) {
+  GpuCtx ctx;
+  rpsfd::d4_own(ctx, W, labels, roots, stats, (long)blockIdx.x, peak, peaks, nb, bcomp, sig, nsig, stars_lds, owner, ostats);
+}
+__global__ __launch_bounds__(256) void deblend_objects_kernel(long nb, const int* bcomp, const uint8_t* sig, const int* nsig, const int* ostats,
+                                                              long min_area, long max_area, uint8_t* want) {
+  rpsfd::d4_want(global_id(), nb, bcomp, sig, nsig, ostats, min_area, max_area, want);
+}
+
 struct rpsf_stars {
   int device = 0, H = 0, W = 0, box = 0, nby = 0, nbx = 0;
   bool have_frame = false;
@@ -118,6 +169,16 @@ struct rpsf_stars {
   Buf<double> level, rms, moments;
   Buf<int> segcnt, segoff, total, roots, stats;
   std::vector<double> found;  // rows (row, col, flux, area) of the last detect
+  // the deblend option: everything below is allocated by the first call that needs it
+  bool deblend = false;
+  double contrast = 0.005, prominence = 1.0;
+  Buf<double> f, bflux, omoments;  // the filtered residual per pixel; (sum d, .., .., area) per basin and per object
+  Buf<int32_t> up, peak, owner;
+  Buf<int> peaks, bstats, ostats, bcomp, nsig;
+  Buf<uint64_t> saddle;
+  Buf<uint8_t> sig, want;
+  size_t n_components = 0, n_basins = 0, n_split = 0;  // of the last detect
+  double deblend_ms = 0;
   hipEvent_t ev[2] = {nullptr, nullptr};
   double ms[4] = {0, 0, 0, 0};
   long npix() const { return (long)H * W; }
@@ -238,6 +299,7 @@ extern "C" int rpsf_stars_background(rpsf_stars* s, const void* image_host, int 
 }
 
 static int detect_on_device(rpsf_stars* s, const double* L, const double* T_dev, double T, long min_area, long max_area, size_t* count);
+static int deblend_on_device(rpsf_stars* s, const double* L, const double* T_dev, double T, long min_area, long max_area, long n);
 
 extern "C" int rpsf_stars_detect(rpsf_stars* s, const double* level_host, double threshold_abs, long min_area, long max_area,
                                  size_t* count) {
@@ -256,10 +318,15 @@ extern "C" int rpsf_stars_detect(rpsf_stars* s, const double* level_host, double
 static int detect_on_device(rpsf_stars* s, const double* L, const double* T_dev, double T, long min_area, long max_area, size_t* count) {
   s->found.clear();
   *count = 0;
-  s->ms[1] = s->ms[2] = s->ms[3] = 0;
+  s->ms[1] = s->ms[2] = s->ms[3] = s->deblend_ms = 0;
+  s->n_components = s->n_basins = s->n_split = 0;
   const dim3 tiles((s->W + TILE_C - 1) / TILE_C, (s->H + TILE_R - 1) / TILE_R);
+  if (s->deblend) HIP_TRY(s->f.reserve((size_t)s->npix()));
   if (const int rc = timed(s, &s->ms[1], [&] {
-        if (T_dev) {
+        if (s->deblend) {
+          hipLaunchKernelGGL(stars_detect_f_kernel, tiles, dim3(TILE_THREADS), s2_lds_bytes(), nullptr, s->view(), L, T_dev, T, s->det.p,
+                             s->f.p);
+        } else if (T_dev) {
           hipLaunchKernelGGL(stars_detect_device_kernel, tiles, dim3(TILE_THREADS), s2_lds_bytes(), nullptr, s->view(), L, T_dev, s->det.p);
         } else {
           hipLaunchKernelGGL(stars_detect_kernel, tiles, dim3(TILE_THREADS), s2_lds_bytes(), nullptr, s->view(), L, T, s->det.p);
@@ -277,6 +344,8 @@ static int detect_on_device(rpsf_stars* s, const double* L, const double* T_dev,
   HIP_TRY(hipMemcpy(&total, s->total.p, sizeof(int), hipMemcpyDeviceToHost));
   if (total <= 0) return RPSF_OK;
   const long n = total;
+  s->n_components = (size_t)n;
+  const long walk_max = s->deblend ? -1 : max_area;  // D3 needs every component's sum; the area limits are applied to the rows below
   HIP_TRY(s->roots.reserve((size_t)n));
   HIP_TRY(s->stats.reserve(4 * (size_t)n));
   HIP_TRY(s->moments.reserve(4 * (size_t)n));
@@ -287,9 +356,14 @@ static int detect_on_device(rpsf_stars* s, const double* L, const double* T_dev,
         hipLaunchKernelGGL(stars_accumulate_kernel, dim3(blocks_for(s->npix())), dim3(256), 0, nullptr, s->npix(), s->W, s->labels.p,
                            s->roots.p, n, s->stats.p);
         hipLaunchKernelGGL(stars_walk_kernel, dim3((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS), s4_walk_lds_bytes(),
-                           nullptr, s->view(), L, s->labels.p, s->roots.p, s->stats.p, n, min_area, max_area, s->moments.p);
+                           nullptr, s->view(), L, s->labels.p, s->roots.p, s->stats.p, n, min_area, walk_max, s->moments.p);
       }))
     return rc;
+  if (s->deblend) {
+    if (const int rc = deblend_on_device(s, L, T_dev, T, min_area, max_area, n)) return rc;
+    *count = s->found.size() / 4;
+    return RPSF_OK;
+  }
   std::vector<double> m(4 * (size_t)n);
   HIP_TRY(hipMemcpy(m.data(), s->moments.p, m.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (long k = 0; k < n; ++k) {  // roots ascend: this is the raster order of each component's first pixel
@@ -298,6 +372,117 @@ static int detect_on_device(rpsf_stars* s, const double* L, const double* T_dev,
     s->found.insert(s->found.end(), {m[4 * k + 1] / flux, m[4 * k + 2] / flux, flux, area});
   }
   *count = s->found.size() / 4;
+  return RPSF_OK;
+}
+
+static void launch_ascent(rpsf_stars* s) {
+  hipLaunchKernelGGL(deblend_up_kernel, dim3(blocks_for(s->npix())), dim3(256), 0, nullptr, s->H, s->W, s->f.p, s->det.p, s->up.p);
+  hipLaunchKernelGGL(deblend_peak_kernel, dim3(blocks_for(s->npix())), dim3(256), 0, nullptr, s->npix(), s->up.p, s->peak.p);
+}
+
+// D1 - D4 after S2 (with f) - S4 (every component of at least min_area walked) of the same frame: the rows into s->found
+static int deblend_on_device(rpsf_stars* s, const double* L, const double* T_dev, double T, long min_area, long max_area, long n) {
+  const size_t npix = (size_t)s->npix();
+  HIP_TRY(s->up.reserve(npix));
+  HIP_TRY(s->peak.reserve(npix));
+  HIP_TRY(s->owner.reserve(npix));
+  if (const int rc = timed(s, &s->deblend_ms, [&] {
+        launch_ascent(s);
+        hipLaunchKernelGGL(stars_count_kernel, dim3(blocks_for(s->nseg())), dim3(256), 0, nullptr, s->H, s->W, s->peak.p, s->segcnt.p);
+        hipLaunchKernelGGL(stars_scan_kernel, dim3(1), dim3(SCAN_THREADS), (SCAN_THREADS + 32) * sizeof(int), nullptr, s->nseg(),
+                           s->segcnt.p, s->segoff.p, s->total.p);
+      }))
+    return rc;
+  int total = 0;
+  HIP_TRY(hipMemcpy(&total, s->total.p, sizeof(int), hipMemcpyDeviceToHost));
+  if (total < 1) return fail(RPSF_E_HIP, "deblend: components without a peak");  // every component has its highest pixel
+  const long nb = total;
+  s->n_basins = (size_t)nb;
+  HIP_TRY(s->peaks.reserve((size_t)nb));
+  HIP_TRY(s->bstats.reserve(rpsfd::BOX * (size_t)nb));
+  HIP_TRY(s->ostats.reserve(rpsfd::BOX * (size_t)nb));
+  HIP_TRY(s->bcomp.reserve((size_t)nb));
+  HIP_TRY(s->saddle.reserve((size_t)nb));
+  HIP_TRY(s->sig.reserve((size_t)nb));
+  HIP_TRY(s->want.reserve((size_t)nb));
+  HIP_TRY(s->bflux.reserve(4 * (size_t)nb));
+  HIP_TRY(s->omoments.reserve(4 * (size_t)nb));
+  HIP_TRY(s->nsig.reserve((size_t)n));
+  const rpsfd::Significance test{min_area, s->contrast, s->prominence, T};
+  const unsigned per_basin = blocks_for(nb), walks = (unsigned)((nb + WALK_WAVES - 1) / WALK_WAVES);
+  if (const int rc = timed(s, &s->deblend_ms, [&] {
+        hipLaunchKernelGGL(stars_roots_kernel, dim3(blocks_for(s->nseg())), dim3(256), 0, nullptr, s->H, s->W, s->peak.p, s->segoff.p,
+                           s->peaks.p);
+        hipLaunchKernelGGL(deblend_init_kernel, dim3(per_basin), dim3(256), 0, nullptr, nb, s->W, s->peaks.p, s->bstats.p, s->saddle.p);
+        hipLaunchKernelGGL(deblend_accumulate_kernel, dim3(blocks_for(s->npix())), dim3(256), 0, nullptr, s->H, s->W, s->f.p, s->peak.p,
+                           s->peaks.p, nb, s->bstats.p, s->saddle.p);
+        hipLaunchKernelGGL(deblend_want_kernel, dim3(per_basin), dim3(256), 0, nullptr, nb, s->saddle.p, s->want.p);
+        hipLaunchKernelGGL(deblend_walk_kernel, dim3(walks), dim3(WALK_THREADS), s4_walk_lds_bytes(), nullptr, s->view(), L, s->labels.p,
+                           rpsfd::Objects{s->peak.p, s->peaks.p, s->bstats.p, s->want.p, nb}, s->bflux.p);
+        (void)hipMemsetAsync(s->nsig.p, 0, (size_t)n * sizeof(int), nullptr);
+        hipLaunchKernelGGL(deblend_significant_kernel, dim3(per_basin), dim3(256), 0, nullptr, nb, s->W, s->f.p, s->labels.p, s->roots.p, n,
+                           s->moments.p, s->peaks.p, s->bstats.p, s->saddle.p, s->bflux.p, test, T_dev, s->bcomp.p, s->sig.p, s->nsig.p,
+                           s->ostats.p);
+        hipLaunchKernelGGL(deblend_own_kernel, dim3((unsigned)n), dim3(rpsfd::OWN_THREADS), rpsfd::d4_own_lds_bytes(), nullptr, s->W,
+                           s->labels.p, s->roots.p, s->stats.p, s->peak.p, s->peaks.p, nb, s->bcomp.p, s->sig.p, s->nsig.p, s->owner.p,
+                           s->ostats.p);
+        hipLaunchKernelGGL(deblend_objects_kernel, dim3(per_basin), dim3(256), 0, nullptr, nb, s->bcomp.p, s->sig.p, s->nsig.p, s->ostats.p,
+                           min_area, max_area, s->want.p);
+        hipLaunchKernelGGL(deblend_walk_kernel, dim3(walks), dim3(WALK_THREADS), s4_walk_lds_bytes(), nullptr, s->view(), L, s->labels.p,
+                           rpsfd::Objects{s->owner.p, s->peaks.p, s->ostats.p, s->want.p, nb}, s->omoments.p);
+      }))
+    return rc;
+  std::vector<double> moments(4 * (size_t)n), omoments(4 * (size_t)nb);
+  std::vector<int> roots((size_t)n), nsig((size_t)n), bcomp((size_t)nb), ostats(rpsfd::BOX * (size_t)nb);
+  std::vector<uint8_t> sig((size_t)nb);
+  HIP_TRY(hipMemcpy(moments.data(), s->moments.p, moments.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(omoments.data(), s->omoments.p, omoments.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(roots.data(), s->roots.p, roots.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(nsig.data(), s->nsig.p, nsig.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(bcomp.data(), s->bcomp.p, bcomp.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ostats.data(), s->ostats.p, ostats.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(sig.data(), s->sig.p, sig.size(), hipMemcpyDeviceToHost));
+  s->found = rpsfd::deblend_rows(n, roots.data(), moments.data(), nsig.data(), nb, bcomp.data(), sig.data(), ostats.data(), omoments.data(),
+                                 min_area, max_area, &s->n_split);
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_set_deblend(rpsf_stars* s, int on, double contrast, double prominence) {
+  if (!s) return fail(RPSF_E_BADARG, "null argument");
+  if (!(contrast >= 0.0 && contrast <= 1.0)) return fail(RPSF_E_BADARG, "deblend contrast must lie in 0 ... 1");
+  if (!(prominence >= 0.0) || !std::isfinite(prominence)) return fail(RPSF_E_BADARG, "deblend prominence must be finite and not negative");
+  s->deblend = on != 0, s->contrast = contrast, s->prominence = prominence;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_basins(rpsf_stars* s, const double* f_host, const uint8_t* detected_host, int32_t* peak_host) {
+  if (!s || !f_host || !detected_host || !peak_host) return fail(RPSF_E_BADARG, "null argument");
+  const size_t npix = (size_t)s->npix();
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(s->f.reserve(npix));
+  HIP_TRY(s->up.reserve(npix));
+  HIP_TRY(s->peak.reserve(npix));
+  std::vector<uint8_t> flags(npix);
+  for (size_t i = 0; i < npix; ++i) flags[i] = detected_host[i] != 0;
+  HIP_TRY(hipMemcpy(s->det.p, flags.data(), npix, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->f.p, f_host, npix * sizeof(double), hipMemcpyHostToDevice));
+  s->deblend_ms = 0;
+  if (const int rc = timed(s, &s->deblend_ms, [&] { launch_ascent(s); })) return rc;
+  HIP_TRY(hipMemcpy(peak_host, s->peak.p, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_deblend_info(const rpsf_stars* s, size_t* components, size_t* basins, size_t* split_components) {
+  if (!s) return fail(RPSF_E_BADARG, "null argument");
+  if (components) *components = s->n_components;
+  if (basins) *basins = s->n_basins;
+  if (split_components) *split_components = s->n_split;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_deblend_ms(const rpsf_stars* s, double* ms) {
+  if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
+  *ms = s->deblend_ms;
   return RPSF_OK;
 }
 

@@ -4,12 +4,14 @@
 a sigma-clipped background mesh, a bilinear surface through it, a 3 x 3 smoothing filter, a threshold in units of the global
 background rms, 8-connected components and their flux-weighted centroids (the definition is DESIGN.md 3.7).
 
-It is NOT ``sep``: there is no deblending, the box statistic is a clipped median / mean rule without ``sep``'s histogram mode
-estimate, and the background surface is bilinear where ``sep``'s is bicubic.  Positions differ from ``sep``'s for blended or
-extended sources.  Isolated stars on a smooth background - what a PSF model is built from - come out at their centroids.
+It is NOT ``sep``: deblending is an option (``deblend=True``, off by default) and then one watershed level on the filtered residual
+with a significance test per basin, not ``sep``'s multi-threshold tree; without it touching stars come out as
+one detection at their common centroid.  The box statistic is a clipped median / mean rule without ``sep``'s histogram mode estimate,
+and the background surface is bilinear where ``sep``'s is bicubic.  Positions differ from ``sep``'s for blended or extended sources.
+Isolated stars on a smooth background - what a PSF model is built from - come out at their centroids.
 
 Four kernel groups behind ``rpsf_stars_*`` (include/rpsf.h) do the work on whole frames: the mesh (S1), detection (S2),
-labelling (S3) and moments (S4).  For host frames the host keeps the bookkeeping: filling and median-filtering the mesh (a few
+labelling (S3) and moments (S4); with ``deblend=True`` a fifth (D1 - D4) splits blended components after S4.  For host frames the host keeps the bookkeeping: filling and median-filtering the mesh (a few
 thousand numbers, ``filter_mesh``) between S1 and S2.  Device frames (``DeviceArray`` or anything with
 ``__cuda_array_interface__``) take the fused route of DESIGN.md 3.11, which ``ArrayPSFBuilder(..., finder="device")`` takes for
 every frame: the frame is read where it lies, kernel S1b does ``filter_mesh``'s work on the device - the same bits - and nothing but
@@ -27,6 +29,22 @@ from regularizepsf_amd.device_array import is_device_array
 from regularizepsf_amd.exceptions import IncorrectShapeError
 
 MIN_BOX, MAX_BOX = 8, 128
+DEBLEND_OPTIONS = {"deblend": False, "deblend_contrast": 0.005, "deblend_prominence": 1.0}  # contrast: sep's deblend_cont
+
+
+def deblend_options(deblend, deblend_contrast, deblend_prominence) -> tuple[bool, float, float]:
+    """The three deblend options of ``find_stars`` and ``finder_options``, range-checked."""
+    if not isinstance(deblend, (bool, np.bool_)):
+        msg = f"deblend must be True or False, not {deblend!r}"
+        raise ValueError(msg)
+    contrast, prominence = float(deblend_contrast), float(deblend_prominence)
+    if not 0.0 <= contrast <= 1.0:
+        msg = f"deblend_contrast must lie in 0 ... 1, got {deblend_contrast}"
+        raise ValueError(msg)
+    if not (prominence >= 0.0 and np.isfinite(prominence)):
+        msg = f"deblend_prominence must be finite and not negative, got {deblend_prominence}"
+        raise ValueError(msg)
+    return bool(deblend), contrast, prominence
 
 
 class _Finder:
@@ -120,6 +138,33 @@ class _Finder:
         self._native.check(self._native.lib().rpsf_stars_frame(self._handle, ctypes.byref(ptr), None, None))
         return ptr.value
 
+    def set_deblend(self, on: bool, contrast: float = 0.005, prominence: float = 1.0) -> None:
+        """Every following ``detect`` / ``detect_device`` splits blended components (D1 - D4), or, ``on`` False, does what it did."""
+        self._native.check(self._native.lib().rpsf_stars_set_deblend(self._handle, int(bool(on)), float(contrast), float(prominence)))
+
+    def basins(self, f: np.ndarray, detected: np.ndarray) -> np.ndarray:
+        """D1 alone: per detected pixel the linear index of its basin's peak in ``f``, -1 elsewhere."""
+        n = self._native
+        f, flags = np.ascontiguousarray(f, np.float64), np.ascontiguousarray(detected, np.uint8)
+        if f.shape != self.shape or flags.shape != self.shape:
+            msg = f"f and the mask must have the finder's shape {self.shape}"
+            raise IncorrectShapeError(msg)
+        peak = np.empty(self.shape, np.int32)
+        n.check(n.lib().rpsf_stars_basins(self._handle, n._ptr(f), n._ptr(flags), n._ptr(peak)))
+        return peak
+
+    def deblend_info(self) -> tuple[int, int, int]:
+        """Of the last detect: components, basins, split components."""
+        counts = [ctypes.c_size_t(0) for _ in range(3)]
+        self._native.check(self._native.lib().rpsf_stars_deblend_info(self._handle, *(ctypes.byref(c) for c in counts)))
+        return tuple(c.value for c in counts)
+
+    def deblend_ms(self) -> float:
+        """Device time of the last D1 - D4."""
+        ms = ctypes.c_double(0)
+        self._native.check(self._native.lib().rpsf_stars_deblend_ms(self._handle, ctypes.byref(ms)))
+        return ms.value
+
     def mesh_ms(self) -> float:
         """Device time of the last S1b."""
         ms = ctypes.c_double(0)
@@ -210,6 +255,7 @@ def _masks(mask, frames: list, shape: tuple[int, int] | None = None) -> list[np.
 
 
 def find_stars(images, threshold: float = 3.0, mask=None, *, box: int = 64, min_area: int = 5, max_area: int | None = None,
+               deblend: bool = False, deblend_contrast: float = 0.005, deblend_prominence: float = 1.0,
                device: int = 0) -> list[np.ndarray]:
     """Star positions per frame, in the form ``ArrayPSFBuilder.build(..., stars=...)`` takes: a list of ``(k, 2)`` float64
     arrays of ``(row, col)``, one per frame; a frame without detections gives shape ``(0, 2)``.
@@ -219,8 +265,14 @@ def find_stars(images, threshold: float = 3.0, mask=None, *, box: int = 64, min_
     and strides ``apply`` takes - they are read where they lie, and the result is the host call's on the same values.  ``threshold``: in units
     of the frame's global background rms.  ``mask``: None, one 2-D boolean array for all frames or one per frame (True = ignore).
     ``box``: the background box in pixels, 8 ... 128.  A component is kept when ``min_area <= area <= max_area`` (None: no
-    upper limit) and its background-subtracted flux is positive.  Not ``sep``: see the module docstring.
+    upper limit) and its background-subtracted flux is positive.  ``deblend``: split touching stars - inside each component every
+    pixel ascends the filtered residual to a peak, and a peak's basin becomes an object of its own when its area is at least
+    ``min_area``, its flux at least ``deblend_contrast`` (0 ... 1; ``sep``'s ``deblend_cont``) of the component's and its peak at least
+    ``deblend_prominence`` thresholds above the saddle to its neighbours; the area and flux rule then applies per object.  Off (the
+    default), every result is what it was.  Not ``sep``, and with ``deblend`` still not ``sep``'s multi-threshold tree: see the module
+    docstring.
     """
+    split = deblend_options(deblend, deblend_contrast, deblend_prominence)
     if not MIN_BOX <= int(box) <= MAX_BOX:
         msg = f"box must lie in {MIN_BOX} ... {MAX_BOX}, got {box}"
         raise ValueError(msg)
@@ -231,6 +283,8 @@ def find_stars(images, threshold: float = 3.0, mask=None, *, box: int = 64, min_
     masks = _masks(mask, frames)
     finder = _Finder(frames[0].shape, box, device)
     try:
+        if split[0]:
+            finder.set_deblend(*split)
         return [np.ascontiguousarray(one_frame(finder, frame, m, float(threshold), int(min_area), max_area)[:, :2])
                 for frame, m in zip(frames, masks)]
     finally:

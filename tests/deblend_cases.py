@@ -1,0 +1,433 @@
+"""The deblend option of the star finder restated in float64 NumPy, seeded frames with blended stars, the CPU
+emulator of its kernels, and the checks the emulator tests (tests/test_deblend_host.py) and the GPU tests (tests/test_gpu_deblend.py)
+share.
+
+As for the detector itself there is no outside implementation: the reference is the restatement below, built on star_cases' (mesh,
+surface, filter, labels) with D1 - D4 in array operations, computed once per case.  A check takes `make_finder(shape, box)`:
+regularizepsf_amd.stars._Finder on the GPU, EmuFinder here.
+"""
+
+from __future__ import annotations
+
+import ctypes
+import functools
+
+import numpy as np
+
+from tests import star_cases as sc
+
+ROOT = sc.ROOT
+NEIGHBOURS = [(dr, dc) for dr in (-1, 0, 1) for dc in (-1, 0, 1) if (dr, dc) != (0, 0)]
+HALF = [(0, 1), (1, -1), (1, 0), (1, 1)]  # every 8-adjacent pair once
+
+
+# ------------------------------------------------------------------------------------------------------------------ the restatement
+def _shifted(a: np.ndarray, dr: int, dc: int, fill):
+    """a[r + dr, c + dc] at (r, c), `fill` outside the frame."""
+    h, w = a.shape
+    return np.pad(a, 1, constant_values=fill)[1 + dr:1 + dr + h, 1 + dc:1 + dc + w]
+
+
+def ref_basins(f: np.ndarray, detected: np.ndarray) -> np.ndarray:
+    """D1: per detected pixel the linear index of the peak its ascent ends at, -1 elsewhere."""
+    f, detected = np.asarray(f, np.float64), np.asarray(detected, bool)
+    index = np.arange(f.size).reshape(f.shape)
+    best_f, best_i = f.copy(), index.copy()
+    for dr, dc in NEIGHBOURS:
+        cand_f, cand_i, there = _shifted(f, dr, dc, 0.0), _shifted(index, dr, dc, -1), _shifted(detected, dr, dc, False)
+        better = there & ((cand_f > best_f) | ((cand_f == best_f) & (cand_i < best_i)))
+        best_f, best_i = np.where(better, cand_f, best_f), np.where(better, cand_i, best_i)
+    peak = np.where(detected, best_i, -1).ravel()
+    on = peak >= 0
+    while True:  # pointer jumping: every pass at least halves the distance to the fixed point
+        nxt = peak.copy()
+        nxt[on] = peak[peak[on]]
+        if np.array_equal(nxt, peak):
+            return peak.reshape(f.shape).astype(np.int32)
+        peak = nxt
+
+
+def ref_deblend(frame: np.ndarray, mask: np.ndarray | None, box: int, threshold: float = 3.0, min_area: int = 5,
+                max_area: int | None = None, contrast: float = 0.005, prominence: float = 1.0) -> dict:
+    """The definition with the option on.  rows: (k, 4) of (row, col, flux, area) in raster order of each object's first pixel, abs_flux
+    = sum |d| per kept object; components, basins, split; the preconditions' figures gap_clip, gap_threshold (star_cases.ref_detect's)
+    and gap_ascent, gap_prominence, gap_contrast."""
+    frame = np.asarray(frame, np.float32).astype(np.float64)
+    ok = np.isfinite(frame) & (~mask if mask is not None else True)
+    level, rms, gap_clip = sc.ref_mesh(frame, mask, box)
+    filtered = sc.ref_filter_mesh(level, rms)
+    out = {"rows": np.zeros((0, 4)), "abs_flux": np.zeros(0), "components": 0, "basins": 0, "split": 0, "gap_clip": gap_clip,
+           "gap_threshold": np.inf, "gap_ascent": np.inf, "gap_prominence": np.inf, "gap_contrast": np.inf}
+    if filtered is None:
+        return out
+    level_f, _, global_rms = filtered
+    T = threshold * global_rms
+    with np.errstate(invalid="ignore"):
+        d = np.where(ok, frame - sc.ref_surface(level_f, frame.shape, box), 0.0)
+    f = sc.ref_filter(d)
+    detected = (f > T) & ok
+    out["gap_threshold"] = float(np.min(np.abs(f - T)) / abs(T)) if T != 0 else np.inf
+    if not detected.any():
+        return out
+    labels, peak = sc.ref_labels(detected).ravel(), ref_basins(f, detected).ravel()
+    pix = np.flatnonzero(detected)
+    rr, cc = np.divmod(pix, frame.shape[1])
+    dv, fv = d.ravel()[pix], f.ravel()
+    comps, comp_of = np.unique(labels[pix], return_inverse=True)  # ascending roots
+    basins, basin_of = np.unique(peak[pix], return_inverse=True)  # ascending peaks
+    bcomp = np.searchsorted(comps, labels[basins])
+    area = np.bincount(basin_of)
+    flux = np.bincount(basin_of, dv)
+    F = np.bincount(comp_of, dv)
+    # D2: the saddles, and the ascent's gap on the way
+    saddle, slot = np.full(len(basins), -np.inf), np.full(frame.size, -1)
+    slot[pix] = basin_of
+    slot = slot.reshape(frame.shape)
+    for dr, dc in HALF:
+        both = detected & _shifted(detected, dr, dc, False)
+        fq, sq = _shifted(f, dr, dc, 0.0), _shifted(slot, dr, dc, -1)
+        differ = both & (f != fq)
+        if differ.any():
+            out["gap_ascent"] = min(out["gap_ascent"], float(np.min(np.abs(f - fq)[differ]) / abs(T)))
+        across = both & (slot != sq)
+        low = np.minimum(f, fq)[across]
+        np.maximum.at(saddle, slot[across], low)
+        np.maximum.at(saddle, sq[across], low)
+    # D3
+    share, need, rise = contrast * F[bcomp], prominence * T, fv[basins] - saddle
+    significant = (area >= min_area) & (flux >= share) & (rise >= need)
+    several = np.isfinite(saddle)  # the basins of components with more than one
+    if several.any():
+        out["gap_prominence"] = float(np.min(np.abs(rise - need)[several]) / abs(T))
+        out["gap_contrast"] = float(np.min((np.abs(flux - share) / np.abs(F[bcomp]))[several]))
+    count = np.bincount(bcomp, significant, minlength=len(comps))
+    # D4: the owner of every pixel of a split component
+    owner, is_split = peak[pix].copy(), count[comp_of] >= 2
+    for k in np.flatnonzero(count >= 2):
+        tops = basins[(bcomp == k) & significant]  # ascending: argmin takes the smaller index on a tie
+        stray = np.flatnonzero((comp_of == k) & ~significant[basin_of])
+        tr, tc = np.divmod(tops, frame.shape[1])
+        dist = (rr[stray, None] - tr[None, :]) ** 2 + (cc[stray, None] - tc[None, :]) ** 2
+        owner[stray] = tops[np.argmin(dist, axis=1)]
+    key = np.where(is_split, owner, labels[pix])  # a root names an unsplit component, a peak an object of a split one
+    _, obj = np.unique(key, return_inverse=True)
+    first = np.full(obj.max() + 1, frame.size)
+    np.minimum.at(first, obj, pix)
+    order = np.argsort(first)
+    o_area, o_flux, o_abs = np.bincount(obj)[order], np.bincount(obj, dv)[order], np.bincount(obj, np.abs(dv))[order]
+    o_r, o_c = np.bincount(obj, dv * rr)[order], np.bincount(obj, dv * cc)[order]
+    keep = (o_area >= min_area) & (o_flux > 0)
+    if max_area is not None:
+        keep &= o_area <= max_area
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rows = np.stack([o_r / o_flux, o_c / o_flux, o_flux, o_area.astype(np.float64)], axis=-1)[keep]
+    out.update(rows=rows, abs_flux=o_abs[keep], components=len(comps), basins=len(basins), split=int(np.count_nonzero(count >= 2)), T=T)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ the frames
+def blend_frame(shape: tuple[int, int], pos: np.ndarray, amp: np.ndarray, rng: np.random.Generator, noise: float = 0.3) -> np.ndarray:
+    """star_cases.star_frame with given amplitudes: tilted background, noise, Gaussians of sigma 1.1 ... 1.5; float32 values."""
+    h, w = shape
+    rows, cols = np.mgrid[0:h, 0:w].astype(np.float64)
+    sig_r, sig_c = rng.uniform(1.1, 1.5, len(pos)), rng.uniform(1.1, 1.5, len(pos))
+    frame = 10.0 + 0.004 * rows - 0.003 * cols + rng.normal(0.0, noise, (h, w))
+    for (r, c), a, sr, sc_ in zip(pos, amp, sig_r, sig_c):
+        frame += a * np.exp(-0.5 * (((rows - r) / sr) ** 2 + ((cols - c) / sc_) ** 2))
+    return frame.astype(np.float32).astype(np.float64)
+
+
+# name: separation in pixels, amplitude range of the primary, seed.  12 pairs in 150 x 200, box 64, the companion at 0.3 ... 1.0 of the primary
+PAIRS = {
+    "pairs 8": {"apart": 8.0, "amp": (100, 400), "seed": 11},
+    "pairs 6": {"apart": 6.0, "amp": (100, 400), "seed": 12},
+    "pairs 5": {"apart": 5.0, "amp": (100, 400), "seed": 13},
+    "faint pairs 6": {"apart": 6.0, "amp": (5, 20), "seed": 14},
+}
+# Every member of every bright pair is found within this distance of its Gaussian's centre.  The centroid of a hard partition is biased by
+# the neighbour's wing; the bound is the restatement's own worst distance on the committed seed (MEASURED, pixels) times 1.5, the margin
+# for other seeds of the same generator.
+MEASURED = {"pairs 8": 0.017, "pairs 6": 0.140}
+TRUTH_BOUND = {name: 1.5 * worst for name, worst in MEASURED.items()}
+
+
+def _case(frame, truth, box, mask=None, **ref_options) -> dict:
+    return sc._freeze({"frame": frame, "truth": truth, "box": box, "mask": mask, "ref": ref_deblend(frame, mask, box, **ref_options),
+                       "plain": sc.ref_detect(frame, mask, box, **ref_options)})
+
+
+@functools.lru_cache(maxsize=None)
+def pair_case(name: str) -> dict:
+    """truth: (24, 2), pair k is rows 2 k (the primary) and 2 k + 1."""
+    spec, shape = PAIRS[name], (150, 200)
+    rng = np.random.default_rng([spec["seed"], 41])
+    centre = sc.scattered(shape, 12, rng, margin=14.0, apart=26.0)
+    angle = rng.uniform(0, 2 * np.pi, 12)
+    step = 0.5 * spec["apart"] * np.stack([np.sin(angle), np.cos(angle)], axis=-1)
+    truth = np.stack([centre - step, centre + step], axis=1).reshape(-1, 2)
+    amp = rng.uniform(*spec["amp"], 12)
+    amp = np.stack([amp, amp * rng.uniform(0.3, 1.0, 12)], axis=1).ravel()
+    return _case(blend_frame(shape, truth, amp, rng), truth, 64)
+
+
+def _small(shape, box, truth, amp, seed, mask=None) -> dict:
+    truth = np.array(truth, np.float64)
+    return _case(blend_frame(shape, truth, np.array(amp, np.float64), np.random.default_rng([seed, 43])), truth, box, mask)
+
+
+@functools.lru_cache(maxsize=None)
+def special_case(name: str) -> dict:
+    if name == "tile corner":  # the members in tiles (0, 0) and (1, 1) of the 32 x 32 tiling
+        return _small((70, 70), 32, [(29.3, 29.6), (33.9, 34.2)], [300, 200], 1)
+    if name == "tile seams":  # one pair across the row seam, one across the column seam
+        return _small((70, 70), 32, [(29.4, 12.3), (35.2, 13.1), (52.2, 29.1), (51.6, 35.0)], [250, 180, 300, 150], 2)
+    if name == "triple":  # three in a line
+        return _small((70, 70), 32, [(30.2, 20.3), (30.6, 26.4), (30.1, 32.6)], [300, 220, 260], 3)
+    if name == "masked member":  # the mask covers the core of the second member
+        mask = np.zeros((70, 70), bool)
+        mask[38:43, 44:49] = True
+        return _small((70, 70), 32, [(40.3, 40.2), (40.6, 46.3)], [300, 250], 4, mask)
+    if name == "frame edge":
+        return _small((70, 70), 32, [(0.4, 30.2), (0.9, 36.3), (40.2, 0.3), (46.1, 0.8), (68.8, 50.1), (68.6, 56.2)], [300, 200, 250, 180, 280, 210], 5)
+    if name == "one box":
+        return _small((64, 64), 64, [(20.3, 20.6), (24.4, 24.9), (45.2, 40.1)], [300, 200, 250], 6)
+    raise KeyError(name)
+
+
+SPECIAL = ("tile corner", "tile seams", "triple", "masked member", "frame edge", "one box")
+
+
+@functools.lru_cache(maxsize=None)
+def plain_case(name: str) -> dict:
+    """A frame of star_cases.FRAMES (no blends) with the deblended restatement."""
+    base = sc.frame_case(name)
+    return sc._freeze({**base, "plain": base["ref"], "ref": ref_deblend(base["frame"], None, base["box"])})
+
+
+CASES = {**{name: functools.partial(plain_case, name) for name in sc.FRAMES}, **{name: functools.partial(pair_case, name) for name in PAIRS},
+         **{name: functools.partial(special_case, name) for name in SPECIAL}}
+
+# star_cases.check_special_frames makes the frame one component with threshold -1000.  The ascent's gap is measured in units of |T|, and
+# among 9 100 pixels of noise two neighbours always lie within some 1e-5 of each other: at |T| = 300 no such frame passes the precondition.
+# A threshold of -5 (T = -1.5, thirteen sd of the filtered noise below zero) detects every pixel all the same.
+ONE_COMPONENT = {"threshold": -5.0, "max_area": 130 * 70}
+
+
+@functools.lru_cache(maxsize=None)
+def one_component_case() -> dict:
+    """star_cases.check_special_frames' frame that is a single component of 9 100 pixels, with two bright cores planted:
+    every pixel is detected, the noise makes hundreds of peaks, and D4 gathers the significant ones in several chunks."""
+    base = sc.frame_case("tall")
+    rows, cols = np.mgrid[0:130, 0:70].astype(np.float64)
+    frame = base["frame"].copy()
+    for r, c in ((100.3, 20.4), (105.1, 24.2)):
+        frame += 500.0 * np.exp(-0.5 * (((rows - r) / 1.3) ** 2 + ((cols - c) / 1.3) ** 2))
+    frame = frame.astype(np.float32).astype(np.float64)
+    return _case(frame, np.array([(100.3, 20.4), (105.1, 24.2)]), base["box"], None, **ONE_COMPONENT)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the emulator
+@functools.cache
+def emulator():
+    """tests/emu/libemu_deblend.so: the kernels' drivers on the CPU, compiled here when missing or older than its sources."""
+    import os
+    import pathlib
+    import shutil
+    import subprocess
+
+    src, out = ROOT / "tests" / "emu" / "emu_deblend.cpp", ROOT / "tests" / "emu" / "libemu_deblend.so"
+    cores = [ROOT / "regularizepsf_amd" / "csrc" / n for n in ("rpsf_core_stars.hpp", "rpsf_core_stars_deblend.hpp")]
+    if not out.exists() or out.stat().st_mtime < max(src.stat().st_mtime, *(c.stat().st_mtime for c in cores)):
+        clang = "/opt/rocm/lib/llvm/bin/clang++"
+        if not pathlib.Path(clang).exists():
+            clang = shutil.which("clang++") or shutil.which("hipcc")
+        assert clang is not None, "no clang++ to build tests/emu/emu_deblend.cpp"
+        fresh = out.with_name(f"libemu_deblend.{os.getpid()}.so")
+        subprocess.run([clang, "-std=c++20", "-O1", "-shared", "-fPIC", "-o", str(fresh), str(src)], check=True)
+        os.replace(fresh, out)
+    lib = ctypes.CDLL(str(out))
+    vp, i, d, n = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_long
+    lib.emud_basins.argtypes = [vp, vp, i, i, vp]
+    lib.emud_detect.argtypes = [vp, vp, i, i, i, vp, d, n, n, i, d, d, vp, n, vp, vp]
+    return lib
+
+
+class EmuFinder(sc.EmuFinder):
+    """star_cases.EmuFinder with the deblend option: regularizepsf_amd.stars._Finder's interface on the emulator."""
+
+    def __init__(self, shape, box, device=0) -> None:
+        super().__init__(shape, box, device)
+        self._deblend, self._info = (False, 0.005, 1.0), (0, 0, 0)
+
+    def set_deblend(self, on, contrast=0.005, prominence=1.0) -> None:
+        self._deblend = (bool(on), float(contrast), float(prominence))
+
+    def detect(self, level, threshold_abs, min_area, max_area):
+        level = np.ascontiguousarray(level, np.float64)
+        capacity = self.shape[0] * self.shape[1]
+        out, count, info = np.empty((capacity, 4)), ctypes.c_long(0), (ctypes.c_long * 3)()
+        on, contrast, prominence = self._deblend
+        assert emulator().emud_detect(self._frame.ctypes.data, None if self._mask is None else self._mask.ctypes.data, *self.shape, self.box,
+                                      level.ctypes.data, float(threshold_abs), int(min_area), -1 if max_area is None else int(max_area),
+                                      int(on), contrast, prominence, out.ctypes.data, capacity, ctypes.byref(count), info) == 0
+        self._info = tuple(info) if on else (info[0], 0, 0)
+        return out[:count.value].copy()
+
+    def basins(self, f, detected):
+        f, flags = np.ascontiguousarray(f, np.float64), np.ascontiguousarray(detected, np.uint8)
+        peak = np.full(self.shape, -9, np.int32)
+        assert emulator().emud_basins(f.ctypes.data, flags.ctypes.data, *self.shape, peak.ctypes.data) == 0
+        return peak
+
+    def deblend_info(self):
+        return self._info
+
+
+# ------------------------------------------------------------------------------------------------------------------ D1
+def basin_tables(tr: int, tc: int) -> dict[str, tuple[np.ndarray, np.ndarray]]:
+    """name -> (f, detected) for a kernel tile of tr x tc: frames of (2 tr + 3) x (2 tc + 5), where four tiles meet and both far edges are
+    partial, and the degenerate frames."""
+    h, w = 2 * tr + 3, 2 * tc + 5
+    rows, cols = np.indices((h, w))
+    masks = sc.label_masks(tr, tc)
+    full = np.ones((h, w), bool)
+    out: dict[str, tuple[np.ndarray, np.ndarray]] = {}
+    for density in (0.3, 0.6, 1.0):
+        for seed in (1, 2):
+            rng = np.random.default_rng([seed, int(density * 10), 5])
+            out[f"random f, mask {density}, seed {seed}"] = (rng.standard_normal((h, w)), rng.random((h, w)) < density)
+            # few distinct values: many ties, decided by the index
+            out[f"quantised f, mask {density}, seed {seed}"] = (rng.integers(0, 4, (h, w)).astype(np.float64), rng.random((h, w)) < density)
+    out["plateau"] = (np.full((h, w), 2.5), full)  # one peak, pixel 0, reached by all
+    out["plateau on a serpentine"] = (np.full((h, w), -1.0), masks["serpentine"])
+    two = np.zeros((h, w))
+    two[5, 7] = two[tr + 8, tc + 4] = 9.0
+    slope = -np.hypot(rows - 5, cols - 7) / 100
+    out["two equal peaks"] = (two + np.maximum(slope, -np.hypot(rows - tr - 8, cols - tc - 4) / 100), full)
+    ridge = np.zeros((h, w))  # ridges along every tile seam, rising towards the far corner: the walks run along and across the seams
+    for r0 in (tr - 1, tr, 2 * tr - 1, 2 * tr):
+        ridge[r0, :] = 1.0 + cols[r0] / 1000.0
+    for c0 in (tc - 1, tc, 2 * tc - 1, 2 * tc):
+        ridge[:, c0] = 1.0 + rows[:, c0] / 1000.0
+    out["ridges along the seams"] = (ridge, full)
+    out["ridges alone"] = (ridge, ridge > 0)
+    climb = np.where(rows % 4 == 0, cols, np.where(rows % 4 == 2, w - 1 - cols, -0.5)) + w * ((rows + 1) // 2)  # rises all along the serpentine
+    out["serpentine climb"] = (climb.astype(np.float64), masks["serpentine"])  # one walk through all tiles, thousands of steps
+    out["serpentine descent"] = (-climb.astype(np.float64), masks["serpentine"])
+    for name in ("checkerboard", "sparse checkerboard", "tile corners", "diagonal link", "anti-diagonal link"):
+        out[name] = (np.random.default_rng(len(name)).standard_normal((h, w)), masks[name])
+    out["checkerboard f"] = (((rows + cols) % 2).astype(np.float64), full)
+    out["empty mask"] = (np.random.default_rng(3).standard_normal((h, w)), np.zeros((h, w), bool))
+    for shape in ((1, 1), (1, w), (h, 1)):
+        rng = np.random.default_rng(shape)
+        out[f"{shape} full"] = (rng.standard_normal(shape), np.ones(shape, bool))
+        out[f"{shape} random"] = (rng.integers(0, 3, shape).astype(np.float64), rng.random(shape) < 0.7)
+    return out
+
+
+def check_basins(make_finder) -> None:
+    """Every table of basin_tables: `peak` exactly the restatement's."""
+    probe = make_finder((1, 1), 64)
+    tr, tc = probe.info()
+    probe.close()
+    finders: dict[tuple[int, int], object] = {}
+    tables = basin_tables(tr, tc)
+    for name, (f, detected) in tables.items():
+        finder = finders.get(f.shape) or finders.setdefault(f.shape, make_finder(f.shape, 64))
+        got, want = finder.basins(f, detected), ref_basins(f, detected)
+        assert got.dtype == np.int32 and got.shape == want.shape
+        assert np.array_equal(got, want), f"{name}: {np.count_nonzero(got != want)} of {f.size} peaks differ"
+    for finder in finders.values():
+        finder.close()
+    plateau = ref_basins(*tables["plateau"])
+    assert np.unique(plateau).tolist() == [0]  # the index breaks the tie: one peak, the smallest index
+    assert np.unique(ref_basins(*tables["two equal peaks"])).size == 2
+    climb = ref_basins(*tables["serpentine climb"])
+    assert np.unique(climb[climb >= 0]).size == 1  # one walk through every tile
+
+
+# ------------------------------------------------------------------------------------------------------------------ detection
+def run(make_finder, case: dict, deblend: bool = True, contrast: float = 0.005, prominence: float = 1.0, threshold: float = 3.0,
+        min_area: int = 5, max_area: int | None = None, info: list | None = None) -> np.ndarray:
+    """The product's per-frame pipeline on a finder with the option set: (k, 4) rows."""
+    from regularizepsf_amd import stars
+
+    finder = make_finder(case["frame"].shape, case["box"])
+    try:
+        finder.set_deblend(deblend, contrast, prominence)
+        rows = stars.frame_stars(finder, case["frame"], case["mask"], threshold, min_area, max_area)
+        if info is not None:
+            info.append(finder.deblend_info())
+        return rows
+    finally:
+        finder.close()
+
+
+def admitted(name: str, ref: dict) -> None:
+    """The preconditions, from the restatement alone: no decision of the case hangs on rounding."""
+    gaps = {k: ref[k] for k in ("gap_threshold", "gap_ascent", "gap_prominence", "gap_contrast")}
+    print(f"{name}: " + ", ".join(f"{k} {v:.1e}" for k, v in gaps.items()))
+    assert ref["gap_clip"] >= sc.GAP_CLIP and all(v >= sc.GAP_THRESHOLD for v in gaps.values()), (name, ref["gap_clip"], gaps)
+
+
+def check_detect(make_finder, name: str) -> None:
+    """Rows equal to the restatement's in count, order and area, positions and flux within compare_rows' bound; the counts of
+    components, basins and split components equal too."""
+    case = CASES[name]()
+    ref, info = case["ref"], []
+    admitted(name, ref)
+    rows = run(make_finder, case, info=info)
+    sc.compare_rows(rows, ref, case["frame"].shape, name)
+    assert info[0] == (ref["components"], ref["basins"], ref["split"]), (name, info[0])
+    if name in sc.FRAMES:
+        assert ref["split"] == 0 and rows.tobytes() == run(make_finder, case, deblend=False).tobytes()  # no blends: bit for bit the plain rows
+    else:
+        assert ref["split"] >= 1 and len(ref["rows"]) > len(case["plain"]["rows"])
+
+
+def check_one_component(make_finder) -> None:
+    case = one_component_case()
+    ref, info = case["ref"], []
+    admitted("one component", ref)
+    assert ref["components"] == 1 and ref["split"] == 1 and ref["basins"] > 256 and len(ref["rows"]) >= 2  # more basins than one chunk of D4 holds
+    rows = run(make_finder, case, info=info, **ONE_COMPONENT)
+    sc.compare_rows(rows, ref, case["frame"].shape, "one component")
+    assert info[0] == (1, ref["basins"], 1)
+    dist = np.hypot(*(rows[:, None, :2] - case["truth"][None, :, :]).transpose(2, 0, 1))
+    # the two cores, 6.1 px apart, are objects of their own: each has its own row nearer than half their distance (the objects also
+    # take the background pixels around them, which pulls their centroids)
+    assert dist.min(axis=0).max() < 3.0 and len(set(dist.argmin(axis=0).tolist())) == 2, dist.min(axis=0)
+    assert len(run(make_finder, case, deblend=False, **ONE_COMPONENT)) == 1
+
+
+def check_limits(make_finder, name: str) -> None:
+    """contrast = 1 and a very large prominence each give the plain rows bit for bit; prominence = contrast = 0 gives one object per
+    basin of at least min_area in every component that has two of them."""
+    case = CASES[name]()
+    plain = run(make_finder, case, deblend=False)
+    sc.compare_rows(plain, case["plain"], case["frame"].shape, name + ", off")
+    assert run(make_finder, case, contrast=1.0).tobytes() == plain.tobytes()
+    assert run(make_finder, case, prominence=1e30).tobytes() == plain.tobytes()
+    ref = ref_deblend(case["frame"], case["mask"], case["box"], contrast=0.0, prominence=0.0)
+    assert ref["gap_ascent"] >= sc.GAP_THRESHOLD
+    rows = run(make_finder, case, contrast=0.0, prominence=0.0)
+    sc.compare_rows(rows, ref, case["frame"].shape, name + ", every basin")
+    assert len(rows) >= len(run(make_finder, case))
+
+
+def check_truth(name: str) -> None:
+    """The definition itself, on the restatement alone: both members of every pair are found, each within TRUTH_BOUND of its centre;
+    without the option every pair is one detection between its members."""
+    case = pair_case(name)
+    rows, truth, plain = case["ref"]["rows"], case["truth"], case["plain"]["rows"]
+    admitted(name, case["ref"])
+    assert len(plain) == len(truth) // 2, f"{name}: {len(plain)} detections for {len(truth) // 2} pairs without the option"
+    centre = 0.5 * (truth[0::2] + truth[1::2])
+    assert np.hypot(*(plain[:, None, :2] - centre[None]).transpose(2, 0, 1)).min(axis=0).max() < 0.5 * PAIRS[name]["apart"]
+    assert np.hypot(*(plain[:, None, :2] - truth[None]).transpose(2, 0, 1)).min(axis=0).max() > 1.0  # a member is missed by pixels
+    assert len(rows) == len(truth)
+    dist = np.hypot(*(rows[:, None, :2] - truth[None, :, :]).transpose(2, 0, 1))
+    assert sorted(dist.argmin(axis=1).tolist()) == list(range(len(truth)))  # one object per member
+    worst = dist.min(axis=0).max()
+    print(f"{name}: {len(truth)} members, worst distance to the truth {worst:.3f} px (bound {TRUTH_BOUND[name]:.3f})")
+    assert worst <= TRUTH_BOUND[name]
