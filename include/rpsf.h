@@ -245,7 +245,7 @@ int rpsf_saturation_fill_device(rpsf_plan* plan, const float* image_host, int he
  * RPSF_E_BADARG, n_frames == 0: RPSF_OK and nothing is done (the pointers may then be NULL).  RPSF_E_UNSUPPORTED when a frame-group
  * holds 2^31 masked pixels or more (cut it smaller).  n_masked_per_frame_or_null: n_frames entries, masked pixels of padded frame f.
  * SCRATCH per frame of a frame-group: what rpsf_apply_device_saturated lists for one frame (every per-frame array starts on a
- * multiple of 4 elements), 28 B of counters and offsets, and the batch launch's own 16 B per output pixel; 8 B more per group. */
+ * multiple of 4 elements), 32 B of counters and offsets, and the batch launch's own 16 B per output pixel; 8 B more per group. */
 int rpsf_apply_batch_device_saturated(rpsf_plan* plan, const void* images_dev, void* outs_dev, int n_frames, size_t image_stride,
                                       size_t out_stride, int height, int width, int pad_mode, double threshold, int dilation,
                                       int neighborhood_width, void* stream, size_t* n_masked_per_frame_or_null);
@@ -381,6 +381,44 @@ int rpsf_apply_view(rpsf_plan* plan, const rpsf_view* image, const rpsf_view* ou
  * from one staging stack (RPSF_ROUTE_STAGED with RPSF_ROUTE_C1 for the input).  n_frames == 0: RPSF_OK; < 0: RPSF_E_BADARG. */
 int rpsf_apply_batch_view(rpsf_plan* plan, const rpsf_view* images, const rpsf_view* outs, int n_frames, int pad_mode, float pad_value,
                           double threshold, int dilation, int neighborhood_width, void* stream, int* route_or_null);
+/* BAD-PIXEL MASKS ("Bad-pixel masks"; not in the reference): the device saturation route with, besides the pixels above
+ * the threshold, pixels the caller names.  On the 2N-padded frame P: M = the dilated hot mask as above; E = the caller's mask taken
+ * through pad_mode's index map (0 in the pad of RPSF_PAD_CONSTANT), or-ed with "P is NaN or +-Inf" when fill_nonfinite != 0; the mask of
+ * F3 - F5 is M | E.  E is NOT dilated.  Fill, correction, restore and lists are those of the entry points these stand beside, from which
+ * they differ by the mask arguments only; threshold == +inf leaves E alone.  A mask is a uint8 rpsf_view of the frame's shape in device
+ * memory, nonzero = masked, any positive strides; n_masks is 0 (with masks_or_null == NULL), 1 (one mask for every frame) or n_frames.
+ * A view of another dtype or shape, null data, a stride that is not positive or another n_masks: RPSF_E_BADARG before anything runs.
+ * masks_or_null == NULL with fill_nonfinite == 0 IS the call of the unmasked entry point (rpsf_apply_batch_device_saturated,
+ * rpsf_apply_view, rpsf_apply_batch_view, rpsf_apply_frames_host_saturated_device): that code runs, nothing else.  Otherwise the route
+ * runs whatever the threshold, and a frame with nothing hot and nothing in E still leaves F2 - F4 at their first instruction.
+ * SCRATCH, owned by the plan, besides what rpsf_apply_device_saturated lists: per pixel of the padded frame 1 B more (the exact plane E),
+ * 24 B per frame (the mask views, device and pinned host) and 4 B per frame (the count of E); rpsf_apply_frames_host_masked_device
+ * uploads its host masks into uint8 scratch of 1 B per pixel of the frame-group (of one frame for a shared mask).  All of it is made
+ * at the first masked call, reused, grown on demand and freed with the plan. */
+int rpsf_apply_batch_device_masked(rpsf_plan* plan, const void* images_dev, void* outs_dev, int n_frames, size_t image_stride,
+                                   size_t out_stride, int height, int width, int pad_mode, double threshold, int dilation,
+                                   int neighborhood_width, const rpsf_view* masks_or_null, int n_masks, int fill_nonfinite, void* stream,
+                                   size_t* n_masked_per_frame_or_null);
+/* rpsf_apply_view / rpsf_apply_batch_view with masks; RPSF_ROUTE_SATURATED is set whenever a mask or fill_nonfinite is given */
+int rpsf_apply_view_masked(rpsf_plan* plan, const rpsf_view* image, const rpsf_view* out, int pad_mode, float pad_value, double threshold,
+                           int dilation, int neighborhood_width, const rpsf_view* mask_or_null, int fill_nonfinite, void* stream,
+                           int* route_or_null);
+int rpsf_apply_batch_view_masked(rpsf_plan* plan, const rpsf_view* images, const rpsf_view* outs, int n_frames, int pad_mode, float pad_value,
+                                 double threshold, int dilation, int neighborhood_width, const rpsf_view* masks_or_null, int n_masks,
+                                 int fill_nonfinite, void* stream, int* route_or_null);
+/* rpsf_apply_frames_host_saturated_device with HOST masks: masks_host_or_null[f] is a dense height x width uint8 array */
+int rpsf_apply_frames_host_masked_device(rpsf_plan* plan, const void* const* images_host, int image_is_f64, int n_frames, int height,
+                                         int width, int pad_mode, double threshold, int dilation, int neighborhood_width,
+                                         const uint8_t* const* masks_host_or_null, int n_masks, int fill_nonfinite, void* const* outs_host,
+                                         int out_is_f64);
+/* Test entry in the style of rpsf_saturation_fill_batch_device: F1 - F4 alone with masks.  masks_in_host_or_null: n_masks host masks
+ * mask_frame_bytes apart, element (r, c) at r * mask_row_stride + c * mask_col_stride bytes; they are uploaded as they lie and read
+ * through those strides.  masks_host receives M | E, masked_per_frame_or_null[f] its pixel count in padded frame f. */
+int rpsf_saturation_fill_masked_device(rpsf_plan* plan, const float* images_host, int n_frames, int height, int width, int pad_mode,
+                                       double threshold, int dilation, int neighborhood_width, int order, const uint8_t* masks_in_host_or_null,
+                                       int n_masks, size_t mask_frame_bytes, int64_t mask_row_stride, int64_t mask_col_stride,
+                                       int fill_nonfinite, float* padded_host, uint8_t* masks_host, int* groups_per_frame_or_null,
+                                       int* masked_per_frame_or_null);
 /* The plan's own stream (hipStream_t), for callers that enqueue follow-up work such as the seam exchange. */
 void* rpsf_plan_stream(rpsf_plan* plan);
 

@@ -65,6 +65,16 @@ _PROTOTYPES = {
     "rpsf_convert_view": (c_int, [c_int, POINTER(View), POINTER(View), c_void_p]),
     "rpsf_apply_view": (c_int, [c_void_p, POINTER(View), POINTER(View), *_VIEW_APPLY]),
     "rpsf_apply_batch_view": (c_int, [c_void_p, POINTER(View), POINTER(View), c_int, *_VIEW_APPLY]),
+    "rpsf_apply_view_masked": (c_int, [c_void_p, POINTER(View), POINTER(View), c_int, c_float, c_double, c_int, c_int, POINTER(View), c_int,
+                                       c_void_p, POINTER(c_int)]),
+    "rpsf_apply_batch_view_masked": (c_int, [c_void_p, POINTER(View), POINTER(View), c_int, c_int, c_float, c_double, c_int, c_int, POINTER(View),
+                                             c_int, c_int, c_void_p, POINTER(c_int)]),
+    "rpsf_apply_batch_device_masked": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_int, c_int, c_int, c_double, c_int, c_int,
+                                               POINTER(View), c_int, c_int, c_void_p, POINTER(c_size_t)]),
+    "rpsf_apply_frames_host_masked_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_int,
+                                                     c_int, c_void_p, c_int]),
+    "rpsf_saturation_fill_masked_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_int,
+                                                   c_size_t, ctypes.c_int64, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rpsf_last_error": (c_char_p, []),
     "rpsf_device_count": (c_int, [POINTER(c_int)]),
     "rpsf_device_info": (c_int, [c_int, POINTER(c_int), c_char_p, c_size_t]),
@@ -613,6 +623,99 @@ class Plan:
         check(lib().rpsf_apply_batch_view(self._handle, (View * max(1, n))(*images), (View * max(1, n))(*outs), n, pad_mode, pad_value,
                                           float(threshold), int(dilation), int(neighborhood_width), stream, ctypes.byref(route)))
         return route.value
+
+    # ---- bad-pixel masks: the saturation route with pixels the caller names
+    def apply_view_masked(self, image: View, out: View, pad_mode: int, threshold: float, dilation: int, neighborhood_width: int,
+                          mask: View | None, fill_nonfinite: bool, stream: c_void_p | None = None, pad_value: float = 0.0) -> int:
+        """rpsf_apply_view_masked: ``apply_view`` with a uint8 device view as mask and / or the non-finite pixels; returns the route bits."""
+        route = c_int(0)
+        check(lib().rpsf_apply_view_masked(self._handle, ctypes.byref(image), ctypes.byref(out), pad_mode, pad_value, float(threshold), int(dilation),
+                                           int(neighborhood_width), ctypes.byref(mask) if mask is not None else None, int(bool(fill_nonfinite)),
+                                           stream, ctypes.byref(route)))
+        return route.value
+
+    def apply_batch_view_masked(self, images, outs, pad_mode: int, threshold: float, dilation: int, neighborhood_width: int, masks,
+                                fill_nonfinite: bool, stream: c_void_p | None = None, pad_value: float = 0.0) -> int:
+        """rpsf_apply_batch_view_masked; ``masks``: None, or a sequence of one view (for every frame) or of one view per frame."""
+        n = len(images)
+        if len(outs) != n:
+            msg = "as many out views as image views"
+            raise ValueError(msg)
+        masks = list(masks) if masks is not None else []
+        route = c_int(0)
+        check(lib().rpsf_apply_batch_view_masked(self._handle, (View * max(1, n))(*images), (View * max(1, n))(*outs), n, pad_mode, pad_value,
+                                                 float(threshold), int(dilation), int(neighborhood_width),
+                                                 (View * len(masks))(*masks) if masks else None, len(masks), int(bool(fill_nonfinite)), stream,
+                                                 ctypes.byref(route)))
+        return route.value
+
+    def apply_batch_device_masked(self, images_ptr: c_void_p, outs_ptr: c_void_p, n_frames: int, image_stride: int, out_stride: int,
+                                  height: int, width: int, pad_mode: int, threshold: float, dilation: int, neighborhood_width: int, masks,
+                                  fill_nonfinite: bool, stream: c_void_p | None = None) -> np.ndarray:
+        """``apply_batch_device_saturated`` with uint8 device views as masks (None, one, or one per frame); the masked pixels per padded frame."""
+        masks = list(masks) if masks is not None else []
+        counts = (c_size_t * max(1, int(n_frames)))()
+        check(lib().rpsf_apply_batch_device_masked(self._handle, images_ptr, outs_ptr, int(n_frames), int(image_stride), int(out_stride), int(height),
+                                                   int(width), pad_mode, float(threshold), int(dilation), int(neighborhood_width),
+                                                   (View * len(masks))(*masks) if masks else None, len(masks), int(bool(fill_nonfinite)), stream,
+                                                   counts))
+        return np.array(counts[: max(0, int(n_frames))], dtype=np.int64)
+
+    def apply_frames_host_masked_device(self, images, pad_mode: int, threshold: float, dilation: int, neighborhood_width: int, masks,
+                                        fill_nonfinite: bool, out_dtype=np.float64) -> np.ndarray:
+        """``apply_frames_host_saturated_device`` with host masks: None, or a sequence of one (for every frame) or one per frame of
+        C-contiguous uint8 arrays of the frames' shape, nonzero = masked."""
+        frames = [np.asarray(im) for im in images]
+        if any(f.ndim != 2 or f.shape != frames[0].shape for f in frames):
+            msg = "frames must be two dimensional and of one shape"
+            raise ValueError(msg)
+        is_f32 = all(f.dtype == np.float32 for f in frames)
+        want = np.float32 if is_f32 else np.float64
+        frames = [np.ascontiguousarray(f if f.dtype == want and f.dtype.byteorder != ">" else f.astype(want)) for f in frames]
+        n, shape = len(frames), (frames[0].shape if frames else (0, 0))
+        masks = [np.ascontiguousarray(m, dtype=np.uint8) for m in masks] if masks is not None else []
+        if len(masks) not in (0, 1, n) or any(m.shape != shape for m in masks):
+            msg = "masks: none, one or one per frame, each of the frames' shape"
+            raise ValueError(msg)
+        out = np.empty((n, *shape), out_dtype)
+        in_ptrs = (c_void_p * max(1, n))(*[f.ctypes.data for f in frames])
+        out_ptrs = (c_void_p * max(1, n))(*[out[i].ctypes.data for i in range(n)])
+        mask_ptrs = (c_void_p * len(masks))(*[m.ctypes.data for m in masks]) if masks else None
+        check(lib().rpsf_apply_frames_host_masked_device(self._handle, in_ptrs, int(not is_f32), n, shape[0], shape[1], pad_mode, float(threshold),
+                                                         int(dilation), int(neighborhood_width), mask_ptrs, len(masks), int(bool(fill_nonfinite)),
+                                                         out_ptrs, int(np.dtype(out_dtype) == np.float64)))
+        return out
+
+    def saturation_fill_masked_device(self, images, pad_mode: int, threshold: float, dilation: int, neighborhood_width: int, masks,
+                                      fill_nonfinite: bool = False, order: int = 0):
+        """Test entry: F1 - F4 alone with masks; (filled padded float32 frames, masks M | E, groups per frame, masked pixels per frame).
+        ``masks``: None or a uint8 array ``(n_masks, H, W)`` with n_masks 1 or the number of frames, at ANY positive strides of its last two
+        axes: the bytes it spans are uploaded as they lie and the kernel reads them through those strides."""
+        stack = np.ascontiguousarray(np.stack([np.asarray(im, dtype=np.float32) for im in images]))
+        n, h, w = stack.shape
+        shape = (n, h + 4 * self.patch_size, w + 4 * self.patch_size)
+        padded, out_masks = np.empty(shape, np.float32), np.empty(shape, np.uint8)
+        groups, masked = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        m_ptr, n_masks, frame_bytes, rs, cs = None, 0, 0, 0, 0
+        if masks is not None:
+            if masks.dtype != np.uint8 or masks.ndim != 3 or masks.shape[1:] != (h, w) or min(masks.strides[1:]) <= 0:
+                msg = "masks must be uint8 of shape (n_masks, H, W) with positive strides"
+                raise ValueError(msg)
+            n_masks, (fs, rs, cs) = masks.shape[0], masks.strides
+            span = (h - 1) * rs + (w - 1) * cs + 1
+            frame_bytes = span if n_masks == 1 else fs
+            if n_masks > 1 and fs < span:
+                msg = "masks overlap"
+                raise ValueError(msg)
+            # one contiguous host copy of exactly the bytes the views span (the array may be a view into a larger one)
+            raw = np.zeros(n_masks * frame_bytes, np.uint8)
+            for f in range(n_masks):
+                np.lib.stride_tricks.as_strided(raw[f * frame_bytes:], (h, w), (rs, cs))[...] = masks[f]
+            m_ptr = _ptr(raw)
+        check(lib().rpsf_saturation_fill_masked_device(self._handle, _ptr(stack), n, h, w, pad_mode, float(threshold), int(dilation),
+                                                       int(neighborhood_width), int(order), m_ptr, n_masks, frame_bytes, rs, cs,
+                                                       int(bool(fill_nonfinite)), _ptr(padded), _ptr(out_masks), _ptr(groups), _ptr(masked)))
+        return padded, out_masks.astype(bool), groups, masked
 
     def synchronize(self) -> None:
         check(lib().rpsf_device_synchronize(self.device))

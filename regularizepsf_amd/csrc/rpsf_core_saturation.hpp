@@ -6,7 +6,9 @@
 // keeps between two each() calls is computed from LDS words that all threads read alike.
 //
 //   F1  f1_pad        4 pixels of the 2N-padded frame per thread: pad index map, float32 frame, hot byte (value > threshold), hot count
+//       f1_pad_masked   the same with a bad-pixel mask: an EXACT byte per pixel beside the hot one (the caller's mask through the pad map, non-finite values)
 //   F2  f2_cross      one pass of the cross element over the bytes, 4 pixels per thread; `dilation` passes make the mask
+//       f2_cross_merge  the last pass on the masked route: the exact bytes are or-ed in undilated
 //   F3  f3_rows, f3_cols   box dilation of the mask by box_reach(h), separable; the S3 / S4 drivers of rpsf_core_stars.hpp label it
 //                          8-connected and list the roots; f3_init, f3_accumulate: count and bounding box of the MASKED pixels of a group
 //   F4  f4_group      one wave per group: the group's bounding box in raster order, 64 pixels at a time; per masked pixel of the group
@@ -100,6 +102,49 @@ RPSFS_HD void f1_pad(long gid, const Padded& f, const float* image, double thres
   if (count) fetch_add(n_hot, count);
 }
 
+// ------------------------------------------------------------------------------------------------ F1 with a bad-pixel mask
+// The caller's mask of one frame: H x W bytes, nonzero = masked, element (r, c) at data + r * row_stride + c * col_stride (bytes,
+// positive).  data == null: no mask.
+struct MaskView {
+  const uint8_t* data;
+  long row_stride, col_stride;
+};
+
+RPSFS_HD bool nonfinite(float v) { return (__builtin_bit_cast(uint32_t, v) & 0x7F800000u) == 0x7F800000u; }  // NaN, +Inf, -Inf
+
+// f1_pad, and next to the hot byte the EXACT byte: the mask byte of the pad-mapped source pixel (0 where the pad is "the constant"),
+// or-ed with "the padded value is not finite" when fill_nonfinite.  Exact pixels are masked as they are: F2 does not dilate them.
+RPSFS_HD void f1_pad_masked(long gid, const Padded& f, const float* image, double threshold, MaskView m, int fill_nonfinite, float* padded,
+                            uint8_t* hot, uint8_t* exact, int* n_hot, int* n_exact) {
+  const long q0 = 4 * gid, npix = f.npix();
+  if (q0 >= npix) return;
+  Quad out;
+  uint32_t bytes = 0, ebytes = 0;
+  int count = 0, ecount = 0;
+  const int n = npix - q0 < 4 ? (int)(npix - q0) : 4;
+  for (int k = 0; k < n; ++k) {
+    const long q = q0 + k;
+    const int r = (int)(q / f.PW), c = (int)(q % f.PW);
+    const int sr = pad_index(r - 2 * f.N, f.H, f.pad_mode), sc = pad_index(c - 2 * f.N, f.W, f.pad_mode);
+    const bool inside = sr >= 0 && sc >= 0;
+    const float v = inside ? image[(size_t)sr * f.W + sc] : 0.f;
+    out.v[k] = v;
+    if ((double)v > threshold) bytes |= 1u << (8 * k), ++count;  // NaN is not hot
+    bool e = inside && m.data && m.data[sr * m.row_stride + sc * m.col_stride];
+    if (fill_nonfinite && nonfinite(v)) e = true;
+    if (e) ebytes |= 1u << (8 * k), ++ecount;
+  }
+  if (n == 4) {
+    *reinterpret_cast<Quad*>(padded + q0) = out;
+    *reinterpret_cast<uint32_t*>(hot + q0) = bytes;
+    *reinterpret_cast<uint32_t*>(exact + q0) = ebytes;
+  } else {
+    for (int k = 0; k < n; ++k) padded[q0 + k] = out.v[k], hot[q0 + k] = (uint8_t)(bytes >> (8 * k)), exact[q0 + k] = (uint8_t)(ebytes >> (8 * k));
+  }
+  if (count) fetch_add(n_hot, count);
+  if (ecount) fetch_add(n_exact, ecount);
+}
+
 // ------------------------------------------------------------------------------------------------ F2
 // One pass of scipy's cross element, background outside: dst = src or any of its four neighbours.  n_set (optional) counts dst.
 RPSFS_HD void f2_cross(long gid, int PH, int PW, const uint8_t* src, uint8_t* dst, int* n_set) {
@@ -118,6 +163,24 @@ RPSFS_HD void f2_cross(long gid, int PH, int PW, const uint8_t* src, uint8_t* ds
   else
     for (int k = 0; k < n; ++k) dst[q0 + k] = (uint8_t)(bytes >> (8 * k));
   if (n_set && count) fetch_add(n_set, count);
+}
+// F2's LAST pass with the exact plane carried along: dst = (src dilated once) or exact; n_set counts the union
+RPSFS_HD void f2_cross_merge(long gid, int PH, int PW, const uint8_t* src, const uint8_t* exact, uint8_t* dst, int* n_set) {
+  const long q0 = 4 * gid, npix = (long)PH * PW;
+  if (q0 >= npix) return;
+  uint32_t bytes = 0;
+  int count = 0;
+  const int n = npix - q0 < 4 ? (int)(npix - q0) : 4;
+  for (int k = 0; k < n; ++k) {
+    const long q = q0 + k;
+    const int r = (int)(q / PW), c = (int)(q % PW);
+    const bool on = exact[q] || src[q] || (c > 0 && src[q - 1]) || (c < PW - 1 && src[q + 1]) || (r > 0 && src[q - PW]) || (r < PH - 1 && src[q + PW]);
+    if (on) bytes |= 1u << (8 * k), ++count;
+  }
+  if (n == 4) *reinterpret_cast<uint32_t*>(dst + q0) = bytes;
+  else
+    for (int k = 0; k < n; ++k) dst[q0 + k] = (uint8_t)(bytes >> (8 * k));
+  if (count) fetch_add(n_set, count);
 }
 
 // ------------------------------------------------------------------------------------------------ F3

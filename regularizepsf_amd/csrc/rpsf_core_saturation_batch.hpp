@@ -3,7 +3,7 @@
 //
 // Every function here is the single-frame function of the same number with a frame index: the frame's pointers are the stack's
 // pointers plus frame x stride, its counters are its own block of FRAME_COUNTERS ints, and "nothing hot" is that frame's own hot
-// count.  Labels and roots stay linear indices WITHIN the frame, so two frames with the same hot layout have the same root values;
+// count (on the masked route, b1_pad_masked / b2_cross_merge: its hot and its exact count).  Labels and roots stay linear indices WITHIN the frame, so two frames with the same hot layout have the same root values;
 // nothing is united, dilated or searched across frames (the last padded row of frame f and the first of frame f + 1 are neighbours
 // in memory and in nothing else: every neighbour test is the single-frame test against PH and PW).
 //
@@ -21,7 +21,7 @@ namespace rpsfsatb {
 
 using namespace rpsfsat;
 
-enum { C_HOT, C_MASK, C_GROUPS, C_LIST, FRAME_COUNTERS };  // per frame, zeroed before F1
+enum { C_HOT, C_MASK, C_GROUPS, C_LIST, C_EXACT, FRAME_COUNTERS };  // per frame, zeroed before F1; C_EXACT: pixels of the exact plane (masked route)
 enum { I_GROUP0, I_GROUPS, I_LIST0, FRAME_INFO };          // per frame, from the host after its one wait
 constexpr int ORDER_BUCKETS = 32;
 enum { S_CURSOR, S_HIST, S_TAKEN = S_HIST + ORDER_BUCKETS, SHARED_COUNTERS = S_TAKEN + ORDER_BUCKETS };  // per frame-group, zeroed before F1
@@ -37,8 +37,9 @@ RPSFS_HD size_t frame_stride(size_t count) { return (count + 3) & ~(size_t)3; }
 
 // frames per frame-group: 11 bytes per padded pixel (frame, three byte planes, labels), the output rows of the correction and the 16
 // bytes per output pixel the shared-K launch keeps per frame in flight
-RPSFS_HD int auto_group_frames(size_t padded_pixels, size_t out_pixels) {
-  const size_t per_frame = 11 * frame_stride(padded_pixels) + (4 + 16) * frame_stride(out_pixels);
+// (masked: one more byte plane, and the caller's mask of the frame in the plan's scratch)
+RPSFS_HD int auto_group_frames(size_t padded_pixels, size_t out_pixels, bool masked = false) {
+  const size_t per_frame = (masked ? 12 : 11) * frame_stride(padded_pixels) + (4 + 16 + (masked ? 1 : 0)) * frame_stride(out_pixels);
   const size_t g = GROUP_BUDGET_BYTES / per_frame;
   return g < 1 ? 1 : g > (size_t)MAX_GROUP_FRAMES ? MAX_GROUP_FRAMES : (int)g;
 }
@@ -49,11 +50,14 @@ struct Stack {  // the frames of a frame-group
   size_t nseg;    // of segcnt and segoff
   float* padded;
   uint8_t* bytes[3];
+  uint8_t* exact = nullptr;  // the masked route's exact plane (b1_pad_masked, b2_cross_merge); nobody else looks at it
   int32_t* labels;
   int *segcnt, *segoff;
   int* counters;  // FRAME_COUNTERS per frame
   RPSFS_HD int* counter(int fr, int which) const { return counters + (size_t)FRAME_COUNTERS * fr + which; }
-  RPSFS_HD bool idle(int fr) const { return *counter(fr, C_HOT) == 0; }  // the same word for all threads of the frame
+  // nothing hot and nothing exact (C_EXACT stays 0 off the masked route); the same two words for all threads of the frame
+  RPSFS_HD static bool busy(const int* frame_counters) { return (frame_counters[C_HOT] | frame_counters[C_EXACT]) != 0; }
+  RPSFS_HD bool idle(int fr) const { return !busy(counter(fr, 0)); }
 };
 
 struct Tables {  // what the host sized after its wait
@@ -76,6 +80,16 @@ RPSFS_HD void b1_pad(long gid, int fr, const Stack& s, const float* images, size
 RPSFS_HD void b2_cross(long gid, int fr, const Stack& s, int from, int last) {
   if (s.idle(fr)) return;
   f2_cross(gid, s.f.PH, s.f.PW, s.bytes[from] + fr * s.stride, s.bytes[from ^ 1] + fr * s.stride, last ? s.counter(fr, C_MASK) : nullptr);
+}
+// The masked route: masks[fr] is frame fr's view (masks == null: no frame has one); the last pass of F2 takes the exact plane in
+RPSFS_HD void b1_pad_masked(long gid, int fr, const Stack& s, const float* images, size_t image_stride, double threshold, const MaskView* masks,
+                            int fill_nonfinite) {
+  f1_pad_masked(gid, s.f, images + fr * image_stride, threshold, masks ? masks[fr] : MaskView{nullptr, 0, 0}, fill_nonfinite,
+                s.padded + fr * s.stride, s.bytes[0] + fr * s.stride, s.exact + fr * s.stride, s.counter(fr, C_HOT), s.counter(fr, C_EXACT));
+}
+RPSFS_HD void b2_cross_merge(long gid, int fr, const Stack& s, int from) {
+  if (s.idle(fr)) return;
+  f2_cross_merge(gid, s.f.PH, s.f.PW, s.bytes[from] + fr * s.stride, s.exact + fr * s.stride, s.bytes[from ^ 1] + fr * s.stride, s.counter(fr, C_MASK));
 }
 
 // ------------------------------------------------------------------------------------------------ F3
@@ -118,7 +132,7 @@ inline bool plan_tables(const int* counters, int frames, size_t in_frame, int* i
   for (int fr = 0; fr < frames; ++fr) {
     const int* c = counters + (size_t)FRAME_COUNTERS * fr;
     int* o = info + (size_t)FRAME_INFO * fr;
-    const bool hot = c[C_HOT] != 0;
+    const bool hot = Stack::busy(c);
     if (hot && (c[C_GROUPS] <= 0 || c[C_MASK] <= 0)) return false;
     o[I_GROUP0] = (int)g, o[I_GROUPS] = hot ? c[C_GROUPS] : 0, o[I_LIST0] = (int)l;
     g += o[I_GROUPS];

@@ -214,6 +214,9 @@ struct rpsf_plan : PlanStream {
   // frames rounded up to 4 pixels; made at the first such call, grown on demand), and the end of the last call that used it
   DevBuf<float> d_view_in, d_view_out;
   size_t view_in_floats = 0, view_out_floats = 0;
+  // rpsf_apply_frames_host_masked_device: the host masks of a frame-group as uploaded (1 B per pixel per frame, or one shared mask)
+  DevBuf<uint8_t> d_host_masks;
+  size_t host_mask_bytes = 0;
   hipEvent_t ev_view = nullptr;
   hipStream_t view_stream = nullptr;
   bool view_busy = false;

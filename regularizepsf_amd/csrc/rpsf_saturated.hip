@@ -280,18 +280,57 @@ struct SatBatchStats {
   }
 };
 
-static int sat_group_frames(const rpsf_plan* p, const SatDeviceRun& run) {
-  if (p->sat_group_opt > 0) return p->sat_group_opt;
-  return rpsfsatb::auto_group_frames((size_t)run.g.height * run.g.width, (size_t)run.call.out_rows * run.g.width);
+// The bad-pixel masks of a masked call ("Bad-pixel masks"): uint8 views in device memory - none, one for every frame or
+// one per frame - and whether the non-finite values of the padded frame are masked too
+struct SatMasks {
+  const rpsf_view* views = nullptr;
+  int n = 0;
+  int fill_nonfinite = 0;
+};
+
+static int check_masks(const SatMasks& m, int n_frames, int height, int width) {
+  if (m.n < 0 || (m.n > 0 && !m.views)) return fail(RPSF_E_BADARG, "mask: null views");
+  if (m.n > 1 && m.n != n_frames) return fail(RPSF_E_BADARG, "mask: no mask, one mask or one mask per frame");
+  for (int f = 0; f < m.n; ++f) {
+    const rpsf_view& v = m.views[f];
+    if (v.dtype != RPSF_DTYPE_UINT8) return fail(RPSF_E_BADARG, "mask: views must be uint8");
+    if (v.rows != height || v.cols != width) return fail(RPSF_E_BADARG, "mask: every mask must have the frame's shape");
+    if (!v.data || v.row_stride <= 0 || v.col_stride <= 0) return fail(RPSF_E_BADARG, "mask: null data or a stride that is not positive");
+  }
+  return RPSF_OK;
 }
 
-// one frame-group, resident; asynchronous on st but for the one wait inside rpsf_sat_fill_batch
+// the kernel's views of frames f0 ... f0 + frames - 1 (empty: the call has no mask)
+static std::vector<rpsfsat::MaskView> group_views(const SatMasks& m, int f0, int frames) {
+  std::vector<rpsfsat::MaskView> views(m.n ? (size_t)frames : 0);
+  for (int f = 0; f < (int)views.size(); ++f) {
+    const rpsf_view& v = m.views[m.n == 1 ? 0 : f0 + f];
+    views[f] = rpsfsat::MaskView{static_cast<const uint8_t*>(v.data), (long)v.row_stride, (long)v.col_stride};
+  }
+  return views;
+}
+
+static int sat_group_frames(const rpsf_plan* p, const SatDeviceRun& run, bool masked = false) {
+  if (p->sat_group_opt > 0) return p->sat_group_opt;
+  return rpsfsatb::auto_group_frames((size_t)run.g.height * run.g.width, (size_t)run.call.out_rows * run.g.width, masked);
+}
+
+// one frame-group, resident; asynchronous on st but for the one wait inside rpsf_sat_fill_batch.  masks: null on the unmasked route,
+// else the call's masks and f0, the group's first frame among the call's
 static int sat_device_apply_group(rpsf_plan* p, const SatDeviceRun& run, int frames, const float* images_dev, size_t image_stride, float* outs_dev,
-                                  size_t out_stride, int order, hipStream_t st, SatBatchStats* stats, size_t* n_masked_or_null) {
+                                  size_t out_stride, int order, hipStream_t st, SatBatchStats* stats, size_t* n_masked_or_null,
+                                  const SatMasks* masks = nullptr, int f0 = 0) {
   float *padded = nullptr, *corrected = nullptr;
   size_t p_stride = 0, c_stride = 0;
   SatDevice* sd = p->sat_dev.get();
-  int rc = rpsf_sat_fill_batch(sd, run.call, frames, images_dev, image_stride, order, st, &padded, &p_stride, &corrected, &c_stride);
+  int rc;
+  if (!masks) {
+    rc = rpsf_sat_fill_batch(sd, run.call, frames, images_dev, image_stride, order, st, &padded, &p_stride, &corrected, &c_stride);
+  } else {
+    const std::vector<rpsfsat::MaskView> views = group_views(*masks, f0, frames);
+    rc = rpsf_sat_fill_batch_masked(sd, run.call, frames, images_dev, image_stride, views.empty() ? nullptr : views.data(), masks->fill_nonfinite,
+                                    order, st, &padded, &p_stride, &corrected, &c_stride);
+  }
   if (rc != RPSF_OK) return rc;
   rc = rpsf_detail_launch_batch(p, padded + (size_t)run.r_lo * run.g.width, corrected, frames, p_stride, c_stride, run.g, st);
   if (rc != RPSF_OK) return rc;
@@ -311,7 +350,7 @@ static int sat_device_apply_group(rpsf_plan* p, const SatDeviceRun& run, int fra
 // one frame-group of host arrays through the plan's staging slot 0 (room for `frames` frames: pipe_ensure): staged as float32, uploaded,
 // sat_device_apply_group, downloaded, widened; T: parts of the host pool's copies
 static int sat_host_group(rpsf_plan* p, const SatDeviceRun& run, int frames, const void* const* images_host, int image_is_f64, void* const* outs_host,
-                          int out_is_f64, int order, int T, SatBatchStats* stats) {
+                          int out_is_f64, int order, int T, SatBatchStats* stats, const SatMasks* group_masks = nullptr) {
   const size_t npix = (size_t)run.call.H * run.call.W, total = npix * frames;
   HostPipe& q = *p->pipe;
   HostPool& pool = HostPool::get(p->device);
@@ -326,7 +365,7 @@ static int sat_host_group(rpsf_plan* p, const SatDeviceRun& run, int frames, con
   });
   hipError_t err = hipMemcpyAsync(q.d_in[0], q.h_in[0], total * sizeof(float), hipMemcpyHostToDevice, p->stream);
   if (err != hipSuccess) return rpsf_detail_drain_after_error(p, err, "saturated host frames, device route");
-  int rc = sat_device_apply_group(p, run, frames, q.d_in[0], npix, q.d_out[0], npix, order, p->stream, stats, nullptr);
+  int rc = sat_device_apply_group(p, run, frames, q.d_in[0], npix, q.d_out[0], npix, order, p->stream, stats, nullptr, group_masks, 0);
   if (rc != RPSF_OK) {
     (void)hipStreamSynchronize(p->stream);
     return rc;
@@ -357,7 +396,7 @@ static int sat_host_group(rpsf_plan* p, const SatDeviceRun& run, int frames, con
     for (int f = 0; f < frames; ++f) {
       const double* src = static_cast<const double*>(images_host[f]);
       const int32_t* mine = list + info[rpsfsatb::FRAME_INFO * f + rpsfsatb::I_LIST0];
-      const int n = counters[rpsfsatb::FRAME_COUNTERS * f + rpsfsatb::C_HOT] ? counters[rpsfsatb::FRAME_COUNTERS * f + rpsfsatb::C_LIST] : 0;
+      const int n = rpsfsatb::Stack::busy(counters + rpsfsatb::FRAME_COUNTERS * f) ? counters[rpsfsatb::FRAME_COUNTERS * f + rpsfsatb::C_LIST] : 0;
       for (int k = 0; k < n; ++k) {
         if (out_is_f64) static_cast<double*>(outs_host[f])[mine[k]] = src[mine[k]];
         else static_cast<float*>(outs_host[f])[mine[k]] = (float)src[mine[k]];
@@ -490,7 +529,7 @@ static int view_staging(DevBuf<float>& buf, size_t& cap, size_t floats) {
 }
 
 static int apply_views(rpsf_plan* p, const rpsf_view* images, const rpsf_view* outs, int n, int pad_mode, float pad_value, double threshold, int dilation,
-                       int neighborhood_width, void* stream, int* route_or_null, bool batch) {
+                       int neighborhood_width, void* stream, int* route_or_null, bool batch, const SatMasks* masks = nullptr) {
   if (route_or_null) *route_or_null = 0;
   if (!p) return fail(RPSF_E_BADARG, "null plan");
   if (n < 0) return fail(RPSF_E_BADARG, "n_frames must not be negative");
@@ -509,7 +548,9 @@ static int apply_views(rpsf_plan* p, const rpsf_view* images, const rpsf_view* o
   if (pad_mode < 0 || pad_mode > RPSF_PAD_WRAP) return fail(RPSF_E_BADARG, "unknown pad mode");
   if (!p->have_k) return fail(RPSF_E_STATE, "no transfer kernel installed (call rpsf_plan_set_transfer first)");
   const int H = images[0].rows, W = images[0].cols;
-  const bool saturated = !(threshold == std::numeric_limits<double>::infinity());
+  const bool saturated = masks || !(threshold == std::numeric_limits<double>::infinity());  // (a masked call takes the route whatever the threshold)
+  if (masks)
+    if (const int bad = check_masks(*masks, n, H, W)) return bad;
   const ViewSide in = view_side(images, n, saturated), out = view_side(outs, n, saturated);
   rpsf_geometry g{H, W, pad_mode, pad_value, 0, 0, 0, H, in.direct ? (int)(images[0].row_stride / 4) : W, 0, H, out.direct ? (int)(outs[0].row_stride / 4) : W};
   SatDeviceRun run;
@@ -544,12 +585,12 @@ static int apply_views(rpsf_plan* p, const rpsf_view* images, const rpsf_view* o
   if (!saturated) {
     rc = rpsf_detail_launch_batch(p, d_in, d_out, n, in_stride, out_stride, g, st);
   } else {
-    const int G = batch ? sat_group_frames(p, run) : 1;
+    const int G = batch ? sat_group_frames(p, run, masks != nullptr) : 1;
     SatBatchStats stats;
     stats.frames = n;
     for (int f0 = 0; f0 < n && rc == RPSF_OK; f0 += G)
       rc = sat_device_apply_group(p, run, std::min(G, n - f0), d_in + (size_t)f0 * in_stride, in_stride, d_out + (size_t)f0 * out_stride, out_stride,
-                                  batch ? rpsfsatb::ORDER_LONGEST_FIRST : rpsfsatb::ORDER_FRAMES, st, &stats, nullptr);
+                                  batch ? rpsfsatb::ORDER_LONGEST_FIRST : rpsfsatb::ORDER_FRAMES, st, &stats, nullptr, masks, f0);
     if (batch && rc == RPSF_OK) stats.store(p);
   }
   if (rc == RPSF_OK && !out.direct) {
@@ -575,6 +616,121 @@ extern "C" int rpsf_apply_batch_view(rpsf_plan* p, const rpsf_view* images, cons
   return apply_views(p, images, outs, n_frames, pad_mode, pad_value, threshold, dilation, neighborhood_width, stream, route_or_null, true);
 }
 
+// The masked entry points: a null mask with fill_nonfinite == 0 IS the unmasked entry point
+extern "C" int rpsf_apply_view_masked(rpsf_plan* p, const rpsf_view* image, const rpsf_view* out, int pad_mode, float pad_value, double threshold,
+                                      int dilation, int neighborhood_width, const rpsf_view* mask_or_null, int fill_nonfinite, void* stream,
+                                      int* route_or_null) {
+  if (!mask_or_null && !fill_nonfinite) return rpsf_apply_view(p, image, out, pad_mode, pad_value, threshold, dilation, neighborhood_width, stream, route_or_null);
+  const SatMasks masks{mask_or_null, mask_or_null ? 1 : 0, fill_nonfinite};
+  return apply_views(p, image, out, 1, pad_mode, pad_value, threshold, dilation, neighborhood_width, stream, route_or_null, false, &masks);
+}
+
+extern "C" int rpsf_apply_batch_view_masked(rpsf_plan* p, const rpsf_view* images, const rpsf_view* outs, int n_frames, int pad_mode, float pad_value,
+                                            double threshold, int dilation, int neighborhood_width, const rpsf_view* masks_or_null, int n_masks,
+                                            int fill_nonfinite, void* stream, int* route_or_null) {
+  if (!masks_or_null && !fill_nonfinite)
+    return rpsf_apply_batch_view(p, images, outs, n_frames, pad_mode, pad_value, threshold, dilation, neighborhood_width, stream, route_or_null);
+  const SatMasks masks{masks_or_null, masks_or_null ? n_masks : 0, fill_nonfinite};
+  return apply_views(p, images, outs, n_frames, pad_mode, pad_value, threshold, dilation, neighborhood_width, stream, route_or_null, true, &masks);
+}
+
+extern "C" int rpsf_apply_batch_device_masked(rpsf_plan* p, const void* images_dev, void* outs_dev, int n_frames, size_t image_stride, size_t out_stride,
+                                              int height, int width, int pad_mode, double threshold, int dilation, int neighborhood_width,
+                                              const rpsf_view* masks_or_null, int n_masks, int fill_nonfinite, void* stream,
+                                              size_t* n_masked_per_frame_or_null) {
+  if (!masks_or_null && !fill_nonfinite)
+    return rpsf_apply_batch_device_saturated(p, images_dev, outs_dev, n_frames, image_stride, out_stride, height, width, pad_mode, threshold, dilation,
+                                             neighborhood_width, stream, n_masked_per_frame_or_null);
+  if (p && n_frames == 0) {
+    SatBatchStats().store(p);
+    return RPSF_OK;
+  }
+  int rc = check_saturated_call(p, images_dev, outs_dev, height, width, pad_mode, dilation, neighborhood_width);
+  if (rc != RPSF_OK) return rc;
+  if (n_frames < 0) return fail(RPSF_E_BADARG, "n_frames must not be negative");
+  if (n_frames > 1 && (image_stride < (size_t)height * width || out_stride < (size_t)height * width))
+    return fail(RPSF_E_BADARG, "frame stride smaller than one frame");
+  const SatMasks masks{masks_or_null, masks_or_null ? n_masks : 0, fill_nonfinite};
+  if ((rc = check_masks(masks, n_frames, height, width)) != RPSF_OK) return rc;
+  SatDeviceRun run;
+  rc = sat_device_init(p, height, width, pad_mode, threshold, dilation, neighborhood_width, &run);
+  if (rc != RPSF_OK) return rc;
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : p->stream;
+  const int G = sat_group_frames(p, run, true);
+  SatBatchStats stats;
+  stats.frames = n_frames;
+  for (int f0 = 0; f0 < n_frames; f0 += G) {
+    rc = sat_device_apply_group(p, run, std::min(G, n_frames - f0), static_cast<const float*>(images_dev) + (size_t)f0 * image_stride, image_stride,
+                                static_cast<float*>(outs_dev) + (size_t)f0 * out_stride, out_stride, rpsfsatb::ORDER_LONGEST_FIRST, st, &stats,
+                                n_masked_per_frame_or_null ? n_masked_per_frame_or_null + f0 : nullptr, &masks, f0);
+    if (rc != RPSF_OK) return rc;
+  }
+  stats.store(p);
+  return RPSF_OK;
+}
+
+// `count` dense height x width uint8 host masks into the plan's mask scratch, on the plan's stream; views[f]: mask f there
+static int upload_host_masks(rpsf_plan* p, const uint8_t* const* masks_host, int count, int height, int width, std::vector<rpsf_view>* views) {
+  const size_t npix = (size_t)height * width;
+  if (npix * count > p->host_mask_bytes) {
+    HIP_TRY(hipDeviceSynchronize());  // an earlier call may still read the old scratch
+    p->host_mask_bytes = 0;
+    HIP_TRY(p->d_host_masks.alloc(npix * count));
+    p->host_mask_bytes = npix * count;
+  }
+  views->resize(count);
+  for (int f = 0; f < count; ++f) {
+    uint8_t* dst = p->d_host_masks + f * npix;
+    HIP_TRY(hipMemcpyAsync(dst, masks_host[f], npix, hipMemcpyHostToDevice, p->stream));
+    (*views)[f] = rpsf_view{dst, RPSF_DTYPE_UINT8, height, width, (int64_t)width, 1};
+  }
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_apply_frames_host_masked_device(rpsf_plan* p, const void* const* images_host, int image_is_f64, int n_frames, int height, int width,
+                                                    int pad_mode, double threshold, int dilation, int neighborhood_width,
+                                                    const uint8_t* const* masks_host_or_null, int n_masks, int fill_nonfinite, void* const* outs_host,
+                                                    int out_is_f64) {
+  if (!masks_host_or_null && !fill_nonfinite)
+    return rpsf_apply_frames_host_saturated_device(p, images_host, image_is_f64, n_frames, height, width, pad_mode, threshold, dilation,
+                                                   neighborhood_width, outs_host, out_is_f64);
+  if (p && n_frames == 0) {
+    SatBatchStats().store(p);
+    return RPSF_OK;
+  }
+  int rc = check_saturated_call(p, images_host, outs_host, height, width, pad_mode, dilation, neighborhood_width);
+  if (rc != RPSF_OK) return rc;
+  if (n_frames < 0) return fail(RPSF_E_BADARG, "n_frames must not be negative");
+  for (int f = 0; f < n_frames; ++f)
+    if (!images_host[f] || !outs_host[f]) return fail(RPSF_E_BADARG, "null frame pointer");
+  if (!masks_host_or_null) n_masks = 0;
+  if (n_masks < 0 || (n_masks > 1 && n_masks != n_frames)) return fail(RPSF_E_BADARG, "mask: no mask, one mask or one mask per frame");
+  for (int f = 0; f < n_masks; ++f)
+    if (!masks_host_or_null[f]) return fail(RPSF_E_BADARG, "mask: null mask pointer");
+  SatDeviceRun run;
+  rc = sat_device_init(p, height, width, pad_mode, threshold, dilation, neighborhood_width, &run);
+  if (rc != RPSF_OK) return rc;
+  const size_t npix = (size_t)height * width;
+  const int G = std::min(sat_group_frames(p, run, true), n_frames);
+  rc = rpsf_detail_pipe_ensure(p, npix * G, 1);
+  if (rc != RPSF_OK) return rc;
+  const int T = rpsf_detail_host_parts_for(npix * G * sizeof(float));
+  SatBatchStats stats;
+  stats.frames = n_frames;
+  std::vector<rpsf_view> views;
+  if (n_masks == 1 && (rc = upload_host_masks(p, masks_host_or_null, 1, height, width, &views)) != RPSF_OK) return rc;
+  for (int f0 = 0; f0 < n_frames; f0 += G) {
+    const int fg = std::min(G, n_frames - f0);
+    // (the scratch of the group before is free: sat_host_group returned after its stream had finished)
+    if (n_masks > 1 && (rc = upload_host_masks(p, masks_host_or_null + f0, fg, height, width, &views)) != RPSF_OK) return rc;
+    const SatMasks masks{views.empty() ? nullptr : views.data(), (int)views.size(), fill_nonfinite};
+    rc = sat_host_group(p, run, fg, images_host + f0, image_is_f64, outs_host + f0, out_is_f64, rpsfsatb::ORDER_LONGEST_FIRST, T, &stats, &masks);
+    if (rc != RPSF_OK) return rc;
+  }
+  stats.store(p);
+  return rpsf_detail_sweep_check(p);
+}
+
 extern "C" int rpsf_saturation_kernel_ms(rpsf_plan* p, double ms[5]) {
   if (!p || !ms) return fail(RPSF_E_BADARG, "null argument");
   for (int i = 0; i < 5; ++i) ms[i] = 0.0;
@@ -593,7 +749,7 @@ extern "C" int rpsf_saturation_batch_info(rpsf_plan* p, int info[4]) {
 // ((H + 4N) x (W + 4N) float32 each) and the masks come back
 static int sat_fill_frames(rpsf_plan* p, const float* images_host, int n_frames, int height, int width, int pad_mode, double threshold, int dilation,
                            int neighborhood_width, int order, float* padded_host, uint8_t* masks_host, int* groups_per_frame_or_null,
-                           SatBatchStats* stats) {
+                           SatBatchStats* stats, const SatMasks* masks = nullptr, int* masked_per_frame_or_null = nullptr) {
   if (!p || !images_host || !padded_host || !masks_host) return fail(RPSF_E_BADARG, "null argument");
   if (n_frames < 1) return fail(RPSF_E_BADARG, "n_frames must be positive");
   if (height <= 0 || width <= 0) return fail(RPSF_E_BADARG, "image shape must be positive");
@@ -607,7 +763,7 @@ static int sat_fill_frames(rpsf_plan* p, const float* images_host, int n_frames,
   SatDevice* sd = p->sat_dev.get();
   const SatCall call{height, width, p->N, pad_mode, dilation, neighborhood_width, threshold, 0, 0, 1};
   const size_t npix = (size_t)height * width, np = (size_t)PH * PW;
-  const int G = std::min(n_frames, p->sat_group_opt > 0 ? p->sat_group_opt : rpsfsatb::auto_group_frames(np, (size_t)height * PW));
+  const int G = std::min(n_frames, p->sat_group_opt > 0 ? p->sat_group_opt : rpsfsatb::auto_group_frames(np, (size_t)height * PW, masks != nullptr));
   DevBuf<float> d_images;
   HIP_TRY(d_images.upload(images_host, npix * n_frames));
   stats->frames = n_frames;
@@ -616,7 +772,14 @@ static int sat_fill_frames(rpsf_plan* p, const float* images_host, int n_frames,
     float *padded = nullptr, *corrected = nullptr;
     size_t p_stride = 0, c_stride = 0;
     const float* d_first = d_images;
-    int rc = rpsf_sat_fill_batch(sd, call, fg, d_first + (size_t)f0 * npix, npix, order, p->stream, &padded, &p_stride, &corrected, &c_stride);
+    int rc;
+    if (!masks) {
+      rc = rpsf_sat_fill_batch(sd, call, fg, d_first + (size_t)f0 * npix, npix, order, p->stream, &padded, &p_stride, &corrected, &c_stride);
+    } else {
+      const std::vector<rpsfsat::MaskView> views = group_views(*masks, f0, fg);
+      rc = rpsf_sat_fill_batch_masked(sd, call, fg, d_first + (size_t)f0 * npix, npix, views.empty() ? nullptr : views.data(), masks->fill_nonfinite,
+                                      order, p->stream, &padded, &p_stride, &corrected, &c_stride);
+    }
     if (rc == RPSF_OK) rc = rpsf_sat_masks_batch(sd, call, p->stream, masks_host + (size_t)f0 * np);  // waits for the stream
     if (rc != RPSF_OK) {
       (void)hipStreamSynchronize(p->stream);
@@ -627,6 +790,7 @@ static int sat_fill_frames(rpsf_plan* p, const float* images_host, int n_frames,
       int n_hot, n_mask, n_groups;
       rpsf_sat_frame_counts(sd, f, &n_hot, &n_mask, &n_groups);
       if (groups_per_frame_or_null) groups_per_frame_or_null[f0 + f] = n_groups;
+      if (masked_per_frame_or_null) masked_per_frame_or_null[f0 + f] = n_mask;
     }
     long groups = 0, masked = 0;
     rpsf_sat_batch_totals(sd, &groups, &masked);
@@ -651,6 +815,30 @@ extern "C" int rpsf_saturation_fill_batch_device(rpsf_plan* p, const float* imag
                                  masks_host, groups_per_frame_or_null, &stats);
   if (rc == RPSF_OK) stats.store(p);
   return rc;
+}
+
+// The masked test entry: n_masks (0, 1 or n_frames) host masks, mask_frame_bytes apart, element (r, c) of a mask at r * mask_row_stride +
+// c * mask_col_stride bytes - uploaded as they lie and read through those strides
+extern "C" int rpsf_saturation_fill_masked_device(rpsf_plan* p, const float* images_host, int n_frames, int height, int width, int pad_mode,
+                                                  double threshold, int dilation, int neighborhood_width, int order, const uint8_t* masks_in_host,
+                                                  int n_masks, size_t mask_frame_bytes, int64_t mask_row_stride, int64_t mask_col_stride,
+                                                  int fill_nonfinite, float* padded_host, uint8_t* masks_host, int* groups_per_frame_or_null,
+                                                  int* masked_per_frame_or_null) {
+  if (!p) return fail(RPSF_E_BADARG, "null argument");
+  if (!masks_in_host) n_masks = 0;
+  if (n_masks < 0 || (n_masks > 1 && n_masks != n_frames)) return fail(RPSF_E_BADARG, "mask: no mask, one mask or one mask per frame");
+  if (n_masks && (height <= 0 || width <= 0 || mask_row_stride <= 0 || mask_col_stride <= 0 ||
+                  (size_t)(height - 1) * mask_row_stride + (size_t)(width - 1) * mask_col_stride + 1 > mask_frame_bytes))
+    return fail(RPSF_E_BADARG, "mask: the strides do not fit mask_frame_bytes");
+  HIP_TRY(hipSetDevice(p->device));
+  DevBuf<uint8_t> d_masks;
+  std::vector<rpsf_view> views((size_t)n_masks);
+  if (n_masks) HIP_TRY(d_masks.upload(masks_in_host, mask_frame_bytes * n_masks));
+  for (int f = 0; f < n_masks; ++f) views[f] = rpsf_view{d_masks + f * mask_frame_bytes, RPSF_DTYPE_UINT8, height, width, mask_row_stride, mask_col_stride};
+  const SatMasks masks{views.empty() ? nullptr : views.data(), n_masks, fill_nonfinite};
+  SatBatchStats stats;
+  return sat_fill_frames(p, images_host, n_frames, height, width, pad_mode, threshold, dilation, neighborhood_width, order, padded_host, masks_host,
+                         groups_per_frame_or_null, &stats, &masks, masked_per_frame_or_null);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -7,6 +7,9 @@
 #include <cstddef>
 #include <cstdint>
 
+namespace rpsfsat {
+struct MaskView;  // csrc/rpsf_core_saturation.hpp
+}
 struct SatDevice;  // scratch, events and counters; owned by the plan, made at the first call, grown when a larger frame-group arrives
 
 struct SatCall {
@@ -25,6 +28,12 @@ __attribute__((visibility("hidden"))) int rpsf_sat_kernel_ms(SatDevice* s, doubl
 __attribute__((visibility("hidden"))) int rpsf_sat_fill_batch(SatDevice* s, const SatCall& c, int frames, const float* images_dev, size_t image_stride,
                                                                int order_mode, hipStream_t st, float** padded, size_t* p_stride, float** corrected,
                                                                size_t* c_stride);
+// The same with a bad-pixel mask ("Bad-pixel masks"): masks_host[f] is frame f's uint8 view in DEVICE memory (null: no
+// frame has one), fill_nonfinite: NaN and +-Inf of the padded frame are masked too.  These pixels are masked as they are, not dilated.
+__attribute__((visibility("hidden"))) int rpsf_sat_fill_batch_masked(SatDevice* s, const SatCall& c, int frames, const float* images_dev,
+                                                                      size_t image_stride, const rpsfsat::MaskView* masks_host, int fill_nonfinite,
+                                                                      int order_mode, hipStream_t st, float** padded, size_t* p_stride,
+                                                                      float** corrected, size_t* c_stride);
 // F5 of every frame of the last rpsf_sat_fill_batch, one launch
 __attribute__((visibility("hidden"))) int rpsf_sat_restore_batch(SatDevice* s, const SatCall& c, const float* images_dev, size_t image_stride,
                                                                   float* outs_dev, size_t out_stride, hipStream_t st);

@@ -3,7 +3,9 @@
 // frame-group of one.  The frame is a grid index (blockIdx.y; the labeller's tiles: blockIdx.z).
 //
 //   F1  sat_pad_batch_kernel                  2N-padded float32 frames and one hot byte per pixel (value > threshold), hot counts
+//       sat_pad_masked_batch_kernel           the masked route's F1: the exact plane as well (the caller's mask through the pad map, non-finite values)
 //   F2  sat_cross_batch_kernel x dilation     mask = hot dilated with the cross element (two byte planes in turn), masked counts
+//       sat_cross_merge_batch_kernel          the masked route's last pass: mask = dilated | exact
 //   F3  sat_rows / sat_cols_batch_kernel      mask grown by a box of reach h / 2, then the star finder's labeller (S3) and root list (S4)
 //       sat_group_init / accumulate_batch     per group: masked pixels and their bounding box
 //   F4  sat_order_hist / scatter_kernel       the groups of all frames longest first (not run when the table's own order is asked for)
@@ -12,8 +14,8 @@
 //
 // The phases are the drivers of rpsf_core_saturation_batch.hpp, which call the per-thread functions of rpsf_core_saturation.hpp.  Every
 // launch goes to the caller's stream; the host waits for it ONCE per frame-group, between the root count and the root list, to size the
-// group table.  A frame in which nothing is hot leaves every kernel after F1 at its first instruction, and when no frame has a hot
-// pixel F4 is not launched.  The only atomics are integer adds / min / max.
+// group table.  A frame in which nothing is hot (masked route: and nothing exact) leaves every kernel after F1 at its first instruction,
+// and when no frame has such a pixel F4 is not launched.  The only atomics are integer adds / min / max.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +39,11 @@ __global__ __launch_bounds__(256) void sat_pad_batch_kernel(Stack s, const float
 __global__ __launch_bounds__(256) void sat_cross_batch_kernel(Stack s, int from, int last) {
   rpsfsatb::b2_cross(global_id(), (int)blockIdx.y, s, from, last);
 }
+__global__ __launch_bounds__(256) void sat_pad_masked_batch_kernel(Stack s, const float* images, size_t image_stride, double threshold,
+                                                                   const MaskView* masks, int fill_nonfinite) {
+  rpsfsatb::b1_pad_masked(global_id(), (int)blockIdx.y, s, images, image_stride, threshold, masks, fill_nonfinite);
+}
+__global__ __launch_bounds__(256) void sat_cross_merge_batch_kernel(Stack s, int from) { rpsfsatb::b2_cross_merge(global_id(), (int)blockIdx.y, s, from); }
 __global__ __launch_bounds__(256) void sat_rows_batch_kernel(Stack s, int reach, int at) { rpsfsatb::b3_rows(global_id(), (int)blockIdx.y, s, reach, at); }
 __global__ __launch_bounds__(256) void sat_cols_batch_kernel(Stack s, int reach, int at) { rpsfsatb::b3_cols(global_id(), (int)blockIdx.y, s, reach, at); }
 __global__ __launch_bounds__(TILE_THREADS) void sat_label_tile_batch_kernel(Stack s, int grown) {
@@ -92,6 +99,9 @@ struct PinnedBuf {  // Buf in page-locked host memory
 struct SatDevice {  // the arrays hold the `frames` frames of the last fill, `stride` (corrected: `cstride`) elements apart
   Buf<float> padded, corrected;
   Buf<uint8_t> bytes[3];  // hot / mask in turn, the row-grown and the grown mask
+  Buf<uint8_t> exact;     // the masked route: the pixels masked as they are (the caller's mask through the pad map, non-finite values)
+  Buf<MaskView> mask_views;  // the masked route: one per frame
+  PinnedBuf<MaskView> h_mask_views;
   Buf<int32_t> labels, list;
   Buf<int> segcnt, segoff, roots, stats;
   Buf<int> counters, info, gframe, order;  // FRAME_COUNTERS per frame + SHARED_COUNTERS; FRAME_INFO per frame; per group
@@ -143,8 +153,10 @@ Stack stack_of(const SatDevice* s, const SatCall& c) {
 }
 }  // namespace
 
-int rpsf_sat_fill_batch(SatDevice* s, const SatCall& c, int frames, const float* images_dev, size_t image_stride, int order_mode, hipStream_t st,
-                        float** padded, size_t* p_stride, float** corrected, size_t* c_stride) {
+// masked: the route of rpsf_sat_fill_batch_masked (F1's and F2's last pass's variants); masks_host: `frames` views or null
+static int fill_batch(SatDevice* s, const SatCall& c, int frames, const float* images_dev, size_t image_stride, bool masked,
+                      const MaskView* masks_host, int fill_nonfinite, int order_mode, hipStream_t st, float** padded, size_t* p_stride,
+                      float** corrected, size_t* c_stride) {
   using namespace rpsfsatb;
   if (frames < 1 || frames > MAX_GROUP_FRAMES) return fail(RPSF_E_BADARG, "saturation: frames per frame-group out of range");
   const int PH = c.H + 4 * c.N, PW = c.W + 4 * c.N, h = c.width / 2;
@@ -165,19 +177,38 @@ int rpsf_sat_fill_batch(SatDevice* s, const SatCall& c, int frames, const float*
   HIP_TRY(s->h_counters.reserve(F * FRAME_COUNTERS));
   HIP_TRY(s->info.reserve(F * FRAME_INFO));
   HIP_TRY(s->h_info.reserve(F * FRAME_INFO));
+  if (masked) {
+    HIP_TRY(s->exact.reserve(F * stride));
+    if (masks_host) {
+      HIP_TRY(s->mask_views.reserve(F));
+      HIP_TRY(s->h_mask_views.reserve(F));
+    }
+  }
   s->stride = stride, s->cstride = cstride, s->nseg = (size_t)nseg;
   *padded = s->padded.p, *p_stride = stride, *corrected = s->corrected.p, *c_stride = cstride;
-  const Stack k = stack_of(s, c);
+  Stack k = stack_of(s, c);
+  k.exact = masked ? s->exact.p : nullptr;
   const unsigned fy = (unsigned)frames;
   const dim3 quads(blocks_for((npix + 3) / 4), fy), pixels(blocks_for(npix), fy), segs(blocks_for(nseg), fy);
 
   HIP_TRY(hipMemsetAsync(s->counters.p, 0, n_counters * sizeof(int), st));
   HIP_TRY(hipEventRecord(s->ev[SatDevice::E_START], st));
-  hipLaunchKernelGGL(sat_pad_batch_kernel, quads, dim3(256), 0, st, k, images_dev, image_stride, c.threshold);
+  if (masked) {
+    if (masks_host) {  // (the pinned copy is free again: every earlier fill waited for its stream after this copy)
+      std::copy(masks_host, masks_host + F, s->h_mask_views.p);
+      HIP_TRY(hipMemcpyAsync(s->mask_views.p, s->h_mask_views.p, F * sizeof(MaskView), hipMemcpyHostToDevice, st));
+    }
+    hipLaunchKernelGGL(sat_pad_masked_batch_kernel, quads, dim3(256), 0, st, k, images_dev, image_stride, c.threshold,
+                       masks_host ? s->mask_views.p : nullptr, fill_nonfinite);
+  } else {
+    hipLaunchKernelGGL(sat_pad_batch_kernel, quads, dim3(256), 0, st, k, images_dev, image_stride, c.threshold);
+  }
   HIP_TRY(hipEventRecord(s->ev[SatDevice::E_F1], st));
   int at = 0;
-  for (int pass = 0; pass < c.dilation; ++pass, at ^= 1)
-    hipLaunchKernelGGL(sat_cross_batch_kernel, quads, dim3(256), 0, st, k, at, pass == c.dilation - 1);
+  for (int pass = 0; pass < c.dilation; ++pass, at ^= 1) {
+    if (masked && pass == c.dilation - 1) hipLaunchKernelGGL(sat_cross_merge_batch_kernel, quads, dim3(256), 0, st, k, at);
+    else hipLaunchKernelGGL(sat_cross_batch_kernel, quads, dim3(256), 0, st, k, at, pass == c.dilation - 1);
+  }
   HIP_TRY(hipEventRecord(s->ev[SatDevice::E_F2], st));
   int grown = at;
   if (const int reach = box_reach(h); reach > 0) {
@@ -225,6 +256,17 @@ int rpsf_sat_fill_batch(SatDevice* s, const SatCall& c, int frames, const float*
   return RPSF_OK;
 }
 
+int rpsf_sat_fill_batch(SatDevice* s, const SatCall& c, int frames, const float* images_dev, size_t image_stride, int order_mode, hipStream_t st,
+                        float** padded, size_t* p_stride, float** corrected, size_t* c_stride) {
+  return fill_batch(s, c, frames, images_dev, image_stride, false, nullptr, 0, order_mode, st, padded, p_stride, corrected, c_stride);
+}
+
+int rpsf_sat_fill_batch_masked(SatDevice* s, const SatCall& c, int frames, const float* images_dev, size_t image_stride, const MaskView* masks_host,
+                               int fill_nonfinite, int order_mode, hipStream_t st, float** padded, size_t* p_stride, float** corrected,
+                               size_t* c_stride) {
+  return fill_batch(s, c, frames, images_dev, image_stride, true, masks_host, fill_nonfinite, order_mode, st, padded, p_stride, corrected, c_stride);
+}
+
 int rpsf_sat_restore_batch(SatDevice* s, const SatCall& c, const float* images_dev, size_t image_stride, float* outs_dev, size_t out_stride,
                            hipStream_t st) {
   if (s->frames < 1) return fail(RPSF_E_STATE, "saturation: no filled frame-group to restore");
@@ -259,7 +301,7 @@ int rpsf_sat_masks_batch(SatDevice* s, const SatCall& c, hipStream_t st, uint8_t
   HIP_TRY(hipStreamSynchronize(st));
   for (int fr = 0; fr < s->frames; ++fr) {
     uint8_t* dst = masks_host + fr * np;
-    if (s->h_counters.p[rpsfsatb::FRAME_COUNTERS * fr + rpsfsatb::C_HOT] == 0) std::fill(dst, dst + np, (uint8_t)0);
+    if (!Stack::busy(s->h_counters.p + rpsfsatb::FRAME_COUNTERS * fr)) std::fill(dst, dst + np, (uint8_t)0);
     else HIP_TRY(hipMemcpy(dst, s->bytes[s->at].p + fr * s->stride, np, hipMemcpyDeviceToHost));
   }
   return RPSF_OK;
@@ -267,7 +309,7 @@ int rpsf_sat_masks_batch(SatDevice* s, const SatCall& c, hipStream_t st, uint8_t
 
 int rpsf_sat_frame_counts(SatDevice* s, int fr, int* n_hot, int* n_mask, int* n_groups) {
   const int* c = s->h_counters.p + rpsfsatb::FRAME_COUNTERS * fr;
-  const bool hot = c[rpsfsatb::C_HOT] != 0;
+  const bool hot = Stack::busy(c);
   *n_hot = c[rpsfsatb::C_HOT], *n_mask = hot ? c[rpsfsatb::C_MASK] : 0, *n_groups = hot ? c[rpsfsatb::C_GROUPS] : 0;
   return RPSF_OK;
 }

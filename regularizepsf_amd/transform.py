@@ -61,6 +61,82 @@ def _kernel_stamp(cube: IndexedCube) -> tuple:
     return (id(values), cube._edits, values.shape, values.dtype.str, digest)
 
 
+_INDEX_MAP_MODES = ("symmetric", "reflect", "edge", "wrap")  # np.pad modes that copy pixels: a mask follows the image through them
+
+
+def _check_masks(mask, shape, frames: int | None, device: int, frames_on_device: bool):
+    """The ``mask=`` argument of apply (``frames`` None: one 2-D mask) or apply_batch (one 2-D mask for all frames, or ``frames`` of them as a
+    3-D stack or a sequence) as ``(on_device, [masks])`` with one mask or one per frame: host masks as bool arrays, device masks as uint8
+    ``DeviceArray`` views.  Raises before anything runs: ``TypeError`` for a device mask with host frames, ``ValueError`` for a wrong
+    shape, a wrong count or a device mask that is not uint8.  Touches no GPU."""
+    if mask is None:
+        return False, None
+    shape = tuple(shape)
+    if not device_array.is_device_array(mask) and not isinstance(mask, np.ndarray) and isinstance(mask, (list, tuple)):
+        kinds = {device_array.is_device_array(m) for m in mask}
+        if len(kinds) == 2:
+            msg = "mask mixes host and device arrays"
+            raise ValueError(msg)
+        on_device = kinds == {True}
+        items = list(mask) if on_device else None
+    else:
+        on_device, items = device_array.is_device_array(mask), None
+    if on_device and not frames_on_device:
+        msg = "a device mask goes with device frames; pass a NumPy mask with NumPy frames"
+        raise TypeError(msg)
+    if on_device:
+        if items is None:
+            stack = device_array.as_device_array(mask, device, what="mask")
+            items = [stack] if stack.ndim == 2 else [stack[i] for i in range(stack.shape[0])] if stack.ndim == 3 and frames is not None else None
+            if items is None:
+                msg = f"mask must have the frame's shape {shape}, got {stack.shape}"
+                raise ValueError(msg)
+        else:
+            items = [device_array.as_device_array(m, device, what="mask") for m in items]
+        for m in items:
+            if m.dtype != np.uint8:
+                msg = f"a device mask must be uint8, got {m.dtype}"
+                raise ValueError(msg)
+            if any(s <= 0 for s, n in zip(m.strides, m.shape) if n > 1):
+                msg = "a device mask needs positive strides"
+                raise ValueError(msg)
+    else:
+        host = np.asarray(mask)
+        if host.dtype == object:
+            msg = "masks must be arrays of one shape"
+            raise ValueError(msg)
+        host = host.astype(bool)
+        if host.ndim == 2:
+            items = [host]
+        elif host.ndim == 3 and frames is not None:
+            items = list(host)
+        else:
+            msg = f"mask must have the frame's shape {shape}, got {host.shape}"
+            raise ValueError(msg)
+    for m in items:
+        if m.ndim != 2 or tuple(m.shape) != shape:
+            msg = f"mask must have the frame's shape {shape}, got {tuple(m.shape)}"
+            raise ValueError(msg)
+    if len(items) != 1 and len(items) != frames:
+        msg = f"{len(items)} masks for {frames} frames: pass one mask, or one per frame"
+        raise ValueError(msg)
+    return on_device, items
+
+
+def _mask_view(m: "device_array.DeviceArray") -> _native.View:
+    """rpsf_view of a 2-D uint8 device mask (an axis of length one may carry any stride: it is never stepped along)."""
+    return _native.View(m.ptr or None, _native.DTYPES["|u1"], m.shape[0], m.shape[1], max(1, m.strides[0]), max(1, m.strides[1]))
+
+
+def _pad_mask(mask: np.ndarray | None, shape, n: int, pad_mode) -> np.ndarray:
+    """The caller's mask on the 2N-padded frame: through the pad mode's index map where there is one, False in the pad otherwise."""
+    if mask is None:
+        return np.zeros((shape[0] + 4 * n, shape[1] + 4 * n), bool)
+    if isinstance(pad_mode, str) and pad_mode in _INDEX_MAP_MODES:
+        return np.pad(mask, 2 * n, mode=pad_mode)
+    return np.pad(mask, 2 * n, mode="constant", constant_values=False)
+
+
 class ArrayPSFTransform:
     """Transformation from a source PSF to a target PSF that can be applied to images."""
 
@@ -281,7 +357,8 @@ class ArrayPSFTransform:
     # ------------------------------------------------------------------ apply (transform.py:85-177)
     def apply(self, image: np.ndarray, workers: int | None = None, pad_mode: str = "symmetric",
               saturation_threshold: float = math.inf, saturation_dilation: int = 1,
-              neighborhood_width: int = 7, *, out: np.ndarray | None = None, stream=None) -> np.ndarray:
+              neighborhood_width: int = 7, *, out: np.ndarray | None = None, stream=None, mask=None,
+              fill_nonfinite: bool = False) -> np.ndarray:
         """Apply the transform to an image and return the corrected image (float64, same shape).
 
         Parameters follow the reference: ``pad_mode`` is any ``np.pad`` mode; pixels brighter than
@@ -311,16 +388,35 @@ class ArrayPSFTransform:
         What the device routes do not cover comes down, runs the host route above and goes back up, cast to the result dtype:
         ``np.pad`` modes the kernels do not evaluate (anything but constant, symmetric, reflect, edge, wrap) and the corner cases of the
         saturation arguments (a threshold that is not finite, ``saturation_dilation < 1`` or not integral, ``neighborhood_width // 2 < 1``).
+
+        BAD PIXELS (keyword only, not in the reference): ``mask`` names pixels to treat as the saturated ones are -
+        replaced by the mean of their neighbourhood before the correction, returned as the caller's own values after it - without being
+        brighter than anything: an array of the image's shape, nonzero = masked; a NumPy array of any dtype ``astype(bool)`` takes, or,
+        with a device frame, a uint8 ``DeviceArray`` / ``__cuda_array_interface__`` object at any positive strides (a NumPy mask with a
+        device frame is uploaded; a device mask with a NumPy frame is a ``TypeError``).  ``fill_nonfinite=True`` treats every NaN and
+        +-Inf pixel of the frame so.  Unlike the pixels above ``saturation_threshold`` these are NOT dilated: the mask goes onto the
+        padded frame through the pad mode's index map (symmetric, reflect, edge, wrap; no pad pixel is masked otherwise) and is or-ed
+        with the dilated saturation mask.  Either keyword sends the frame down the device saturation route (kernels F1 - F5) whatever
+        ``saturation=`` says, also with ``saturation_threshold=inf``; arguments that route does not cover take the NumPy steps of the
+        definition.  With both at their defaults nothing changes.  A wrong mask shape or dtype raises ``ValueError`` before any work.
         """
         del workers
+        masked = mask is not None or bool(fill_nonfinite)
         if device_array.is_device_array(image):
             with self._lock:
+                if masked:
+                    return self._apply_device_locked(image, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, out, stream,
+                                                     mask, True, bool(fill_nonfinite))
                 return self._apply_device_locked(image, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, out, stream)
         if stream is not None:
             msg = "stream= goes with device arrays; a NumPy frame is corrected when the call returns"
             raise ValueError(msg)
         with self._lock:
-            result = self._apply_locked(image, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, out)
+            if masked:
+                result = self._apply_locked(image, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, out, mask, True,
+                                            bool(fill_nonfinite))
+            else:
+                result = self._apply_locked(image, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, out)
         if out is not None and result is not out:  # (the branches that build their result on the host)
             if out.shape != result.shape:
                 msg = "out must have the image's shape"
@@ -329,11 +425,16 @@ class ArrayPSFTransform:
             return out
         return result
 
-    def _apply_locked(self, image, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, out=None) -> np.ndarray:
+    def _apply_locked(self, image, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, out=None, mask=None, masked=False,
+                      fill_nonfinite=False) -> np.ndarray:
+        """``masked``: the call names bad pixels (``mask``: what the caller gave, or a checked bool array; ``fill_nonfinite``)."""
         image = np.asarray(image)
         if image.ndim != 2:
             msg = f"image must be two dimensional, got shape {image.shape}"
             raise ValueError(msg)
+        if masked:
+            _, items = _check_masks(mask, image.shape, None, self._device, False)
+            mask = items[0] if items else None
         if len(self) == 0:  # the reference fails in np.stack([]) (transform.py:157-162)
             msg = "need at least one array to stack"
             raise ValueError(msg)
@@ -342,10 +443,15 @@ class ArrayPSFTransform:
         height, width = image.shape
         self._check_corners(n, height, width)
 
-        if saturation_threshold == math.inf and pad_mode in _native.PAD_MODES:  # nothing can exceed +inf
+        if masked and self._device_route(pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, masked=True):
+            # F1 - F5 with the exact plane (rpsf_apply_frames_host_masked_device, a frame-group of one); a float64 frame gets its own bits back on the mask
+            return plan.apply_frames_host_masked_device([image], _native.PAD_MODES[pad_mode], saturation_threshold, saturation_dilation,
+                                                        neighborhood_width, None if mask is None else [mask], fill_nonfinite)[0]
+
+        if not masked and saturation_threshold == math.inf and pad_mode in _native.PAD_MODES:  # nothing can exceed +inf
             return plan.apply_host(image, _native.PAD_MODES[pad_mode], out=out)  # float64 out (or the caller's array); conversions inside the library
 
-        if (pad_mode in _native.PAD_MODES and isinstance(saturation_dilation, numbers.Integral) and saturation_dilation >= 1
+        if (not masked and pad_mode in _native.PAD_MODES and isinstance(saturation_dilation, numbers.Integral) and saturation_dilation >= 1
                 and isinstance(neighborhood_width, numbers.Integral) and neighborhood_width >= 0):
             # the saturation branch in one library call: the reference's host steps (pad, mask, dilation, sequential fill, restore) on the
             # plan's own scratch, the correction of the padded frame on the GPU (rpsf_apply_host_saturated)
@@ -360,11 +466,18 @@ class ArrayPSFTransform:
         # iterates to a fixed point; negative widths), which work on the padded image (transform.py:119-138,171-172).
         padded = np.pad(image.astype(float), ((2 * n, 2 * n), (2 * n, 2 * n)), mode=pad_mode)
         raw = padded.copy()
+        bad = mask
         mask = padded > saturation_threshold
         if np.any(mask):
             from scipy.ndimage import binary_dilation
 
             mask = binary_dilation(mask, iterations=saturation_dilation)
+        if masked:  # the pixels masked as they are: not dilated ("Bad-pixel masks")
+            exact = _pad_mask(bad, image.shape, n, pad_mode)
+            if fill_nonfinite:
+                exact |= ~np.isfinite(padded)
+            mask = mask | exact
+        if np.any(mask):
             padded[mask] = np.nan
             if neighborhood_width >= 0:
                 # the reference's per-pixel np.nanmean loop, restated in C (same order, same window rule)
@@ -380,13 +493,14 @@ class ArrayPSFTransform:
         return corrected[2 * n : height + 2 * n, 2 * n : width + 2 * n]
 
     # ------------------------------------------------------------------ device frames
-    def _device_route(self, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width) -> bool:
-        """Whether rpsf_apply_view / rpsf_apply_batch_view cover these arguments (else: down, the host route, up)."""
+    def _device_route(self, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, masked=False) -> bool:
+        """Whether rpsf_apply_view / rpsf_apply_batch_view cover these arguments (else: down, the host route, up).  ``masked``: the
+        saturation kernels run whatever the threshold, so their preconditions hold for +inf as well."""
         if pad_mode not in _native.PAD_MODES or not isinstance(saturation_threshold, numbers.Real):
             return False
-        if saturation_threshold == math.inf:
+        if saturation_threshold == math.inf and not masked:
             return True
-        return (math.isfinite(saturation_threshold) and isinstance(saturation_dilation, numbers.Integral) and saturation_dilation >= 1
+        return ((math.isfinite(saturation_threshold) or saturation_threshold == math.inf) and isinstance(saturation_dilation, numbers.Integral) and saturation_dilation >= 1
                 and isinstance(neighborhood_width, numbers.Integral) and neighborhood_width // 2 >= 1)
 
     def _enter_stream(self, stream, inputs, outputs):
@@ -420,11 +534,16 @@ class ArrayPSFTransform:
             raise ValueError(msg)
         return out
 
-    def _apply_device_locked(self, image, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, out, stream):
+    def _apply_device_locked(self, image, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, out, stream, mask=None,
+                             masked=False, fill_nonfinite=False):
         image = device_array.as_device_array(image, self._device)
         if image.ndim != 2:
             msg = f"image must be two dimensional, got shape {image.shape}"
             raise ValueError(msg)
+        mask_on_device = False
+        if masked:
+            mask_on_device, items = _check_masks(mask, image.shape, None, self._device, True)
+            mask = items[0] if items else None
         if len(self) == 0:
             msg = "need at least one array to stack"
             raise ValueError(msg)
@@ -432,17 +551,29 @@ class ArrayPSFTransform:
         plan = self._device_plan()
         self._check_corners(n, *image.shape)
         result = self._device_out(out, image.shape, np.float32)
-        if not self._device_route(pad_mode, saturation_threshold, saturation_dilation, neighborhood_width):
-            host = self._apply_locked(image.to_host(), pad_mode, saturation_threshold, saturation_dilation, neighborhood_width)
+        if not self._device_route(pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, masked):
+            if masked:
+                host = self._apply_locked(image.to_host(), pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, None,
+                                          mask.to_host() if mask_on_device else mask, True, fill_nonfinite)
+            else:
+                host = self._apply_locked(image.to_host(), pad_mode, saturation_threshold, saturation_dilation, neighborhood_width)
             result._assign(host.astype(result.dtype))
             return result
-        handle, s = self._enter_stream(stream, (image,), (result,))
-        self.last_route = plan.apply_view(image._view2d(), result._view2d(), _native.PAD_MODES[pad_mode], saturation_threshold,
-                                          saturation_dilation, neighborhood_width, s)
+        if masked and mask is not None and not mask_on_device:
+            mask = device_array.to_device(mask.astype(np.uint8), self._device)  # (F1 has read it when the call returns: the route's one wait comes later)
+        handle, s = self._enter_stream(stream, (image,) if mask is None else (image, mask), (result,))
+        if masked:
+            self.last_route = plan.apply_view_masked(image._view2d(), result._view2d(), _native.PAD_MODES[pad_mode], saturation_threshold,
+                                                     saturation_dilation, neighborhood_width, None if mask is None else _mask_view(mask),
+                                                     fill_nonfinite, s)
+        else:
+            self.last_route = plan.apply_view(image._view2d(), result._view2d(), _native.PAD_MODES[pad_mode], saturation_threshold,
+                                              saturation_dilation, neighborhood_width, s)
         self._leave_stream(plan, handle, (result,))
         return result
 
-    def _apply_batch_device_locked(self, images, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, dtype, out, stream):
+    def _apply_batch_device_locked(self, images, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, dtype, out, stream,
+                                   mask=None, masked=False, fill_nonfinite=False):
         if device_array.is_device_array(images):
             stack = device_array.as_device_array(images, self._device, what="images")
             if stack.ndim != 3:
@@ -462,11 +593,17 @@ class ArrayPSFTransform:
             if out.shape != (len(frames), *shape):
                 msg = "out must have shape (frames, H, W)"
                 raise ValueError(msg)
+        masks, masks_on_device = None, False
+        if masked:
+            masks_on_device, masks = _check_masks(mask, shape, len(frames), self._device, True)
         covered = (dtype in device_array.RESULT_DTYPES and len(frames) > 0
-                   and self._device_route(pad_mode, saturation_threshold, saturation_dilation, neighborhood_width))
+                   and self._device_route(pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, masked))
         if not covered:  # down, the host route, up: the host route's result, whatever it is for these arguments
+            bad = ()
+            if masked:
+                bad = (None if masks is None else [m.to_host() if masks_on_device else m for m in masks], True, fill_nonfinite)
             host = self._apply_batch_locked([f.to_host() for f in frames], None, pad_mode, saturation_threshold, saturation_dilation,
-                                            neighborhood_width, dtype if dtype in device_array.RESULT_DTYPES else np.float64, None)
+                                            neighborhood_width, dtype if dtype in device_array.RESULT_DTYPES else np.float64, None, *bad)
             if out is None:
                 return device_array.to_device(host.astype(dtype if dtype in device_array.DTYPES else np.float64, copy=False), self._device)
             out._assign(host)
@@ -478,9 +615,18 @@ class ArrayPSFTransform:
         plan = self._device_plan()
         self._check_corners(n, *shape)
         result = out if out is not None else device_array.device_empty((len(frames), *shape), dtype, self._device)
-        handle, s = self._enter_stream(stream, frames, (result,))
-        self.last_route = plan.apply_batch_view([f._view2d() for f in frames], [result[i]._view2d() for i in range(len(frames))],
-                                                _native.PAD_MODES[pad_mode], saturation_threshold, saturation_dilation, neighborhood_width, s)
+        if masks is not None and not masks_on_device:  # one upload for the call (F1 has read it when the call returns)
+            stack = device_array.to_device(np.stack(masks).astype(np.uint8), self._device)
+            masks = [stack[i] for i in range(len(masks))]
+        handle, s = self._enter_stream(stream, (*frames, *(masks or ())), (result,))
+        if masked:
+            self.last_route = plan.apply_batch_view_masked([f._view2d() for f in frames], [result[i]._view2d() for i in range(len(frames))],
+                                                           _native.PAD_MODES[pad_mode], saturation_threshold, saturation_dilation,
+                                                           neighborhood_width, None if masks is None else [_mask_view(m) for m in masks],
+                                                           fill_nonfinite, s)
+        else:
+            self.last_route = plan.apply_batch_view([f._view2d() for f in frames], [result[i]._view2d() for i in range(len(frames))],
+                                                    _native.PAD_MODES[pad_mode], saturation_threshold, saturation_dilation, neighborhood_width, s)
         self._leave_stream(plan, handle, (result,))
         return result
 
@@ -505,7 +651,8 @@ class ArrayPSFTransform:
 
     def apply_batch(self, images, workers: int | None = None, pad_mode: str = "symmetric",
                     saturation_threshold: float = math.inf, saturation_dilation: int = 1,
-                    neighborhood_width: int = 7, dtype: type = np.float64, out: np.ndarray | None = None, stream=None) -> np.ndarray:
+                    neighborhood_width: int = 7, dtype: type = np.float64, out: np.ndarray | None = None, stream=None, *, mask=None,
+                    fill_nonfinite: bool = False) -> np.ndarray:
         """Apply the transform to a stack ``(frames, H, W)`` or a sequence of equally shaped images; returns a stack.
 
         Equivalent to ``np.stack([self.apply(im, ...) for im in images])`` - the loop a user of the reference writes
@@ -520,8 +667,13 @@ class ArrayPSFTransform:
         With a finite ``saturation_threshold`` and ``saturation="device"``, float32 / float64 frames go through the batched device route
         (``rpsf_apply_frames_host_saturated_device``: the frames of a frame-group share the launches of kernels F1 - F3, the host waits for
         the device once and one launch fills every frame's groups), again bit-identical to the loop.
+        ``mask`` and ``fill_nonfinite`` (keyword only) are :meth:`apply`'s: ``mask`` is one 2-D mask for all frames, or one per frame as a
+        3-D stack or a sequence (NumPy, or uint8 device arrays with device frames).  The frames of a frame-group share the masked
+        launches as they share the saturation ones (``rpsf_apply_frames_host_masked_device``, ``rpsf_apply_batch_view_masked``).
         Extension of the reference API - there is no ``apply_batch`` upstream.
         """
+        masked = mask is not None or bool(fill_nonfinite)
+        bad = (mask, True, bool(fill_nonfinite)) if masked else ()
         on_device = device_array.is_device_array(images)
         if not on_device and not isinstance(images, np.ndarray):
             images = list(images)
@@ -533,16 +685,16 @@ class ArrayPSFTransform:
         if on_device:
             with self._lock:
                 return self._apply_batch_device_locked(images, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width,
-                                                       dtype, out, stream)
+                                                       dtype, out, stream, *bad)
         if stream is not None:
             msg = "stream= goes with device arrays; NumPy frames are corrected when the call returns"
             raise ValueError(msg)
         with self._lock:
             return self._apply_batch_locked(images, workers, pad_mode, saturation_threshold, saturation_dilation,
-                                            neighborhood_width, dtype, out)
+                                            neighborhood_width, dtype, out, *bad)
 
     def _apply_batch_locked(self, images, workers, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width,
-                            dtype, out) -> np.ndarray:
+                            dtype, out, mask=None, masked=False, fill_nonfinite=False) -> np.ndarray:
         stack = None
         if isinstance(images, np.ndarray):
             if images.ndim != 3:
@@ -558,6 +710,25 @@ class ArrayPSFTransform:
                 msg = "images must be a sequence of two dimensional arrays of one shape"
                 raise ValueError(msg)
         dtype = np.dtype(out.dtype if out is not None else dtype)
+        if masked:
+            _, masks = _check_masks(mask, shape, len(frames), self._device, False)
+            if (self._device_route(pad_mode, saturation_threshold, saturation_dilation, neighborhood_width, masked=True) and len(frames) > 0
+                    and len(self) > 0 and dtype in (np.float32, np.float64)):
+                # every frame of a frame-group through the masked launches (rpsf_apply_frames_host_masked_device); the bits of the loop over apply
+                n = self._checked_patch_size()
+                plan = self._device_plan()
+                self._check_corners(n, *shape)
+                res = plan.apply_frames_host_masked_device(frames, _native.PAD_MODES[pad_mode], saturation_threshold, saturation_dilation,
+                                                           neighborhood_width, masks, fill_nonfinite, out_dtype=dtype)
+            else:
+                outs = [self.apply(im, workers, pad_mode, saturation_threshold, saturation_dilation, neighborhood_width,
+                                   mask=None if masks is None else masks[i if len(masks) > 1 else 0], fill_nonfinite=fill_nonfinite)
+                        for i, im in enumerate(frames)]
+                res = np.stack(outs).astype(dtype, copy=False) if outs else np.empty((0, *shape), dtype)
+            if out is not None:
+                out[...] = res
+                return out
+            return res
         if (self._saturation == "device" and isinstance(saturation_threshold, numbers.Real) and math.isfinite(saturation_threshold)
                 and pad_mode in _native.PAD_MODES and len(frames) > 0 and len(self) > 0 and dtype in (np.float32, np.float64)
                 and isinstance(saturation_dilation, numbers.Integral) and saturation_dilation >= 1
