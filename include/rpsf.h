@@ -618,6 +618,26 @@ int rpsf_stars_deblend_info(const rpsf_stars* finder, size_t* components, size_t
 /* Device time of the last D1 - D4 (or of the last rpsf_stars_basins), milliseconds; 0 when the option was off. */
 int rpsf_stars_deblend_ms(const rpsf_stars* finder, double* ms);
 
+/* SHAPES (kernel S5): second moments and the peak of every row of the last detect.  Never called, nothing of it runs and
+ * no launch, allocation or download of the finder differs.  For a row (row, col, flux, area) with P the pixels of its component (or, with
+ * the deblend option, of its object), d the residual of rpsf_stars_detect, dr = r - row and dc = c - col:
+ *   rr = sum_P d (dr dr) / flux, cc = sum_P d (dc dc) / flux, rc = sum_P d (dr dc) / flux, abs_flux = sum_P |d|, peak = max_P d at
+ *   (peak_row, peak_col), the first pixel in raster order that attains it, and the bounding box of P;
+ * float64, in S4's summation order (lane-strided raster order over the bounding box, 8 groups of 8).  This is not sep: no 1 / 12 pixel
+ * term, no clamp of a singular matrix, and the footprint is this detector's.  A row is RPSF_STARS_SHAPE_COLUMNS float64:
+ *   row, col, flux, area (the bits of rpsf_stars_positions), peak, peak_row, peak_col, row_min, row_max, col_min, col_max, abs_flux,
+ *   rr, cc, rc. */
+#define RPSF_STARS_SHAPE_COLUMNS 15
+/* Kernel S5 on the rows of the last rpsf_stars_detect / rpsf_stars_detect_device; *count receives their number (0: nothing is launched).
+ * RPSF_E_BADARG when there is no such detect, or when a call since has replaced the finder's frame, a mesh or its labels
+ * (rpsf_stars_background*, rpsf_stars_filter_mesh, rpsf_stars_label, rpsf_stars_basins). */
+int rpsf_stars_measure(rpsf_stars* finder, size_t* count);
+/* Rows first .. first + count of the last rpsf_stars_measure, in the order of rpsf_stars_positions: count x RPSF_STARS_SHAPE_COLUMNS
+ * float64.  A range outside them: RPSF_E_BADARG.  A new detect empties them. */
+int rpsf_stars_shapes(rpsf_stars* finder, size_t first, size_t count, double* out);
+/* Device time of the last S5, milliseconds. */
+int rpsf_stars_shape_ms(const rpsf_stars* finder, double* ms);
+
 /* rpsf_builder_add_frame on a dense float32 frame that is already on the builder's device - a finder's (rpsf_stars_frame) or the caller's
  * own; it is only read, nothing is uploaded but the star list.  On a scaled builder the frame is the SCALED one and height and width are
  * its. */

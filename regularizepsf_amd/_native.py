@@ -171,6 +171,9 @@ _PROTOTYPES = {
     "rpsf_stars_basins": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "rpsf_stars_deblend_info": (c_int, [c_void_p, POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t)]),
     "rpsf_stars_deblend_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rpsf_stars_measure": (c_int, [c_void_p, POINTER(c_size_t)]),
+    "rpsf_stars_shapes": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p]),
+    "rpsf_stars_shape_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rpsf_builder_add_frame_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double, c_double,
                                               c_void_p]),
     "rpsf_saturation_fill": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),

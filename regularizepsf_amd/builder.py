@@ -217,6 +217,18 @@ def scale_image(images, interpolation_scale: int, *, device: int = 0):
     return out
 
 
+def star_positions(stars) -> np.ndarray:
+    """One frame's entry of ``build(..., stars=)`` as ``(k, 2)`` float64 ``(row, col)``: a plain array as it is, a structured array
+    (``star_catalog``'s, whole or filtered) by its ``row`` and ``col`` fields."""
+    stars = np.asarray(stars)
+    if stars.dtype.names is None:
+        return np.asarray(stars, np.float64).reshape(-1, 2)
+    if "row" not in stars.dtype.names or "col" not in stars.dtype.names:
+        msg = f"A structured star array needs the fields 'row' and 'col', not {stars.dtype.names}"
+        raise ValueError(msg)
+    return np.stack([stars["row"].astype(np.float64).ravel(), stars["col"].astype(np.float64).ravel()], axis=-1)
+
+
 def star_geometry(positions: np.ndarray, psf_size: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     """Per star of one frame: the float corner ``position - N / 2`` that keys the patch (image_processing.py:76-79), the rounded
     corner (:96; ``np.rint`` rounds half to even exactly as Python's ``round``) and the shift amounts (:101)."""
@@ -499,7 +511,9 @@ class ArrayPSFBuilder:
 
         Parameters, their order and their defaults are the reference's (builder.py:139-153); ``num_workers`` is accepted and
         ignored (the patches are cut on the GPU).  ``stars`` is this package's addition: one ``(k, 2)`` float array of
-        ``(row, col)`` star positions per frame - the ``y``, ``x`` columns of ``sep.extract`` - which skips star finding.
+        ``(row, col)`` star positions per frame - the ``y``, ``x`` columns of ``sep.extract`` - which skips star finding; a structured
+        array with ``row`` and ``col`` fields, as ``star_catalog`` returns per frame (whole or filtered, e.g.
+        ``cat[cat["elongation"] < 1.5]``), is taken by those two fields.
         ``patches`` maps ``(frame, row - N / 2, col - N / 2)`` to the float64 copy of the float32 patch kept on the device
         (background-subtracted, not normalised); ``counts`` maps every corner of the covering to its number of stars.
 
@@ -569,6 +583,8 @@ class ArrayPSFBuilder:
         elif len(stars) != len(frames):
             msg = f"stars has {len(stars)} entries for {len(frames)} frames"
             raise ValueError(msg)
+        else:
+            stars = [star_positions(s) for s in stars]
 
         capacity = 1 if fused else sum(len(np.asarray(s).reshape(-1, 2)) for s in stars)  # (the stack grows by itself)
         stack = None

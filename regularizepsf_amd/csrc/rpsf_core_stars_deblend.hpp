@@ -278,24 +278,29 @@ RPSFS_HD void d4_want(long b, long nb, const int* bcomp, const uint8_t* sig, con
 
 // ------------------------------------------------------------------------------------------------ the rows (host)
 // Rows (row, col, flux, area) in raster order of each object's first pixel: an unsplit component is S4's row (first pixel: its root),
-// a split one gives its objects.  *split: the number of split components.
+// a split one gives its objects.  *split: the number of split components.  `sources`, when given, receives per kept row the component
+// slot and the object slot (-1 for an unsplit component).
 inline std::vector<double> deblend_rows(long count, const int* roots, const double* moments, const int* nsig, long nb, const int* bcomp,
                                         const uint8_t* sig, const int* ostats, const double* omoments, long min_area, long max_area,
-                                        size_t* split) {
-  std::vector<std::pair<int, const double*>> order;
+                                        size_t* split, std::vector<std::pair<long, long>>* sources = nullptr) {
+  std::vector<std::pair<int, long>> order;  // (first pixel, slot): component k as k, object b as count + b; first pixels are distinct
   *split = 0;
   for (long k = 0; k < count; ++k) {
     if (nsig[k] >= 2) ++*split;
-    else order.emplace_back(roots[k], moments + 4 * k);
+    else order.emplace_back(roots[k], k);
   }
   for (long b = 0; b < nb; ++b)
-    if (sig[b] && nsig[bcomp[b]] >= 2) order.emplace_back(ostats[BOX * b + 1], omoments + 4 * b);
+    if (sig[b] && nsig[bcomp[b]] >= 2) order.emplace_back(ostats[BOX * b + 1], count + b);
   std::sort(order.begin(), order.end());
   std::vector<double> rows;
-  for (const auto& [first, m] : order) {
+  if (sources) sources->clear();
+  for (const auto& [first, slot] : order) {
+    const long b = slot - count;
+    const double* m = b < 0 ? moments + 4 * slot : omoments + 4 * b;
     const double flux = m[0], area = m[3];
     if (area < (double)min_area || (max_area >= 0 && area > (double)max_area) || !(flux > 0.0)) continue;
     rows.insert(rows.end(), {m[1] / flux, m[2] / flux, flux, area});
+    if (sources) sources->emplace_back(b < 0 ? slot : (long)bcomp[b], b < 0 ? -1 : b);
   }
   return rows;
 }

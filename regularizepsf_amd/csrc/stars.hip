@@ -15,6 +15,9 @@
 //                              the filtered residual; ascent to the peaks, basins, significance, ownership, moments per object
 //                              (the drivers of rpsf_core_stars_deblend.hpp)
 //
+//   S5  stars_shape_kernel     rpsf_stars_measure, and only then: one wave per row of the last detect, a second walk around the finished
+//                              centroid for central second moments, sum |d| and the peak (the driver of rpsf_core_stars_shape.hpp)
+//
 // The phases are the drivers of rpsf_core_stars.hpp.  Launches follow one another on the null stream; no workgroup ever waits for
 // another one, and the only atomics are integer min / max / add - labels and moments are the same on every run.
 #include <hip/hip_runtime.h>
@@ -28,10 +31,12 @@
 #include "rpsf_core_stars.hpp"
 #include "rpsf_core_stars_deblend.hpp"
 #include "rpsf_core_stars_mesh.hpp"
+#include "rpsf_core_stars_shape.hpp"
 #include "rpsf_scale.hpp"
 #include "rpsf_side_unit.hpp"
 
 using namespace rpsfs;
+static_assert(rpsfh::SHAPE_COLUMNS == RPSF_STARS_SHAPE_COLUMNS, "the shape columns of rpsf_core_stars_shape.hpp and include/rpsf.h");
 
 extern __shared__ __attribute__((aligned(16))) char stars_lds[];
 
@@ -107,6 +112,12 @@ __global__ __launch_bounds__(WALK_THREADS) void stars_walk_kernel(Frame fr, cons
           moments);
 }
 
+__global__ __launch_bounds__(WALK_THREADS) void stars_shape_kernel(Frame fr, const double* L, const int32_t* labels, const int32_t* owner,
+                                                                   const rpsfh::ShapeRow* rows, long count, double* out) {
+  GpuCtx ctx;
+  rpsfh::s5_walk(ctx, fr, L, labels, owner, rows, count, (long)blockIdx.x * WALK_WAVES, reinterpret_cast<rpsfh::Seen*>(stars_lds), out);
+}
+
 // ------------------------------------------------------------------------------------------------ the deblend option
 // S2 that also stores the filtered residual; T from device memory when T_dev is given
 __global__ __launch_bounds__(TILE_THREADS) void stars_detect_f_kernel(Frame fr, const double* L, const double* T_dev, double T, uint8_t* det,
@@ -169,6 +180,14 @@ struct rpsf_stars {
   Buf<double> level, rms, moments;
   Buf<int> segcnt, segoff, total, roots, stats;
   std::vector<double> found;  // rows (row, col, flux, area) of the last detect
+  // S5 (rpsf_stars_measure): where each row of `found` came from, and whether what the detect left on the device is still there
+  std::vector<rpsfh::Source> sources;
+  unsigned long generation = 0, detected_at = 0;  // every call that replaces the frame, a mesh or the labels moves `generation` on
+  const double* detected_mesh = nullptr;          // the filtered mesh of the last detect, on the device
+  Buf<rpsfh::ShapeRow> shape_rows;
+  Buf<double> shapes_dev;
+  std::vector<double> shapes;  // rows of RPSF_STARS_SHAPE_COLUMNS of the last measure
+  double shape_ms = 0;
   // the deblend option: everything below is allocated by the first call that needs it
   bool deblend = false;
   double contrast = 0.005, prominence = 1.0;
@@ -289,6 +308,7 @@ extern "C" int rpsf_stars_background(rpsf_stars* s, const void* image_host, int 
   const size_t nmesh = (size_t)s->nby * s->nbx;
   HIP_TRY(hipSetDevice(s->device));
   s->have_frame = s->have_mesh = false;
+  ++s->generation;
   if (const int rc = upload_frame_f32(s->frame.p, image_host, image_is_f64, (size_t)s->npix())) return rc;
   if (const int rc = upload_mask(s, mask_host_or_null)) return rc;
   if (const int rc = mesh_on_device(s)) return rc;
@@ -311,12 +331,16 @@ extern "C" int rpsf_stars_detect(rpsf_stars* s, const double* level_host, double
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipMemcpy(s->level.p, level_host, nmesh * sizeof(double), hipMemcpyHostToDevice));
   s->have_mesh = false;  // S1b's filled mesh is gone
+  ++s->generation;
   return detect_on_device(s, s->level.p, nullptr, threshold_abs, min_area, max_area, count);
 }
 
 // S2 - S4 on the finder's frame with the filtered mesh L (on the device) and the threshold T_dev[0] (on the device) or, T_dev null, T
 static int detect_on_device(rpsf_stars* s, const double* L, const double* T_dev, double T, long min_area, long max_area, size_t* count) {
   s->found.clear();
+  s->sources.clear();
+  s->shapes.clear();
+  s->detected_at = 0, s->detected_mesh = L;
   *count = 0;
   s->ms[1] = s->ms[2] = s->ms[3] = s->deblend_ms = 0;
   s->n_components = s->n_basins = s->n_split = 0;
@@ -342,7 +366,10 @@ static int detect_on_device(rpsf_stars* s, const double* L, const double* T_dev,
     return rc;
   int total = 0;
   HIP_TRY(hipMemcpy(&total, s->total.p, sizeof(int), hipMemcpyDeviceToHost));
-  if (total <= 0) return RPSF_OK;
+  if (total <= 0) {
+    s->detected_at = ++s->generation;
+    return RPSF_OK;
+  }
   const long n = total;
   s->n_components = (size_t)n;
   const long walk_max = s->deblend ? -1 : max_area;  // D3 needs every component's sum; the area limits are applied to the rows below
@@ -362,6 +389,7 @@ static int detect_on_device(rpsf_stars* s, const double* L, const double* T_dev,
   if (s->deblend) {
     if (const int rc = deblend_on_device(s, L, T_dev, T, min_area, max_area, n)) return rc;
     *count = s->found.size() / 4;
+    s->detected_at = ++s->generation;
     return RPSF_OK;
   }
   std::vector<double> m(4 * (size_t)n);
@@ -370,8 +398,10 @@ static int detect_on_device(rpsf_stars* s, const double* L, const double* T_dev,
     const double flux = m[4 * k], area = m[4 * k + 3];
     if (area < (double)min_area || (max_area >= 0 && area > (double)max_area) || !(flux > 0.0)) continue;
     s->found.insert(s->found.end(), {m[4 * k + 1] / flux, m[4 * k + 2] / flux, flux, area});
+    s->sources.emplace_back(k, -1);
   }
   *count = s->found.size() / 4;
+  s->detected_at = ++s->generation;
   return RPSF_OK;
 }
 
@@ -443,7 +473,7 @@ static int deblend_on_device(rpsf_stars* s, const double* L, const double* T_dev
   HIP_TRY(hipMemcpy(ostats.data(), s->ostats.p, ostats.size() * sizeof(int), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(sig.data(), s->sig.p, sig.size(), hipMemcpyDeviceToHost));
   s->found = rpsfd::deblend_rows(n, roots.data(), moments.data(), nsig.data(), nb, bcomp.data(), sig.data(), ostats.data(), omoments.data(),
-                                 min_area, max_area, &s->n_split);
+                                 min_area, max_area, &s->n_split, &s->sources);
   return RPSF_OK;
 }
 
@@ -464,6 +494,7 @@ extern "C" int rpsf_stars_basins(rpsf_stars* s, const double* f_host, const uint
   HIP_TRY(s->peak.reserve(npix));
   std::vector<uint8_t> flags(npix);
   for (size_t i = 0; i < npix; ++i) flags[i] = detected_host[i] != 0;
+  ++s->generation;
   HIP_TRY(hipMemcpy(s->det.p, flags.data(), npix, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(s->f.p, f_host, npix * sizeof(double), hipMemcpyHostToDevice));
   s->deblend_ms = 0;
@@ -494,12 +525,67 @@ extern "C" int rpsf_stars_positions(rpsf_stars* s, size_t first, size_t count, d
   return RPSF_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ S5
+extern "C" int rpsf_stars_measure(rpsf_stars* s, size_t* count) {
+  if (!s || !count) return fail(RPSF_E_BADARG, "null argument");
+  if (!s->detected_at)
+    return fail(RPSF_E_BADARG, "rpsf_stars_measure before a rpsf_stars_detect / rpsf_stars_detect_device gave the rows to measure");
+  if (s->detected_at != s->generation)
+    return fail(RPSF_E_BADARG, "rpsf_stars_measure: the frame, the mesh or the labels of the last detect have been replaced since");
+  const size_t k = s->found.size() / 4;
+  s->shapes.clear();
+  s->shape_ms = 0;
+  *count = k;
+  if (k == 0) return RPSF_OK;  // nothing to launch
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t n = s->n_components, nb = s->n_basins;
+  std::vector<int> roots(n), stats(4 * n), peaks(nb), ostats(rpsfd::BOX * nb);
+  HIP_TRY(hipMemcpy(roots.data(), s->roots.p, roots.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(stats.data(), s->stats.p, stats.size() * sizeof(int), hipMemcpyDeviceToHost));
+  if (nb) {
+    HIP_TRY(hipMemcpy(peaks.data(), s->peaks.p, peaks.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ostats.data(), s->ostats.p, ostats.size() * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  const std::vector<rpsfh::ShapeRow> rows = rpsfh::describe(s->found, s->sources, s->W, roots.data(), stats.data(), peaks.data(), ostats.data());
+  for (const rpsfh::ShapeRow& row : rows)  // the walk reads the whole box: it lies inside the frame, or nothing is launched
+    if (row.r0 < 0 || row.r1 < row.r0 || row.r1 >= s->H || row.c0 < 0 || row.c1 < row.c0 || row.c1 >= s->W)
+      return fail(RPSF_E_HIP, "rpsf_stars_measure: a bounding box outside the frame");
+  HIP_TRY(s->shape_rows.reserve(k));
+  HIP_TRY(s->shapes_dev.reserve(RPSF_STARS_SHAPE_COLUMNS * k));
+  HIP_TRY(hipMemcpy(s->shape_rows.p, rows.data(), k * sizeof(rpsfh::ShapeRow), hipMemcpyHostToDevice));
+  if (const int rc = timed(s, &s->shape_ms, [&] {
+        hipLaunchKernelGGL(stars_shape_kernel, dim3((unsigned)((k + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS),
+                           rpsfh::s5_walk_lds_bytes(), nullptr, s->view(), s->detected_mesh, s->labels.p, s->owner.p, s->shape_rows.p, (long)k,
+                           s->shapes_dev.p);
+      }))
+    return rc;
+  std::vector<double> shapes(RPSF_STARS_SHAPE_COLUMNS * k);
+  HIP_TRY(hipMemcpy(shapes.data(), s->shapes_dev.p, shapes.size() * sizeof(double), hipMemcpyDeviceToHost));
+  s->shapes = std::move(shapes);
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_shapes(rpsf_stars* s, size_t first, size_t count, double* out) {
+  if (!s || (!out && count)) return fail(RPSF_E_BADARG, "null argument");
+  const size_t have = s->shapes.size() / RPSF_STARS_SHAPE_COLUMNS;
+  if (first > have || count > have - first) return fail(RPSF_E_BADARG, "range outside the rows of the last rpsf_stars_measure");
+  for (size_t i = 0; i < RPSF_STARS_SHAPE_COLUMNS * count; ++i) out[i] = s->shapes[RPSF_STARS_SHAPE_COLUMNS * first + i];
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_shape_ms(const rpsf_stars* s, double* ms) {
+  if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
+  *ms = s->shape_ms;
+  return RPSF_OK;
+}
+
 extern "C" int rpsf_stars_label(rpsf_stars* s, const uint8_t* detected_host, int32_t* labels_host) {
   if (!s || !detected_host || !labels_host) return fail(RPSF_E_BADARG, "null argument");
   const size_t npix = (size_t)s->npix();
   HIP_TRY(hipSetDevice(s->device));
   std::vector<uint8_t> flags(npix);
   for (size_t i = 0; i < npix; ++i) flags[i] = detected_host[i] != 0;
+  ++s->generation;
   HIP_TRY(hipMemcpy(s->det.p, flags.data(), npix, hipMemcpyHostToDevice));
   s->ms[2] = 0;
   if (const int rc = timed(s, &s->ms[2], [&] { launch_label(s); })) return rc;
@@ -570,6 +656,7 @@ extern "C" int rpsf_stars_background_view(rpsf_stars* s, const rpsf_view* image,
                                    std::to_string(s->H) + " x " + std::to_string(s->W));
   HIP_TRY(hipSetDevice(s->device));
   s->have_frame = s->have_mesh = false;
+  ++s->generation;
   if (rpsfconv::dense_f32(*image)) {  // the same bits, device to device; the caller's array is only ever read
     HIP_TRY(hipMemcpyAsync(s->frame.p, image->data, (size_t)s->npix() * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
   } else if (const int rc = rpsf_conv_gather(*image, 1, 0, s->frame.p, 0, nullptr)) {  // C1
@@ -582,6 +669,7 @@ extern "C" int rpsf_stars_background_host(rpsf_stars* s, const void* image_host,
   if (!s || !image_host) return fail(RPSF_E_BADARG, "null argument");
   HIP_TRY(hipSetDevice(s->device));
   s->have_frame = s->have_mesh = false;
+  ++s->generation;
   if (const int rc = upload_frame_f32(s->frame.p, image_host, image_is_f64, (size_t)s->npix())) return rc;
   return background_on_device(s, mask_host_or_null);
 }
@@ -597,6 +685,7 @@ extern "C" int rpsf_stars_background_scaled(rpsf_stars* s, const void* image_hos
                                    std::to_string(s->H) + " x " + std::to_string(s->W));
   HIP_TRY(hipSetDevice(s->device));
   s->have_frame = s->have_mesh = false;
+  ++s->generation;
   if (!s->upscale) s->upscale = rpsf_detail_scale_scratch_new();
   // the unscaled frame crosses PCIe once, in its own type; U1 / U2 leave the scaled one, rounded to float32 once, where S1 reads it
   if (const int rc = rpsf_detail_scale_upload(s->upscale, image_host, image_is_f64, height, width)) return rc;
@@ -610,6 +699,7 @@ extern "C" int rpsf_stars_filter_mesh(rpsf_stars* s, const double* level_host, c
   const size_t nmesh = (size_t)s->nby * s->nbx;
   HIP_TRY(hipSetDevice(s->device));
   s->have_mesh = false;  // the meshes are the caller's, not the frame's
+  ++s->generation;
   HIP_TRY(hipMemcpy(s->level.p, level_host, nmesh * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(s->rms.p, rms_host, nmesh * sizeof(double), hipMemcpyHostToDevice));
   if (const int rc = filter_mesh_on_device(s)) return rc;

@@ -16,6 +16,11 @@ thousand numbers, ``filter_mesh``) between S1 and S2.  Device frames (``DeviceAr
 ``__cuda_array_interface__``) take the fused route of DESIGN.md 3.11, which ``ArrayPSFBuilder(..., finder="device")`` takes for
 every frame: the frame is read where it lies, kernel S1b does ``filter_mesh``'s work on the device - the same bits - and nothing but
 the positions comes back.
+
+``star_catalog`` is ``find_stars`` with a catalogue per frame instead of bare positions: one more kernel (S5, ``rpsf_stars_measure``)
+walks every detection again around its finished centroid and returns central second moments, the peak and the bounding box; the
+ellipse (``a``, ``b``, ``theta``, ``elongation``) is derived from them here in NumPy float64.  The moments are NOT ``sep``'s either: no
+1 / 12 pixel term, no clamp of a singular matrix, and the footprint is this detector's.
 """
 
 from __future__ import annotations
@@ -29,6 +34,11 @@ from regularizepsf_amd.device_array import is_device_array
 from regularizepsf_amd.exceptions import IncorrectShapeError
 
 MIN_BOX, MAX_BOX = 8, 128
+# a shape row of kernel S5 (RPSF_STARS_SHAPE_COLUMNS float64, include/rpsf.h), and the catalogue: those columns and the derived ones
+SHAPE_COLUMNS = ("row", "col", "flux", "area", "peak", "peak_row", "peak_col", "row_min", "row_max", "col_min", "col_max", "abs_flux",
+                 "rr", "cc", "rc")
+CATALOG_FIELDS = (*SHAPE_COLUMNS, "a", "b", "theta", "elongation")
+CATALOG_DTYPE = np.dtype([(name, np.float64) for name in CATALOG_FIELDS])
 DEBLEND_OPTIONS = {"deblend": False, "deblend_contrast": 0.005, "deblend_prominence": 1.0}  # contrast: sep's deblend_cont
 
 
@@ -152,6 +162,22 @@ class _Finder:
         peak = np.empty(self.shape, np.int32)
         n.check(n.lib().rpsf_stars_basins(self._handle, n._ptr(f), n._ptr(flags), n._ptr(peak)))
         return peak
+
+    def measure(self) -> np.ndarray:
+        """Kernel S5 on the rows of the last ``detect`` / ``detect_device``: (k, len(SHAPE_COLUMNS)) float64, the first four columns the
+        detect's rows bit for bit.  An error when there is no such detect or the frame or mesh has been replaced since."""
+        n = self._native
+        count = ctypes.c_size_t(0)
+        n.check(n.lib().rpsf_stars_measure(self._handle, ctypes.byref(count)))
+        out = np.empty((count.value, len(SHAPE_COLUMNS)))
+        n.check(n.lib().rpsf_stars_shapes(self._handle, 0, count.value, n._ptr(out)))
+        return out
+
+    def shape_ms(self) -> float:
+        """Device time of the last S5."""
+        ms = ctypes.c_double(0)
+        self._native.check(self._native.lib().rpsf_stars_shape_ms(self._handle, ctypes.byref(ms)))
+        return ms.value
 
     def deblend_info(self) -> tuple[int, int, int]:
         """Of the last detect: components, basins, split components."""
@@ -287,5 +313,67 @@ def find_stars(images, threshold: float = 3.0, mask=None, *, box: int = 64, min_
             finder.set_deblend(*split)
         return [np.ascontiguousarray(one_frame(finder, frame, m, float(threshold), int(min_area), max_area)[:, :2])
                 for frame, m in zip(frames, masks)]
+    finally:
+        finder.close()
+
+
+def ellipse(rr: np.ndarray, cc: np.ndarray, rc: np.ndarray) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """``(a, b, theta, elongation)`` of central second moments, NumPy float64: the eigenvalues ``(rr + cc) / 2 +- sqrt(((rr - cc) / 2)^2
+    + rc^2)``, ``a`` and ``b`` their square roots (NaN for a negative one), ``theta = atan2(2 rc, cc - rr) / 2`` - the major axis
+    from the column axis towards the row axis, ``sep``'s ``theta`` with x = col and y = row - and ``elongation = a / b`` by IEEE rules."""
+    rr, cc, rc = (np.asarray(v, np.float64) for v in (rr, cc, rc))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean, half = (rr + cc) / 2, np.sqrt(((rr - cc) / 2) ** 2 + rc ** 2)
+        a, b = np.sqrt(mean + half), np.sqrt(mean - half)
+        return a, b, 0.5 * np.arctan2(2 * rc, cc - rr), a / b
+
+
+def catalog_from_shapes(shapes: np.ndarray) -> np.ndarray:
+    """The structured catalogue (``CATALOG_DTYPE``) of S5's shape rows."""
+    shapes = np.asarray(shapes, np.float64).reshape(-1, len(SHAPE_COLUMNS))
+    out = np.empty(len(shapes), CATALOG_DTYPE)
+    for j, name in enumerate(SHAPE_COLUMNS):
+        out[name] = shapes[:, j]
+    out["a"], out["b"], out["theta"], out["elongation"] = ellipse(out["rr"], out["cc"], out["rc"])
+    return out
+
+
+def star_catalog(images, threshold: float = 3.0, mask=None, *, box: int = 64, min_area: int = 5, max_area: int | None = None,
+                 deblend: bool = False, deblend_contrast: float = 0.005, deblend_prominence: float = 1.0,
+                 device: int = 0) -> list[np.ndarray]:
+    """``find_stars`` with a catalogue per frame: a list of NumPy structured arrays, one per frame, with the float64 fields ``row, col,
+    flux, area, peak, peak_row, peak_col, row_min, row_max, col_min, col_max, abs_flux, rr, cc, rc, a, b, theta, elongation``; a frame
+    without detections gives length 0 with the same dtype.  The arguments are ``find_stars``'s, device frames included, and
+    ``row, col`` are its positions bit for bit.
+
+    For each detection, with ``P`` the pixels of its component (with ``deblend``: of its object), ``d`` the background-subtracted
+    pixel, ``dr = r - row`` and ``dc = c - col``: ``rr = sum_P d dr^2 / flux``, ``cc = sum_P d dc^2 / flux``, ``rc = sum_P d dr dc /
+    flux``, ``abs_flux = sum_P |d|``, ``peak = max_P d`` at ``(peak_row, peak_col)``, and the bounding box of ``P``.  ``a``, ``b``,
+    ``theta`` and ``elongation`` are ``ellipse``'s: ``theta`` is the major axis measured from the column axis towards the row axis.
+    ``b`` (and ``elongation``) is NaN where the smaller eigenvalue is negative, which a detected pixel with ``d < 0`` can cause.
+
+    This is NOT ``sep``'s catalogue: no 1 / 12 pixel term, no clamp of a singular matrix, and the moments are taken over the detection
+    footprint of this detector, which biases ``a`` and ``b`` low.  ``cat[cat["elongation"] < 1.5]`` goes to
+    ``ArrayPSFBuilder.build(..., stars=...)`` as it is.
+    """
+    split = deblend_options(deblend, deblend_contrast, deblend_prominence)
+    if not MIN_BOX <= int(box) <= MAX_BOX:
+        msg = f"box must lie in {MIN_BOX} ... {MAX_BOX}, got {box}"
+        raise ValueError(msg)
+    frames = _device_frames(images, device)
+    one_frame = frame_stars_device
+    if frames is None:
+        frames, one_frame = _frames(images), frame_stars
+    masks = _masks(mask, frames)
+    finder = _Finder(frames[0].shape, box, device)
+    try:
+        if split[0]:
+            finder.set_deblend(*split)
+        catalogs = []
+        for frame, m in zip(frames, masks):
+            rows = one_frame(finder, frame, m, float(threshold), int(min_area), max_area)
+            # (no usable box at all: frame_stars returns before any detect, and there is nothing to measure)
+            catalogs.append(catalog_from_shapes(finder.measure() if len(rows) else np.zeros((0, len(SHAPE_COLUMNS)))))
+        return catalogs
     finally:
         finder.close()
