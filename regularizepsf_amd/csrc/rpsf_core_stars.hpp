@@ -123,7 +123,11 @@ RPSFS_HD Part fold16(const Part* p) {  // in index order
   }
   return r;
 }
-RPSFS_HD size_t s1_lds_bytes(int box) { return (size_t)box * box * sizeof(unsigned) + (S1_THREADS + 16) * sizeof(Part); }
+// S1's LDS: box * box keys, then the Part records.  A Part holds a double, and box * box keys of an odd box end 4 bytes off an 8-byte
+// boundary: the records start at the next multiple of 16 bytes.
+constexpr size_t S1_RECORDS = S1_THREADS + 16;
+RPSFS_HD size_t s1_part_offset(int box) { return ((size_t)box * box * sizeof(unsigned) + 15) & ~(size_t)15; }
+RPSFS_HD size_t s1_lds_bytes(int box) { return s1_part_offset(box) + S1_RECORDS * sizeof(Part); }
 
 enum { PASS_SUM, PASS_SSD, PASS_BELOW, PASS_NEXT, PASS_CLIP };
 struct Kept {  // the kept set is the keys in [lo, hi]
@@ -164,7 +168,7 @@ RPSFS_HD Part s1_partial(int tid, int cnt, const unsigned* keys, int pass, const
 template <class Ctx>
 RPSFS_HD void s1_box(Ctx& ctx, const Frame& fr, int bi, int bj, void* lds, double* level, double* rms) {
   unsigned* keys = static_cast<unsigned*>(lds);
-  Part* part = reinterpret_cast<Part*>(keys + (size_t)fr.box * fr.box);
+  Part* part = reinterpret_cast<Part*>(static_cast<char*>(lds) + s1_part_offset(fr.box));
   Part* part2 = part + S1_THREADS;
   const int r0 = bi * fr.box, c0 = bj * fr.box;
   const int bh = (fr.H - r0 < fr.box ? fr.H - r0 : fr.box), bw = (fr.W - c0 < fr.box ? fr.W - c0 : fr.box);

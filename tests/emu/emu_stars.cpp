@@ -40,6 +40,11 @@ void label(const uint8_t* det, int H, int W, int32_t* labels) {
 
 extern "C" void emus_info(int* tile_rows, int* tile_cols) { *tile_rows = TILE_R, *tile_cols = TILE_C; }
 
+// S1's LDS carve as the kernel and the launch read it: where the Part records start, what they take, what a workgroup asks for
+extern "C" void emus_s1_carve(int box, size_t* offset, size_t* records, size_t* bytes) {
+  *offset = s1_part_offset(box), *records = S1_RECORDS * sizeof(Part), *bytes = s1_lds_bytes(box);
+}
+
 extern "C" int emus_background(const float* img, const uint8_t* mask, int H, int W, int box, double* level, double* rms) {
   if (H <= 0 || W <= 0 || box < MIN_BOX || box > MAX_BOX) return -1;
   const std::vector<uint8_t> m = mask_or_zeros(mask, (size_t)H * W);
