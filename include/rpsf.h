@@ -638,6 +638,29 @@ int rpsf_stars_shapes(rpsf_stars* finder, size_t first, size_t count, double* ou
 /* Device time of the last S5, milliseconds. */
 int rpsf_stars_shape_ms(const rpsf_stars* finder, double* ms);
 
+/* APERTURES (kernel S6): forced aperture photometry at n positions (y, x) the caller supplies (finite, |y|, |x| < 2^20;
+ * they may lie off the frame), on the frame, the mask and the filtered mesh a rpsf_stars_background_view / _host / _scaled left on the
+ * device (RPSF_E_STATE before such a call).  m radii (1 .. 8, strictly ascending, 0 < R <= 64) and subpix = s (1 .. 8), anything else
+ * or a non-finite position: RPSF_E_BADARG.  d is the residual of rpsf_stars_detect_device (use_mesh != 0) or the pixel itself on usable
+ * pixels (use_mesh == 0: a frame that is already background-subtracted).  For the pixel (r, c) of the box floor(y - R_max) - 1 ..
+ * ceil(y + R_max) + 1 (likewise in x; not clipped to the frame): pr = r - y, pc = c - x, o_a = (2a + 1 - s) / (2s),
+ * q_ab = (pr + o_a)(pr + o_a) + (pc + o_b)(pc + o_b), n_k = #{(a, b): q_ab <= R_k R_k}, w_k = n_k / (s s).  Per radius
+ * flux_k = sum w_k d and N_use_k = sum n_k over the usable pixels of the frame, N_all_k = sum n_k over the whole box; on the outermost
+ * radius, with t = w d: abs = sum w |d|, mr = sum t pr, mc = sum t pc, mrr = sum t (pr pr), mcc = sum t (pc pc), mrc = sum t (pr pc),
+ * and peak = max d where n > 0 at (peak_row, peak_col), the first such pixel in raster order (NaN at (-1, -1) when there is none).
+ * float64, in S4's summation order; two runs agree bit for bit.  With use_mesh != 0 and no valid mesh node every flux, sum and the peak
+ * is NaN and the counts are delivered.  This is not sep's sum_circle / flux_radius: the comparison is <=, there is no error column and no
+ * 1 / 12 term, and masked pixels are left out and reported through the counts, not corrected for.  A row of out_host is
+ * RPSF_STARS_PHOTOMETRY_COLUMNS(m) float64:
+ *   row, col, flux[m], N_use[m], N_all[m], abs, mr, mc, mrr, mcc, mrc, peak, peak_row, peak_col.
+ * n == 0 launches nothing.  The call replaces nothing of the finder: a rpsf_stars_positions or rpsf_stars_measure after it gives the
+ * bits it gave before. */
+#define RPSF_STARS_PHOTOMETRY_COLUMNS(m) (2 + 3 * (m) + 9)
+int rpsf_stars_photometry(rpsf_stars* finder, size_t n, const double* positions_host, int m, const double* radii, int subpix,
+                          int use_mesh, double* out_host);
+/* Device time of the last S6, milliseconds; 0 when it launched nothing. */
+int rpsf_stars_photometry_ms(const rpsf_stars* finder, double* ms);
+
 /* rpsf_builder_add_frame on a dense float32 frame that is already on the builder's device - a finder's (rpsf_stars_frame) or the caller's
  * own; it is only read, nothing is uploaded but the star list.  On a scaled builder the frame is the SCALED one and height and width are
  * its. */

@@ -18,6 +18,10 @@
 //   S5  stars_shape_kernel     rpsf_stars_measure, and only then: one wave per row of the last detect, a second walk around the finished
 //                              centroid for central second moments, sum |d| and the peak (the driver of rpsf_core_stars_shape.hpp)
 //
+//   S6  stars_photometry_kernel   rpsf_stars_photometry, and only then: one wave per position the caller supplies, circular apertures with
+//                              sub-pixel coverage on the frame and the filtered mesh of the fused route (the driver of
+//                              rpsf_core_stars_photometry.hpp); it writes its own rows and nothing the other kernels read
+//
 // The phases are the drivers of rpsf_core_stars.hpp.  Launches follow one another on the null stream; no workgroup ever waits for
 // another one, and the only atomics are integer min / max / add - labels and moments are the same on every run.
 #include <hip/hip_runtime.h>
@@ -31,12 +35,15 @@
 #include "rpsf_core_stars.hpp"
 #include "rpsf_core_stars_deblend.hpp"
 #include "rpsf_core_stars_mesh.hpp"
+#include "rpsf_core_stars_photometry.hpp"
 #include "rpsf_core_stars_shape.hpp"
 #include "rpsf_scale.hpp"
 #include "rpsf_side_unit.hpp"
 
 using namespace rpsfs;
 static_assert(rpsfh::SHAPE_COLUMNS == RPSF_STARS_SHAPE_COLUMNS, "the shape columns of rpsf_core_stars_shape.hpp and include/rpsf.h");
+static_assert(rpsfp::photometry_columns(3) == RPSF_STARS_PHOTOMETRY_COLUMNS(3), "the photometry columns of rpsf_core_stars_photometry.hpp and include/rpsf.h");
+static_assert(rpsfp::s6_lds_bytes(rpsfp::MAX_RADII) <= 64 * 1024, "S6's records fit the LDS a launch gets without asking");
 
 extern __shared__ __attribute__((aligned(16))) char stars_lds[];
 
@@ -118,6 +125,12 @@ __global__ __launch_bounds__(WALK_THREADS) void stars_shape_kernel(Frame fr, con
   rpsfh::s5_walk(ctx, fr, L, labels, owner, rows, count, (long)blockIdx.x * WALK_WAVES, reinterpret_cast<rpsfh::Seen*>(stars_lds), out);
 }
 
+__global__ __launch_bounds__(WALK_THREADS) void stars_photometry_kernel(Frame fr, const double* L, const int* none, int use_mesh,
+                                                                        rpsfp::Apertures ap, const double* pos, long count, double* out) {
+  GpuCtx ctx;
+  rpsfp::s6_apertures(ctx, fr, L, none, use_mesh, ap, pos, count, (long)blockIdx.x * WALK_WAVES, stars_lds, out);
+}
+
 // ------------------------------------------------------------------------------------------------ the deblend option
 // S2 that also stores the filtered residual; T from device memory when T_dev is given
 __global__ __launch_bounds__(TILE_THREADS) void stars_detect_f_kernel(Frame fr, const double* L, const double* T_dev, double T, uint8_t* det,
@@ -188,6 +201,9 @@ struct rpsf_stars {
   Buf<double> shapes_dev;
   std::vector<double> shapes;  // rows of RPSF_STARS_SHAPE_COLUMNS of the last measure
   double shape_ms = 0;
+  // S6 (rpsf_stars_photometry): its own positions and rows, nothing of the above
+  Buf<double> phot_pos, phot_out;
+  double photometry_ms = 0;
   // the deblend option: everything below is allocated by the first call that needs it
   bool deblend = false;
   double contrast = 0.005, prominence = 1.0;
@@ -576,6 +592,40 @@ extern "C" int rpsf_stars_shapes(rpsf_stars* s, size_t first, size_t count, doub
 extern "C" int rpsf_stars_shape_ms(const rpsf_stars* s, double* ms) {
   if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
   *ms = s->shape_ms;
+  return RPSF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ S6 (Apertures)
+extern "C" int rpsf_stars_photometry(rpsf_stars* s, size_t n, const double* positions_host, int m, const double* radii, int subpix,
+                                     int use_mesh, double* out_host) {
+  if (!s || (n && (!positions_host || !out_host))) return fail(RPSF_E_BADARG, "null argument");
+  if (const char* why = rpsfp::apertures_problem(m, radii, subpix)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_photometry: ") + why);
+  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_photometry: more than 2^30 positions in one call");
+  for (size_t i = 0; i < n; ++i)
+    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
+      return fail(RPSF_E_BADARG, "rpsf_stars_photometry: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
+  if (!s->have_mesh) return fail(RPSF_E_STATE, "rpsf_stars_photometry before a rpsf_stars_background_view / _host / _scaled of the frame");
+  s->photometry_ms = 0;
+  if (n == 0) return RPSF_OK;  // nothing to launch
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t columns = (size_t)rpsfp::photometry_columns(m);
+  HIP_TRY(s->phot_pos.reserve(2 * n));
+  HIP_TRY(s->phot_out.reserve(columns * n));
+  HIP_TRY(hipMemcpy(s->phot_pos.p, positions_host, 2 * n * sizeof(double), hipMemcpyHostToDevice));
+  const rpsfp::Apertures ap = rpsfp::make_apertures(m, radii, subpix);
+  if (const int rc = timed(s, &s->photometry_ms, [&] {
+        hipLaunchKernelGGL(stars_photometry_kernel, dim3((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS),
+                           rpsfp::s6_lds_bytes(m), nullptr, s->view(), s->level_f.p, s->none.p, use_mesh != 0, ap, s->phot_pos.p, (long)n,
+                           s->phot_out.p);
+      }))
+    return rc;
+  HIP_TRY(hipMemcpy(out_host, s->phot_out.p, columns * n * sizeof(double), hipMemcpyDeviceToHost));
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_photometry_ms(const rpsf_stars* s, double* ms) {
+  if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
+  *ms = s->photometry_ms;
   return RPSF_OK;
 }
 

@@ -21,6 +21,13 @@ the positions comes back.
 walks every detection again around its finished centroid and returns central second moments, the peak and the bounding box; the
 ellipse (``a``, ``b``, ``theta``, ``elongation``) is derived from them here in NumPy float64.  The moments are NOT ``sep``'s either: no
 1 / 12 pixel term, no clamp of a singular matrix, and the footprint is this detector's.
+
+``star_photometry`` measures at positions the caller supplies - ``find_stars``' output, a filtered catalogue, any list - instead of at
+what this detector finds: circular apertures at several radii with sub-pixel coverage (kernel S6, ``rpsf_stars_photometry``; DESIGN.md
+3.7 "Apertures"), on the outermost one the peak and the moments around the given position, and a half-light radius from the curve of
+growth.  The footprint is the aperture, not the threshold's, so the same stars can be compared before and after ``apply``.  It is NOT
+``sep``'s ``sum_circle`` / ``flux_radius``: a sub-sample counts when ``q <= R^2``, there is no error column and no 1 / 12 term, and
+masked pixels are excluded and reported through ``coverage``, not corrected for.
 """
 
 from __future__ import annotations
@@ -29,7 +36,7 @@ import ctypes
 
 import numpy as np
 
-from regularizepsf_amd.builder import _device_frames, _frames
+from regularizepsf_amd.builder import _device_frames, _frames, star_positions
 from regularizepsf_amd.device_array import is_device_array
 from regularizepsf_amd.exceptions import IncorrectShapeError
 
@@ -39,6 +46,9 @@ SHAPE_COLUMNS = ("row", "col", "flux", "area", "peak", "peak_row", "peak_col", "
                  "rr", "cc", "rc")
 CATALOG_FIELDS = (*SHAPE_COLUMNS, "a", "b", "theta", "elongation")
 CATALOG_DTYPE = np.dtype([(name, np.float64) for name in CATALOG_FIELDS])
+# a photometry row of kernel S6 for m radii (RPSF_STARS_PHOTOMETRY_COLUMNS(m) float64): row, col, flux[m], N_use[m], N_all[m], then these
+PHOTOMETRY_SUMS = ("abs_flux", "mr", "mc", "mrr", "mcc", "mrc", "peak", "peak_row", "peak_col")
+MAX_RADII, MAX_RADIUS, MAX_SUBPIX, MAX_COORD = 8, 64.0, 8, 2.0 ** 20
 DEBLEND_OPTIONS = {"deblend": False, "deblend_contrast": 0.005, "deblend_prominence": 1.0}  # contrast: sep's deblend_cont
 
 
@@ -177,6 +187,23 @@ class _Finder:
         """Device time of the last S5."""
         ms = ctypes.c_double(0)
         self._native.check(self._native.lib().rpsf_stars_shape_ms(self._handle, ctypes.byref(ms)))
+        return ms.value
+
+    def photometry(self, positions: np.ndarray, radii, subpix: int = 5, use_mesh: bool = True) -> np.ndarray:
+        """Kernel S6 on the frame given to ``background_device`` / ``background_scaled`` last, at ``positions`` ((k, 2) of (row, col)):
+        (k, photometry_columns(m)) float64.  Nothing of the finder is replaced: ``detect`` rows and ``measure`` stay what they were."""
+        n = self._native
+        positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 2)
+        radii = np.ascontiguousarray(radii, np.float64).ravel()
+        out = np.empty((len(positions), photometry_columns(len(radii))))
+        n.check(n.lib().rpsf_stars_photometry(self._handle, len(positions), n._ptr(positions), len(radii), n._ptr(radii), int(subpix),
+                                              int(bool(use_mesh)), n._ptr(out)))
+        return out
+
+    def photometry_ms(self) -> float:
+        """Device time of the last S6; 0.0 when it launched nothing."""
+        ms = ctypes.c_double(0)
+        self._native.check(self._native.lib().rpsf_stars_photometry_ms(self._handle, ctypes.byref(ms)))
         return ms.value
 
     def deblend_info(self) -> tuple[int, int, int]:
@@ -375,5 +402,145 @@ def star_catalog(images, threshold: float = 3.0, mask=None, *, box: int = 64, mi
             # (no usable box at all: frame_stars returns before any detect, and there is nothing to measure)
             catalogs.append(catalog_from_shapes(finder.measure() if len(rows) else np.zeros((0, len(SHAPE_COLUMNS)))))
         return catalogs
+    finally:
+        finder.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------- apertures
+def photometry_columns(m: int) -> int:
+    """The float64 per row of kernel S6 for ``m`` radii (``RPSF_STARS_PHOTOMETRY_COLUMNS``)."""
+    return 2 + 3 * int(m) + len(PHOTOMETRY_SUMS)
+
+
+def photometry_dtype(m: int) -> np.dtype:
+    """The structured dtype of ``star_photometry`` for ``m`` radii: ``flux``, ``area`` and ``coverage`` are sub-arrays of shape ``(m,)``."""
+    per_radius = {"flux", "area", "coverage"}
+    names = ("row", "col", "flux", "area", "coverage", "abs_flux", "peak", "peak_row", "peak_col", "drow", "dcol", "rr", "cc", "rc", "a", "b",
+             "theta", "elongation", "half_light_radius")
+    return np.dtype([(name, np.float64, (int(m),)) if name in per_radius else (name, np.float64) for name in names])
+
+
+def aperture_radii(radii) -> np.ndarray:
+    """``radii`` as S6 takes them, range-checked: 1 ... 8 values, strictly ascending, ``0 < R <= 64``."""
+    try:
+        radii = np.atleast_1d(np.asarray(radii, np.float64))
+    except (TypeError, ValueError) as error:
+        msg = f"radii must be numbers, not {radii!r}"
+        raise TypeError(msg) from error
+    if radii.ndim != 1 or not 1 <= len(radii) <= MAX_RADII:
+        msg = f"radii must be 1 ... {MAX_RADII} values, got shape {radii.shape}"
+        raise ValueError(msg)
+    if not np.all((radii > 0.0) & (radii <= MAX_RADIUS)):
+        msg = f"radii must lie in 0 < R <= {MAX_RADIUS:g}, got {radii.tolist()}"
+        raise ValueError(msg)
+    if np.any(np.diff(radii) <= 0.0):
+        msg = f"radii must ascend strictly, got {radii.tolist()}"
+        raise ValueError(msg)
+    return np.ascontiguousarray(radii)
+
+
+def half_light_radius(radii: np.ndarray, flux: np.ndarray) -> np.ndarray:
+    """Per row of ``flux`` ((k, m), the curve of growth at ``radii``): the radius where the piecewise-linear curve through ``(0, 0)`` and
+    ``(R_k, flux_k)`` first reaches half of the outermost flux ``F``; NaN where ``F <= 0`` or ``F`` is not finite."""
+    radii, flux = np.asarray(radii, np.float64), np.asarray(flux, np.float64).reshape(-1, len(radii))
+    total = flux[:, -1]
+    good = np.isfinite(total) & (total > 0.0)
+    half = np.where(good, total / 2, np.nan)
+    out, open_ = np.full(len(flux), np.nan), good.copy()
+    r_before, f_before = 0.0, np.zeros(len(flux))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for k, r in enumerate(radii):
+            here = open_ & (flux[:, k] >= half)  # f_before < half <= flux_k: the segment crosses, and its slope is positive
+            out[here] = r_before + (half[here] - f_before[here]) * (r - r_before) / (flux[here, k] - f_before[here])
+            open_ &= ~here
+            r_before, f_before = r, flux[:, k]
+    return out
+
+
+def photometry_from_sums(rows: np.ndarray, radii, subpix: int) -> np.ndarray:
+    """The structured result (``photometry_dtype``) of S6's rows, everything derived in NumPy float64: ``area = N_use / s^2``, ``coverage =
+    N_use / N_all`` (0 / 0 = NaN), ``drow = mr / F`` and ``dcol = mc / F`` with ``F`` the outermost flux, ``rr = mrr / F - drow^2`` (``cc``,
+    ``rc`` alike), the ellipse of ``ellipse`` and ``half_light_radius``."""
+    radii = np.asarray(radii, np.float64).ravel()
+    m = len(radii)
+    rows = np.asarray(rows, np.float64).reshape(-1, photometry_columns(m))
+    out = np.empty(len(rows), photometry_dtype(m))
+    out["row"], out["col"] = rows[:, 0], rows[:, 1]
+    flux, n_use, n_all = rows[:, 2:2 + m], rows[:, 2 + m:2 + 2 * m], rows[:, 2 + 2 * m:2 + 3 * m]
+    sums = {name: rows[:, 2 + 3 * m + j] for j, name in enumerate(PHOTOMETRY_SUMS)}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["flux"], out["area"], out["coverage"] = flux, n_use / float(subpix * subpix), n_use / n_all
+        for name in ("abs_flux", "peak", "peak_row", "peak_col"):
+            out[name] = sums[name]
+        total = flux[:, -1]
+        drow, dcol = sums["mr"] / total, sums["mc"] / total
+        out["drow"], out["dcol"] = drow, dcol
+        out["rr"], out["cc"], out["rc"] = sums["mrr"] / total - drow * drow, sums["mcc"] / total - dcol * dcol, sums["mrc"] / total - drow * dcol
+    out["a"], out["b"], out["theta"], out["elongation"] = ellipse(out["rr"], out["cc"], out["rc"])
+    out["half_light_radius"] = half_light_radius(radii, flux)
+    return out
+
+
+def star_photometry(images, stars, radii, mask=None, *, background: str = "mesh", box: int = 64, subpix: int = 5,
+                    device: int = 0) -> list[np.ndarray]:
+    """Forced aperture photometry at given positions: a list of NumPy structured arrays, one per frame and one row per position, with the
+    float64 fields ``row, col, flux (m,), area (m,), coverage (m,), abs_flux, peak, peak_row, peak_col, drow, dcol, rr, cc, rc, a, b,
+    theta, elongation, half_light_radius`` for ``m = len(radii)``.
+
+    ``images``: what ``find_stars`` takes, device frames included.  ``stars``: what ``build(..., stars=)`` takes - per frame a ``(k, 2)``
+    array of ``(row, col)`` or a structured array with those fields (``star_catalog``'s, whole or filtered); positions are finite with
+    ``|row|, |col| < 2^20`` and may lie off the frame.  ``radii``: 1 ... 8 aperture radii in pixels, strictly ascending, ``0 < R <= 64``.
+    ``mask``: as for ``find_stars``.  ``background``: ``"mesh"`` subtracts ``find_stars``' background surface (``box``: its box), ``"none"``
+    takes the pixels as they are, for frames that are already background-subtracted (the mesh kernels S1 and S1b still run then; their
+    result is not read).  ``subpix`` = ``s``, 1 ... 8: every pixel is sampled on an ``s x s`` lattice.
+
+    A sub-sample of pixel ``(r, c)`` at offsets ``o_a = (2a + 1 - s) / (2s)`` lies in aperture ``k`` when ``(r - row + o_a)^2 + (c - col +
+    o_b)^2 <= R_k^2``, and the pixel's weight ``w_k`` is the fraction of its ``s^2`` sub-samples that do.  With ``d`` the background-subtracted
+    pixel: ``flux[k] = sum w_k d`` over usable (finite, unmasked) pixels of the frame, ``area[k]`` the sum of their ``w_k``, ``coverage[k]``
+    that area over the aperture's whole area, off-frame part included (0 for an aperture wholly off the frame).  On the outermost aperture,
+    with ``F = flux[-1]``: ``abs_flux = sum w |d|``, ``peak`` the largest ``d`` at ``(peak_row, peak_col)`` (NaN at (-1, -1) without a
+    usable pixel), ``(drow, dcol) = sum w d (r - row, c - col) / F`` the centroid's offset from the given position, ``rr, cc, rc`` the
+    central second moments ``sum w d (r - row)^2 / F - drow^2`` etc. and ``a, b, theta, elongation`` as in ``star_catalog``.
+    ``half_light_radius``: where the piecewise-linear curve of growth through ``(0, 0)`` and ``(R_k, flux[k])`` first reaches ``F / 2``;
+    NaN when ``F <= 0`` or not finite.  With ``background="mesh"`` a frame without a usable pixel has no background: every flux and
+    moment is NaN, the areas are delivered.
+
+    This is NOT ``sep``'s ``sum_circle`` / ``flux_radius``: the comparison is ``<=`` on this lattice, there is no error column and no
+    1 / 12 term, and masked pixels are excluded and reported through ``coverage``, not corrected for.
+    """
+    if background not in ("mesh", "none"):
+        msg = f'background must be "mesh" or "none", not {background!r}'
+        raise ValueError(msg)
+    if not MIN_BOX <= int(box) <= MAX_BOX:
+        msg = f"box must lie in {MIN_BOX} ... {MAX_BOX}, got {box}"
+        raise ValueError(msg)
+    if isinstance(subpix, (bool, np.bool_)) or not isinstance(subpix, (int, np.integer)):
+        msg = f"subpix must be an integer, not {subpix!r}"
+        raise TypeError(msg)
+    if not 1 <= subpix <= MAX_SUBPIX:
+        msg = f"subpix must lie in 1 ... {MAX_SUBPIX}, got {subpix}"
+        raise ValueError(msg)
+    radii = aperture_radii(radii)
+    frames = _device_frames(images, device)
+    if frames is None:
+        frames = _frames(images)
+    if isinstance(stars, np.ndarray) and (stars.dtype.names is not None or stars.ndim == 2):
+        stars = [stars]  # one frame's stars, as they are
+    if len(stars) != len(frames):
+        msg = f"stars has {len(stars)} entries for {len(frames)} frames"
+        raise ValueError(msg)
+    positions = [np.ascontiguousarray(star_positions(s)) for s in stars]
+    for i, p in enumerate(positions):
+        if not np.all(np.abs(p) < MAX_COORD):  # (false for NaN)
+            msg = f"stars[{i}] has a position that is not finite or not inside |row|, |col| < 2^20"
+            raise ValueError(msg)
+    masks = _masks(mask, frames)
+    finder = _Finder(frames[0].shape, box, device)
+    try:
+        out = []
+        for frame, m, p in zip(frames, masks, positions):
+            finder.background_device(frame, m)
+            out.append(photometry_from_sums(finder.photometry(p, radii, subpix, background == "mesh"), radii, subpix))
+        return out
     finally:
         finder.close()
