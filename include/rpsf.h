@@ -661,6 +661,34 @@ int rpsf_stars_photometry(rpsf_stars* finder, size_t n, const double* positions_
 /* Device time of the last S6, milliseconds; 0 when it launched nothing. */
 int rpsf_stars_photometry_ms(const rpsf_stars* finder, double* ms);
 
+/* WINDOWED POSITIONS (kernel S7): the Gaussian-windowed position and moments at n positions (y, x) the caller supplies
+ * (finite, |y|, |x| < 2^20; they may lie off the frame), on the frame, the mask and the filtered mesh a rpsf_stars_background_view /
+ * _host / _scaled left on the device (RPSF_E_STATE before such a call).  sigma_host holds one window sigma per position, 0.5 <= sigma
+ * <= 16; max_iter lies in 0 .. 64, eps > 0 and finite, 0 < max_shift <= 64; anything else is RPSF_E_BADARG, before anything is launched.
+ * d is the residual of rpsf_stars_detect_device (use_mesh != 0) or the pixel itself on usable pixels (finite, not masked).  A WALK at
+ * p = (y, x): R = 4 sigma, h = 1 / (2 sigma sigma); over the pixels (r, c) with q = (r - y)^2 + (c - x)^2 <= R R (N_all of them, N_use
+ * usable and on the frame), w = g(q h) with g this library's own exp(-t) in plain float64 arithmetic, t = w d:
+ *   S = sum t, A = sum w |d|, mr = sum t (r - y), mc = sum t (c - x), mrr = sum t (r - y)^2, mcc = sum t (c - x)^2, mrc = sum t (r - y)(c - x)
+ * in float64, in S4's summation order.  From p_0 = the input, j = 0: (1) walk at p_j; (2) S not finite or S <= 0: stop, NO_FLUX; (3) dy =
+ * mr / S, dx = mc / S, p' = p_j + 2 (dy, dx); (4) p' not finite or farther than max_shift from p_0: stop, RAN_AWAY; (5) p_(j+1) = p',
+ * niter = j + 1, dy dy + dx dx < eps eps: stop, converged; (6) niter == max_iter: stop, NOT_CONVERGED; else j += 1 and (1).  max_iter = 0
+ * iterates nothing and sets no flag.  The sums and counts delivered are those of one more walk at the position returned (after a stop at
+ * 2 or 4: p_j and the walk just made).  With use_mesh != 0 and no valid mesh node nothing iterates: NO_FLUX, every sum NaN, the counts
+ * delivered.  Two runs agree bit for bit.  This is not sep's winpos: no sub-pixel sampling of the window's rim, the comparison is <=,
+ * there is no error column, and masked pixels are left out and reported through the counts, not corrected for.  A row of out_host is
+ * RPSF_STARS_REFINE_COLUMNS float64:
+ *   y0, x0, y, x, sigma, niter, flags, dy, dx (the last step taken or rejected, NaN if none), N_use, N_all, S, A, mr, mc, mrr, mcc, mrc.
+ * n == 0 launches nothing.  The call replaces nothing of the finder: a rpsf_stars_positions, rpsf_stars_measure or rpsf_stars_photometry
+ * after it gives the bits it gave before. */
+#define RPSF_STARS_REFINE_COLUMNS 18
+#define RPSF_STARS_REFINE_NO_FLUX 1
+#define RPSF_STARS_REFINE_RAN_AWAY 2
+#define RPSF_STARS_REFINE_NOT_CONVERGED 4
+int rpsf_stars_refine(rpsf_stars* finder, size_t n, const double* positions_host, const double* sigma_host, int max_iter, double eps,
+                      double max_shift, int use_mesh, double* out_host);
+/* Device time of the last S7, milliseconds; 0 when it launched nothing. */
+int rpsf_stars_refine_ms(const rpsf_stars* finder, double* ms);
+
 /* rpsf_builder_add_frame on a dense float32 frame that is already on the builder's device - a finder's (rpsf_stars_frame) or the caller's
  * own; it is only read, nothing is uploaded but the star list.  On a scaled builder the frame is the SCALED one and height and width are
  * its. */

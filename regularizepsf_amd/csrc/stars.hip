@@ -22,6 +22,10 @@
 //                              sub-pixel coverage on the frame and the filtered mesh of the fused route (the driver of
 //                              rpsf_core_stars_photometry.hpp); it writes its own rows and nothing the other kernels read
 //
+//   S7  stars_refine_kernel    rpsf_stars_refine, and only then: one wave per position the caller supplies, the Gaussian-windowed
+//                              position iterated to convergence and the windowed moments there (the driver of
+//                              rpsf_core_stars_refine.hpp); it writes its own rows and nothing the other kernels read
+//
 // The phases are the drivers of rpsf_core_stars.hpp.  Launches follow one another on the null stream; no workgroup ever waits for
 // another one, and the only atomics are integer min / max / add - labels and moments are the same on every run.
 #include <hip/hip_runtime.h>
@@ -36,6 +40,7 @@
 #include "rpsf_core_stars_deblend.hpp"
 #include "rpsf_core_stars_mesh.hpp"
 #include "rpsf_core_stars_photometry.hpp"
+#include "rpsf_core_stars_refine.hpp"
 #include "rpsf_core_stars_shape.hpp"
 #include "rpsf_scale.hpp"
 #include "rpsf_side_unit.hpp"
@@ -44,6 +49,8 @@ using namespace rpsfs;
 static_assert(rpsfh::SHAPE_COLUMNS == RPSF_STARS_SHAPE_COLUMNS, "the shape columns of rpsf_core_stars_shape.hpp and include/rpsf.h");
 static_assert(rpsfp::photometry_columns(3) == RPSF_STARS_PHOTOMETRY_COLUMNS(3), "the photometry columns of rpsf_core_stars_photometry.hpp and include/rpsf.h");
 static_assert(rpsfp::s6_lds_bytes(rpsfp::MAX_RADII) <= 64 * 1024, "S6's records fit the LDS a launch gets without asking");
+static_assert(rpsfr::REFINE_COLUMNS == RPSF_STARS_REFINE_COLUMNS, "the refine columns of rpsf_core_stars_refine.hpp and include/rpsf.h");
+static_assert(rpsfr::s7_lds_bytes() <= 64 * 1024 && rpsfr::s7_lds_bytes() % 16 == 0, "S7's records fit the LDS a launch gets without asking");
 
 extern __shared__ __attribute__((aligned(16))) char stars_lds[];
 
@@ -131,6 +138,12 @@ __global__ __launch_bounds__(WALK_THREADS) void stars_photometry_kernel(Frame fr
   rpsfp::s6_apertures(ctx, fr, L, none, use_mesh, ap, pos, count, (long)blockIdx.x * WALK_WAVES, stars_lds, out);
 }
 
+__global__ __launch_bounds__(WALK_THREADS) void stars_refine_kernel(Frame fr, const double* L, const int* none, int use_mesh, rpsfr::Refine rf,
+                                                                    const double* pos, const double* sigma, long count, double* out) {
+  GpuCtx ctx;
+  rpsfr::s7_refine(ctx, fr, L, none, use_mesh, rf, pos, sigma, count, (long)blockIdx.x * WALK_WAVES, stars_lds, out);
+}
+
 // ------------------------------------------------------------------------------------------------ the deblend option
 // S2 that also stores the filtered residual; T from device memory when T_dev is given
 __global__ __launch_bounds__(TILE_THREADS) void stars_detect_f_kernel(Frame fr, const double* L, const double* T_dev, double T, uint8_t* det,
@@ -204,6 +217,9 @@ struct rpsf_stars {
   // S6 (rpsf_stars_photometry): its own positions and rows, nothing of the above
   Buf<double> phot_pos, phot_out;
   double photometry_ms = 0;
+  // S7 (rpsf_stars_refine): likewise its own
+  Buf<double> refine_pos, refine_sigma, refine_out;
+  double refine_ms = 0;
   // the deblend option: everything below is allocated by the first call that needs it
   bool deblend = false;
   double contrast = 0.005, prominence = 1.0;
@@ -626,6 +642,44 @@ extern "C" int rpsf_stars_photometry(rpsf_stars* s, size_t n, const double* posi
 extern "C" int rpsf_stars_photometry_ms(const rpsf_stars* s, double* ms) {
   if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
   *ms = s->photometry_ms;
+  return RPSF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ S7 (Windowed positions)
+extern "C" int rpsf_stars_refine(rpsf_stars* s, size_t n, const double* positions_host, const double* sigma_host, int max_iter, double eps,
+                                 double max_shift, int use_mesh, double* out_host) {
+  if (!s || (n && (!positions_host || !sigma_host || !out_host))) return fail(RPSF_E_BADARG, "null argument");
+  if (const char* why = rpsfr::refine_problem(max_iter, eps, max_shift)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_refine: ") + why);
+  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_refine: more than 2^30 positions in one call");
+  for (size_t i = 0; i < n; ++i) {
+    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
+      return fail(RPSF_E_BADARG, "rpsf_stars_refine: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
+    if (!rpsfr::sigma_ok(sigma_host[i]))
+      return fail(RPSF_E_BADARG, "rpsf_stars_refine: sigma " + std::to_string(i) + " is not inside 0.5 <= sigma <= 16");
+  }
+  if (!s->have_mesh) return fail(RPSF_E_STATE, "rpsf_stars_refine before a rpsf_stars_background_view / _host / _scaled of the frame");
+  s->refine_ms = 0;
+  if (n == 0) return RPSF_OK;  // nothing to launch
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(s->refine_pos.reserve(2 * n));
+  HIP_TRY(s->refine_sigma.reserve(n));
+  HIP_TRY(s->refine_out.reserve(RPSF_STARS_REFINE_COLUMNS * n));
+  HIP_TRY(hipMemcpy(s->refine_pos.p, positions_host, 2 * n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->refine_sigma.p, sigma_host, n * sizeof(double), hipMemcpyHostToDevice));
+  const rpsfr::Refine rf = rpsfr::make_refine(max_iter, eps, max_shift);
+  if (const int rc = timed(s, &s->refine_ms, [&] {
+        hipLaunchKernelGGL(stars_refine_kernel, dim3((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS), rpsfr::s7_lds_bytes(),
+                           nullptr, s->view(), s->level_f.p, s->none.p, use_mesh != 0, rf, s->refine_pos.p, s->refine_sigma.p, (long)n,
+                           s->refine_out.p);
+      }))
+    return rc;
+  HIP_TRY(hipMemcpy(out_host, s->refine_out.p, RPSF_STARS_REFINE_COLUMNS * n * sizeof(double), hipMemcpyDeviceToHost));
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_refine_ms(const rpsf_stars* s, double* ms) {
+  if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
+  *ms = s->refine_ms;
   return RPSF_OK;
 }
 

@@ -28,6 +28,13 @@ what this detector finds: circular apertures at several radii with sub-pixel cov
 growth.  The footprint is the aperture, not the threshold's, so the same stars can be compared before and after ``apply``.  It is NOT
 ``sep``'s ``sum_circle`` / ``flux_radius``: a sub-sample counts when ``q <= R^2``, there is no error column and no 1 / 12 term, and
 masked pixels are excluded and reported through ``coverage``, not corrected for.
+
+``refine_stars`` moves given positions to their Gaussian-windowed centroids (kernel S7, ``rpsf_stars_refine``; DESIGN.md 3.7 "Windowed
+positions"): the iteration ``p <- p + 2 sum w d (r - p) / sum w d`` with ``w = exp(-q / 2 sigma^2)`` inside ``q <= (4 sigma)^2``, and the
+windowed second moments at the position it ends at.  The builder's ``finder_options={"refine_sigma": s}`` applies it to the detections of
+the fused route.  It is NOT ``sep``'s ``winpos``: no sub-pixel sampling of the window's
+rim, the comparison is ``<=``, there is no error column, and masked pixels are excluded and reported through ``coverage``, not corrected
+for.
 """
 
 from __future__ import annotations
@@ -49,6 +56,11 @@ CATALOG_DTYPE = np.dtype([(name, np.float64) for name in CATALOG_FIELDS])
 # a photometry row of kernel S6 for m radii (RPSF_STARS_PHOTOMETRY_COLUMNS(m) float64): row, col, flux[m], N_use[m], N_all[m], then these
 PHOTOMETRY_SUMS = ("abs_flux", "mr", "mc", "mrr", "mcc", "mrc", "peak", "peak_row", "peak_col")
 MAX_RADII, MAX_RADIUS, MAX_SUBPIX, MAX_COORD = 8, 64.0, 8, 2.0 ** 20
+# a row of kernel S7 (RPSF_STARS_REFINE_COLUMNS float64) and its flags
+REFINE_COLUMNS = ("row0", "col0", "row", "col", "sigma", "niter", "flags", "step_row", "step_col", "n_use", "n_all", "flux", "abs_flux", "mr",
+                  "mc", "mrr", "mcc", "mrc")
+NO_FLUX, RAN_AWAY, NOT_CONVERGED = 1, 2, 4
+MIN_SIGMA, MAX_SIGMA, MAX_ITER = 0.5, 16.0, 64
 DEBLEND_OPTIONS = {"deblend": False, "deblend_contrast": 0.005, "deblend_prominence": 1.0}  # contrast: sep's deblend_cont
 
 
@@ -206,6 +218,24 @@ class _Finder:
         self._native.check(self._native.lib().rpsf_stars_photometry_ms(self._handle, ctypes.byref(ms)))
         return ms.value
 
+    def refine(self, positions: np.ndarray, sigma, max_iter: int = 16, eps: float = 1e-4, max_shift: float = 2.0,
+               use_mesh: bool = True) -> np.ndarray:
+        """Kernel S7 on the frame given to ``background_device`` / ``background_scaled`` last, from ``positions`` ((k, 2) of (row, col)) with
+        the window ``sigma`` (a scalar or one per position): (k, len(REFINE_COLUMNS)) float64.  Nothing of the finder is replaced."""
+        n = self._native
+        positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 2)
+        sigma = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, np.float64), (len(positions),)))
+        out = np.empty((len(positions), len(REFINE_COLUMNS)))
+        n.check(n.lib().rpsf_stars_refine(self._handle, len(positions), n._ptr(positions), n._ptr(sigma), int(max_iter), float(eps),
+                                          float(max_shift), int(bool(use_mesh)), n._ptr(out)))
+        return out
+
+    def refine_ms(self) -> float:
+        """Device time of the last S7; 0.0 when it launched nothing."""
+        ms = ctypes.c_double(0)
+        self._native.check(self._native.lib().rpsf_stars_refine_ms(self._handle, ctypes.byref(ms)))
+        return ms.value
+
     def deblend_info(self) -> tuple[int, int, int]:
         """Of the last detect: components, basins, split components."""
         counts = [ctypes.c_size_t(0) for _ in range(3)]
@@ -283,6 +313,43 @@ def frame_stars_device(finder, frame, mask: np.ndarray | None, threshold: float,
     """``frame_stars`` on the fused route: ``frame`` is a host array or a 2-D ``DeviceArray``; the mesh never leaves the device."""
     finder.background_device(frame, mask)
     return finder.detect_device(threshold, min_area, max_area)
+
+
+def refine_sigma_option(refine_sigma) -> float | None:
+    """``refine_sigma`` of the builder's ``finder_options``, range-checked: None or one window sigma."""
+    if refine_sigma is None:
+        return None
+    if isinstance(refine_sigma, (bool, np.bool_)) or not isinstance(refine_sigma, (int, float, np.integer, np.floating)):
+        msg = f"refine_sigma must be None or a number, not {refine_sigma!r}"
+        raise TypeError(msg)
+    if not MIN_SIGMA <= float(refine_sigma) <= MAX_SIGMA:
+        msg = f"refine_sigma must lie in {MIN_SIGMA:g} ... {MAX_SIGMA:g}, got {refine_sigma}"
+        raise ValueError(msg)
+    return float(refine_sigma)
+
+
+def refined_positions(positions: np.ndarray, rows: np.ndarray) -> np.ndarray:
+    """The positions the builder's ``refine_sigma`` option takes for its detections ``positions``: the refined one, and the detected one
+    where the iteration stopped with ``NO_FLUX`` or ``RAN_AWAY``.  ``rows``: S7's rows for those positions, or ``refine_stars``' structured
+    array of them."""
+    positions = np.asarray(positions, np.float64).reshape(-1, 2)
+    rows = np.asarray(rows)
+    if rows.dtype.names is not None:
+        flags, refined = rows["flags"].astype(np.int64), np.stack([rows["row"], rows["col"]], axis=-1).astype(np.float64)
+    else:
+        rows = np.asarray(rows, np.float64).reshape(-1, len(REFINE_COLUMNS))
+        flags, refined = rows[:, REFINE_COLUMNS.index("flags")].astype(np.int64), rows[:, 2:4]
+    failed = (flags & (NO_FLUX | RAN_AWAY)) != 0
+    return np.ascontiguousarray(np.where(failed[:, None], positions, refined))
+
+
+def refine_detections(finder, positions: np.ndarray, refine_sigma: float) -> np.ndarray:
+    """S7 with its defaults and the finder's own background on the detections of the frame the finder holds (after a ``detect_device``):
+    ``(k, 2)`` positions, ``refined_positions``' rule applied.  Nothing is launched for no detections."""
+    positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 2)
+    if len(positions) == 0:
+        return positions
+    return refined_positions(positions, finder.refine(positions, refine_sigma))
 
 
 def _masks(mask, frames: list, shape: tuple[int, int] | None = None) -> list[np.ndarray | None]:
@@ -541,6 +608,155 @@ def star_photometry(images, stars, radii, mask=None, *, background: str = "mesh"
         for frame, m, p in zip(frames, masks, positions):
             finder.background_device(frame, m)
             out.append(photometry_from_sums(finder.photometry(p, radii, subpix, background == "mesh"), radii, subpix))
+        return out
+    finally:
+        finder.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------- windowed positions
+REFINE_FIELDS = ("row", "col", "row0", "col0", "sigma", "niter", "flags", "converged", "step_row", "step_col", "flux", "abs_flux", "coverage",
+                 "drow", "dcol", "wrr", "wcc", "wrc", "rr", "cc", "rc", "a", "b", "theta", "elongation")
+
+
+def refine_dtype() -> np.dtype:
+    """The structured dtype of ``refine_stars``: float64 fields but for ``niter`` and ``flags`` (int32) and ``converged`` (bool)."""
+    kinds = {"niter": np.int32, "flags": np.int32, "converged": np.bool_}
+    return np.dtype([(name, kinds.get(name, np.float64)) for name in REFINE_FIELDS])
+
+
+def window_corrected(wrr, wcc, wrc, sigma) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(rr, cc, rc)``: the matrix ``(M_w^-1 - I / sigma^2)^-1`` of the windowed central moments ``M_w = [[wrr, wrc], [wrc, wcc]]``, NumPy
+    float64, where that difference is positive definite; NaN otherwise.  A Gaussian source of covariance ``M`` seen through a Gaussian
+    window of ``sigma`` has ``M_w^-1 = M^-1 + I / sigma^2``: the correction is exact for a Gaussian under the continuous, untruncated
+    window, and only there."""
+    wrr, wcc, wrc, sigma = (np.asarray(v, np.float64) for v in (wrr, wcc, wrc, sigma))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        det_w = wrr * wcc - wrc * wrc
+        inv = 1.0 / (sigma * sigma)
+        drr, dcc, drc = wcc / det_w - inv, wrr / det_w - inv, -wrc / det_w  # M_w^-1 - I / sigma^2
+        det = drr * dcc - drc * drc
+        good = (drr > 0.0) & (det > 0.0) & np.isfinite(det)
+        rr, cc, rc = dcc / det, drr / det, -drc / det
+    nan = np.float64(np.nan)
+    return np.where(good, rr, nan), np.where(good, cc, nan), np.where(good, rc, nan)
+
+
+def refine_from_sums(rows: np.ndarray) -> np.ndarray:
+    """The structured result (``refine_dtype``) of S7's rows, everything derived in NumPy float64: ``coverage = N_use / N_all``, ``drow = mr /
+    S`` and ``dcol = mc / S`` (what is left of the offset at the position returned), the windowed central moments ``wrr = mrr / S -
+    drow^2`` (``wcc``, ``wrc`` alike), ``rr, cc, rc`` by ``window_corrected``, the ellipse of ``ellipse`` on those, and ``converged = flags
+    == 0 and niter > 0``."""
+    rows = np.asarray(rows, np.float64).reshape(-1, len(REFINE_COLUMNS))
+    col = {name: rows[:, j] for j, name in enumerate(REFINE_COLUMNS)}
+    out = np.empty(len(rows), refine_dtype())
+    for name in ("row", "col", "row0", "col0", "sigma", "step_row", "step_col", "flux", "abs_flux"):
+        out[name] = col[name]
+    out["niter"], out["flags"] = col["niter"].astype(np.int32), col["flags"].astype(np.int32)
+    out["converged"] = (out["flags"] == 0) & (out["niter"] > 0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        total = col["flux"]
+        out["coverage"] = col["n_use"] / col["n_all"]
+        drow, dcol = col["mr"] / total, col["mc"] / total
+        out["drow"], out["dcol"] = drow, dcol
+        out["wrr"], out["wcc"], out["wrc"] = col["mrr"] / total - drow * drow, col["mcc"] / total - dcol * dcol, col["mrc"] / total - drow * dcol
+    out["rr"], out["cc"], out["rc"] = window_corrected(out["wrr"], out["wcc"], out["wrc"], out["sigma"])
+    out["a"], out["b"], out["theta"], out["elongation"] = ellipse(out["rr"], out["cc"], out["rc"])
+    return out
+
+
+def _refine_sigmas(sigma, counts: list[int]) -> list[np.ndarray]:
+    """``sigma`` of ``refine_stars`` as one float64 array per frame: a scalar, one array for all frames, or a list with one entry (a scalar
+    or an array) per frame."""
+    per_frame = isinstance(sigma, (list, tuple)) and any(np.ndim(s) > 0 for s in sigma)
+    if per_frame and len(sigma) != len(counts):
+        msg = f"sigma has {len(sigma)} entries for {len(counts)} frames"
+        raise ValueError(msg)
+    out = []
+    for i, k in enumerate(counts):
+        try:
+            one = np.asarray(sigma[i] if per_frame else sigma, np.float64)
+        except (TypeError, ValueError) as error:
+            msg = f"sigma must be numbers, not {sigma!r}"
+            raise TypeError(msg) from error
+        if one.ndim > 1 or (one.ndim == 1 and len(one) != k):
+            msg = f"sigma has shape {one.shape} for the {k} stars of frame {i}: a scalar or one value per star"
+            raise ValueError(msg)
+        one = np.ascontiguousarray(np.broadcast_to(one, (k,)))
+        if not np.all((one >= MIN_SIGMA) & (one <= MAX_SIGMA)):  # (false for NaN)
+            msg = f"sigma must lie in {MIN_SIGMA:g} ... {MAX_SIGMA:g}"
+            raise ValueError(msg)
+        out.append(one)
+    return out
+
+
+def refine_stars(images, stars, sigma, mask=None, *, background: str = "mesh", box: int = 64, max_iter: int = 16, eps: float = 1e-4,
+                 max_shift: float = 2.0, device: int = 0) -> list[np.ndarray]:
+    """Gaussian-windowed positions and moments at given positions (SExtractor's ``XWIN`` iteration): a list of NumPy structured arrays
+    (``refine_dtype``), one per frame and one row per position, with the fields ``row, col`` (the refined position), ``row0, col0`` (the
+    input), ``sigma, niter, flags, converged, step_row, step_col, flux, abs_flux, coverage, drow, dcol, wrr, wcc, wrc, rr, cc, rc, a, b,
+    theta, elongation``.  ``build(..., stars=refine_stars(...))`` and ``star_photometry(frames, refine_stars(...), radii)`` take it as it is.
+
+    ``images``, ``stars``, ``mask``, ``background`` and ``box`` are ``star_photometry``'s.  ``sigma``: the window's sigma in pixels, 0.5 ...
+    16 - a scalar, one array for all frames (one value per star), or a list with one array per frame; the star's own sigma is the usual
+    choice.  ``max_iter``: 0 ... 64; 0 measures at the given positions.  ``eps > 0``: the iteration has converged when a step ``(dy, dx)`` has
+    ``dy^2 + dx^2 < eps^2``.  ``max_shift``: ``0 < max_shift <= 64``, the farthest a position may move from its start.
+
+    One walk at ``p = (row, col)``: over the pixels with ``q = (r - row)^2 + (c - col)^2 <= (4 sigma)^2``, usable (finite, unmasked, on
+    the frame), with ``d`` the background-subtracted pixel and ``w = exp(-q / (2 sigma^2))`` (this package's own ``exp`` in plain float64
+    arithmetic, the same bits on the GPU and on the CPU): ``S = sum w d``, ``A = sum w |d|`` and the first and second moments of ``w d``
+    around ``p``.  From the given position: walk; without flux (``S <= 0`` or not finite) stop with flag ``NO_FLUX`` (1); step ``p' = p + 2
+    (mr, mc) / S``; if ``p'`` is farther than ``max_shift`` from the start, stop with ``RAN_AWAY`` (2) at ``p``; else accept it, and stop
+    when the step is below ``eps`` (converged) or after ``max_iter`` steps (``NOT_CONVERGED``, 4).  ``step_row, step_col`` are the last step
+    computed (NaN if none), ``niter`` the steps accepted.  One more walk at the position returned gives ``flux = S``, ``abs_flux = A``,
+    ``coverage`` (the usable share of the window's pixels), ``drow, dcol`` (the offset that is left), the windowed central moments
+    ``wrr, wcc, wrc``, and ``rr, cc, rc``: those corrected for the window, ``(M_w^-1 - I / sigma^2)^-1``, NaN where that difference is not
+    positive definite; ``a, b, theta, elongation`` as in ``star_catalog``, of the corrected moments.  ``converged`` is ``flags == 0 and
+    niter > 0``.  With ``background="mesh"`` a frame without a usable pixel has no background: every position stays, flagged ``NO_FLUX``,
+    with NaN sums.
+
+    The correction is exact for a Gaussian source under the continuous, untruncated window only.  This is NOT ``sep``'s ``winpos``: no
+    sub-pixel sampling of the window's rim, the comparison is ``<=``, there is no error column, and masked pixels are excluded and
+    reported through ``coverage``, not corrected for.
+    """
+    if background not in ("mesh", "none"):
+        msg = f'background must be "mesh" or "none", not {background!r}'
+        raise ValueError(msg)
+    if not MIN_BOX <= int(box) <= MAX_BOX:
+        msg = f"box must lie in {MIN_BOX} ... {MAX_BOX}, got {box}"
+        raise ValueError(msg)
+    if isinstance(max_iter, (bool, np.bool_)) or not isinstance(max_iter, (int, np.integer)):
+        msg = f"max_iter must be an integer, not {max_iter!r}"
+        raise TypeError(msg)
+    if not 0 <= max_iter <= MAX_ITER:
+        msg = f"max_iter must lie in 0 ... {MAX_ITER}, got {max_iter}"
+        raise ValueError(msg)
+    if not (float(eps) > 0.0 and np.isfinite(eps)):
+        msg = f"eps must be positive and finite, got {eps}"
+        raise ValueError(msg)
+    if not 0.0 < float(max_shift) <= MAX_RADIUS:
+        msg = f"max_shift must lie in 0 < max_shift <= {MAX_RADIUS:g}, got {max_shift}"
+        raise ValueError(msg)
+    frames = _device_frames(images, device)
+    if frames is None:
+        frames = _frames(images)
+    if isinstance(stars, np.ndarray) and (stars.dtype.names is not None or stars.ndim == 2):
+        stars = [stars]  # one frame's stars, as they are
+    if len(stars) != len(frames):
+        msg = f"stars has {len(stars)} entries for {len(frames)} frames"
+        raise ValueError(msg)
+    positions = [np.ascontiguousarray(star_positions(s)) for s in stars]
+    for i, p in enumerate(positions):
+        if not np.all(np.abs(p) < MAX_COORD):  # (false for NaN)
+            msg = f"stars[{i}] has a position that is not finite or not inside |row|, |col| < 2^20"
+            raise ValueError(msg)
+    sigmas = _refine_sigmas(sigma, [len(p) for p in positions])
+    masks = _masks(mask, frames)
+    finder = _Finder(frames[0].shape, box, device)
+    try:
+        out = []
+        for frame, m, p, sg in zip(frames, masks, positions, sigmas):
+            finder.background_device(frame, m)
+            out.append(refine_from_sums(finder.refine(p, sg, max_iter, eps, max_shift, background == "mesh")))
         return out
     finally:
         finder.close()
