@@ -689,6 +689,46 @@ int rpsf_stars_refine(rpsf_stars* finder, size_t n, const double* positions_host
 /* Device time of the last S7, milliseconds; 0 when it launched nothing. */
 int rpsf_stars_refine_ms(const rpsf_stars* finder, double* ms);
 
+/* MODEL FITS (kernel S8): the linear least-squares fit of a cell of a PSF model to each of n stars, and its residual.
+ * A rpsf_stars_model is a cube of n_cells x N x N float64 values (4 <= N <= 256, 1 <= n_cells <= 2^24; anything else is RPSF_E_BADARG)
+ * uploaded to `device` once and used by any number of rpsf_stars_fit calls.  The values are taken as they are: a cell of NaN, which
+ * ArrayPSFBuilder leaves where it had no star, makes Smm NaN and the fit DEGENERATE.
+ * rpsf_stars_fit: n positions (y, x) the caller supplies (finite, |y|, |x| < 2^20; they may lie off the frame) with one cell index each,
+ * on the frame, the mask and the filtered mesh a rpsf_stars_background_view / _host / _scaled left on the device (RPSF_E_STATE before
+ * such a call).  0 < radius = R <= min(64, N / 2 - 1), fit_background is 0 or 1, the model lies on the finder's device; anything else is
+ * RPSF_E_BADARG, before anything is launched.  d is the residual of rpsf_stars_detect_device (use_mesh != 0) or the pixel itself, on usable
+ * pixels (finite, not masked, on the frame).  The cell C holds the star as ArrayPSFBuilder cuts it: its centre at index h = N / 2.0 - 0.5
+ * on both axes.  THE MODEL at pixel (r, c):  u = (r - y) + h, v = (c - x) + h, i = floor(u), j = floor(v), a = u - i, b = v - j,
+ *   m = ((1 - a) * ((1 - b) * C[i, j] + b * C[i, j + 1])) + (a * ((1 - b) * C[i + 1, j] + b * C[i + 1, j + 1]))
+ * in exactly this order of float64 operations, nothing fused.  PASS 1 over the pixels with (r - y)^2 + (c - x)^2 <= R R: n_all and Sm_all =
+ * sum m over all of them, and over the usable ones n, Sm = sum m, Smm = sum m m, Sd = sum d, Sdm = sum d m, Sdd = sum d d, in S4's
+ * summation order (lane-strided raster order over the box floor(y - R) - 1 .. ceil(y + R) + 1, 8 groups of 8).  THE SOLVE: with
+ * fit_background D = n Smm - Sm Sm, f = (n Sdm - Sm Sd) / D, bg = (Sd - f Sm) / n; without, D = Smm, f = Sdm / Smm, bg = 0.  FLAGS:
+ *   NO_MESH     use_mesh != 0 and no valid mesh node: every sum NaN, the counts delivered;
+ *   BAD_CELL    the cell index is outside 0 .. n_cells - 1: nothing is read from the cube, every sum NaN, the counts delivered;
+ *   TOO_FEW     n < 3 with fit_background, n < 1 without;   DEGENERATE (when not TOO_FEW)   D not finite or D <= 0;
+ * with any flag f, bg and PASS 2's columns are NaN and the peak sits at (-1, -1).  PASS 2 over the same pixels in the same order, with
+ * e = d - (f m + bg): chi2 = sum e e, abs_res = sum |e|, peak_res = max |e| with the signed e there (peak_e) at (peak_row, peak_col), the
+ * first such pixel in raster order (a NaN e counts as the largest).  Two runs agree bit for bit.  This is not a PSF-photometry package's
+ * fit: the weights are uniform (no error column, no variance weighting), the position is given and not fitted (rpsf_stars_refine supplies
+ * positions), the interpolation is bilinear and does not conserve flux below the pixel scale, and masked pixels are left out and reported
+ * through the counts, not corrected for.  A row of out_host is RPSF_STARS_FIT_COLUMNS float64:
+ *   y, x, cell, flags, n, n_all, Sm, Sm_all, Smm, Sd, Sdm, Sdd, f, bg, chi2, abs_res, peak_res, peak_e, peak_row, peak_col.
+ * n == 0 launches nothing and needs no pointers.  The call replaces nothing of the finder: a rpsf_stars_positions, rpsf_stars_measure,
+ * rpsf_stars_photometry or rpsf_stars_refine after it gives the bits it gave before. */
+#define RPSF_STARS_FIT_COLUMNS 20
+#define RPSF_STARS_FIT_NO_MESH 1
+#define RPSF_STARS_FIT_TOO_FEW 2
+#define RPSF_STARS_FIT_DEGENERATE 4
+#define RPSF_STARS_FIT_BAD_CELL 8
+typedef struct rpsf_stars_model rpsf_stars_model;
+int rpsf_stars_model_create(int device, size_t n_cells, int N, const double* values_host, rpsf_stars_model** out);
+void rpsf_stars_model_destroy(rpsf_stars_model* model);
+int rpsf_stars_fit(rpsf_stars* finder, const rpsf_stars_model* model, size_t n, const double* positions_host, const int32_t* cells_host,
+                   double radius, int fit_background, int use_mesh, double* out_host);
+/* Device time of the last S8, milliseconds; 0 when it launched nothing. */
+int rpsf_stars_fit_ms(const rpsf_stars* finder, double* ms);
+
 /* rpsf_builder_add_frame on a dense float32 frame that is already on the builder's device - a finder's (rpsf_stars_frame) or the caller's
  * own; it is only read, nothing is uploaded but the star list.  On a scaled builder the frame is the SCALED one and height and width are
  * its. */

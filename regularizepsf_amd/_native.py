@@ -178,6 +178,10 @@ _PROTOTYPES = {
     "rpsf_stars_photometry_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rpsf_stars_refine": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_void_p]),
     "rpsf_stars_refine_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rpsf_stars_model_create": (c_int, [c_int, c_size_t, c_int, c_void_p, POINTER(c_void_p)]),
+    "rpsf_stars_model_destroy": (None, [c_void_p]),
+    "rpsf_stars_fit": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_double, c_int, c_int, c_void_p]),
+    "rpsf_stars_fit_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rpsf_builder_add_frame_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double, c_double,
                                               c_void_p]),
     "rpsf_saturation_fill": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),

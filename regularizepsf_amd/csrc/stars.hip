@@ -26,6 +26,10 @@
 //                              position iterated to convergence and the windowed moments there (the driver of
 //                              rpsf_core_stars_refine.hpp); it writes its own rows and nothing the other kernels read
 //
+//   S8  stars_fit_kernel       rpsf_stars_fit, and only then: one wave per position the caller supplies, the least-squares fit of a cell of
+//                              a PSF model cube (rpsf_stars_model) and its residual (the driver of rpsf_core_stars_fit.hpp); it writes
+//                              its own rows and nothing the other kernels read
+//
 // The phases are the drivers of rpsf_core_stars.hpp.  Launches follow one another on the null stream; no workgroup ever waits for
 // another one, and the only atomics are integer min / max / add - labels and moments are the same on every run.
 #include <hip/hip_runtime.h>
@@ -38,6 +42,7 @@
 #include "rpsf_core_convert.hpp"
 #include "rpsf_core_stars.hpp"
 #include "rpsf_core_stars_deblend.hpp"
+#include "rpsf_core_stars_fit.hpp"
 #include "rpsf_core_stars_mesh.hpp"
 #include "rpsf_core_stars_photometry.hpp"
 #include "rpsf_core_stars_refine.hpp"
@@ -51,6 +56,11 @@ static_assert(rpsfp::photometry_columns(3) == RPSF_STARS_PHOTOMETRY_COLUMNS(3), 
 static_assert(rpsfp::s6_lds_bytes(rpsfp::MAX_RADII) <= 64 * 1024, "S6's records fit the LDS a launch gets without asking");
 static_assert(rpsfr::REFINE_COLUMNS == RPSF_STARS_REFINE_COLUMNS, "the refine columns of rpsf_core_stars_refine.hpp and include/rpsf.h");
 static_assert(rpsfr::s7_lds_bytes() <= 64 * 1024 && rpsfr::s7_lds_bytes() % 16 == 0, "S7's records fit the LDS a launch gets without asking");
+static_assert(rpsff::FIT_COLUMNS == RPSF_STARS_FIT_COLUMNS, "the fit columns of rpsf_core_stars_fit.hpp and include/rpsf.h");
+static_assert(rpsff::FLAG_NO_MESH == RPSF_STARS_FIT_NO_MESH && rpsff::FLAG_TOO_FEW == RPSF_STARS_FIT_TOO_FEW &&
+                  rpsff::FLAG_DEGENERATE == RPSF_STARS_FIT_DEGENERATE && rpsff::FLAG_BAD_CELL == RPSF_STARS_FIT_BAD_CELL,
+              "the fit flags of rpsf_core_stars_fit.hpp and include/rpsf.h");
+static_assert(rpsff::s8_lds_bytes() <= 64 * 1024 && rpsff::s8_lds_bytes() % 16 == 0, "S8's records fit the LDS a launch gets without asking");
 
 extern __shared__ __attribute__((aligned(16))) char stars_lds[];
 
@@ -144,6 +154,12 @@ __global__ __launch_bounds__(WALK_THREADS) void stars_refine_kernel(Frame fr, co
   rpsfr::s7_refine(ctx, fr, L, none, use_mesh, rf, pos, sigma, count, (long)blockIdx.x * WALK_WAVES, stars_lds, out);
 }
 
+__global__ __launch_bounds__(WALK_THREADS) void stars_fit_kernel(Frame fr, const double* L, const int* none, int use_mesh, rpsff::Model model,
+                                                                 rpsff::Fit fit, const double* pos, const int* cell, long count, double* out) {
+  GpuCtx ctx;
+  rpsff::s8_fit(ctx, fr, L, none, use_mesh, model, fit, pos, cell, count, (long)blockIdx.x * WALK_WAVES, stars_lds, out);
+}
+
 // ------------------------------------------------------------------------------------------------ the deblend option
 // S2 that also stores the filtered residual; T from device memory when T_dev is given
 __global__ __launch_bounds__(TILE_THREADS) void stars_detect_f_kernel(Frame fr, const double* L, const double* T_dev, double T, uint8_t* det,
@@ -220,6 +236,10 @@ struct rpsf_stars {
   // S7 (rpsf_stars_refine): likewise its own
   Buf<double> refine_pos, refine_sigma, refine_out;
   double refine_ms = 0;
+  // S8 (rpsf_stars_fit): likewise its own
+  Buf<double> fit_pos, fit_out;
+  Buf<int> fit_cell;
+  double fit_ms = 0;
   // the deblend option: everything below is allocated by the first call that needs it
   bool deblend = false;
   double contrast = 0.005, prominence = 1.0;
@@ -680,6 +700,78 @@ extern "C" int rpsf_stars_refine(rpsf_stars* s, size_t n, const double* position
 extern "C" int rpsf_stars_refine_ms(const rpsf_stars* s, double* ms) {
   if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
   *ms = s->refine_ms;
+  return RPSF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ S8 (Model fits)
+struct rpsf_stars_model {
+  int device = 0, n_cells = 0, N = 0;
+  Buf<double> values;
+};
+
+extern "C" int rpsf_stars_model_create(int device, size_t n_cells, int N, const double* values_host, rpsf_stars_model** out) {
+  if (!out || !values_host) return fail(RPSF_E_BADARG, "null argument");
+  if (!rpsff::model_size_ok(N)) return fail(RPSF_E_BADARG, "rpsf_stars_model_create: the cells must be N x N with 4 <= N <= 256");
+  if (n_cells < 1 || n_cells > ((size_t)1 << 24)) return fail(RPSF_E_BADARG, "rpsf_stars_model_create: the number of cells must lie in 1 ... 2^24");
+  const size_t words = n_cells * (size_t)N * N;
+  HIP_TRY(hipSetDevice(device));
+  rpsf_stars_model* m = new rpsf_stars_model;
+  m->device = device, m->n_cells = (int)n_cells, m->N = N;
+  auto made = [&]() -> int {
+    HIP_TRY(m->values.reserve(words));
+    HIP_TRY(hipMemcpy(m->values.p, values_host, words * sizeof(double), hipMemcpyHostToDevice));
+    return RPSF_OK;
+  };
+  if (const int rc = made()) {
+    delete m;
+    return rc;
+  }
+  *out = m;
+  return RPSF_OK;
+}
+
+extern "C" void rpsf_stars_model_destroy(rpsf_stars_model* m) {
+  if (!m) return;
+  (void)hipSetDevice(m->device);
+  delete m;
+}
+
+extern "C" int rpsf_stars_fit(rpsf_stars* s, const rpsf_stars_model* model, size_t n, const double* positions_host, const int32_t* cells_host,
+                              double radius, int fit_background, int use_mesh, double* out_host) {
+  if (!s || !model || (n && (!positions_host || !cells_host || !out_host))) return fail(RPSF_E_BADARG, "null argument");
+  if (const char* why = rpsff::fit_problem(radius, fit_background)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit: ") + why);
+  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_fit: more than 2^30 positions in one call");
+  for (size_t i = 0; i < n; ++i)
+    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
+      return fail(RPSF_E_BADARG, "rpsf_stars_fit: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
+  if (!(radius <= rpsff::max_fit_radius(model->N)))
+    return fail(RPSF_E_BADARG, "rpsf_stars_fit: radius " + std::to_string(radius) + " is above min(64, N / 2 - 1) of the model's N = " +
+                                   std::to_string(model->N));
+  if (model->device != s->device) return fail(RPSF_E_BADARG, "rpsf_stars_fit: the model is on another device than the finder");
+  if (!s->have_mesh) return fail(RPSF_E_STATE, "rpsf_stars_fit before a rpsf_stars_background_view / _host / _scaled of the frame");
+  s->fit_ms = 0;
+  if (n == 0) return RPSF_OK;  // nothing to launch
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(s->fit_pos.reserve(2 * n));
+  HIP_TRY(s->fit_cell.reserve(n));
+  HIP_TRY(s->fit_out.reserve(RPSF_STARS_FIT_COLUMNS * n));
+  HIP_TRY(hipMemcpy(s->fit_pos.p, positions_host, 2 * n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->fit_cell.p, cells_host, n * sizeof(int32_t), hipMemcpyHostToDevice));
+  const rpsff::Model cube{model->values.p, model->n_cells, model->N};
+  const rpsff::Fit fit = rpsff::make_fit(radius, fit_background, model->N);
+  if (const int rc = timed(s, &s->fit_ms, [&] {
+        hipLaunchKernelGGL(stars_fit_kernel, dim3((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS), rpsff::s8_lds_bytes(),
+                           nullptr, s->view(), s->level_f.p, s->none.p, use_mesh != 0, cube, fit, s->fit_pos.p, s->fit_cell.p, (long)n,
+                           s->fit_out.p);
+      }))
+    return rc;
+  HIP_TRY(hipMemcpy(out_host, s->fit_out.p, RPSF_STARS_FIT_COLUMNS * n * sizeof(double), hipMemcpyDeviceToHost));
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_fit_ms(const rpsf_stars* s, double* ms) {
+  if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
+  *ms = s->fit_ms;
   return RPSF_OK;
 }
 

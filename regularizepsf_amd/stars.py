@@ -35,6 +35,13 @@ windowed second moments at the position it ends at.  The builder's ``finder_opti
 the fused route.  It is NOT ``sep``'s ``winpos``: no sub-pixel sampling of the window's
 rim, the comparison is ``<=``, there is no error column, and masked pixels are excluded and reported through ``coverage``, not corrected
 for.
+
+``fit_stars`` judges a PSF model by the stars: every star is fitted, by linear least squares over a disc, with the cell of the model it
+belongs to, bilinearly interpolated to the star's position (kernel S8, ``rpsf_stars_fit``; DESIGN.md 3.7 "Model fits"), and the residual
+of that fit is reported; ``cell_fit_summary`` folds the stars into one row per cell, the map that shows where a model is bad.  It is
+NOT a PSF-photometry package's fit: the weights are uniform - no error column, no variance weighting -, the position is given and
+not fitted (``refine_stars`` supplies positions), the interpolation is bilinear and does not conserve flux below the pixel scale, and
+masked pixels are excluded and reported through ``coverage``, not corrected for.
 """
 
 from __future__ import annotations
@@ -61,6 +68,11 @@ REFINE_COLUMNS = ("row0", "col0", "row", "col", "sigma", "niter", "flags", "step
                   "mc", "mrr", "mcc", "mrc")
 NO_FLUX, RAN_AWAY, NOT_CONVERGED = 1, 2, 4
 MIN_SIGMA, MAX_SIGMA, MAX_ITER = 0.5, 16.0, 64
+# a row of kernel S8 (RPSF_STARS_FIT_COLUMNS float64) and its flags
+FIT_COLUMNS = ("row", "col", "cell", "flags", "n_use", "n_all", "sm", "sm_all", "smm", "sd", "sdm", "sdd", "flux", "background", "chi2", "abs_res",
+               "peak_res", "peak_e", "peak_row", "peak_col")
+NO_MESH, TOO_FEW, DEGENERATE, BAD_CELL = 1, 2, 4, 8
+MIN_MODEL, MAX_MODEL = 4, 256
 DEBLEND_OPTIONS = {"deblend": False, "deblend_contrast": 0.005, "deblend_prominence": 1.0}  # contrast: sep's deblend_cont
 
 
@@ -236,6 +248,27 @@ class _Finder:
         self._native.check(self._native.lib().rpsf_stars_refine_ms(self._handle, ctypes.byref(ms)))
         return ms.value
 
+    def fit(self, model, positions: np.ndarray, cells, radius: float, fit_background: bool = True, use_mesh: bool = True) -> np.ndarray:
+        """Kernel S8 on the frame given to ``background_device`` / ``background_scaled`` last: ``model`` (a ``_Model``) fitted at ``positions``
+        ((k, 2) of (row, col)), each with its cell of ``cells`` ((k,) integers): (k, len(FIT_COLUMNS)) float64.  Nothing of the finder is
+        replaced."""
+        n = self._native
+        positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 2)
+        cells = np.ascontiguousarray(cells, np.int32).ravel()
+        if len(cells) != len(positions):
+            msg = f"{len(cells)} cells for {len(positions)} positions"
+            raise ValueError(msg)
+        out = np.empty((len(positions), len(FIT_COLUMNS)))
+        n.check(n.lib().rpsf_stars_fit(self._handle, model._handle, len(positions), n._ptr(positions), n._ptr(cells), float(radius),
+                                       int(bool(fit_background)), int(bool(use_mesh)), n._ptr(out)))
+        return out
+
+    def fit_ms(self) -> float:
+        """Device time of the last S8; 0.0 when it launched nothing."""
+        ms = ctypes.c_double(0)
+        self._native.check(self._native.lib().rpsf_stars_fit_ms(self._handle, ctypes.byref(ms)))
+        return ms.value
+
     def deblend_info(self) -> tuple[int, int, int]:
         """Of the last detect: components, basins, split components."""
         counts = [ctypes.c_size_t(0) for _ in range(3)]
@@ -276,6 +309,34 @@ class _Finder:
     def close(self) -> None:
         if self._handle is not None and self._handle.value:
             self._native.lib().rpsf_stars_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self) -> None:
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+class _Model:
+    """A native model handle: a cube of ``n_cells x N x N`` float64 values on the device, uploaded once (``rpsf_stars_model``)."""
+
+    def __init__(self, values: np.ndarray, device: int = 0) -> None:
+        from regularizepsf_amd import _native
+
+        self._native = _native
+        self.values = np.ascontiguousarray(values, np.float64)
+        if self.values.ndim != 3 or self.values.shape[1] != self.values.shape[2]:
+            msg = f"a model is a cube of n_cells x N x N values, not of shape {self.values.shape}"
+            raise IncorrectShapeError(msg)
+        self.size, self.device = int(self.values.shape[1]), int(device)
+        self._handle = ctypes.c_void_p()
+        _native.check(_native.lib().rpsf_stars_model_create(int(device), len(self.values), self.size, _native._ptr(self.values),
+                                                            ctypes.byref(self._handle)))
+
+    def close(self) -> None:
+        if self._handle is not None and self._handle.value:
+            self._native.lib().rpsf_stars_model_destroy(self._handle)
             self._handle = None
 
     def __del__(self) -> None:
@@ -760,3 +821,213 @@ def refine_stars(images, stars, sigma, mask=None, *, background: str = "mesh", b
         return out
     finally:
         finder.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------- model fits
+FIT_FIELDS = ("row", "col", "cell", "flags", "flux", "background", "n_use", "n_all", "coverage", "dof", "chi2", "rms", "abs_res",
+              "residual_fraction", "peak_res", "peak_e", "peak_row", "peak_col", "sm", "sm_all", "smm", "sd", "sdm", "sdd", "no_mesh", "too_few",
+              "degenerate", "bad_cell")
+
+
+def fit_dtype() -> np.dtype:
+    """The structured dtype of ``fit_stars``: float64 fields but for ``cell``, ``flags``, ``n_use``, ``n_all`` and ``dof`` (int32) and the four
+    booleans of the flags."""
+    kinds = {"cell": np.int32, "flags": np.int32, "n_use": np.int32, "n_all": np.int32, "dof": np.int32, "no_mesh": np.bool_,
+             "too_few": np.bool_, "degenerate": np.bool_, "bad_cell": np.bool_}
+    return np.dtype([(name, kinds.get(name, np.float64)) for name in FIT_FIELDS])
+
+
+def fit_from_sums(rows: np.ndarray, fit_background: bool = True) -> np.ndarray:
+    """The structured result (``fit_dtype``) of S8's rows, everything derived in NumPy float64: ``coverage = Sm / Sm_all``, ``dof = n - 2``
+    (``n - 1`` without a fitted background), ``rms = sqrt(chi2 / dof)`` (NaN when ``dof <= 0``), ``residual_fraction = abs_res / (|flux|
+    |Sm|)`` and one boolean per flag."""
+    rows = np.asarray(rows, np.float64).reshape(-1, len(FIT_COLUMNS))
+    col = {name: rows[:, j] for j, name in enumerate(FIT_COLUMNS)}
+    out = np.empty(len(rows), fit_dtype())
+    for name in ("row", "col", "flux", "background", "chi2", "abs_res", "peak_res", "peak_e", "peak_row", "peak_col", "sm", "sm_all", "smm", "sd",
+                 "sdm", "sdd"):
+        out[name] = col[name]
+    for name in ("cell", "flags", "n_use", "n_all"):
+        out[name] = col[name].astype(np.int32)
+    out["dof"] = out["n_use"] - (2 if fit_background else 1)
+    for name, bit in (("no_mesh", NO_MESH), ("too_few", TOO_FEW), ("degenerate", DEGENERATE), ("bad_cell", BAD_CELL)):
+        out[name] = (out["flags"] & bit) != 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dof = out["dof"].astype(np.float64)
+        out["coverage"] = col["sm"] / col["sm_all"]
+        out["rms"] = np.where(dof > 0, np.sqrt(col["chi2"] / np.where(dof > 0, dof, np.nan)), np.nan)
+        out["residual_fraction"] = col["abs_res"] / (np.abs(col["flux"]) * np.abs(col["sm"]))
+    return out
+
+
+def nearest_cells(positions: np.ndarray, coordinates, size: int) -> np.ndarray:
+    """Per position the index of the cell whose centre ``corner + N / 2`` is nearest in squared Euclidean distance ``(row - cy)^2 + (col -
+    cx)^2``, float64; among equals the first in the order of ``coordinates``.  (k,) int32.  Many cells are searched through a k-d tree, which
+    only proposes the candidates: every cell within the nearest one's distance (and a little beyond) is compared by the formula above."""
+    positions = np.asarray(positions, np.float64).reshape(-1, 2)
+    centres = np.asarray(coordinates, np.float64).reshape(-1, 2) + size / 2
+    if len(positions) == 0:
+        return np.zeros(0, np.int32)
+    if len(centres) <= 64:
+        candidates = np.broadcast_to(np.arange(len(centres)), (len(positions), len(centres)))
+    else:
+        from scipy.spatial import cKDTree
+
+        tree = cKDTree(centres)
+        nearest = tree.query(positions)[0]
+        found = tree.query_ball_point(positions, nearest * (1 + 1e-9) + 1e-9, return_sorted=True)  # every cell that can be the nearest or tie
+        counts = np.array([len(f) for f in found])
+        flat, starts = np.concatenate([np.asarray(f, np.int64) for f in found]), np.cumsum(counts) - counts
+        # ascending indices per position, the last one repeated up to the longest list: argmin takes the first of equals
+        candidates = flat[starts[:, None] + np.minimum(np.arange(counts.max())[None, :], counts[:, None] - 1)]
+    dy, dx = positions[:, 0, None] - centres[candidates, 0], positions[:, 1, None] - centres[candidates, 1]
+    return candidates[np.arange(len(positions)), np.argmin(dy * dy + dx * dx, axis=1)].astype(np.int32)
+
+
+def model_cube(psf) -> tuple[list, np.ndarray]:
+    """``(coordinates, values)`` of an ``ArrayPSF`` or an ``IndexedCube`` of real values: the values as a C-contiguous float64 cube of
+    ``n_cells x N x N``, ``4 <= N <= 256``, NaN cells (``build``'s cells without a star) as they are."""
+    if not (hasattr(psf, "coordinates") and hasattr(psf, "values")):
+        msg = f"psf must be an ArrayPSF or an IndexedCube, not {type(psf).__name__}"
+        raise TypeError(msg)
+    values = np.asarray(psf.values)
+    if np.iscomplexobj(values) or values.dtype.kind not in "fiu":
+        msg = f"the model's values must be real numbers, not {values.dtype}"
+        raise TypeError(msg)
+    if values.ndim != 3 or values.shape[1] != values.shape[2] or not MIN_MODEL <= values.shape[1] <= MAX_MODEL or len(values) == 0:
+        msg = f"the model must be a cube of at least one cell of N x N values with {MIN_MODEL} <= N <= {MAX_MODEL}, not of shape {values.shape}"
+        raise IncorrectShapeError(msg)
+    return list(psf.coordinates), np.ascontiguousarray(values, np.float64)
+
+
+def fit_stars(images, stars, psf, radius: float, mask=None, *, background: str = "mesh", box: int = 64, fit_background: bool = True,
+              cells=None, device: int = 0) -> list[np.ndarray]:
+    """Fit every star with the cell of a PSF model it belongs to and report the residual: a list of NumPy structured arrays
+    (``fit_dtype``), one per frame and one row per position, with the fields ``row, col, cell, flags, flux, background, n_use, n_all,
+    coverage, dof, chi2, rms, abs_res, residual_fraction, peak_res, peak_e, peak_row, peak_col``, the raw sums ``sm, sm_all, smm, sd, sdm,
+    sdd`` and the booleans ``no_mesh, too_few, degenerate, bad_cell``.  On the frames a model was built from it says whether the model
+    describes its stars, cell by cell; on frames after ``apply``, with the target PSF as the model, whether the correction worked.
+
+    ``images``, ``stars``, ``mask``, ``background`` and ``box`` are ``star_photometry``'s, device frames included; ``refine_stars``' output and
+    catalogues are taken by ``row`` / ``col``.  ``psf``: an ``ArrayPSF`` (``ArrayPSFBuilder.build``'s) or an ``IndexedCube`` of real
+    values, cells of ``N x N`` with ``4 <= N <= 256``; it is uploaded once.  ``radius`` = ``R``: ``0 < R <= min(64, N / 2 - 1)``, the disc
+    the fit sees.  ``fit_background``: fit a constant beside the flux.  ``cells``: None, or one integer array per frame (one array for a
+    single frame) with the cell index of every star in the order of ``psf.coordinates``; None takes, per star, the cell whose centre ``corner
+    + N / 2`` is nearest (squared Euclidean distance in float64; the first such cell in the cube's coordinate order wins a tie).
+
+    A cell holds a star the way ``build`` cuts it: its centre at index ``h = N / 2 - 0.5`` on both axes.  The model at pixel ``(r, c)`` is
+    the bilinear interpolation of the cell at ``(r - row + h, c - col + h)``.  Over the usable pixels (finite, unmasked, on the frame) with
+    ``(r - row)^2 + (c - col)^2 <= R^2``, with ``d`` the background-subtracted pixel and ``m`` the model: ``n_use``, ``sm = sum m``, ``smm =
+    sum m^2``, ``sd = sum d``, ``sdm = sum d m``, ``sdd = sum d^2``; ``n_all`` and ``sm_all`` take the whole disc, usable or not, and
+    ``coverage = sm / sm_all`` is the share of the model the fit saw.  With ``fit_background``: ``D = n smm - sm^2``, ``flux = (n sdm - sm
+    sd) / D``, ``background = (sd - flux sm) / n``; without: ``flux = sdm / smm``, ``background = 0``.  Then, with ``e = d - (flux m +
+    background)``: ``chi2 = sum e^2``, ``abs_res = sum |e|``, ``peak_res = max |e|`` with its signed value ``peak_e`` at ``(peak_row,
+    peak_col)``; ``dof = n_use - 2`` (``- 1`` without a fitted background), ``rms = sqrt(chi2 / dof)`` (NaN when ``dof <= 0``) and
+    ``residual_fraction = abs_res / (|flux| |sm|)``, the residual's share of the fitted star.  Flags: ``NO_MESH`` (1: ``background="mesh"`` on
+    a frame without a usable pixel), ``TOO_FEW`` (2: ``n_use < 3``, or ``< 1`` without a fitted background), ``DEGENERATE`` (4: ``D``, or
+    ``smm``, not finite or ``<= 0`` - an all-zero cell, a cell of NaN as ``build`` leaves where it had no star, or a constant one with
+    ``fit_background``), ``BAD_CELL`` (8: a cell index outside the
+    model); with any of them ``flux``, ``background`` and the residual's columns are NaN.
+
+    This is NOT a PSF-photometry package's fit: the weights are uniform - there is no error column and no variance weighting -, the position
+    is given and not fitted (``refine_stars`` supplies positions), the interpolation is bilinear and does not conserve flux below the pixel
+    scale, and masked pixels are excluded and reported through ``coverage``, not corrected for.
+    """
+    if background not in ("mesh", "none"):
+        msg = f'background must be "mesh" or "none", not {background!r}'
+        raise ValueError(msg)
+    if not MIN_BOX <= int(box) <= MAX_BOX:
+        msg = f"box must lie in {MIN_BOX} ... {MAX_BOX}, got {box}"
+        raise ValueError(msg)
+    if not isinstance(fit_background, (bool, np.bool_)):
+        msg = f"fit_background must be True or False, not {fit_background!r}"
+        raise TypeError(msg)
+    coordinates, values = model_cube(psf)
+    size = values.shape[1]
+    try:
+        radius = float(radius)
+    except (TypeError, ValueError) as error:
+        msg = f"radius must be a number, not {radius!r}"
+        raise TypeError(msg) from error
+    limit = min(MAX_RADIUS, size / 2 - 1)
+    if not 0.0 < radius <= limit:
+        msg = f"radius must lie in 0 < R <= min({MAX_RADIUS:g}, N / 2 - 1) = {limit:g} for cells of {size}, got {radius}"
+        raise ValueError(msg)
+    frames = _device_frames(images, device)
+    if frames is None:
+        frames = _frames(images)
+    if isinstance(stars, np.ndarray) and (stars.dtype.names is not None or stars.ndim == 2):
+        stars = [stars]  # one frame's stars, as they are
+    if len(stars) != len(frames):
+        msg = f"stars has {len(stars)} entries for {len(frames)} frames"
+        raise ValueError(msg)
+    positions = [np.ascontiguousarray(star_positions(s)) for s in stars]
+    for i, p in enumerate(positions):
+        if not np.all(np.abs(p) < MAX_COORD):  # (false for NaN)
+            msg = f"stars[{i}] has a position that is not finite or not inside |row|, |col| < 2^20"
+            raise ValueError(msg)
+    if cells is None:
+        cells = [nearest_cells(p, coordinates, size) for p in positions]
+    else:
+        if isinstance(cells, np.ndarray) and cells.ndim == 1 and len(frames) == 1:
+            cells = [cells]
+        if len(cells) != len(frames):
+            msg = f"cells has {len(cells)} entries for {len(frames)} frames"
+            raise ValueError(msg)
+        given, cells = cells, []
+        for i, (c, p) in enumerate(zip(given, positions)):
+            c = np.asarray(c)
+            if c.dtype.kind not in "iu" and c.size:
+                msg = f"cells[{i}] must be integers, not {c.dtype}"
+                raise TypeError(msg)
+            if c.shape != (len(p),):
+                msg = f"cells[{i}] has shape {c.shape} for the {len(p)} stars of frame {i}"
+                raise ValueError(msg)
+            if c.size and (c.min() < -(2 ** 31) or c.max() >= 2 ** 31):
+                msg = f"cells[{i}] has an index outside int32"
+                raise ValueError(msg)
+            cells.append(np.ascontiguousarray(c, np.int32))
+    masks = _masks(mask, frames)
+    finder = _Finder(frames[0].shape, box, device)
+    model = None
+    try:
+        model = _Model(values, device)
+        out = []
+        for frame, m, p, c in zip(frames, masks, positions, cells):
+            finder.background_device(frame, m)
+            out.append(fit_from_sums(finder.fit(model, p, c, radius, bool(fit_background), background == "mesh"), bool(fit_background)))
+        return out
+    finally:
+        if model is not None:
+            model.close()
+        finder.close()
+
+
+CELL_FIT_DTYPE = np.dtype([("count", np.int64), ("residual_fraction", np.float64), ("relative_rms", np.float64), ("flux", np.float64)])
+
+
+def cell_fit_summary(fits, psf) -> np.ndarray:
+    """``fit_stars``' result folded into one row per cell of ``psf`` (in the order of ``psf.coordinates``; host NumPy only): ``count``, the
+    number of stars of all frames fitted with the cell without a flag, and over those the medians of ``residual_fraction``, of ``rms /
+    |flux|`` (``relative_rms``) and of ``flux``.  A cell without such a star has NaN everywhere except ``count``.  The map that shows where
+    a model is bad.  ``fits``: the list ``fit_stars`` returns, or one frame's array."""
+    n_cells = len(psf.coordinates)
+    if isinstance(fits, np.ndarray):
+        fits = [fits]
+    rows = np.concatenate([np.asarray(f, fit_dtype()).ravel() for f in fits]) if len(fits) else np.zeros(0, fit_dtype())
+    rows = rows[(rows["flags"] == 0) & (rows["cell"] >= 0) & (rows["cell"] < n_cells)]
+    out = np.zeros(n_cells, CELL_FIT_DTYPE)
+    for name in ("residual_fraction", "relative_rms", "flux"):
+        out[name] = np.nan
+    order = np.argsort(rows["cell"], kind="stable")
+    rows = rows[order]
+    out["count"] = np.bincount(rows["cell"], minlength=n_cells)
+    bounds = np.concatenate([[0], np.cumsum(out["count"])])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        relative = rows["rms"] / np.abs(rows["flux"])
+    for cell in np.flatnonzero(out["count"]):
+        part = slice(bounds[cell], bounds[cell + 1])
+        out["residual_fraction"][cell] = np.median(rows["residual_fraction"][part])
+        out["relative_rms"][cell] = np.median(relative[part])
+        out["flux"][cell] = np.median(rows["flux"][part])
+    return out
