@@ -729,6 +729,56 @@ int rpsf_stars_fit(rpsf_stars* finder, const rpsf_stars_model* model, size_t n, 
 /* Device time of the last S8, milliseconds; 0 when it launched nothing. */
 int rpsf_stars_fit_ms(const rpsf_stars* finder, double* ms);
 
+/* FITTED POSITIONS (kernel S9): the position of each of n stars fitted with its cell of a rpsf_stars_model, by a
+ * Gauss-Newton iteration around S8's linear fit, and S8's own row at the position it ends at.  The inputs are rpsf_stars_fit's (the
+ * positions, one int32 cell index per star that stays fixed for the whole iteration, 0 < radius = R <= min(64, N / 2 - 1), fit_background
+ * 0 or 1, the model on the finder's device, RPSF_E_STATE before a rpsf_stars_background_view / _host / _scaled), and max_iter in 0 .. 64,
+ * eps > 0 and finite, 0 < max_shift <= 64, 0 < max_step <= 64; anything else is RPSF_E_BADARG, before anything is launched.
+ * THE MODEL AND ITS GRADIENT at pixel offset (pr, pc) = (r - y, c - x): u, v, i, j, a, b and m are exactly S8's, and
+ *   g_u = ((1 - b) * (C[i + 1, j] - C[i, j])) + (b * (C[i + 1, j + 1] - C[i, j + 1]))
+ *   g_v = ((1 - a) * (C[i, j + 1] - C[i, j])) + (a * (C[i + 1, j + 1] - C[i + 1, j]))
+ * the exact derivatives of the bilinear interpolant inside its cell, in exactly this order of float64 operations, nothing fused.
+ * A WALK at p = (y, x) covers S8's box with S8's disc test q <= R R, S8's usable-pixel rule and S8's d, in S4's summation order
+ * (lane-strided raster order, 64 partials folded as 8 groups of 8).  Over the usable pixels it takes n and the thirteen sums of the
+ * linearised problem d ~ f m + bg + a_u g_u + a_v g_v:
+ *   Smm = sum m m, Sm = sum m, Smu = sum m g_u, Smv = sum m g_v, Su = sum g_u, Sv = sum g_v, Suu = sum g_u g_u, Suv = sum g_u g_v,
+ *   Svv = sum g_v g_v, and the right-hand sides Sdm = sum d m, Sd = sum d, Sdu = sum d g_u, Sdv = sum d g_v.
+ * THE SOLVE, in the wave's first lane: the symmetric system in the unknowns (f, bg, a_u, a_v)
+ *   (Smm Sm Smu Smv) (f  )   (Sdm)
+ *   (Sm  n  Su  Sv ) (bg ) = (Sd )         K = 4; without fit_background the row and the column of the constant drop out, K = 3
+ *   (Smu Su Suu Suv) (a_u)   (Sdu)
+ *   (Smv Sv Suv Svv) (a_v)   (Sdv)
+ * by an LDL^T elimination on the upper triangle without pivoting and without square roots: for j = 0 .. K - 1: the pivot A[j][j] must be
+ * finite and > 0; for i = j + 1 .. K - 1: l = A[j][i] / A[j][j], for c = i .. K - 1: A[i][c] = A[i][c] - l A[j][c], b[i] = b[i] - l b[j];
+ * then back, for j = K - 1 .. 0: s = b[j], for c = j + 1 .. K - 1: s = s - A[j][c] x[c], x[j] = s / A[j][j].  The step is dy = -a_u / f,
+ * dx = -a_v / f.  From p_0 = the input, j = 0:
+ *   SKIPPED (8)        the star has S8's NO_MESH or BAD_CELL: nothing iterates;
+ *   (1) walk at p_j and solve;  SINGULAR (4): n < K, a pivot not finite or <= 0, or dy or dx not finite: stop at p_j, the last step stays
+ *       what it was;
+ *   (2) each of dy, dx is clamped to [-max_step, max_step] and is now the last step; p' = p_j + (dy, dx);
+ *   (3) RAN_AWAY (1): (p' - p_0)^2 > max_shift^2: stop at p_j;
+ *   (4) p_(j+1) = p', niter = j + 1; dy dy + dx dx < eps eps: stop, converged;
+ *   (5) NOT_CONVERGED (2): niter == max_iter: stop; else j += 1 and (1).
+ * max_iter = 0 iterates nothing and sets no flag but SKIPPED.  A row of iter_out_host is RPSF_STARS_FITPOS_COLUMNS float64:
+ *   y0, x0, y, x, niter, flags, dy, dx (the last step taken or rejected, NaN if none was computed).
+ * A row of fit_out_host is rpsf_stars_fit's row (RPSF_STARS_FIT_COLUMNS float64, S8's flags) at the (y, x) returned, computed by kernel S8
+ * itself on those positions: it is what rpsf_stars_fit gives there, bit for bit.  No atomics, no workgroup waits for another, two runs
+ * agree bit for bit.  This is not a PSF-photometry package's fit: the weights are uniform (no error column, no variance weighting), the
+ * interpolation is bilinear, the cell is fixed, one star is fitted at a time (neighbours are not fitted together), and masked pixels are
+ * left out, not corrected for.  n == 0 launches nothing and needs no pointers.  The call replaces nothing of the finder: a
+ * rpsf_stars_positions, rpsf_stars_measure, rpsf_stars_photometry, rpsf_stars_refine or rpsf_stars_fit after it gives the bits it gave
+ * before. */
+#define RPSF_STARS_FITPOS_COLUMNS 8
+#define RPSF_STARS_FITPOS_RAN_AWAY 1
+#define RPSF_STARS_FITPOS_NOT_CONVERGED 2
+#define RPSF_STARS_FITPOS_SINGULAR 4
+#define RPSF_STARS_FITPOS_SKIPPED 8
+int rpsf_stars_fit_positions(rpsf_stars* finder, const rpsf_stars_model* model, size_t n, const double* positions_host,
+                             const int32_t* cells_host, double radius, int fit_background, int max_iter, double eps, double max_shift,
+                             double max_step, int use_mesh, double* iter_out_host, double* fit_out_host);
+/* Device time of the last S9 and the S8 that follows it, milliseconds; 0 when it launched nothing. */
+int rpsf_stars_fit_positions_ms(const rpsf_stars* finder, double* ms);
+
 /* rpsf_builder_add_frame on a dense float32 frame that is already on the builder's device - a finder's (rpsf_stars_frame) or the caller's
  * own; it is only read, nothing is uploaded but the star list.  On a scaled builder the frame is the SCALED one and height and width are
  * its. */

@@ -27,7 +27,7 @@ from regularizepsf_amd._native import pinned_empty
 from regularizepsf_amd.builder import ArrayPSFBuilder, scale_image
 from regularizepsf_amd.device_array import DeviceArray, device_empty, to_device
 from regularizepsf_amd.psf import ArrayPSF
-from regularizepsf_amd.stars import cell_fit_summary, find_stars, fit_stars, refine_stars, star_catalog, star_photometry
+from regularizepsf_amd.stars import cell_fit_summary, find_stars, fit_positions, fit_stars, refine_stars, star_catalog, star_photometry
 from regularizepsf_amd.transform import ArrayPSFTransform
 from regularizepsf_amd.util import IndexedCube, calculate_covering
 
@@ -53,6 +53,7 @@ __all__ = [
     "device_empty",
     "elliptical_gaussian",
     "find_stars",
+    "fit_positions",
     "fit_stars",
     "moffat",
     "pinned_empty",

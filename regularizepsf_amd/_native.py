@@ -182,6 +182,9 @@ _PROTOTYPES = {
     "rpsf_stars_model_destroy": (None, [c_void_p]),
     "rpsf_stars_fit": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_double, c_int, c_int, c_void_p]),
     "rpsf_stars_fit_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rpsf_stars_fit_positions": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_double, c_int, c_int, c_double, c_double,
+                                         c_double, c_int, c_void_p, c_void_p]),
+    "rpsf_stars_fit_positions_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rpsf_builder_add_frame_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double, c_double,
                                               c_void_p]),
     "rpsf_saturation_fill": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),

@@ -30,6 +30,11 @@
 //                              a PSF model cube (rpsf_stars_model) and its residual (the driver of rpsf_core_stars_fit.hpp); it writes
 //                              its own rows and nothing the other kernels read
 //
+//   S9  stars_fitpos_kernel    rpsf_stars_fit_positions, and only then: one wave per position the caller supplies, (y, x) iterated with
+//                              the star's cell of the model until the Gauss-Newton step is below eps (the driver of
+//                              rpsf_core_stars_fitpos.hpp), then stars_fit_kernel at the positions it ends at; both write rows of
+//                              their own and nothing the other kernels read
+//
 // The phases are the drivers of rpsf_core_stars.hpp.  Launches follow one another on the null stream; no workgroup ever waits for
 // another one, and the only atomics are integer min / max / add - labels and moments are the same on every run.
 #include <hip/hip_runtime.h>
@@ -43,6 +48,7 @@
 #include "rpsf_core_stars.hpp"
 #include "rpsf_core_stars_deblend.hpp"
 #include "rpsf_core_stars_fit.hpp"
+#include "rpsf_core_stars_fitpos.hpp"
 #include "rpsf_core_stars_mesh.hpp"
 #include "rpsf_core_stars_photometry.hpp"
 #include "rpsf_core_stars_refine.hpp"
@@ -61,6 +67,12 @@ static_assert(rpsff::FLAG_NO_MESH == RPSF_STARS_FIT_NO_MESH && rpsff::FLAG_TOO_F
                   rpsff::FLAG_DEGENERATE == RPSF_STARS_FIT_DEGENERATE && rpsff::FLAG_BAD_CELL == RPSF_STARS_FIT_BAD_CELL,
               "the fit flags of rpsf_core_stars_fit.hpp and include/rpsf.h");
 static_assert(rpsff::s8_lds_bytes() <= 64 * 1024 && rpsff::s8_lds_bytes() % 16 == 0, "S8's records fit the LDS a launch gets without asking");
+
+static_assert(rpsfg::FITPOS_COLUMNS == RPSF_STARS_FITPOS_COLUMNS, "the iteration columns of rpsf_core_stars_fitpos.hpp and include/rpsf.h");
+static_assert(rpsfg::POS_RAN_AWAY == RPSF_STARS_FITPOS_RAN_AWAY && rpsfg::POS_NOT_CONVERGED == RPSF_STARS_FITPOS_NOT_CONVERGED &&
+                  rpsfg::POS_SINGULAR == RPSF_STARS_FITPOS_SINGULAR && rpsfg::POS_SKIPPED == RPSF_STARS_FITPOS_SKIPPED,
+              "the iteration flags of rpsf_core_stars_fitpos.hpp and include/rpsf.h");
+static_assert(rpsfg::s9_lds_bytes() <= 64 * 1024 && rpsfg::s9_lds_bytes() % 16 == 0, "S9's records fit the LDS a launch gets without asking");
 
 extern __shared__ __attribute__((aligned(16))) char stars_lds[];
 
@@ -160,6 +172,13 @@ __global__ __launch_bounds__(WALK_THREADS) void stars_fit_kernel(Frame fr, const
   rpsff::s8_fit(ctx, fr, L, none, use_mesh, model, fit, pos, cell, count, (long)blockIdx.x * WALK_WAVES, stars_lds, out);
 }
 
+__global__ __launch_bounds__(WALK_THREADS) void stars_fitpos_kernel(Frame fr, const double* L, const int* none, int use_mesh, rpsff::Model model,
+                                                                    rpsff::Fit fit, rpsfg::FitPos fp, const double* pos, const int* cell,
+                                                                    long count, double* out, double* final_pos) {
+  GpuCtx ctx;
+  rpsfg::s9_fit_positions(ctx, fr, L, none, use_mesh, model, fit, fp, pos, cell, count, (long)blockIdx.x * WALK_WAVES, stars_lds, out, final_pos);
+}
+
 // ------------------------------------------------------------------------------------------------ the deblend option
 // S2 that also stores the filtered residual; T from device memory when T_dev is given
 __global__ __launch_bounds__(TILE_THREADS) void stars_detect_f_kernel(Frame fr, const double* L, const double* T_dev, double T, uint8_t* det,
@@ -240,6 +259,10 @@ struct rpsf_stars {
   Buf<double> fit_pos, fit_out;
   Buf<int> fit_cell;
   double fit_ms = 0;
+  // S9 (rpsf_stars_fit_positions): likewise its own, S8's rows at the fitted positions among them
+  Buf<double> fitpos_pos, fitpos_final, fitpos_iter, fitpos_fit;
+  Buf<int> fitpos_cell;
+  double fitpos_ms = 0;
   // the deblend option: everything below is allocated by the first call that needs it
   bool deblend = false;
   double contrast = 0.005, prominence = 1.0;
@@ -772,6 +795,57 @@ extern "C" int rpsf_stars_fit(rpsf_stars* s, const rpsf_stars_model* model, size
 extern "C" int rpsf_stars_fit_ms(const rpsf_stars* s, double* ms) {
   if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
   *ms = s->fit_ms;
+  return RPSF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ S9 (Fitted positions)
+extern "C" int rpsf_stars_fit_positions(rpsf_stars* s, const rpsf_stars_model* model, size_t n, const double* positions_host,
+                                        const int32_t* cells_host, double radius, int fit_background, int max_iter, double eps,
+                                        double max_shift, double max_step, int use_mesh, double* iter_out_host, double* fit_out_host) {
+  if (!s || !model || (n && (!positions_host || !cells_host || !iter_out_host || !fit_out_host))) return fail(RPSF_E_BADARG, "null argument");
+  if (const char* why = rpsff::fit_problem(radius, fit_background)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit_positions: ") + why);
+  if (const char* why = rpsfg::fitpos_problem(max_iter, eps, max_shift, max_step))
+    return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit_positions: ") + why);
+  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_fit_positions: more than 2^30 positions in one call");
+  for (size_t i = 0; i < n; ++i)
+    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
+      return fail(RPSF_E_BADARG, "rpsf_stars_fit_positions: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
+  if (!(radius <= rpsff::max_fit_radius(model->N)))
+    return fail(RPSF_E_BADARG, "rpsf_stars_fit_positions: radius " + std::to_string(radius) + " is above min(64, N / 2 - 1) of the model's N = " +
+                                   std::to_string(model->N));
+  if (model->device != s->device) return fail(RPSF_E_BADARG, "rpsf_stars_fit_positions: the model is on another device than the finder");
+  if (!s->have_mesh)
+    return fail(RPSF_E_STATE, "rpsf_stars_fit_positions before a rpsf_stars_background_view / _host / _scaled of the frame");
+  s->fitpos_ms = 0;
+  if (n == 0) return RPSF_OK;  // nothing to launch
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(s->fitpos_pos.reserve(2 * n));
+  HIP_TRY(s->fitpos_final.reserve(2 * n));
+  HIP_TRY(s->fitpos_cell.reserve(n));
+  HIP_TRY(s->fitpos_iter.reserve(RPSF_STARS_FITPOS_COLUMNS * n));
+  HIP_TRY(s->fitpos_fit.reserve(RPSF_STARS_FIT_COLUMNS * n));
+  HIP_TRY(hipMemcpy(s->fitpos_pos.p, positions_host, 2 * n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->fitpos_cell.p, cells_host, n * sizeof(int32_t), hipMemcpyHostToDevice));
+  const rpsff::Model cube{model->values.p, model->n_cells, model->N};
+  const rpsff::Fit fit = rpsff::make_fit(radius, fit_background, model->N);
+  const rpsfg::FitPos fp = rpsfg::make_fitpos(max_iter, eps, max_shift, max_step);
+  if (const int rc = timed(s, &s->fitpos_ms, [&] {
+        const dim3 grid((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES));
+        hipLaunchKernelGGL(stars_fitpos_kernel, grid, dim3(WALK_THREADS), rpsfg::s9_lds_bytes(), nullptr, s->view(), s->level_f.p, s->none.p,
+                           use_mesh != 0, cube, fit, fp, s->fitpos_pos.p, s->fitpos_cell.p, (long)n, s->fitpos_iter.p, s->fitpos_final.p);
+        // S8 itself at the positions S9 ended at (the null stream orders the two)
+        hipLaunchKernelGGL(stars_fit_kernel, grid, dim3(WALK_THREADS), rpsff::s8_lds_bytes(), nullptr, s->view(), s->level_f.p, s->none.p,
+                           use_mesh != 0, cube, fit, s->fitpos_final.p, s->fitpos_cell.p, (long)n, s->fitpos_fit.p);
+      }))
+    return rc;
+  HIP_TRY(hipMemcpy(iter_out_host, s->fitpos_iter.p, RPSF_STARS_FITPOS_COLUMNS * n * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(fit_out_host, s->fitpos_fit.p, RPSF_STARS_FIT_COLUMNS * n * sizeof(double), hipMemcpyDeviceToHost));
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_fit_positions_ms(const rpsf_stars* s, double* ms) {
+  if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
+  *ms = s->fitpos_ms;
   return RPSF_OK;
 }
 

@@ -42,6 +42,12 @@ of that fit is reported; ``cell_fit_summary`` folds the stars into one row per c
 NOT a PSF-photometry package's fit: the weights are uniform - no error column, no variance weighting -, the position is given and
 not fitted (``refine_stars`` supplies positions), the interpolation is bilinear and does not conserve flux below the pixel scale, and
 masked pixels are excluded and reported through ``coverage``, not corrected for.
+
+``fit_positions`` lets the model say where a star is: a Gauss-Newton iteration of ``(row, col)`` around ``fit_stars``' linear fit, with the
+exact gradient of the bilinearly interpolated cell (kernel S9, ``rpsf_stars_fit_positions``; DESIGN.md 3.7 "Fitted positions"), and
+``fit_stars``' own row at the position it ends at.  It is the other half of the effective-PSF loop: build a model, fit positions with it,
+rebuild at the fitted positions.  It shares ``fit_stars``' limits - uniform weights, no error column, bilinear interpolation, masked
+pixels excluded and not corrected for - and adds its own: the cell is fixed at the input position and one star is fitted at a time.
 """
 
 from __future__ import annotations
@@ -73,6 +79,9 @@ FIT_COLUMNS = ("row", "col", "cell", "flags", "n_use", "n_all", "sm", "sm_all", 
                "peak_res", "peak_e", "peak_row", "peak_col")
 NO_MESH, TOO_FEW, DEGENERATE, BAD_CELL = 1, 2, 4, 8
 MIN_MODEL, MAX_MODEL = 4, 256
+# an iteration row of kernel S9 (RPSF_STARS_FITPOS_COLUMNS float64) and its flags
+FITPOS_COLUMNS = ("row0", "col0", "row", "col", "niter", "flags", "step_row", "step_col")
+FITPOS_RAN_AWAY, FITPOS_NOT_CONVERGED, FITPOS_SINGULAR, FITPOS_SKIPPED = 1, 2, 4, 8
 DEBLEND_OPTIONS = {"deblend": False, "deblend_contrast": 0.005, "deblend_prominence": 1.0}  # contrast: sep's deblend_cont
 
 
@@ -267,6 +276,29 @@ class _Finder:
         """Device time of the last S8; 0.0 when it launched nothing."""
         ms = ctypes.c_double(0)
         self._native.check(self._native.lib().rpsf_stars_fit_ms(self._handle, ctypes.byref(ms)))
+        return ms.value
+
+    def fit_positions(self, model, positions: np.ndarray, cells, radius: float, fit_background: bool = True, max_iter: int = 16,
+                      eps: float = 1e-4, max_shift: float = 2.0, max_step: float = 0.5, use_mesh: bool = True) -> tuple[np.ndarray, np.ndarray]:
+        """Kernel S9 and then S8 on the frame given to ``background_device`` / ``background_scaled`` last: ``positions`` iterated with their
+        cells of ``model``, and S8's rows where they end.  ((k, len(FITPOS_COLUMNS)), (k, len(FIT_COLUMNS))) float64.  Nothing of the finder
+        is replaced."""
+        n = self._native
+        positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 2)
+        cells = np.ascontiguousarray(cells, np.int32).ravel()
+        if len(cells) != len(positions):
+            msg = f"{len(cells)} cells for {len(positions)} positions"
+            raise ValueError(msg)
+        steps, fits = np.empty((len(positions), len(FITPOS_COLUMNS))), np.empty((len(positions), len(FIT_COLUMNS)))
+        n.check(n.lib().rpsf_stars_fit_positions(self._handle, model._handle, len(positions), n._ptr(positions), n._ptr(cells), float(radius),
+                                                 int(bool(fit_background)), int(max_iter), float(eps), float(max_shift), float(max_step),
+                                                 int(bool(use_mesh)), n._ptr(steps), n._ptr(fits)))
+        return steps, fits
+
+    def fit_positions_ms(self) -> float:
+        """Device time of the last S9 with the S8 behind it; 0.0 when it launched nothing."""
+        ms = ctypes.c_double(0)
+        self._native.check(self._native.lib().rpsf_stars_fit_positions_ms(self._handle, ctypes.byref(ms)))
         return ms.value
 
     def deblend_info(self) -> tuple[int, int, int]:
@@ -900,39 +932,9 @@ def model_cube(psf) -> tuple[list, np.ndarray]:
     return list(psf.coordinates), np.ascontiguousarray(values, np.float64)
 
 
-def fit_stars(images, stars, psf, radius: float, mask=None, *, background: str = "mesh", box: int = 64, fit_background: bool = True,
-              cells=None, device: int = 0) -> list[np.ndarray]:
-    """Fit every star with the cell of a PSF model it belongs to and report the residual: a list of NumPy structured arrays
-    (``fit_dtype``), one per frame and one row per position, with the fields ``row, col, cell, flags, flux, background, n_use, n_all,
-    coverage, dof, chi2, rms, abs_res, residual_fraction, peak_res, peak_e, peak_row, peak_col``, the raw sums ``sm, sm_all, smm, sd, sdm,
-    sdd`` and the booleans ``no_mesh, too_few, degenerate, bad_cell``.  On the frames a model was built from it says whether the model
-    describes its stars, cell by cell; on frames after ``apply``, with the target PSF as the model, whether the correction worked.
-
-    ``images``, ``stars``, ``mask``, ``background`` and ``box`` are ``star_photometry``'s, device frames included; ``refine_stars``' output and
-    catalogues are taken by ``row`` / ``col``.  ``psf``: an ``ArrayPSF`` (``ArrayPSFBuilder.build``'s) or an ``IndexedCube`` of real
-    values, cells of ``N x N`` with ``4 <= N <= 256``; it is uploaded once.  ``radius`` = ``R``: ``0 < R <= min(64, N / 2 - 1)``, the disc
-    the fit sees.  ``fit_background``: fit a constant beside the flux.  ``cells``: None, or one integer array per frame (one array for a
-    single frame) with the cell index of every star in the order of ``psf.coordinates``; None takes, per star, the cell whose centre ``corner
-    + N / 2`` is nearest (squared Euclidean distance in float64; the first such cell in the cube's coordinate order wins a tie).
-
-    A cell holds a star the way ``build`` cuts it: its centre at index ``h = N / 2 - 0.5`` on both axes.  The model at pixel ``(r, c)`` is
-    the bilinear interpolation of the cell at ``(r - row + h, c - col + h)``.  Over the usable pixels (finite, unmasked, on the frame) with
-    ``(r - row)^2 + (c - col)^2 <= R^2``, with ``d`` the background-subtracted pixel and ``m`` the model: ``n_use``, ``sm = sum m``, ``smm =
-    sum m^2``, ``sd = sum d``, ``sdm = sum d m``, ``sdd = sum d^2``; ``n_all`` and ``sm_all`` take the whole disc, usable or not, and
-    ``coverage = sm / sm_all`` is the share of the model the fit saw.  With ``fit_background``: ``D = n smm - sm^2``, ``flux = (n sdm - sm
-    sd) / D``, ``background = (sd - flux sm) / n``; without: ``flux = sdm / smm``, ``background = 0``.  Then, with ``e = d - (flux m +
-    background)``: ``chi2 = sum e^2``, ``abs_res = sum |e|``, ``peak_res = max |e|`` with its signed value ``peak_e`` at ``(peak_row,
-    peak_col)``; ``dof = n_use - 2`` (``- 1`` without a fitted background), ``rms = sqrt(chi2 / dof)`` (NaN when ``dof <= 0``) and
-    ``residual_fraction = abs_res / (|flux| |sm|)``, the residual's share of the fitted star.  Flags: ``NO_MESH`` (1: ``background="mesh"`` on
-    a frame without a usable pixel), ``TOO_FEW`` (2: ``n_use < 3``, or ``< 1`` without a fitted background), ``DEGENERATE`` (4: ``D``, or
-    ``smm``, not finite or ``<= 0`` - an all-zero cell, a cell of NaN as ``build`` leaves where it had no star, or a constant one with
-    ``fit_background``), ``BAD_CELL`` (8: a cell index outside the
-    model); with any of them ``flux``, ``background`` and the residual's columns are NaN.
-
-    This is NOT a PSF-photometry package's fit: the weights are uniform - there is no error column and no variance weighting -, the position
-    is given and not fitted (``refine_stars`` supplies positions), the interpolation is bilinear and does not conserve flux below the pixel
-    scale, and masked pixels are excluded and reported through ``coverage``, not corrected for.
-    """
+def _fit_inputs(images, stars, psf, radius, mask, background, box, fit_background, cells, device) -> tuple:
+    """What ``fit_stars`` and ``fit_positions`` make of their common arguments: ``(frames, masks, positions, cells, values, radius)``, one
+    entry per frame in the first four."""
     if background not in ("mesh", "none"):
         msg = f'background must be "mesh" or "none", not {background!r}'
         raise ValueError(msg)
@@ -987,7 +989,44 @@ def fit_stars(images, stars, psf, radius: float, mask=None, *, background: str =
                 msg = f"cells[{i}] has an index outside int32"
                 raise ValueError(msg)
             cells.append(np.ascontiguousarray(c, np.int32))
-    masks = _masks(mask, frames)
+    return frames, _masks(mask, frames), positions, cells, values, radius
+
+
+def fit_stars(images, stars, psf, radius: float, mask=None, *, background: str = "mesh", box: int = 64, fit_background: bool = True,
+              cells=None, device: int = 0) -> list[np.ndarray]:
+    """Fit every star with the cell of a PSF model it belongs to and report the residual: a list of NumPy structured arrays
+    (``fit_dtype``), one per frame and one row per position, with the fields ``row, col, cell, flags, flux, background, n_use, n_all,
+    coverage, dof, chi2, rms, abs_res, residual_fraction, peak_res, peak_e, peak_row, peak_col``, the raw sums ``sm, sm_all, smm, sd, sdm,
+    sdd`` and the booleans ``no_mesh, too_few, degenerate, bad_cell``.  On the frames a model was built from it says whether the model
+    describes its stars, cell by cell; on frames after ``apply``, with the target PSF as the model, whether the correction worked.
+
+    ``images``, ``stars``, ``mask``, ``background`` and ``box`` are ``star_photometry``'s, device frames included; ``refine_stars``' output and
+    catalogues are taken by ``row`` / ``col``.  ``psf``: an ``ArrayPSF`` (``ArrayPSFBuilder.build``'s) or an ``IndexedCube`` of real
+    values, cells of ``N x N`` with ``4 <= N <= 256``; it is uploaded once.  ``radius`` = ``R``: ``0 < R <= min(64, N / 2 - 1)``, the disc
+    the fit sees.  ``fit_background``: fit a constant beside the flux.  ``cells``: None, or one integer array per frame (one array for a
+    single frame) with the cell index of every star in the order of ``psf.coordinates``; None takes, per star, the cell whose centre ``corner
+    + N / 2`` is nearest (squared Euclidean distance in float64; the first such cell in the cube's coordinate order wins a tie).
+
+    A cell holds a star the way ``build`` cuts it: its centre at index ``h = N / 2 - 0.5`` on both axes.  The model at pixel ``(r, c)`` is
+    the bilinear interpolation of the cell at ``(r - row + h, c - col + h)``.  Over the usable pixels (finite, unmasked, on the frame) with
+    ``(r - row)^2 + (c - col)^2 <= R^2``, with ``d`` the background-subtracted pixel and ``m`` the model: ``n_use``, ``sm = sum m``, ``smm =
+    sum m^2``, ``sd = sum d``, ``sdm = sum d m``, ``sdd = sum d^2``; ``n_all`` and ``sm_all`` take the whole disc, usable or not, and
+    ``coverage = sm / sm_all`` is the share of the model the fit saw.  With ``fit_background``: ``D = n smm - sm^2``, ``flux = (n sdm - sm
+    sd) / D``, ``background = (sd - flux sm) / n``; without: ``flux = sdm / smm``, ``background = 0``.  Then, with ``e = d - (flux m +
+    background)``: ``chi2 = sum e^2``, ``abs_res = sum |e|``, ``peak_res = max |e|`` with its signed value ``peak_e`` at ``(peak_row,
+    peak_col)``; ``dof = n_use - 2`` (``- 1`` without a fitted background), ``rms = sqrt(chi2 / dof)`` (NaN when ``dof <= 0``) and
+    ``residual_fraction = abs_res / (|flux| |sm|)``, the residual's share of the fitted star.  Flags: ``NO_MESH`` (1: ``background="mesh"`` on
+    a frame without a usable pixel), ``TOO_FEW`` (2: ``n_use < 3``, or ``< 1`` without a fitted background), ``DEGENERATE`` (4: ``D``, or
+    ``smm``, not finite or ``<= 0`` - an all-zero cell, a cell of NaN as ``build`` leaves where it had no star, or a constant one with
+    ``fit_background``), ``BAD_CELL`` (8: a cell index outside the
+    model); with any of them ``flux``, ``background`` and the residual's columns are NaN.
+
+    This is NOT a PSF-photometry package's fit: the weights are uniform - there is no error column and no variance weighting -, the position
+    is given and not fitted (``refine_stars`` supplies positions), the interpolation is bilinear and does not conserve flux below the pixel
+    scale, and masked pixels are excluded and reported through ``coverage``, not corrected for.
+    """
+    frames, masks, positions, cells, values, radius = _fit_inputs(images, stars, psf, radius, mask, background, box, fit_background, cells,
+                                                                  device)
     finder = _Finder(frames[0].shape, box, device)
     model = None
     try:
@@ -996,6 +1035,107 @@ def fit_stars(images, stars, psf, radius: float, mask=None, *, background: str =
         for frame, m, p, c in zip(frames, masks, positions, cells):
             finder.background_device(frame, m)
             out.append(fit_from_sums(finder.fit(model, p, c, radius, bool(fit_background), background == "mesh"), bool(fit_background)))
+        return out
+    finally:
+        if model is not None:
+            model.close()
+        finder.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------- fitted positions
+FITPOS_FIELDS = ("row", "col", "row0", "col0", "niter", "flags", "converged", "step_row", "step_col", "ran_away", "not_converged", "singular",
+                 "skipped", *("fit_flags" if name == "flags" else name for name in FIT_FIELDS if name not in ("row", "col")))
+
+
+def fitpos_dtype() -> np.dtype:
+    """The structured dtype of ``fit_positions``: the iteration's fields (``niter`` and ``flags`` int32, ``converged`` and the four booleans
+    of the iteration's flags bool, the rest float64), then every field of ``fit_dtype`` but ``row`` and ``col``, ``fit_stars``' ``flags``
+    under the name ``fit_flags``."""
+    fit = fit_dtype()
+    kinds = {"niter": np.int32, "flags": np.int32, "converged": np.bool_, "ran_away": np.bool_, "not_converged": np.bool_, "singular": np.bool_,
+             "skipped": np.bool_, "fit_flags": fit["flags"], **{name: fit[name] for name in fit.names if name not in ("row", "col", "flags")}}
+    return np.dtype([(name, kinds.get(name, np.float64)) for name in FITPOS_FIELDS])
+
+
+def fitpos_from_sums(steps: np.ndarray, fits: np.ndarray, fit_background: bool = True) -> np.ndarray:
+    """The structured result (``fitpos_dtype``) of S9's iteration rows and S8's rows at the positions they end at: ``converged = flags == 0
+    and niter > 0``, one boolean per iteration flag, and ``fit_from_sums`` of the fit rows."""
+    steps = np.asarray(steps, np.float64).reshape(-1, len(FITPOS_COLUMNS))
+    col = {name: steps[:, j] for j, name in enumerate(FITPOS_COLUMNS)}
+    fit = fit_from_sums(fits, fit_background)
+    if len(fit) != len(steps):
+        msg = f"{len(fit)} fit rows for {len(steps)} iteration rows"
+        raise ValueError(msg)
+    out = np.empty(len(steps), fitpos_dtype())
+    for name in ("row", "col", "row0", "col0", "step_row", "step_col"):
+        out[name] = col[name]
+    out["niter"], out["flags"] = col["niter"].astype(np.int32), col["flags"].astype(np.int32)
+    out["converged"] = (out["flags"] == 0) & (out["niter"] > 0)
+    for name, bit in (("ran_away", FITPOS_RAN_AWAY), ("not_converged", FITPOS_NOT_CONVERGED), ("singular", FITPOS_SINGULAR),
+                      ("skipped", FITPOS_SKIPPED)):
+        out[name] = (out["flags"] & bit) != 0
+    for name in fit.dtype.names:
+        if name not in ("row", "col"):
+            out["fit_flags" if name == "flags" else name] = fit[name]
+    return out
+
+
+def fit_positions(images, stars, psf, radius: float, mask=None, *, background: str = "mesh", box: int = 64, fit_background: bool = True,
+                  cells=None, max_iter: int = 16, eps: float = 1e-4, max_shift: float = 2.0, max_step: float = 0.5,
+                  device: int = 0) -> list[np.ndarray]:
+    """Fit the position of every star with the cell of a PSF model it belongs to: a list of NumPy structured arrays (``fitpos_dtype``), one
+    per frame and one row per star, with the fields ``row, col`` (the fitted position), ``row0, col0`` (the input), ``niter, flags,
+    converged, step_row, step_col``, the booleans ``ran_away, not_converged, singular, skipped``, and then every field of ``fit_stars`` at
+    the fitted position (``cell, flux, background, ..., residual_fraction, ...``; ``fit_stars``' flags are ``fit_flags``).  ``build(...,
+    stars=fit_positions(...))``, ``star_photometry``, ``refine_stars`` and ``fit_stars`` take the result as it is.
+
+    ``images``, ``stars``, ``psf``, ``radius``, ``mask``, ``background``, ``box``, ``fit_background`` and ``cells`` are ``fit_stars``'.  The
+    cell of a star is chosen once, at the input position (``nearest_cells``), and stays for the whole iteration.  ``max_iter``: 0 ... 64; 0
+    fits at the given positions.  ``eps > 0``: the iteration has converged when a step ``(dy, dx)`` has ``dy^2 + dx^2 < eps^2``.
+    ``max_shift``: ``0 < max_shift <= 64``, the farthest a position may move from its start.  ``max_step``: ``0 < max_step <= 64``, the
+    bound on either component of one step.
+
+    One round at ``p = (row, col)``: over ``fit_stars``' pixels, with ``m`` the model and ``(g_u, g_v)`` the exact gradient of the bilinear
+    interpolant there, the normal equations of ``d ~ f m + bg + a_u g_u + a_v g_v`` (without ``fit_background``: no ``bg``) are summed and
+    solved by an LDL^T elimination without pivoting; the step is ``(-a_u / f, -a_v / f)``, each component clamped to ``max_step``.
+    ``SKIPPED`` (8): the star has ``fit_stars``' ``NO_MESH`` or ``BAD_CELL``, nothing iterates.  ``SINGULAR`` (4): fewer usable pixels than
+    unknowns, a pivot that is not finite or not positive (an all-zero, constant or NaN cell), or a step that is not finite; the star stays
+    where it is.  ``RAN_AWAY`` (1): the step would end farther than ``max_shift`` from the start; it is rejected.  Otherwise the step is
+    accepted; below ``eps`` the star has converged, after ``max_iter`` steps it is ``NOT_CONVERGED`` (2).  ``step_row, step_col`` are the
+    last step taken or rejected (NaN if none), ``niter`` the steps accepted, ``converged`` is ``flags == 0 and niter > 0``.  The fit fields
+    are kernel S8's at the position returned: ``fit_stars(frames, result, psf, radius, cells=[r["cell"] for r in result])`` gives the same
+    bits.
+
+    This is NOT a PSF-photometry package's fit: the weights are uniform - there is no error column and no variance weighting -, the
+    interpolation is bilinear (the gradient is piecewise constant along its own axis, so the fitted position carries the model's sampling),
+    the cell is fixed and not chosen again while the star moves, one star is fitted at a time - neighbours are not fitted together -, and
+    masked pixels are excluded and reported through ``coverage``, not corrected for.
+    """
+    if isinstance(max_iter, (bool, np.bool_)) or not isinstance(max_iter, (int, np.integer)):
+        msg = f"max_iter must be an integer, not {max_iter!r}"
+        raise TypeError(msg)
+    if not 0 <= max_iter <= MAX_ITER:
+        msg = f"max_iter must lie in 0 ... {MAX_ITER}, got {max_iter}"
+        raise ValueError(msg)
+    if not (float(eps) > 0.0 and np.isfinite(eps)):
+        msg = f"eps must be positive and finite, got {eps}"
+        raise ValueError(msg)
+    for name, value in (("max_shift", max_shift), ("max_step", max_step)):
+        if not 0.0 < float(value) <= MAX_RADIUS:
+            msg = f"{name} must lie in 0 < {name} <= {MAX_RADIUS:g}, got {value}"
+            raise ValueError(msg)
+    frames, masks, positions, cells, values, radius = _fit_inputs(images, stars, psf, radius, mask, background, box, fit_background, cells,
+                                                                  device)
+    finder = _Finder(frames[0].shape, box, device)
+    model = None
+    try:
+        model = _Model(values, device)
+        out = []
+        for frame, m, p, c in zip(frames, masks, positions, cells):
+            finder.background_device(frame, m)
+            steps, fits = finder.fit_positions(model, p, c, radius, bool(fit_background), int(max_iter), eps, max_shift, max_step,
+                                               background == "mesh")
+            out.append(fitpos_from_sums(steps, fits, bool(fit_background)))
         return out
     finally:
         if model is not None:
