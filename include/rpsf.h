@@ -457,7 +457,7 @@ int rpsf_psf_model_fft_device(int device, int model, int patch_size, int count, 
 /* ArrayPSFBuilder.build downstream of the star list (regularizepsf/builder.py:139-265): a builder owns a device stack of float32
  * N x N star patches (background-subtracted, not normalised), filled frame by frame and then averaged per lattice cell.  Star finding
  * (sep, image_processing.py:65-74) and the cell membership (builder.py:45-51) stay with the caller; the final per-cell clean-up
- * (builder.py:231-260) is the caller's after rpsf_builder_average and the device's with rpsf_builder_model.  N from 4 to 128, odd sizes included (anything else: RPSF_E_UNSUPPORTED); `capacity` patches are allocated at once, the
+ * (builder.py:231-260) is the caller's after rpsf_builder_average and the device's with rpsf_builder_model.  N from 4 to 128, odd sizes included (anything else: RPSF_E_UNSUPPORTED; 129 to 256: rpsf_builder_create_wide below); `capacity` patches are allocated at once, the
  * stack grows by itself beyond that.  INVARIANT: every patch of the stack is finite and has a non-zero centre pixel [N/2][N/2]. */
 typedef struct rpsf_builder rpsf_builder;
 int rpsf_builder_create(rpsf_builder** out, int device, int patch_size, size_t capacity);
@@ -527,6 +527,19 @@ int rpsf_builder_add_frame_scaled(rpsf_builder* builder, const void* image_host,
 /* downscale_local_mean (builder.py:234-235), kernel B4 alone: n_cells (> 0) cells of P x P float64 the caller supplies -> cells of
  * patch_size x patch_size, each pixel the sum of its scale x scale block in row-major order, in float64, divided by scale * scale. */
 int rpsf_builder_downscale(rpsf_builder* builder, int n_cells, const double* cells_f64_host, double* out_f64_host);
+
+/* The wide sizes, 129 <= patch_size <= 256 ("Wide sizes"): a builder whose patches and cells do not fit LDS as float64.
+ * null `out`: RPSF_E_BADARG; a patch_size outside 129..256: RPSF_E_UNSUPPORTED with the size in rpsf_last_error() - both before any HIP
+ * call.  rpsf_builder_create and rpsf_builder_create_scaled keep refusing these sizes.  The handle is an ordinary rpsf_builder: _add_frame,
+ * _add_frame_device, _load_patches, _patches, _count, _average, _clean, _model, _kernel_ms, _clean_ms and _destroy take it unchanged and
+ * give what they give at the other sizes (kernels B1w and B3w in the place of B1 and B3; B2 serves every size);
+ * rpsf_builder_add_frame_scaled and rpsf_builder_downscale refuse it (RPSF_E_UNSUPPORTED).  B1w and B3w work through a fixed number of
+ * slots of a workspace in device memory (at most 256 MiB: 256 slots, 255 at N = 256) that belongs to the handle: it is allocated by the first call
+ * that launches either kernel and freed by rpsf_builder_destroy. */
+int rpsf_builder_create_wide(rpsf_builder** out, int device, int patch_size, size_t capacity);
+/* The number of workspace slots of a wide builder: a launch of B1w or B3w is min(items, slots) workgroups, workgroup b takes items
+ * b, b + slots, ...  RPSF_E_UNSUPPORTED for a handle that is not wide. */
+int rpsf_builder_wide_slots(const rpsf_builder* builder, int* slots);
 
 /* find_stars: star positions for the builder, upstream of the star list.  The detector is this library's own, modelled on
  * sep.Background + sep.extract; it is not sep and its positions differ from sep's for blended or extended sources.  Deblending is an

@@ -151,6 +151,8 @@ _PROTOTYPES = {
     "rpsf_builder_add_frame_scaled": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double,
                                               c_double, c_void_p]),
     "rpsf_builder_downscale": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "rpsf_builder_create_wide": (c_int, [POINTER(c_void_p), c_int, c_int, c_size_t]),
+    "rpsf_builder_wide_slots": (c_int, [c_void_p, POINTER(c_int)]),
     "rpsf_stars_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int]),
     "rpsf_stars_destroy": (None, [c_void_p]),
     "rpsf_stars_background": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

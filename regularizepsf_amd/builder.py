@@ -9,6 +9,8 @@ calls per cell, or with ``ArrayPSFBuilder(..., cleanup="device")`` a third kerne
 background fit it flags as degenerate.  ``interpolation_scale`` (image_processing.py:49-59, builder.py:225-235) is opt-in with
 ``ArrayPSFBuilder(..., interpolation="device")``: every frame is upscaled on the device (``scale_image`` is the same resampling as a
 function of its own), the patches are cut at ``N * s`` pixels and every averaged cell is brought back to ``N x N`` by a block mean.
+``psf_size`` goes from 4 to 256: up to 128 the patch of a star lives in LDS, from 129 on in a workspace in device memory that the native
+handle owns (``rpsf_builder_create_wide``, DESIGN.md 3.6 "Wide sizes"); every route of ``build`` works at every size.
 
 The boundary of the feature is the star list: ``build(..., stars=[...])`` takes the ``(row, col)`` positions ``sep.extract``
 returns; without it ``sep`` is imported and called as the reference calls it - or, with ``ArrayPSFBuilder(..., finder="device")``,
@@ -37,7 +39,7 @@ FINDERS = ("sep", "device")
 FINDER_OPTIONS = {"box": 64, "min_area": 5, "max_area": None,
                   "deblend": False, "deblend_contrast": 0.005, "deblend_prominence": 1.0}  # find_stars's defaults
 REFINE_OPTIONS = {"refine_sigma": None}  # what finder_options takes besides: the window sigma of kernel S7 (stars.refine_stars), None = off
-MAX_PATCH = 128  # the largest patch the kernels cut: psf_size * interpolation_scale may not exceed it
+MAX_PATCH = 128  # the largest patch kernel B1 cuts: psf_size * interpolation_scale may not exceed it (psf_size alone goes to 256, B1w)
 
 
 def _frames(images) -> list[np.ndarray]:
@@ -330,7 +332,9 @@ class _Stack:
         self._native, self.psf_size, self.scale = _native, int(psf_size), int(scale)
         self.patch_size = self.psf_size * self.scale
         self._handle = ctypes.c_void_p()
-        if self.scale == 1:
+        if self.scale == 1 and self.psf_size > MAX_PATCH:  # the wide sizes, 129 ... 256 (anything above: the library's refusal)
+            _native.check(_native.lib().rpsf_builder_create_wide(ctypes.byref(self._handle), device, self.psf_size, max(1, int(capacity))))
+        elif self.scale == 1:
             _native.check(_native.lib().rpsf_builder_create(ctypes.byref(self._handle), device, self.psf_size, max(1, int(capacity))))
         else:
             _native.check(_native.lib().rpsf_builder_create_scaled(ctypes.byref(self._handle), device, self.psf_size, self.scale,

@@ -8,6 +8,11 @@
 //   B3  builder_clean_kernel    one workgroup per averaged cell, the driver of rpsf_core_cleanup.hpp: the cell's values in registers,
 //                               byte masks and union-find parents in LDS (N = 128: 96 KiB); writes the cleaned float64 cell and one
 //                               flag byte.
+//   B1w builder_patch_wide_kernel, B3w builder_clean_wide_kernel: B1 and B3 at the wide sizes 129 <= N <= 256 (a handle of
+//                               rpsf_builder_create_wide), the drivers of rpsf_core_builder_wide.hpp and rpsf_core_cleanup_wide.hpp.  A
+//                               float64 patch of that size does not fit LDS: a launch is min(items, slots) workgroups of 1024 threads,
+//                               workgroup b works on items b, b + slots, ... in its own slot of a workspace in global memory that
+//                               belongs to the handle.  B2 and the append kernel are size-generic and serve both.
 //   rpsf_builder_add_frame_device runs B1 on a dense float32 frame that is already on the device (a finder's, DESIGN.md 3.11, or the caller's).
 //   A scaled builder (rpsf_builder_create_scaled, interpolation_scale = s of the reference) runs B1 and B2 at P = N s on frames that
 //   csrc/scale.hip upscales on the device, brings every averaged P x P cell back to N x N with its kernel B4, and runs B3 at N.
@@ -27,7 +32,9 @@
 #include <vector>
 
 #include "rpsf_core_builder.hpp"
+#include "rpsf_core_builder_wide.hpp"
 #include "rpsf_core_cleanup.hpp"
+#include "rpsf_core_cleanup_wide.hpp"
 #include "rpsf_scale.hpp"
 #include "rpsf_side_unit.hpp"
 
@@ -71,6 +78,24 @@ __global__ __launch_bounds__(THREADS) void builder_patch_kernel(B1Params q) {
   if (tid == 0) q.flags[star] = b1_verdict(N, q.star_minimum, q.star_maximum, s);
 }
 
+// B1w: workgroup b owns slot b of `workspace` (rpsfbw::slot_doubles(N) doubles each) and takes stars b, b + gridDim.x, ...
+__global__ __launch_bounds__(rpsfbw::THREADS) void builder_patch_wide_kernel(B1Params q, int n_stars, double* workspace) {
+  extern __shared__ double builder_lds[];
+  const int N = q.N;
+  const rpsfbw::Wide w = rpsfbw::carve(builder_lds, workspace + (size_t)blockIdx.x * rpsfbw::slot_doubles(N), N);
+  const auto each = [](auto&& f) {
+    f((int)threadIdx.x);
+    __syncthreads();
+  };
+  for (int star = blockIdx.x; star < n_stars; star += gridDim.x) {
+    const uint8_t verdict = rpsfbw::b1w_star(each, N, q.image, q.height, q.width, q.corners[2 * star], q.corners[2 * star + 1],
+                                             q.frac[2 * star], q.frac[2 * star + 1], q.saturation, q.star_minimum, q.star_maximum, w,
+                                             q.staging + (size_t)star * N * N);
+    if (threadIdx.x == 0) q.flags[star] = verdict;
+    __syncthreads();  // the verdict reads the flags and the centre: the next star's first phase writes them
+  }
+}
+
 // accepted patch i of the frame: staging slot source[i] -> stack slot first + i
 __global__ __launch_bounds__(256) void builder_append_kernel(const float* staging, const int32_t* source, float* stack, int npix) {
   const float* from = staging + (size_t)source[blockIdx.x] * npix;
@@ -106,10 +131,33 @@ __global__ __launch_bounds__(THREADS) void builder_clean_kernel(int N, const dou
   rpsfc::clean_cell(ctx, N, THREADS, cells + at, cleaned + at, flags + blockIdx.x, builder_lds);
 }
 
+namespace {
+struct CleanWideCtx {
+  template <class F>
+  __device__ __forceinline__ void each(F&& f) {
+    f((int)threadIdx.x);
+    __syncthreads();
+  }
+};
+}  // namespace
+
+// B3w: workgroup b owns slot b of `workspace` (rpsfcw::slot_bytes(N) bytes each) and takes cells b, b + gridDim.x, ...
+__global__ __launch_bounds__(rpsfcw::THREADS) void builder_clean_wide_kernel(int N, int n_cells, const double* cells, double* cleaned,
+                                                                             uint8_t* flags, char* workspace) {
+  extern __shared__ double builder_lds[];
+  CleanWideCtx ctx;
+  for (int cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
+    const size_t at = (size_t)cell * N * N;
+    rpsfcw::clean_cell_wide(ctx, N, cells + at, cleaned + at, flags + cell, builder_lds, workspace + (size_t)blockIdx.x * rpsfcw::slot_bytes(N));
+  }
+}
+
 struct rpsf_builder {
   int device = 0, N = 0;  // N: the size of the patches in the stack (B1, B2)
   int model = 0, scale = 1;  // model: the size of a cell of the model (B3); N = model * scale
   rpsf_scale_scratch* upscale = nullptr;
+  bool wide = false;  // a handle of rpsf_builder_create_wide: N above MAX_N, B1w and B3w
+  Buf<double> workspace;  // wide: the slots of B1w, which those of B3w fit into; allocated by the first launch that needs it
   Buf<double> small;  // scaled builder: the averaged cells after B4, model x model
   size_t count = 0;
   float* stack = nullptr;
@@ -201,6 +249,42 @@ extern "C" int rpsf_builder_create_scaled(rpsf_builder** out, int device, int pa
   return create(out, device, patch_size, scale, capacity);
 }
 
+extern "C" int rpsf_builder_create_wide(rpsf_builder** out, int device, int patch_size, size_t capacity) {
+  if (!out) return fail(RPSF_E_BADARG, "null argument");
+  if (patch_size < rpsfbw::MIN_N || patch_size > rpsfbw::MAX_N)
+    return fail(RPSF_E_UNSUPPORTED, "wide builder patch size " + std::to_string(patch_size) + " is outside 129..256");
+  HIP_TRY(hipSetDevice(device));
+  rpsf_builder* b = new rpsf_builder;
+  b->device = device, b->N = patch_size, b->model = patch_size, b->scale = 1, b->wide = true;
+  auto made = [&]() -> int {
+    for (auto& e : b->ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&builder_clean_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)rpsfcw::lds_bytes(rpsfcw::MAX_N)));
+    return grow_stack(b, capacity ? capacity : 1);
+  }();
+  if (made != RPSF_OK) {
+    delete b;
+    return made;
+  }
+  *out = b;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_builder_wide_slots(const rpsf_builder* b, int* slots) {
+  if (!b || !slots) return fail(RPSF_E_BADARG, "null argument");
+  if (!b->wide) return fail(RPSF_E_UNSUPPORTED, "not a wide builder");
+  *slots = rpsfbw::slots_for(b->N);
+  return RPSF_OK;
+}
+
+// the workspace of a wide handle: slots_for(N) slots of B1w (at most 256 MiB), each of which is large enough for a slot of B3w
+static int wide_workspace(rpsf_builder* b) {
+  // (a slot of B1w is 16 N (N | 1) bytes, one of B3w 4 N^2 + 44160: the first is the larger from N = 61 on)
+  if (rpsfcw::slot_bytes(b->N) > rpsfbw::slot_doubles(b->N) * sizeof(double)) return fail(RPSF_E_STATE, "wide workspace slots");
+  HIP_TRY(b->workspace.reserve((size_t)rpsfbw::slots_for(b->N) * rpsfbw::slot_doubles(b->N)));
+  return RPSF_OK;
+}
+
 extern "C" void rpsf_builder_destroy(rpsf_builder* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
@@ -246,6 +330,7 @@ extern "C" int rpsf_builder_add_frame_scaled(rpsf_builder* b, const void* image_
                                              double saturation_threshold, double star_minimum, double star_maximum,
                                              uint8_t* accepted_u8_host) {
   if (!b || !image_host) return fail(RPSF_E_BADARG, "null argument");
+  if (b->wide) return fail(RPSF_E_UNSUPPORTED, "a wide builder takes no scaled frames");
   if (scale != b->scale) return fail(RPSF_E_BADARG, "scale " + std::to_string(scale) + " is not the builder's " + std::to_string(b->scale));
   if (scale == 1)
     return rpsf_builder_add_frame(b, image_host, image_is_f64, height, width, n_stars, corners_i32, frac_f64, saturation_threshold,
@@ -295,8 +380,14 @@ static int patches_of_frame(rpsf_builder* b, const float* frame_dev, int height,
   HIP_TRY(hipMemcpy(b->frac.p, frac_f64, 2 * (size_t)n_stars * sizeof(double), hipMemcpyHostToDevice));
   const B1Params q{frame_dev, height, width, N, b->corners.p, b->frac.p, saturation_threshold, star_minimum, star_maximum,
                    b->staging.p, b->flags.p};
+  if (b->wide)
+    if (const int rc = wide_workspace(b)) return rc;
   HIP_TRY(hipEventRecord(b->ev[0], nullptr));
-  if (N > 64) {
+  if (b->wide) {
+    const int grid = n_stars < rpsfbw::slots_for(N) ? n_stars : rpsfbw::slots_for(N);
+    hipLaunchKernelGGL(builder_patch_wide_kernel, dim3(grid), dim3(rpsfbw::THREADS), rpsfbw::lds_bytes(N), nullptr, q, n_stars,
+                       b->workspace.p);
+  } else if (N > 64) {
     hipLaunchKernelGGL(builder_patch_kernel<1024>, dim3(n_stars), dim3(1024), lds_bytes(N), nullptr, q);
   } else {
     hipLaunchKernelGGL(builder_patch_kernel<256>, dim3(n_stars), dim3(256), lds_bytes(N), nullptr, q);
@@ -393,6 +484,7 @@ static double* model_cells(rpsf_builder* b) { return b->scale > 1 ? b->small.p :
 extern "C" int rpsf_builder_downscale(rpsf_builder* b, int n_cells, const double* cells_f64_host, double* out_f64_host) {
   if (!b || !cells_f64_host || !out_f64_host) return fail(RPSF_E_BADARG, "null argument");
   if (n_cells <= 0) return fail(RPSF_E_BADARG, "n_cells must be positive");
+  if (b->wide) return fail(RPSF_E_UNSUPPORTED, "a wide builder has no scaled cells to bring down");
   const size_t big = (size_t)n_cells * b->N * b->N, little = (size_t)n_cells * b->model * b->model;
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(b->cells.reserve(big));
@@ -418,8 +510,14 @@ static int clean_on_device(rpsf_builder* b, int n_cells, double* out_f64_host, u
   const double* cells = model_cells(b);
   HIP_TRY(b->cleaned.reserve((size_t)n_cells * npix));
   HIP_TRY(b->clean_flags.reserve((size_t)n_cells));
+  if (b->wide)
+    if (const int rc = wide_workspace(b)) return rc;
   HIP_TRY(hipEventRecord(b->ev[0], nullptr));
-  if (N > 64) {
+  if (b->wide) {
+    const int grid = n_cells < rpsfcw::slots_for(N) ? n_cells : rpsfcw::slots_for(N);
+    hipLaunchKernelGGL(builder_clean_wide_kernel, dim3(grid), dim3(rpsfcw::THREADS), rpsfcw::lds_bytes(N), nullptr, N, n_cells, cells,
+                       b->cleaned.p, b->clean_flags.p, reinterpret_cast<char*>(b->workspace.p));
+  } else if (N > 64) {
     hipLaunchKernelGGL(builder_clean_kernel<1024>, dim3(n_cells), dim3(1024), rpsfc::lds_bytes(N), nullptr, N, cells, b->cleaned.p,
                        b->clean_flags.p);
   } else {
