@@ -792,6 +792,42 @@ int rpsf_stars_fit_positions(rpsf_stars* finder, const rpsf_stars_model* model, 
 /* Device time of the last S9 and the S8 that follows it, milliseconds; 0 when it launched nothing. */
 int rpsf_stars_fit_positions_ms(const rpsf_stars* finder, double* ms);
 
+/* MODEL AND RESIDUAL FRAMES (kernel S10): the sum of n fitted stars drawn with their cells of a rpsf_stars_model, or the
+ * finder's frame with that sum taken out.  positions_host holds (y, x) per star (finite, |y|, |x| < 2^20), flux_host one float64 flux and
+ * cells_host one int32 cell index per star; 0 < radius = R <= min(64, N / 2 - 1); the model on the finder's device; anything else is
+ * RPSF_E_BADARG, before anything is launched or written.  Star i is DRAWN when flux_i is finite and 0 <= cell_i < n_cells; every other
+ * star is skipped (so rpsf_stars_fit's flagged rows, whose flux is NaN, drop out by themselves), and *n_rendered (may be NULL) is the
+ * number of stars drawn, on the frame or off it.
+ * THE SUM at pixel (r, c) of the frame: s = 0.0; for i ascending over the stars drawn: pr = r - y_i, pc = c - x_i, q = pr pr + pc pc; when
+ * q <= R R: s = s + flux_i * m, with m rpsf_stars_fit's model at (pr, pc) of cell_i (h = N / 2 - 0.5, the same float64 operations in
+ * the same order, nothing fused).  mode:
+ *   RPSF_STARS_RENDER_MODEL (0)          out = s; the frame is not read, no state is needed beyond the finder's shape;
+ *   RPSF_STARS_RENDER_RESIDUAL (1)       out = (double)frame[p] - s;
+ *   RPSF_STARS_RENDER_RESIDUAL_MESH (2)  out = ((double)frame[p] - background(r, c)) - s, the d that rpsf_stars_fit fitted with use_mesh.
+ * The two residual modes read the frame, and mode 2 the filtered mesh, a rpsf_stars_background_view / _host / _scaled left on the device:
+ * RPSF_E_STATE before such a call, and for mode 2 on a frame without a usable pixel (rpsf_stars_fit's NO_MESH); nothing is written then.
+ * Masks play no part but through the mesh; NaN and Inf propagate as the arithmetic says; in mode 1 a pixel that no star reaches comes back
+ * as its own bits, in mode 0 it is + 0.0.  out takes height x width elements in dense rows, float32 (s or the difference rounded once from
+ * float64) or with out_float64 float64; it is host memory, or with out_on_device a pointer on the finder's device that the kernel writes
+ * directly.  n == 0 is valid and needs no star pointers: mode 0 gives zeros, mode 1 the frame.
+ * One workgroup owns a tile of RENDER tile rows x tile columns output pixels (rpsf_stars_render_info), one pixel per thread.  The host
+ * builds a list per tile: star i is on it when the box floor(y - R) - 1 .. ceil(y + R) + 1 (likewise in x), clipped to the frame, meets
+ * the tile; indices ascend within a list.  The kernel stages a list into LDS `chunk` records at a time, so no tile has a cap on its stars.
+ * A gather: no atomics, no workgroup waits for another, two runs agree bit for bit.  This is not a PSF-photometry package's subtraction:
+ * the interpolation is bilinear and does not conserve flux below the pixel scale, the disc cuts the model at R, and a per-star fitted
+ * background is not subtracted.  The call replaces nothing of the finder: a rpsf_stars_positions, rpsf_stars_measure,
+ * rpsf_stars_photometry, rpsf_stars_refine, rpsf_stars_fit or rpsf_stars_fit_positions after it gives the bits it gave before. */
+#define RPSF_STARS_RENDER_MODEL 0
+#define RPSF_STARS_RENDER_RESIDUAL 1
+#define RPSF_STARS_RENDER_RESIDUAL_MESH 2
+int rpsf_stars_render(rpsf_stars* finder, const rpsf_stars_model* model, size_t n, const double* positions_host, const double* flux_host,
+                      const int32_t* cells_host, double radius, int mode, int out_float64, int out_on_device, void* out,
+                      size_t* n_rendered);
+/* Device time of the last S10, milliseconds. */
+int rpsf_stars_render_ms(const rpsf_stars* finder, double* ms);
+/* S10's tile (rows, columns) and the records of a chunk; any pointer may be NULL. */
+int rpsf_stars_render_info(int* tile_rows, int* tile_cols, int* chunk);
+
 /* rpsf_builder_add_frame on a dense float32 frame that is already on the builder's device - a finder's (rpsf_stars_frame) or the caller's
  * own; it is only read, nothing is uploaded but the star list.  On a scaled builder the frame is the SCALED one and height and width are
  * its. */
@@ -808,6 +844,9 @@ int rpsf_dev_alloc(int device, size_t bytes, void** out);
 int rpsf_dev_free(int device, void* ptr);
 int rpsf_memcpy_h2d(int device, void* dst_dev, const void* src_host, size_t bytes);
 int rpsf_memcpy_d2h(int device, void* dst_host, const void* src_dev, size_t bytes);
+/* A plain copy between two buffers of one device, finished on return; *ms (may be NULL) takes its device time in milliseconds - the
+ * yardstick the timing scripts put a frame-sized kernel next to. */
+int rpsf_memcpy_d2d(int device, void* dst_dev, const void* src_dev, size_t bytes, double* ms);
 int rpsf_device_synchronize(int device);
 
 /* Multi-GPU row-band sharding (one process per GPU).  The caller splits the patch lattice into

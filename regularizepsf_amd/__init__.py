@@ -27,7 +27,8 @@ from regularizepsf_amd._native import pinned_empty
 from regularizepsf_amd.builder import ArrayPSFBuilder, scale_image
 from regularizepsf_amd.device_array import DeviceArray, device_empty, to_device
 from regularizepsf_amd.psf import ArrayPSF
-from regularizepsf_amd.stars import cell_fit_summary, find_stars, fit_positions, fit_stars, refine_stars, star_catalog, star_photometry
+from regularizepsf_amd.stars import (cell_fit_summary, find_stars, fit_positions, fit_stars, refine_stars, render_stars, star_catalog,
+                                     star_photometry, subtract_stars)
 from regularizepsf_amd.transform import ArrayPSFTransform
 from regularizepsf_amd.util import IndexedCube, calculate_covering
 
@@ -58,10 +59,12 @@ __all__ = [
     "moffat",
     "pinned_empty",
     "refine_stars",
+    "render_stars",
     "scale_image",
     "simple_functional_psf",
     "star_catalog",
     "star_photometry",
+    "subtract_stars",
     "to_device",
     "varied_functional_psf",
 ]

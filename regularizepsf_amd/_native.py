@@ -187,6 +187,10 @@ _PROTOTYPES = {
     "rpsf_stars_fit_positions": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_double, c_int, c_int, c_double, c_double,
                                          c_double, c_int, c_void_p, c_void_p]),
     "rpsf_stars_fit_positions_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rpsf_stars_render": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, c_int, c_void_p,
+                                  POINTER(c_size_t)]),
+    "rpsf_stars_render_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rpsf_stars_render_info": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "rpsf_builder_add_frame_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double, c_double,
                                               c_void_p]),
     "rpsf_saturation_fill": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
@@ -194,6 +198,7 @@ _PROTOTYPES = {
     "rpsf_dev_free": (c_int, [c_int, c_void_p]),
     "rpsf_memcpy_h2d": (c_int, [c_int, c_void_p, c_void_p, c_size_t]),
     "rpsf_memcpy_d2h": (c_int, [c_int, c_void_p, c_void_p, c_size_t]),
+    "rpsf_memcpy_d2d": (c_int, [c_int, c_void_p, c_void_p, c_size_t, POINTER(c_double)]),
     "rpsf_device_synchronize": (c_int, [c_int]),
     "rpsf_comm_unique_id": (c_int, [c_void_p]),
     "rpsf_comm_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_void_p]),

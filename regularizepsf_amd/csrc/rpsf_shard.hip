@@ -38,6 +38,27 @@ extern "C" int rpsf_memcpy_d2h(int device, void* dst, const void* src, size_t by
   HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
   return RPSF_OK;
 }
+extern "C" int rpsf_memcpy_d2d(int device, void* dst, const void* src, size_t bytes, double* ms) {
+  HIP_TRY(hipSetDevice(device));
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  if (ms) {
+    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(ev[0], nullptr));
+  }
+  const hipError_t copied = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, nullptr);
+  if (ms && copied == hipSuccess) {
+    float t = 0;
+    HIP_TRY(hipEventRecord(ev[1], nullptr));
+    HIP_TRY(hipEventSynchronize(ev[1]));
+    HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
+    *ms = t;
+  }
+  for (auto e : ev)
+    if (e) (void)hipEventDestroy(e);
+  HIP_TRY(copied);
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return RPSF_OK;
+}
 extern "C" int rpsf_device_synchronize(int device) {
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipDeviceSynchronize());

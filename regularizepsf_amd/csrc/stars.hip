@@ -35,6 +35,10 @@
 //                              rpsf_core_stars_fitpos.hpp), then stars_fit_kernel at the positions it ends at; both write rows of
 //                              their own and nothing the other kernels read
 //
+//   S10 stars_render_kernel    rpsf_stars_render, and only then: one workgroup per tile of output pixels, the fitted stars on the tile's
+//                              list drawn with their cells of the model in ascending star index, a gather (the driver of
+//                              rpsf_core_stars_render.hpp); it writes the output frame and nothing the other kernels read
+//
 // The phases are the drivers of rpsf_core_stars.hpp.  Launches follow one another on the null stream; no workgroup ever waits for
 // another one, and the only atomics are integer min / max / add - labels and moments are the same on every run.
 #include <hip/hip_runtime.h>
@@ -52,6 +56,7 @@
 #include "rpsf_core_stars_mesh.hpp"
 #include "rpsf_core_stars_photometry.hpp"
 #include "rpsf_core_stars_refine.hpp"
+#include "rpsf_core_stars_render.hpp"
 #include "rpsf_core_stars_shape.hpp"
 #include "rpsf_scale.hpp"
 #include "rpsf_side_unit.hpp"
@@ -73,6 +78,10 @@ static_assert(rpsfg::POS_RAN_AWAY == RPSF_STARS_FITPOS_RAN_AWAY && rpsfg::POS_NO
                   rpsfg::POS_SINGULAR == RPSF_STARS_FITPOS_SINGULAR && rpsfg::POS_SKIPPED == RPSF_STARS_FITPOS_SKIPPED,
               "the iteration flags of rpsf_core_stars_fitpos.hpp and include/rpsf.h");
 static_assert(rpsfg::s9_lds_bytes() <= 64 * 1024 && rpsfg::s9_lds_bytes() % 16 == 0, "S9's records fit the LDS a launch gets without asking");
+
+static_assert(rpsfn::MODE_MODEL == RPSF_STARS_RENDER_MODEL && rpsfn::MODE_RESIDUAL == RPSF_STARS_RENDER_RESIDUAL &&
+                  rpsfn::MODE_RESIDUAL_MESH == RPSF_STARS_RENDER_RESIDUAL_MESH,
+              "the render modes of rpsf_core_stars_render.hpp and include/rpsf.h");
 
 extern __shared__ __attribute__((aligned(16))) char stars_lds[];
 
@@ -179,6 +188,17 @@ __global__ __launch_bounds__(WALK_THREADS) void stars_fitpos_kernel(Frame fr, co
   rpsfg::s9_fit_positions(ctx, fr, L, none, use_mesh, model, fit, fp, pos, cell, count, (long)blockIdx.x * WALK_WAVES, stars_lds, out, final_pos);
 }
 
+// S10's context: the accumulator of a thread's pixel is a register of that thread
+struct RenderCtx : GpuCtx {
+  double s;
+  __device__ __forceinline__ double& reg(int) { return s; }
+};
+__global__ __launch_bounds__(WALK_THREADS) void stars_render_kernel(Frame fr, const double* L, rpsff::Model model, rpsfn::Render rd,
+                                                                    rpsfn::Stars st, void* out) {
+  RenderCtx ctx;
+  rpsfn::s10_render(ctx, fr, L, model, rd, st, (int)blockIdx.y, (int)blockIdx.x, stars_lds, out);
+}
+
 // ------------------------------------------------------------------------------------------------ the deblend option
 // S2 that also stores the filtered residual; T from device memory when T_dev is given
 __global__ __launch_bounds__(TILE_THREADS) void stars_detect_f_kernel(Frame fr, const double* L, const double* T_dev, double T, uint8_t* det,
@@ -263,6 +283,11 @@ struct rpsf_stars {
   Buf<double> fitpos_pos, fitpos_final, fitpos_iter, fitpos_fit;
   Buf<int> fitpos_cell;
   double fitpos_ms = 0;
+  // S10 (rpsf_stars_render): likewise its own - the star records, the tile lists and the frame a host caller gets
+  Buf<double> render_pos, render_flux, render_out;
+  Buf<int> render_cell, render_index;
+  Buf<long long> render_offsets;
+  double render_ms = 0;
   // the deblend option: everything below is allocated by the first call that needs it
   bool deblend = false;
   double contrast = 0.005, prominence = 1.0;
@@ -846,6 +871,74 @@ extern "C" int rpsf_stars_fit_positions(rpsf_stars* s, const rpsf_stars_model* m
 extern "C" int rpsf_stars_fit_positions_ms(const rpsf_stars* s, double* ms) {
   if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
   *ms = s->fitpos_ms;
+  return RPSF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ S10 (Model and residual frames)
+extern "C" int rpsf_stars_render(rpsf_stars* s, const rpsf_stars_model* model, size_t n, const double* positions_host, const double* flux_host,
+                                 const int32_t* cells_host, double radius, int mode, int out_float64, int out_on_device, void* out,
+                                 size_t* n_rendered) {
+  if (!s || !model || !out || (n && (!positions_host || !flux_host || !cells_host))) return fail(RPSF_E_BADARG, "null argument");
+  if (const char* why = rpsfn::render_problem(radius, mode)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_render: ") + why);
+  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_render: more than 2^30 stars in one call");
+  for (size_t i = 0; i < n; ++i)
+    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
+      return fail(RPSF_E_BADARG, "rpsf_stars_render: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
+  if (!(radius <= rpsff::max_fit_radius(model->N)))
+    return fail(RPSF_E_BADARG, "rpsf_stars_render: radius " + std::to_string(radius) + " is above min(64, N / 2 - 1) of the model's N = " +
+                                   std::to_string(model->N));
+  if (model->device != s->device) return fail(RPSF_E_BADARG, "rpsf_stars_render: the model is on another device than the finder");
+  if (mode != rpsfn::MODE_MODEL && !s->have_mesh)
+    return fail(RPSF_E_STATE, "rpsf_stars_render of a residual before a rpsf_stars_background_view / _host / _scaled of the frame");
+  HIP_TRY(hipSetDevice(s->device));
+  if (mode == rpsfn::MODE_RESIDUAL_MESH) {
+    int none = 0;
+    HIP_TRY(hipMemcpy(&none, s->none.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (none) return fail(RPSF_E_STATE, "rpsf_stars_render: the frame has no usable pixel, so there is no mesh to subtract");
+  }
+  s->render_ms = 0;
+  std::vector<long long> offsets;
+  std::vector<int> index;
+  const size_t drawn = rpsfn::tile_lists(s->H, s->W, n, positions_host, flux_host, cells_host, model->n_cells, radius, offsets, index);
+  const size_t npix = (size_t)s->npix(), item = out_float64 ? sizeof(double) : sizeof(float);
+  HIP_TRY(s->render_pos.reserve(2 * n));
+  HIP_TRY(s->render_flux.reserve(n));
+  HIP_TRY(s->render_cell.reserve(n));
+  HIP_TRY(s->render_offsets.reserve(offsets.size()));
+  HIP_TRY(s->render_index.reserve(index.size()));
+  if (!out_on_device) HIP_TRY(s->render_out.reserve(npix));
+  if (n) {
+    HIP_TRY(hipMemcpy(s->render_pos.p, positions_host, 2 * n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->render_flux.p, flux_host, n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->render_cell.p, cells_host, n * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemcpy(s->render_offsets.p, offsets.data(), offsets.size() * sizeof(long long), hipMemcpyHostToDevice));
+  if (!index.empty()) HIP_TRY(hipMemcpy(s->render_index.p, index.data(), index.size() * sizeof(int), hipMemcpyHostToDevice));
+  const rpsff::Model cube{model->values.p, model->n_cells, model->N};
+  const rpsfn::Render rd = rpsfn::make_render(radius, mode, out_float64, model->N);
+  const rpsfn::Stars st{s->render_pos.p, s->render_flux.p, s->render_cell.p, s->render_offsets.p, s->render_index.p};
+  void* out_dev = out_on_device ? out : static_cast<void*>(s->render_out.p);
+  if (const int rc = timed(s, &s->render_ms, [&] {
+        const dim3 grid((unsigned)rpsfn::tiles_across(s->W), (unsigned)rpsfn::tiles_down(s->H));
+        hipLaunchKernelGGL(stars_render_kernel, grid, dim3(WALK_THREADS), rpsfn::s10_lds_bytes(), nullptr, s->view(), s->level_f.p, cube, rd, st,
+                           out_dev);
+      }))
+    return rc;
+  if (!out_on_device) HIP_TRY(hipMemcpy(out, out_dev, npix * item, hipMemcpyDeviceToHost));
+  if (n_rendered) *n_rendered = drawn;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_render_ms(const rpsf_stars* s, double* ms) {
+  if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
+  *ms = s->render_ms;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_render_info(int* tile_rows, int* tile_cols, int* chunk) {
+  if (tile_rows) *tile_rows = rpsfn::RENDER_TILE_R;
+  if (tile_cols) *tile_cols = rpsfn::RENDER_TILE_C;
+  if (chunk) *chunk = rpsfn::RENDER_CHUNK;
   return RPSF_OK;
 }
 

@@ -48,6 +48,11 @@ exact gradient of the bilinearly interpolated cell (kernel S9, ``rpsf_stars_fit_
 ``fit_stars``' own row at the position it ends at.  It is the other half of the effective-PSF loop: build a model, fit positions with it,
 rebuild at the fitted positions.  It shares ``fit_stars``' limits - uniform weights, no error column, bilinear interpolation, masked
 pixels excluded and not corrected for - and adds its own: the cell is fixed at the input position and one star is fitted at a time.
+
+``subtract_stars`` draws the fitted stars with their cells of the model and takes them out of the frame, and ``render_stars`` draws them
+on an empty frame (kernel S10, ``rpsf_stars_render``; DESIGN.md 3.7 "Model and residual frames").  The kernel gathers: a workgroup owns a
+tile of output pixels and every pixel adds its stars in ascending star index, so the bits do not depend on scheduling.  The model is cut
+at the radius ``R``, interpolated bilinearly, and the per-star fitted constant is not subtracted.
 """
 
 from __future__ import annotations
@@ -82,6 +87,8 @@ MIN_MODEL, MAX_MODEL = 4, 256
 # an iteration row of kernel S9 (RPSF_STARS_FITPOS_COLUMNS float64) and its flags
 FITPOS_COLUMNS = ("row0", "col0", "row", "col", "niter", "flags", "step_row", "step_col")
 FITPOS_RAN_AWAY, FITPOS_NOT_CONVERGED, FITPOS_SINGULAR, FITPOS_SKIPPED = 1, 2, 4, 8
+# the modes of kernel S10 (RPSF_STARS_RENDER_* of include/rpsf.h)
+RENDER_MODEL, RENDER_RESIDUAL, RENDER_RESIDUAL_MESH = 0, 1, 2
 DEBLEND_OPTIONS = {"deblend": False, "deblend_contrast": 0.005, "deblend_prominence": 1.0}  # contrast: sep's deblend_cont
 
 
@@ -106,7 +113,7 @@ class _Finder:
     def __init__(self, shape: tuple[int, int], box: int, device: int = 0) -> None:
         from regularizepsf_amd import _native
 
-        self._native, self.shape, self.box = _native, (int(shape[0]), int(shape[1])), int(box)
+        self._native, self.shape, self.box, self.device = _native, (int(shape[0]), int(shape[1])), int(box), int(device)
         self.mesh_shape = (-(-self.shape[0] // self.box), -(-self.shape[1] // self.box))
         self._handle = ctypes.c_void_p()
         _native.check(_native.lib().rpsf_stars_create(ctypes.byref(self._handle), device, self.shape[0], self.shape[1], self.box))
@@ -299,6 +306,43 @@ class _Finder:
         """Device time of the last S9 with the S8 behind it; 0.0 when it launched nothing."""
         ms = ctypes.c_double(0)
         self._native.check(self._native.lib().rpsf_stars_fit_positions_ms(self._handle, ctypes.byref(ms)))
+        return ms.value
+
+    def render(self, model, positions: np.ndarray, flux, cells, radius: float, mode: int = RENDER_RESIDUAL, dtype=np.float32,
+               out=None) -> tuple:
+        """Kernel S10: the stars at ``positions`` ((k, 2) of (row, col)) drawn with ``flux`` ((k,) float64) and their cells of ``model``.
+        ``mode``: ``RENDER_MODEL`` (the sum alone; nothing of the frame is read), ``RENDER_RESIDUAL`` (the frame given to
+        ``background_device`` / ``background_scaled`` last, minus the sum) or ``RENDER_RESIDUAL_MESH`` (the frame minus its mesh, minus
+        the sum).  ``out``: None for a host array of the finder's shape and ``dtype`` (float32 or float64), or a C-contiguous
+        ``DeviceArray`` of that shape and dtype on the finder's device, which the kernel writes and which is returned.  ``(frame, the
+        number of stars drawn)``.  Nothing of the finder is replaced."""
+        n = self._native
+        positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 2)
+        flux = np.ascontiguousarray(flux, np.float64).ravel()
+        cells = np.ascontiguousarray(cells, np.int32).ravel()
+        if len(cells) != len(positions) or len(flux) != len(positions):
+            msg = f"{len(flux)} fluxes and {len(cells)} cells for {len(positions)} positions"
+            raise ValueError(msg)
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            msg = f"dtype must be float32 or float64, not {dtype}"
+            raise TypeError(msg)
+        if out is None:
+            result = np.empty(self.shape, dtype)
+            target, on_device = n._ptr(result), 0
+        else:
+            _check_render_out(out, self.shape, dtype)
+            out.synchronize()  # the finder's launches are on the null stream
+            result, target, on_device = out, ctypes.c_void_p(out.ptr), 1
+        drawn = ctypes.c_size_t(0)
+        n.check(n.lib().rpsf_stars_render(self._handle, model._handle, len(positions), n._ptr(positions), n._ptr(flux), n._ptr(cells),
+                                          float(radius), int(mode), int(dtype == np.float64), on_device, target, ctypes.byref(drawn)))
+        return result, drawn.value
+
+    def render_ms(self) -> float:
+        """Device time of the last S10."""
+        ms = ctypes.c_double(0)
+        self._native.check(self._native.lib().rpsf_stars_render_ms(self._handle, ctypes.byref(ms)))
         return ms.value
 
     def deblend_info(self) -> tuple[int, int, int]:
@@ -1137,6 +1181,200 @@ def fit_positions(images, stars, psf, radius: float, mask=None, *, background: s
                                                background == "mesh")
             out.append(fitpos_from_sums(steps, fits, bool(fit_background)))
         return out
+    finally:
+        if model is not None:
+            model.close()
+        finder.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------- model and residual frames
+def render_info() -> tuple[int, int, int]:
+    """Kernel S10's tile (rows, columns) and the number of star records it stages at a time."""
+    from regularizepsf_amd import _native
+
+    rows, cols, chunk = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    _native.check(_native.lib().rpsf_stars_render_info(ctypes.byref(rows), ctypes.byref(cols), ctypes.byref(chunk)))
+    return rows.value, cols.value, chunk.value
+
+
+def _check_render_out(out, shape: tuple[int, int], dtype: np.dtype, device: int | None = None) -> None:
+    """``out=`` of one frame: a C-contiguous ``DeviceArray`` of the frame's shape and of ``dtype`` (on ``device`` when that is given)."""
+    from regularizepsf_amd.device_array import DeviceArray
+
+    if not isinstance(out, DeviceArray):
+        msg = f"out takes one DeviceArray per frame, not {type(out).__name__}"
+        raise TypeError(msg)
+    if tuple(out.shape) != tuple(shape):
+        msg = f"out has shape {out.shape}, the frame {tuple(shape)}"
+        raise IncorrectShapeError(msg)
+    if out.dtype != np.dtype(dtype):
+        msg = f"out has dtype {out.dtype}, the call asks for {np.dtype(dtype)}"
+        raise TypeError(msg)
+    if not out.c_contiguous:
+        msg = "out must be C-contiguous: the kernel writes dense rows"
+        raise ValueError(msg)
+    if device is not None and out.device != device:
+        msg = f"out lives on device {out.device}, the call runs on device {device}"
+        raise ValueError(msg)
+
+
+def _render_outs(out, n_frames: int, shape: tuple[int, int], dtype: np.dtype, device: int) -> list:
+    """``out=`` as one entry per frame (None: a host array is made), everything checked before anything runs."""
+    if out is None:
+        return [None] * n_frames
+    outs = list(out) if isinstance(out, (list, tuple)) else [out]
+    if len(outs) != n_frames:
+        msg = f"out has {len(outs)} entries for {n_frames} frames"
+        raise ValueError(msg)
+    for o in outs:
+        _check_render_out(o, shape, dtype, device)
+    return outs
+
+
+def _render_inputs(stars, n_frames: int | None, psf, radius, flux, cells, dtype) -> tuple:
+    """What ``subtract_stars`` and ``render_stars`` make of their star arguments: ``(positions, fluxes, cells, values, radius, dtype)``,
+    one entry per frame in the first three."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        msg = f"dtype must be float32 or float64, not {dtype}"
+        raise TypeError(msg)
+    coordinates, values = model_cube(psf)
+    size = values.shape[1]
+    try:
+        radius = float(radius)
+    except (TypeError, ValueError) as error:
+        msg = f"radius must be a number, not {radius!r}"
+        raise TypeError(msg) from error
+    limit = min(MAX_RADIUS, size / 2 - 1)
+    if not 0.0 < radius <= limit:
+        msg = f"radius must lie in 0 < R <= min({MAX_RADIUS:g}, N / 2 - 1) = {limit:g} for cells of {size}, got {radius}"
+        raise ValueError(msg)
+    if isinstance(stars, np.ndarray) and (stars.dtype.names is not None or stars.ndim == 2):
+        stars = [stars]  # one frame's stars, as they are
+    stars = [np.asarray(s) for s in stars]
+    if n_frames is not None and len(stars) != n_frames:
+        msg = f"the stars have {len(stars)} entries for {n_frames} frames"
+        raise ValueError(msg)
+    positions = [np.ascontiguousarray(star_positions(s)) for s in stars]
+    for i, p in enumerate(positions):
+        if not np.all(np.abs(p) < MAX_COORD):  # (false for NaN)
+            msg = f"stars[{i}] has a position that is not finite or not inside |row|, |col| < 2^20"
+            raise ValueError(msg)
+
+    def per_frame(given, name: str, kinds: str, kind_name: str, to) -> list:
+        if isinstance(given, np.ndarray) and given.ndim == 1 and len(stars) == 1:
+            given = [given]
+        if len(given) != len(stars):
+            msg = f"{name} has {len(given)} entries for {len(stars)} frames"
+            raise ValueError(msg)
+        result = []
+        for i, (g, p) in enumerate(zip(given, positions)):
+            g = np.asarray(g)
+            if g.dtype.kind not in kinds and g.size:
+                msg = f"{name}[{i}] must be {kind_name}, not {g.dtype}"
+                raise TypeError(msg)
+            if g.shape != (len(p),):
+                msg = f"{name}[{i}] has shape {g.shape} for the {len(p)} stars of frame {i}"
+                raise ValueError(msg)
+            if to is np.int32 and g.size and (g.min() < -(2 ** 31) or g.max() >= 2 ** 31):
+                msg = f"{name}[{i}] has an index outside int32"
+                raise ValueError(msg)
+            result.append(np.ascontiguousarray(g, to))
+        return result
+
+    if flux is None:
+        if not all(s.dtype.names is not None and "flux" in s.dtype.names for s in stars):
+            msg = "flux= is needed unless every entry of the stars is a structured array with a 'flux' field (fit_stars', fit_positions')"
+            raise ValueError(msg)
+        fluxes = [np.ascontiguousarray(s["flux"].ravel(), np.float64) for s in stars]
+    else:
+        fluxes = per_frame(flux, "flux", "fiu", "real numbers", np.float64)
+    if cells is None:
+        cells = [np.ascontiguousarray(s["cell"].ravel(), np.int32) if s.dtype.names is not None and "cell" in s.dtype.names
+                 else nearest_cells(p, coordinates, size) for s, p in zip(stars, positions)]
+    else:
+        cells = per_frame(cells, "cells", "iu", "integers", np.int32)
+    return positions, fluxes, cells, values, radius, dtype
+
+
+def subtract_stars(images, fits, psf, radius: float, mask=None, *, flux=None, cells=None, background: str = "none", box: int = 64,
+                   dtype=np.float32, out=None, return_model: bool = False, return_counts: bool = False, device: int = 0):
+    """Take fitted stars out of their frames: a list of residual frames, one per frame, ``frame - sum of the stars``, every star drawn with
+    its flux and its cell of the PSF model (kernel S10, DESIGN.md 3.7 "Model and residual frames").  It shows what ``cell_fit_summary``'s
+    one number per cell cannot: wings, a ghost, a neighbour the model does not know.
+
+    ``images`` are ``fit_stars``' images, device frames included.  ``fits``: the list ``fit_stars`` or ``fit_positions`` returns (one
+    frame's array for one frame), taken by its fields ``row``, ``col``, ``flux`` and ``cell``; or anything ``star_positions`` accepts,
+    together with ``flux=`` (one float array per frame).  ``cells=None`` uses the ``cell`` field when there is one, so that a star is
+    drawn with the cell it was fitted with, and ``nearest_cells`` otherwise; or one integer array per frame.  ``psf`` and ``radius`` =
+    ``R`` are ``fit_stars``': ``0 < R <= min(64, N / 2 - 1)``.  ``background``: ``"none"`` subtracts from the frame as it is, ``"mesh"``
+    from the frame minus its background mesh of ``box`` (the ``d`` that ``fit_stars(background="mesh")`` fitted; a frame without a usable
+    pixel is an error).  ``mask`` enters only through that mesh.  ``dtype``: float32 (the float64 result rounded once) or float64.
+    ``out=``: one ``DeviceArray`` per frame (one for a single frame), C-contiguous, of the frame's shape and of ``dtype``, on ``device``;
+    the kernel writes into it and it is returned in the list.  ``return_model=True`` also returns the model frames (host arrays of
+    ``dtype``), ``return_counts=True`` also the number of stars drawn per frame: ``(residuals[, models][, counts])``.
+
+    A star is drawn when its flux is finite and its cell is one of the model's; every other star is skipped, so the flagged rows of
+    ``fit_stars``, whose flux is NaN, drop out by themselves.  At pixel ``(r, c)``: ``s = 0``; for the drawn stars in ascending index,
+    when ``(r - row)^2 + (c - col)^2 <= R^2``: ``s += flux * m`` with ``m`` ``fit_stars``' model there, in float64; the residual is
+    ``frame - s``.  NaN and Inf propagate as the arithmetic says; a pixel no star reaches comes back as its own bits.  Every pixel adds
+    its stars in the same order on every run: two calls agree bit for bit.
+
+    This is NOT a PSF-photometry package's subtraction: the interpolation is bilinear and does not conserve flux below the pixel scale,
+    the disc cuts the model at ``R`` (wings beyond it stay in the residual, with a step at the disc's edge), and the constant that
+    ``fit_stars(fit_background=True)`` fitted per star (``background``) is not subtracted.
+    """
+    if background not in ("mesh", "none"):
+        msg = f'background must be "mesh" or "none", not {background!r}'
+        raise ValueError(msg)
+    if not MIN_BOX <= int(box) <= MAX_BOX:
+        msg = f"box must lie in {MIN_BOX} ... {MAX_BOX}, got {box}"
+        raise ValueError(msg)
+    frames = _device_frames(images, device)
+    if frames is None:
+        frames = _frames(images)
+    positions, fluxes, cells, values, radius, dtype = _render_inputs(fits, len(frames), psf, radius, flux, cells, dtype)
+    shape = tuple(frames[0].shape)
+    outs = _render_outs(out, len(frames), shape, dtype, device)
+    masks = _masks(mask, frames)
+    mode = RENDER_RESIDUAL_MESH if background == "mesh" else RENDER_RESIDUAL
+    finder = _Finder(shape, box, device)
+    model = None
+    try:
+        model = _Model(values, device)
+        residuals, models, counts = [], [], []
+        for frame, m, p, f, c, o in zip(frames, masks, positions, fluxes, cells, outs):
+            finder.background_device(frame, m)
+            residual, drawn = finder.render(model, p, f, c, radius, mode, dtype, o)
+            residuals.append(residual)
+            counts.append(drawn)
+            if return_model:
+                models.append(finder.render(model, p, f, c, radius, RENDER_MODEL, dtype)[0])
+        result = (residuals, *((models,) if return_model else ()), *((counts,) if return_counts else ()))
+        return result[0] if len(result) == 1 else result
+    finally:
+        if model is not None:
+            model.close()
+        finder.close()
+
+
+def render_stars(shape, stars, flux, psf, radius: float, *, cells=None, dtype=np.float32, out=None, device: int = 0) -> list:
+    """Model frames alone: a list with one frame of ``shape`` per entry of ``stars``, the sum of the entry's stars drawn on an empty
+    frame with ``subtract_stars``' rule (kernel S10 in its model mode): frames synthesised from a PSF model.  ``stars``: what
+    ``subtract_stars`` takes as ``fits`` (one array for one frame); ``flux``: one float array per entry, or None to take the ``flux``
+    field; ``cells``, ``psf``, ``radius``, ``dtype`` and ``out=`` are ``subtract_stars``'.  A pixel that no star reaches is ``+0.0``.
+    The same caveats hold: bilinear interpolation, the model cut at ``R``."""
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != 2 or min(shape) <= 0:
+        msg = f"shape must be (rows, columns), both positive, not {shape}"
+        raise IncorrectShapeError(msg)
+    positions, fluxes, cells, values, radius, dtype = _render_inputs(stars, None, psf, radius, flux, cells, dtype)
+    outs = _render_outs(out, len(positions), shape, dtype, device)
+    finder = _Finder(shape, 64, device)  # (the mesh is never computed: any box will do)
+    model = None
+    try:
+        model = _Model(values, device)
+        return [finder.render(model, p, f, c, radius, RENDER_MODEL, dtype, o)[0] for p, f, c, o in zip(positions, fluxes, cells, outs)]
     finally:
         if model is not None:
             model.close()
