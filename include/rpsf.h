@@ -828,6 +828,52 @@ int rpsf_stars_render_ms(const rpsf_stars* finder, double* ms);
 /* S10's tile (rows, columns) and the records of a chunk; any pointer may be NULL. */
 int rpsf_stars_render_info(int* tile_rows, int* tile_cols, int* chunk);
 
+/* GROUP FITS (kernel S11): blended neighbours fitted together - one flux per star, one shared constant, positions fixed -
+ * with rpsf_stars_fit's definitions, so that S8, S10 and S11 agree bit for bit where they meet.
+ * rpsf_stars_link_groups (host only, no handle): two ELIGIBLE stars i < j (eligible_host may be NULL: all are) are LINKED when
+ * dy dy + dx dx <= link link, in float64, nothing fused; the groups are the connected components.  labels_host[i] is the smallest index
+ * of i's component, sizes_host[i] its size as found (an ineligible star is a component of one).  A component of more than max_group
+ * (1 .. RPSF_STARS_MAX_GROUP) members is broken up: each member is fitted alone, crowded_host[i] is RPSF_STARS_FIT_CROWDED (else 0), and
+ * the size stays the component's.  link > 0 and finite, positions finite with |y|, |x| < 2^20; anything else is RPSF_E_BADARG.  Expected
+ * linear time (a hashed grid of cells of side link and a union-find); the result does not depend on any order of visits.
+ * rpsf_stars_fit_groups: rpsf_stars_fit's arguments, state rules and return codes, and 0 < link <= 2 R (beyond 2 R two discs share no
+ * pixel), max_group in 1 .. 8 (1 fits every star alone).  A star is eligible when its cell index is inside the model and that cell is
+ * all finite, and - with use_mesh - the frame has a valid mesh node.  Every star that is alone (a component of one, an ineligible or a
+ * crowded star) goes through kernel S8's own launch: the first RPSF_STARS_FIT_COLUMNS of its row are rpsf_stars_fit's, bit for bit, the
+ * flags included, and group = label, group_size = size, group_n = n, group_chi2 = chi2, group_abs = abs_res.  The groups of g = 2 ..
+ * max_group members go through S11, one wave per group, members b = 0 .. g - 1 in ascending index.  Disc b HOLDS pixel (r, c) when
+ * (r - y_b)^2 + (c - x_b)^2 <= R R, spelled as rpsf_stars_fit spells it.
+ *   PASS 1  for a = 0 .. g - 1 over member a's box in S8's lane-strided raster order, on the pixels that disc a holds and no disc b < a
+ *           does (the union of the discs, every pixel OWNED by the first member that holds it), on the frame and usable: with d and
+ *           m_b = the model of member b for the members that hold the pixel: n += 1, Sd += d, Sdd += d d, Sm[b] += m_b, Sdm[b] += d m_b,
+ *           and for c >= b, both holding: A[b][c] += m_b m_c.  A lane's partial sums run on across the members; one fold, S8's.
+ *   SOLVE   unknowns f_0 .. f_{g-1}, then the constant with fit_background: p = g + fit_background; the matrix is A bordered by Sm and n,
+ *           the right-hand side Sdm, then Sd; TOO_FEW: n < p; else rpsf_stars_fit_positions' LDL^T elimination at order p, in its order;
+ *           DEGENERATE: a pivot not finite or <= 0, or an unknown not finite.  Either flag goes to every member and leaves NaN in f, bg
+ *           and the residual's columns.  Near-coincident stars give a near-singular system and huge fluxes of opposite sign: nothing
+ *           guards that but DEGENERATE at a pivot that is not positive.
+ *   PASS 2  for a = 0 .. g - 1 over member a's disc exactly as S8 walks that star alone: n_all, Sm_all, and on the usable pixels n, Sm,
+ *           Smm, Sd, Sdm, Sdd - rpsf_stars_fit's numbers for that star, bit for bit.  With e = d - (S + bg), S = 0.0 and then S += f_b *
+ *           m_b over the members b (ascending) that hold the pixel (rpsf_stars_render's sum): chi2, abs_res and the peak as S8's; on the
+ *           pixels a owns also the group's chi2 and abs_res, whose lane partials run on across the members and fold once.  A member
+ *           without a usable pixel has no peak (NaN at (-1, -1)).
+ * A row of out_host is RPSF_STARS_FIT_GROUPS_COLUMNS float64: rpsf_stars_fit's 20 columns with their meanings (bg is the shared
+ * constant, or + 0.0), then group, group_size, group_n, group_chi2, group_abs.  No atomics, no workgroup waits for another, two runs agree
+ * bit for bit; nothing of the finder is replaced.  This is not a PSF-photometry package's fit: uniform weights, fixed positions, bilinear
+ * interpolation, the model cut at R, the cell fixed. */
+#define RPSF_STARS_FIT_GROUPS_COLUMNS 25
+#define RPSF_STARS_MAX_GROUP 8
+#define RPSF_STARS_FIT_CROWDED 16
+int rpsf_stars_link_groups(size_t n, const double* positions_host, const uint8_t* eligible_host, double link, int max_group,
+                           int32_t* labels_host, int32_t* sizes_host, uint8_t* crowded_host);
+int rpsf_stars_fit_groups(rpsf_stars* finder, const rpsf_stars_model* model, size_t n, const double* positions_host,
+                          const int32_t* cells_host, double radius, int fit_background, int use_mesh, double link, int max_group,
+                          double* out_host);
+/* Device time of the last S11 with the S8 beside it, milliseconds; 0 when it launched nothing. */
+int rpsf_stars_fit_groups_ms(const rpsf_stars* finder, double* ms);
+/* The columns of a row, the largest group, and the groups a workgroup of S11 takes; any pointer may be NULL. */
+int rpsf_stars_fit_groups_info(int* columns, int* max_group, int* groups_per_workgroup);
+
 /* rpsf_builder_add_frame on a dense float32 frame that is already on the builder's device - a finder's (rpsf_stars_frame) or the caller's
  * own; it is only read, nothing is uploaded but the star list.  On a scaled builder the frame is the SCALED one and height and width are
  * its. */

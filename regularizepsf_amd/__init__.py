@@ -27,8 +27,8 @@ from regularizepsf_amd._native import pinned_empty
 from regularizepsf_amd.builder import ArrayPSFBuilder, scale_image
 from regularizepsf_amd.device_array import DeviceArray, device_empty, to_device
 from regularizepsf_amd.psf import ArrayPSF
-from regularizepsf_amd.stars import (cell_fit_summary, find_stars, fit_positions, fit_stars, refine_stars, render_stars, star_catalog,
-                                     star_photometry, subtract_stars)
+from regularizepsf_amd.stars import (cell_fit_summary, find_stars, fit_groups, fit_positions, fit_stars, refine_stars, render_stars,
+                                     star_catalog, star_groups, star_photometry, subtract_stars)
 from regularizepsf_amd.transform import ArrayPSFTransform
 from regularizepsf_amd.util import IndexedCube, calculate_covering
 
@@ -54,6 +54,7 @@ __all__ = [
     "device_empty",
     "elliptical_gaussian",
     "find_stars",
+    "fit_groups",
     "fit_positions",
     "fit_stars",
     "moffat",
@@ -63,6 +64,7 @@ __all__ = [
     "scale_image",
     "simple_functional_psf",
     "star_catalog",
+    "star_groups",
     "star_photometry",
     "subtract_stars",
     "to_device",

@@ -191,6 +191,10 @@ _PROTOTYPES = {
                                   POINTER(c_size_t)]),
     "rpsf_stars_render_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rpsf_stars_render_info": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "rpsf_stars_link_groups": (c_int, [c_size_t, c_void_p, c_void_p, c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    "rpsf_stars_fit_groups": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_double, c_int, c_int, c_double, c_int, c_void_p]),
+    "rpsf_stars_fit_groups_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rpsf_stars_fit_groups_info": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "rpsf_builder_add_frame_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double, c_double,
                                               c_void_p]),
     "rpsf_saturation_fill": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),

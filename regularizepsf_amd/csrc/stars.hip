@@ -38,6 +38,10 @@
 //   S10 stars_render_kernel    rpsf_stars_render, and only then: one workgroup per tile of output pixels, the fitted stars on the tile's
 //                              list drawn with their cells of the model in ascending star index, a gather (the driver of
 //                              rpsf_core_stars_render.hpp); it writes the output frame and nothing the other kernels read
+//   S11 stars_fit_group_kernel rpsf_stars_fit_groups, and only then: the host links the stars whose fit discs overlap into groups
+//                              (rpsf_core_stars_group.hpp), one wave per group fits its members together (the driver of
+//                              rpsf_core_stars_fit_group.hpp), and stars_fit_kernel fits every star that is alone; both write rows of
+//                              their own and nothing the other kernels read
 //
 // The phases are the drivers of rpsf_core_stars.hpp.  Launches follow one another on the null stream; no workgroup ever waits for
 // another one, and the only atomics are integer min / max / add - labels and moments are the same on every run.
@@ -52,7 +56,9 @@
 #include "rpsf_core_stars.hpp"
 #include "rpsf_core_stars_deblend.hpp"
 #include "rpsf_core_stars_fit.hpp"
+#include "rpsf_core_stars_fit_group.hpp"
 #include "rpsf_core_stars_fitpos.hpp"
+#include "rpsf_core_stars_group.hpp"
 #include "rpsf_core_stars_mesh.hpp"
 #include "rpsf_core_stars_photometry.hpp"
 #include "rpsf_core_stars_refine.hpp"
@@ -78,6 +84,11 @@ static_assert(rpsfg::POS_RAN_AWAY == RPSF_STARS_FITPOS_RAN_AWAY && rpsfg::POS_NO
                   rpsfg::POS_SINGULAR == RPSF_STARS_FITPOS_SINGULAR && rpsfg::POS_SKIPPED == RPSF_STARS_FITPOS_SKIPPED,
               "the iteration flags of rpsf_core_stars_fitpos.hpp and include/rpsf.h");
 static_assert(rpsfg::s9_lds_bytes() <= 64 * 1024 && rpsfg::s9_lds_bytes() % 16 == 0, "S9's records fit the LDS a launch gets without asking");
+
+static_assert(rpsfj::GROUP_COLUMNS == RPSF_STARS_FIT_GROUPS_COLUMNS && rpsfq::MAX_GROUP == RPSF_STARS_MAX_GROUP &&
+                  rpsfq::FLAG_CROWDED == RPSF_STARS_FIT_CROWDED,
+              "the group columns, the largest group and the crowded flag of rpsf_core_stars_fit_group.hpp and include/rpsf.h");
+static_assert(rpsfj::s11_lds_bytes() <= 64 * 1024 && rpsfj::s11_lds_bytes() % 16 == 0, "S11's records fit the LDS a launch gets without asking");
 
 static_assert(rpsfn::MODE_MODEL == RPSF_STARS_RENDER_MODEL && rpsfn::MODE_RESIDUAL == RPSF_STARS_RENDER_RESIDUAL &&
                   rpsfn::MODE_RESIDUAL_MESH == RPSF_STARS_RENDER_RESIDUAL_MESH,
@@ -188,6 +199,18 @@ __global__ __launch_bounds__(WALK_THREADS) void stars_fitpos_kernel(Frame fr, co
   rpsfg::s9_fit_positions(ctx, fr, L, none, use_mesh, model, fit, fp, pos, cell, count, (long)blockIdx.x * WALK_WAVES, stars_lds, out, final_pos);
 }
 
+// S11's context: the sums a lane carries from one each() to the next are registers of that thread
+struct GroupCtx : GpuCtx {
+  rpsfj::Lane lane;
+  __device__ __forceinline__ rpsfj::Lane& regs(int) { return lane; }
+};
+__global__ __launch_bounds__(WALK_THREADS) void stars_fit_group_kernel(Frame fr, const double* L, int use_mesh, rpsff::Model model, rpsff::Fit fit,
+                                                                       const double* pos, const int* cell, rpsfj::GroupList groups,
+                                                                       double* out) {
+  GroupCtx ctx;
+  rpsfj::s11_fit_group(ctx, fr, L, use_mesh, model, fit, pos, cell, groups, (long)blockIdx.x * WALK_WAVES, stars_lds, out);
+}
+
 // S10's context: the accumulator of a thread's pixel is a register of that thread
 struct RenderCtx : GpuCtx {
   double s;
@@ -288,6 +311,11 @@ struct rpsf_stars {
   Buf<int> render_cell, render_index;
   Buf<long long> render_offsets;
   double render_ms = 0;
+  // S11 (rpsf_stars_fit_groups): likewise its own - every star's position and cell, the groups, S11's rows by member and S8's by lone star
+  Buf<double> group_pos, group_out, group_lone_pos, group_lone_out;
+  Buf<int> group_cell, group_members, group_lone_cell;
+  Buf<long long> group_starts;
+  double group_ms = 0;
   // the deblend option: everything below is allocated by the first call that needs it
   bool deblend = false;
   double contrast = 0.005, prominence = 1.0;
@@ -755,6 +783,7 @@ extern "C" int rpsf_stars_refine_ms(const rpsf_stars* s, double* ms) {
 struct rpsf_stars_model {
   int device = 0, n_cells = 0, N = 0;
   Buf<double> values;
+  std::vector<uint8_t> finite;  // per cell: every value is finite (rpsf_stars_fit_groups fits only stars of such cells together)
 };
 
 extern "C" int rpsf_stars_model_create(int device, size_t n_cells, int N, const double* values_host, rpsf_stars_model** out) {
@@ -765,6 +794,9 @@ extern "C" int rpsf_stars_model_create(int device, size_t n_cells, int N, const 
   HIP_TRY(hipSetDevice(device));
   rpsf_stars_model* m = new rpsf_stars_model;
   m->device = device, m->n_cells = (int)n_cells, m->N = N;
+  m->finite.assign(n_cells, 1);
+  for (size_t k = 0; k < n_cells; ++k)
+    for (size_t j = 0; j < (size_t)N * N && m->finite[k]; ++j) m->finite[k] = rpsfr::finite_d(values_host[k * (size_t)N * N + j]);
   auto made = [&]() -> int {
     HIP_TRY(m->values.reserve(words));
     HIP_TRY(hipMemcpy(m->values.p, values_host, words * sizeof(double), hipMemcpyHostToDevice));
@@ -939,6 +971,120 @@ extern "C" int rpsf_stars_render_info(int* tile_rows, int* tile_cols, int* chunk
   if (tile_rows) *tile_rows = rpsfn::RENDER_TILE_R;
   if (tile_cols) *tile_cols = rpsfn::RENDER_TILE_C;
   if (chunk) *chunk = rpsfn::RENDER_CHUNK;
+  return RPSF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ S11 (Group fits)
+extern "C" int rpsf_stars_link_groups(size_t n, const double* positions_host, const uint8_t* eligible_host, double link, int max_group,
+                                      int32_t* labels_host, int32_t* sizes_host, uint8_t* crowded_host) {
+  if (n && (!positions_host || !labels_host || !sizes_host || !crowded_host)) return fail(RPSF_E_BADARG, "null argument");
+  if (const char* why = rpsfq::link_problem(link, max_group)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_link_groups: ") + why);
+  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_link_groups: more than 2^30 positions in one call");
+  for (size_t i = 0; i < n; ++i)
+    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
+      return fail(RPSF_E_BADARG, "rpsf_stars_link_groups: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
+  rpsfq::Groups groups;
+  rpsfq::link_groups(n, positions_host, eligible_host, link, max_group, groups);
+  for (size_t i = 0; i < n; ++i)
+    labels_host[i] = groups.label[i], sizes_host[i] = groups.size[i], crowded_host[i] = groups.crowded[i] ? RPSF_STARS_FIT_CROWDED : 0;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_fit_groups(rpsf_stars* s, const rpsf_stars_model* model, size_t n, const double* positions_host,
+                                     const int32_t* cells_host, double radius, int fit_background, int use_mesh, double link, int max_group,
+                                     double* out_host) {
+  if (!s || !model || (n && (!positions_host || !cells_host || !out_host))) return fail(RPSF_E_BADARG, "null argument");
+  if (const char* why = rpsff::fit_problem(radius, fit_background)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit_groups: ") + why);
+  if (const char* why = rpsfq::group_problem(link, max_group, radius)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit_groups: ") + why);
+  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_fit_groups: more than 2^30 positions in one call");
+  for (size_t i = 0; i < n; ++i)
+    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
+      return fail(RPSF_E_BADARG, "rpsf_stars_fit_groups: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
+  if (!(radius <= rpsff::max_fit_radius(model->N)))
+    return fail(RPSF_E_BADARG, "rpsf_stars_fit_groups: radius " + std::to_string(radius) + " is above min(64, N / 2 - 1) of the model's N = " +
+                                   std::to_string(model->N));
+  if (model->device != s->device) return fail(RPSF_E_BADARG, "rpsf_stars_fit_groups: the model is on another device than the finder");
+  if (!s->have_mesh) return fail(RPSF_E_STATE, "rpsf_stars_fit_groups before a rpsf_stars_background_view / _host / _scaled of the frame");
+  s->group_ms = 0;
+  if (n == 0) return RPSF_OK;  // nothing to launch
+  HIP_TRY(hipSetDevice(s->device));
+  int none = 0;
+  if (use_mesh) HIP_TRY(hipMemcpy(&none, s->none.p, sizeof(int), hipMemcpyDeviceToHost));
+  // a star is fitted with others only when its cell is one of the model's and all finite, and the frame has the mesh it asks for
+  std::vector<uint8_t> eligible(n);
+  for (size_t i = 0; i < n; ++i) eligible[i] = !none && cells_host[i] >= 0 && cells_host[i] < model->n_cells && model->finite[(size_t)cells_host[i]];
+  rpsfq::Groups groups;
+  rpsfq::link_groups(n, positions_host, eligible.data(), link, max_group, groups);
+  const size_t n_groups = groups.count(), n_members = groups.members.size(), n_lone = n - n_members;
+  std::vector<uint8_t> grouped(n, 0);
+  for (const int32_t i : groups.members) grouped[(size_t)i] = 1;
+  std::vector<double> lone_pos(2 * n_lone);
+  std::vector<int32_t> lone_cell(n_lone), lone(n_lone);
+  for (size_t i = 0, k = 0; i < n; ++i)
+    if (!grouped[i]) lone[k] = (int32_t)i, lone_pos[2 * k] = positions_host[2 * i], lone_pos[2 * k + 1] = positions_host[2 * i + 1], lone_cell[k++] = cells_host[i];
+  const rpsff::Model cube{model->values.p, model->n_cells, model->N};
+  const rpsff::Fit fit = rpsff::make_fit(radius, fit_background, model->N);
+  if (n_lone) {
+    HIP_TRY(s->group_lone_pos.reserve(2 * n_lone));
+    HIP_TRY(s->group_lone_cell.reserve(n_lone));
+    HIP_TRY(s->group_lone_out.reserve(RPSF_STARS_FIT_COLUMNS * n_lone));
+    HIP_TRY(hipMemcpy(s->group_lone_pos.p, lone_pos.data(), 2 * n_lone * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->group_lone_cell.p, lone_cell.data(), n_lone * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  if (n_groups) {
+    HIP_TRY(s->group_pos.reserve(2 * n));
+    HIP_TRY(s->group_cell.reserve(n));
+    HIP_TRY(s->group_starts.reserve(n_groups + 1));
+    HIP_TRY(s->group_members.reserve(n_members));
+    HIP_TRY(s->group_out.reserve(RPSF_STARS_FIT_GROUPS_COLUMNS * n_members));
+    HIP_TRY(hipMemcpy(s->group_pos.p, positions_host, 2 * n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->group_cell.p, cells_host, n * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->group_starts.p, groups.starts.data(), (n_groups + 1) * sizeof(long long), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->group_members.p, groups.members.data(), n_members * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  if (const int rc = timed(s, &s->group_ms, [&] {
+        // S8's own launch for every star that is alone: its rows are rpsf_stars_fit's
+        if (n_lone)
+          hipLaunchKernelGGL(stars_fit_kernel, dim3((unsigned)((n_lone + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS), rpsff::s8_lds_bytes(),
+                             nullptr, s->view(), s->level_f.p, s->none.p, use_mesh != 0, cube, fit, s->group_lone_pos.p, s->group_lone_cell.p,
+                             (long)n_lone, s->group_lone_out.p);
+        if (n_groups) {
+          const rpsfj::GroupList list{s->group_starts.p, s->group_members.p, (long)n_groups};
+          hipLaunchKernelGGL(stars_fit_group_kernel, dim3((unsigned)((n_groups + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS),
+                             rpsfj::s11_lds_bytes(), nullptr, s->view(), s->level_f.p, use_mesh != 0, cube, fit, s->group_pos.p, s->group_cell.p,
+                             list, s->group_out.p);
+        }
+      }))
+    return rc;
+  std::vector<double> rows8(RPSF_STARS_FIT_COLUMNS * n_lone), rows11(RPSF_STARS_FIT_GROUPS_COLUMNS * n_members);
+  if (n_lone) HIP_TRY(hipMemcpy(rows8.data(), s->group_lone_out.p, rows8.size() * sizeof(double), hipMemcpyDeviceToHost));
+  if (n_groups) HIP_TRY(hipMemcpy(rows11.data(), s->group_out.p, rows11.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < n_lone; ++k) {  // a star alone: S8's row, and it is its own group
+    const size_t i = (size_t)lone[k];
+    const double* from = rows8.data() + RPSF_STARS_FIT_COLUMNS * k;
+    double* o = out_host + RPSF_STARS_FIT_GROUPS_COLUMNS * i;
+    for (int c = 0; c < RPSF_STARS_FIT_COLUMNS; ++c) o[c] = from[c];
+    o[rpsfj::COL_GROUP] = (double)groups.label[i], o[rpsfj::COL_GROUP_SIZE] = (double)groups.size[i];
+    o[rpsfj::COL_GROUP_N] = from[rpsff::COL_N], o[rpsfj::COL_GROUP_CHI2] = from[rpsff::COL_CHI2], o[rpsfj::COL_GROUP_ABS] = from[rpsff::COL_ABS_RES];
+  }
+  for (size_t k = 0; k < n_members; ++k) {
+    const double* from = rows11.data() + RPSF_STARS_FIT_GROUPS_COLUMNS * k;
+    double* o = out_host + RPSF_STARS_FIT_GROUPS_COLUMNS * (size_t)groups.members[k];
+    for (int c = 0; c < RPSF_STARS_FIT_GROUPS_COLUMNS; ++c) o[c] = from[c];
+  }
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_fit_groups_ms(const rpsf_stars* s, double* ms) {
+  if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
+  *ms = s->group_ms;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_fit_groups_info(int* columns, int* max_group, int* groups_per_workgroup) {
+  if (columns) *columns = rpsfj::GROUP_COLUMNS;
+  if (max_group) *max_group = rpsfq::MAX_GROUP;
+  if (groups_per_workgroup) *groups_per_workgroup = WALK_WAVES;
   return RPSF_OK;
 }
 

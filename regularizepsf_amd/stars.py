@@ -53,6 +53,12 @@ pixels excluded and not corrected for - and adds its own: the cell is fixed at t
 on an empty frame (kernel S10, ``rpsf_stars_render``; DESIGN.md 3.7 "Model and residual frames").  The kernel gathers: a workgroup owns a
 tile of output pixels and every pixel adds its stars in ascending star index, so the bits do not depend on scheduling.  The model is cut
 at the radius ``R``, interpolated bilinearly, and the per-star fitted constant is not subtracted.
+
+``fit_groups`` is ``fit_stars`` for crowded fields: stars whose fit discs overlap are fitted together, one flux each and one shared
+constant, positions fixed (kernel S11, ``rpsf_stars_fit_groups``; DESIGN.md 3.7 "Group fits"); ``star_groups`` is the grouping alone, on
+the host.  It uses ``fit_stars``' and ``subtract_stars``' definitions, so the three agree bit for bit where they meet, and it shares
+their limits: uniform weights, bilinear interpolation, the model cut at ``R``, the cell fixed.  Positions are not fitted jointly, and
+nothing guards near-coincident stars but ``DEGENERATE`` at a non-positive pivot.
 """
 
 from __future__ import annotations
@@ -87,6 +93,9 @@ MIN_MODEL, MAX_MODEL = 4, 256
 # an iteration row of kernel S9 (RPSF_STARS_FITPOS_COLUMNS float64) and its flags
 FITPOS_COLUMNS = ("row0", "col0", "row", "col", "niter", "flags", "step_row", "step_col")
 FITPOS_RAN_AWAY, FITPOS_NOT_CONVERGED, FITPOS_SINGULAR, FITPOS_SKIPPED = 1, 2, 4, 8
+# a row of kernel S11 (RPSF_STARS_FIT_GROUPS_COLUMNS float64): S8's columns, then the group's; the flag of rpsf_stars_link_groups
+GROUP_COLUMNS = (*FIT_COLUMNS, "group", "group_size", "group_n", "group_chi2", "group_abs_res")
+CROWDED, MAX_GROUP = 16, 8
 # the modes of kernel S10 (RPSF_STARS_RENDER_* of include/rpsf.h)
 RENDER_MODEL, RENDER_RESIDUAL, RENDER_RESIDUAL_MESH = 0, 1, 2
 DEBLEND_OPTIONS = {"deblend": False, "deblend_contrast": 0.005, "deblend_prominence": 1.0}  # contrast: sep's deblend_cont
@@ -306,6 +315,29 @@ class _Finder:
         """Device time of the last S9 with the S8 behind it; 0.0 when it launched nothing."""
         ms = ctypes.c_double(0)
         self._native.check(self._native.lib().rpsf_stars_fit_positions_ms(self._handle, ctypes.byref(ms)))
+        return ms.value
+
+    def fit_groups(self, model, positions: np.ndarray, cells, radius: float, fit_background: bool = True, use_mesh: bool = True,
+                   link: float | None = None, max_group: int = MAX_GROUP) -> np.ndarray:
+        """Kernel S11, and S8 for every star that is alone, on the frame given to ``background_device`` / ``background_scaled`` last: the
+        stars of ``positions`` no further than ``link`` (None: ``2 radius``) from one another fitted together with their cells of
+        ``model``: (k, len(GROUP_COLUMNS)) float64.  Nothing of the finder is replaced."""
+        n = self._native
+        positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 2)
+        cells = np.ascontiguousarray(cells, np.int32).ravel()
+        if len(cells) != len(positions):
+            msg = f"{len(cells)} cells for {len(positions)} positions"
+            raise ValueError(msg)
+        out = np.empty((len(positions), len(GROUP_COLUMNS)))
+        n.check(n.lib().rpsf_stars_fit_groups(self._handle, model._handle, len(positions), n._ptr(positions), n._ptr(cells), float(radius),
+                                              int(bool(fit_background)), int(bool(use_mesh)), 2.0 * float(radius) if link is None else float(link),
+                                              int(max_group), n._ptr(out)))
+        return out
+
+    def fit_groups_ms(self) -> float:
+        """Device time of the last S11 with the S8 beside it; 0.0 when it launched nothing."""
+        ms = ctypes.c_double(0)
+        self._native.check(self._native.lib().rpsf_stars_fit_groups_ms(self._handle, ctypes.byref(ms)))
         return ms.value
 
     def render(self, model, positions: np.ndarray, flux, cells, radius: float, mode: int = RENDER_RESIDUAL, dtype=np.float32,
@@ -1392,7 +1424,16 @@ def cell_fit_summary(fits, psf) -> np.ndarray:
     n_cells = len(psf.coordinates)
     if isinstance(fits, np.ndarray):
         fits = [fits]
-    rows = np.concatenate([np.asarray(f, fit_dtype()).ravel() for f in fits]) if len(fits) else np.zeros(0, fit_dtype())
+    def by_name(f) -> np.ndarray:  # fit_groups' rows have more fields than fit_dtype: taken by name
+        f = np.asarray(f)
+        if f.dtype.names is None or f.dtype == fit_dtype() or not set(FIT_FIELDS) <= set(f.dtype.names):
+            return np.asarray(f, fit_dtype()).ravel()
+        out = np.empty(f.size, fit_dtype())
+        for name in FIT_FIELDS:
+            out[name] = f[name].ravel()
+        return out
+
+    rows = np.concatenate([by_name(f) for f in fits]) if len(fits) else np.zeros(0, fit_dtype())
     rows = rows[(rows["flags"] == 0) & (rows["cell"] >= 0) & (rows["cell"] < n_cells)]
     out = np.zeros(n_cells, CELL_FIT_DTYPE)
     for name in ("residual_fraction", "relative_rms", "flux"):
@@ -1409,3 +1450,147 @@ def cell_fit_summary(fits, psf) -> np.ndarray:
         out["relative_rms"][cell] = np.median(relative[part])
         out["flux"][cell] = np.median(rows["flux"][part])
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------- group fits
+GROUP_FIT_FIELDS = (*FIT_FIELDS, "group", "group_size", "group_n", "group_dof", "group_chi2", "group_rms", "group_abs_res", "crowded")
+GROUP_DTYPE = np.dtype([("group", np.int32), ("group_size", np.int32), ("crowded", np.bool_)])
+
+
+def group_fit_dtype() -> np.dtype:
+    """The structured dtype of ``fit_groups``: every field of ``fit_dtype``, then ``group``, ``group_size``, ``group_n`` and ``group_dof``
+    (int32), ``group_chi2``, ``group_rms`` and ``group_abs_res`` (float64) and the boolean ``crowded``."""
+    kinds = {name: fit_dtype()[name] for name in FIT_FIELDS}
+    kinds.update({"group": np.int32, "group_size": np.int32, "group_n": np.int32, "group_dof": np.int32, "crowded": np.bool_})
+    return np.dtype([(name, kinds.get(name, np.float64)) for name in GROUP_FIT_FIELDS])
+
+
+def group_fit_from_sums(rows: np.ndarray, fit_background: bool = True, max_group: int = MAX_GROUP) -> np.ndarray:
+    """The structured result (``group_fit_dtype``) of S11's rows: the fields of ``fit_from_sums`` on the first columns, unchanged, then
+    ``crowded = group_size > max_group``, ``group_dof = group_n - p`` with ``p`` the unknowns of the fit the star was in (the members of
+    a group fitted together, 1 for a star fitted alone, plus 1 with a fitted background) and ``group_rms = sqrt(group_chi2 / group_dof)``
+    (NaN when ``group_dof <= 0``)."""
+    rows = np.asarray(rows, np.float64).reshape(-1, len(GROUP_COLUMNS))
+    single = fit_from_sums(rows[:, :len(FIT_COLUMNS)], fit_background)
+    col = {name: rows[:, j] for j, name in enumerate(GROUP_COLUMNS)}
+    out = np.empty(len(rows), group_fit_dtype())
+    for name in FIT_FIELDS:
+        out[name] = single[name]
+    for name in ("group", "group_size", "group_n"):
+        out[name] = col[name].astype(np.int32)
+    out["crowded"] = out["group_size"] > int(max_group)
+    members = np.where(out["crowded"], 1, out["group_size"])
+    out["group_dof"] = out["group_n"] - (members + (1 if fit_background else 0))
+    out["group_chi2"], out["group_abs_res"] = col["group_chi2"], col["group_abs_res"]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dof = out["group_dof"].astype(np.float64)
+        out["group_rms"] = np.where(dof > 0, np.sqrt(col["group_chi2"] / np.where(dof > 0, dof, np.nan)), np.nan)
+    return out
+
+
+def fit_groups_info() -> tuple[int, int, int]:
+    """The columns of a row of kernel S11, the largest group it fits, and the groups a workgroup takes."""
+    from regularizepsf_amd import _native
+
+    values = [ctypes.c_int(0) for _ in range(3)]
+    _native.check(_native.lib().rpsf_stars_fit_groups_info(*(ctypes.byref(v) for v in values)))
+    return tuple(v.value for v in values)
+
+
+def _group_options(link, max_group, radius: float | None) -> tuple[float, int]:
+    if isinstance(max_group, (bool, np.bool_)) or not isinstance(max_group, (int, np.integer)):
+        msg = f"max_group must be an integer, not {max_group!r}"
+        raise TypeError(msg)
+    if not 1 <= int(max_group) <= MAX_GROUP:
+        msg = f"max_group must lie in 1 ... {MAX_GROUP}, got {max_group}"
+        raise ValueError(msg)
+    if link is None and radius is not None:
+        return 2.0 * radius, int(max_group)
+    try:
+        link = float(link)
+    except (TypeError, ValueError) as error:
+        msg = f"link must be a number, not {link!r}"
+        raise TypeError(msg) from error
+    if radius is None:
+        if not (0.0 < link < np.inf):
+            msg = f"link must be positive and finite, got {link}"
+            raise ValueError(msg)
+    elif not 0.0 < link <= 2.0 * radius:
+        msg = f"link must lie in 0 < link <= 2 R = {2.0 * radius:g} (beyond it two discs share no pixel), got {link}"
+        raise ValueError(msg)
+    return link, int(max_group)
+
+
+def star_groups(stars, link: float, *, max_group: int = MAX_GROUP, eligible=None) -> np.ndarray:
+    """The grouping of ``fit_groups`` alone, on the host: a structured array (``group``, ``group_size``, ``crowded``) with one row per
+    star of one frame.  Two stars are linked when ``(row_i - row_j)^2 + (col_i - col_j)^2 <= link^2`` in float64; the groups are the
+    connected components; ``group`` is the smallest index of the star's component and ``group_size`` its size.  A component of more than
+    ``max_group`` (``1 ... 8``) members is ``crowded``: ``fit_groups`` fits each of its members alone.  ``eligible``: None, or one boolean
+    per star; a star that is not eligible links to nobody.  ``stars``: anything ``star_positions`` accepts."""
+    from regularizepsf_amd import _native
+
+    link, max_group = _group_options(link, max_group, None)
+    positions = np.ascontiguousarray(star_positions(stars), np.float64).reshape(-1, 2)
+    if not np.all(np.abs(positions) < MAX_COORD):
+        msg = "stars has a position that is not finite or not inside |row|, |col| < 2^20"
+        raise ValueError(msg)
+    flags = None
+    if eligible is not None:
+        flags = np.ascontiguousarray(np.asarray(eligible, bool).ravel(), np.uint8)
+        if len(flags) != len(positions):
+            msg = f"eligible has {len(flags)} entries for {len(positions)} stars"
+            raise ValueError(msg)
+    labels, sizes, crowded = np.zeros(len(positions), np.int32), np.zeros(len(positions), np.int32), np.zeros(len(positions), np.uint8)
+    _native.check(_native.lib().rpsf_stars_link_groups(len(positions), _native._ptr(positions), None if flags is None else _native._ptr(flags),
+                                                       link, max_group, _native._ptr(labels), _native._ptr(sizes), _native._ptr(crowded)))
+    out = np.empty(len(positions), GROUP_DTYPE)
+    out["group"], out["group_size"], out["crowded"] = labels, sizes, crowded != 0
+    return out
+
+
+def fit_groups(images, stars, psf, radius: float, mask=None, *, background: str = "mesh", box: int = 64, fit_background: bool = True,
+               cells=None, link: float | None = None, max_group: int = MAX_GROUP, device: int = 0) -> list[np.ndarray]:
+    """``fit_stars`` with blended neighbours fitted together: a list of NumPy structured arrays (``group_fit_dtype``), one per frame and
+    one row per position.  Stars whose fit discs overlap share pixels; fitted one at a time, each takes its neighbour's light as flux.
+    Here the stars no further than ``link`` from one another (None: ``2 radius``, the distance at which two discs stop sharing pixels;
+    ``0 < link <= 2 R``) form a group - the connected components of that graph, ``star_groups`` - and a group of ``2 ... max_group``
+    members (``max_group`` in ``1 ... 8``; 1 fits every star alone) is fitted at once by linear least squares over the union of its
+    discs: one flux per star and, with ``fit_background``, one constant for the group, the positions fixed (kernel S11,
+    ``rpsf_stars_fit_groups``; DESIGN.md 3.7 "Group fits").  Every other argument is ``fit_stars``'.
+
+    Every field of ``fit_dtype`` is there with its meaning: ``n_use, n_all, sm, sm_all, smm, sd, sdm, sdd`` and ``coverage`` are the
+    star's own over its own disc, the bits ``fit_stars`` gives; ``flux`` is the star's flux of the joint fit and ``background`` the group's
+    constant; ``chi2, abs_res, peak_res, peak_e, peak_row, peak_col`` are taken over the star's own disc from ``e = d - (sum of flux_b m_b +
+    background)``, the sum over the members whose disc holds the pixel - what ``subtract_stars`` takes out there.  The per-star ``dof``
+    stays ``fit_stars``' nominal ``n_use - 2`` (``- 1`` without a fitted background) and ``rms = sqrt(chi2 / dof)`` with it: neither
+    counts the neighbours' parameters.  The group's own figures count every pixel of the union once: ``group`` (the smallest index of
+    the group's stars), ``group_size``, ``group_n`` (its usable pixels), ``group_dof = group_n - p`` with ``p`` = members (+ 1 with a
+    fitted background), ``group_chi2``, ``group_rms = sqrt(group_chi2 / group_dof)`` and ``group_abs_res``.  A star that is alone - no
+    neighbour within ``link``, a cell index outside the model or a cell that is not all finite, a frame without a mesh, or ``crowded``: a
+    component of more than ``max_group`` stars, which is broken up - is ``fit_stars``' row, bit for bit, and its group figures are its
+    own.  ``TOO_FEW`` (``group_n < p``) and ``DEGENERATE`` (a pivot of the elimination not finite or ``<= 0``, or a flux that is not
+    finite - an all-zero cell, two stars at one position) go to every member of a group and leave NaN in the fit's fields.
+
+    This is NOT a PSF-photometry package's fit: the weights are uniform - there is no error column and no variance weighting -, the
+    positions are fixed and not fitted (``fit_positions`` fits them, one star at a time), the interpolation is bilinear and does not
+    conserve flux below the pixel scale, the model is cut at ``R``, the cell of a star is fixed, and masked pixels are excluded and
+    reported through ``coverage``, not corrected for.  Near-coincident stars give a near-singular system and huge fluxes of opposite sign:
+    nothing guards that but ``DEGENERATE`` at a non-positive pivot.
+    """
+    frames, masks, positions, cells, values, radius = _fit_inputs(images, stars, psf, radius, mask, background, box, fit_background, cells,
+                                                                  device)
+    link, max_group = _group_options(link, max_group, radius)
+    finder = _Finder(frames[0].shape, box, device)
+    model = None
+    try:
+        model = _Model(values, device)
+        out = []
+        for frame, m, p, c in zip(frames, masks, positions, cells):
+            finder.background_device(frame, m)
+            rows = finder.fit_groups(model, p, c, radius, bool(fit_background), background == "mesh", link, max_group)
+            out.append(group_fit_from_sums(rows, bool(fit_background), max_group))
+        return out
+    finally:
+        if model is not None:
+            model.close()
+        finder.close()
