@@ -881,6 +881,43 @@ int rpsf_builder_add_frame_device(rpsf_builder* builder, const float* frame_dev,
                                   const int32_t* corners_i32, const double* frac_f64, double saturation_threshold, double star_minimum,
                                   double star_maximum, uint8_t* accepted_u8_host);
 
+/* NEIGHBOUR-SUBTRACTED PATCHES (kernel B1n): rpsf_builder_add_frame with the fitted stars of the frame taken out of every
+ * patch except the patch's own star, so that a neighbour inside a patch does not enter the cell's average.  The subtraction set is S10's
+ * (rpsf_stars_render): n_all stars with positions_host (n_all x 2 float64, (row, col)), flux_host (float64), cells_host (int32) and their
+ * cells of `model`; a star is drawn when its flux is finite and its cell is one of the model's, every other star takes no part.  Patch k
+ * (k < n_stars: corners_i32, frac_f64 as in rpsf_builder_add_frame) leaves star own_i32[k] of the set in; own_i32[k] = -1 leaves nobody in
+ * (a patch cut at a position that is not in the set).
+ *
+ * DEFINITION.  For patch pixel (r, c), with (rr, rc) the patch's rounded corner and mirror the reflect index map of
+ * rpsf_builder_add_frame: fr = mirror(rr + r, height), fc = mirror(rc + c, width); s = 0; for the drawn stars j != own[k] in ascending j:
+ * pr = fr - row_j, pc = fc - col_j, and when pr pr + pc pc <= R R: s += flux_j * m with m rpsf_stars_fit's bilinear model of cell_j at
+ * (pr, pc), all in float64.  The pixel enters the patch as (double)(float)((double)frame[fr][fc] - s): bit for bit the value
+ * rpsf_builder_add_frame_device reads from the float32 frame rpsf_stars_render(RPSF_STARS_RENDER_RESIDUAL) writes with star own[k] left out,
+ * and the frame's own bits where no star reaches.  Everything after this gather - the spline shift, the background plane, the tests, the
+ * append to the stack - is rpsf_builder_add_frame's and unchanged (regularizepsf/image_processing.py:82-121).  The host builds one
+ * neighbour list per patch through a bucket grid (time linear in stars and patches); no atomics, two calls agree bit for bit.
+ *
+ * RPSF_E_BADARG before anything is launched or written: a null argument, `radius` outside 0 < R <= min(64, N_m / 2 - 1) of the model's
+ * N_m, a position that is not finite or not inside |row|, |col| < 2^20, an own_i32[k] outside -1 ... n_all - 1, a model on another
+ * device than the builder, and what rpsf_builder_add_frame refuses.  RPSF_E_UNSUPPORTED: a wide builder (rpsf_builder_create_wide) or a
+ * scaled one.  n_all == 0 is valid (model and the three arrays may then be NULL) and is rpsf_builder_add_frame itself.  The device time of
+ * B1n is the patch figure of rpsf_builder_kernel_ms. */
+int rpsf_builder_add_frame_subtracted(rpsf_builder* builder, const void* image_host, int image_is_f64, int height, int width,
+                                      const rpsf_stars_model* model, size_t n_all, const double* positions_host, const double* flux_host,
+                                      const int32_t* cells_host, double radius, int n_stars, const int32_t* own_i32,
+                                      const int32_t* corners_i32, const double* frac_f64, double saturation_threshold, double star_minimum,
+                                      double star_maximum, uint8_t* accepted_u8_host);
+/* The same on a dense float32 frame that is already on the builder's device (rpsf_builder_add_frame_device's frame_dev). */
+int rpsf_builder_add_frame_device_subtracted(rpsf_builder* builder, const float* frame_dev, int height, int width,
+                                             const rpsf_stars_model* model, size_t n_all, const double* positions_host,
+                                             const double* flux_host, const int32_t* cells_host, double radius, int n_stars,
+                                             const int32_t* own_i32, const int32_t* corners_i32, const double* frac_f64,
+                                             double saturation_threshold, double star_minimum, double star_maximum,
+                                             uint8_t* accepted_u8_host);
+/* The star records B1n stages at a time, the side of a bucket of the host's grid in pixels, and the LDS of a B1n workgroup at N = 128 in
+ * bytes; any pointer may be NULL. */
+int rpsf_builder_subtract_info(int* chunk, int* bucket, size_t* lds_bytes_128);
+
 /* Host-side helper for the saturation branch of apply (transform.py:135-138): sequential, row-major
  * NaN-ignoring neighbourhood-mean fill of the masked pixels of the float64 padded image (no GPU involved). */
 int rpsf_saturation_fill(double* padded, int rows, int cols, const uint8_t* mask, int neighborhood_width);

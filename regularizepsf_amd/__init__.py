@@ -24,7 +24,7 @@ from regularizepsf_amd.functional import (
     varied_functional_psf,
 )
 from regularizepsf_amd._native import pinned_empty
-from regularizepsf_amd.builder import ArrayPSFBuilder, scale_image
+from regularizepsf_amd.builder import ArrayPSFBuilder, build_iterative, build_subtracted, scale_image
 from regularizepsf_amd.device_array import DeviceArray, device_empty, to_device
 from regularizepsf_amd.psf import ArrayPSF
 from regularizepsf_amd.stars import (cell_fit_summary, find_stars, fit_groups, fit_positions, fit_stars, refine_stars, render_stars,
@@ -49,6 +49,8 @@ __all__ = [
     "RegularizePSFError",
     "SimpleFunctionalPSF",
     "VariedFunctionalPSF",
+    "build_iterative",
+    "build_subtracted",
     "calculate_covering",
     "cell_fit_summary",
     "device_empty",

@@ -197,6 +197,12 @@ _PROTOTYPES = {
     "rpsf_stars_fit_groups_info": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "rpsf_builder_add_frame_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double, c_double,
                                               c_void_p]),
+    "rpsf_builder_add_frame_subtracted": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                                  c_double, c_int, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
+    "rpsf_builder_add_frame_device_subtracted": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                                         c_double, c_int, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double,
+                                                         c_void_p]),
+    "rpsf_builder_subtract_info": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]),
     "rpsf_saturation_fill": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
     "rpsf_dev_alloc": (c_int, [c_int, c_size_t, POINTER(c_void_p)]),
     "rpsf_dev_free": (c_int, [c_int, c_void_p]),

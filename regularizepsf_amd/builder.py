@@ -16,6 +16,10 @@ The boundary of the feature is the star list: ``build(..., stars=[...])`` takes 
 returns; without it ``sep`` is imported and called as the reference calls it - or, with ``ArrayPSFBuilder(..., finder="device")``,
 this package's own detector (``regularizepsf_amd.stars``) finds them on the fused route of DESIGN.md 3.11: every frame is uploaded at
 most once (not at all when it is a ``DeviceArray``), the stars are found and the patches cut from that one float32 frame on the device.
+
+``build_subtracted`` is the rebuild of the loop build, fit, remove the neighbours, rebuild: every patch is cut with the fitted stars around
+it taken out (kernel B1n, DESIGN.md 3.6 "Neighbour-subtracted patches"), everything after the patches is ``build``'s own code;
+``build_iterative`` drives the loop.
 """
 
 from __future__ import annotations
@@ -373,6 +377,37 @@ class _Stack:
                                                       float(star_maximum), n._ptr(flags)))
         return flags
 
+    def add_frame_subtracted(self, frame, shape: tuple[int, int], model, positions: np.ndarray, flux: np.ndarray, cells: np.ndarray,
+                             radius: float, own: np.ndarray, rounded: np.ndarray, shift: np.ndarray, saturation_threshold: float,
+                             star_minimum: float, star_maximum: float) -> np.ndarray:
+        """Kernel B1n: ``add_frame`` (``frame`` a host array) or ``add_frame_device`` (``frame`` the address of a dense float32 frame of
+        ``shape`` on the builder's device) with the stars ``positions`` / ``flux`` / ``cells`` of ``model`` (a ``stars._Model``, None when
+        there are no stars) taken out of every patch but the patch's own, ``own[k]`` (-1: nobody is left in)."""
+        n = self._native
+        corners = np.ascontiguousarray(rounded, np.int32).reshape(-1, 2)
+        frac = np.ascontiguousarray(shift, np.float64).reshape(-1, 2)
+        own = np.ascontiguousarray(own, np.int32).ravel()
+        positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 2)
+        flux = np.ascontiguousarray(flux, np.float64).ravel()
+        cells = np.ascontiguousarray(cells, np.int32).ravel()
+        if len(own) != len(corners) or len(frac) != len(corners) or len(flux) != len(positions) or len(cells) != len(positions):
+            msg = f"{len(own)} own indices and {len(frac)} shifts for {len(corners)} corners, {len(flux)} fluxes and {len(cells)} cells for {len(positions)} positions"
+            raise ValueError(msg)
+        flags = np.zeros(len(corners), np.uint8)
+        handle = model._handle if len(positions) else None
+        star_args = (handle, len(positions), n._ptr(positions), n._ptr(flux), n._ptr(cells), float(radius), len(corners), n._ptr(own),
+                     n._ptr(corners), n._ptr(frac), float(saturation_threshold), float(star_minimum), float(star_maximum), n._ptr(flags))
+        if isinstance(frame, np.ndarray):
+            if frame.dtype != np.float32:
+                frame = frame.astype(np.float64, copy=False)
+            frame = np.ascontiguousarray(frame)
+            n.check(n.lib().rpsf_builder_add_frame_subtracted(self._handle, n._ptr(frame), int(frame.dtype == np.float64), frame.shape[0],
+                                                              frame.shape[1], *star_args))
+        else:
+            n.check(n.lib().rpsf_builder_add_frame_device_subtracted(self._handle, ctypes.c_void_p(frame), int(shape[0]), int(shape[1]),
+                                                                     *star_args))
+        return flags
+
     def load(self, patches: np.ndarray) -> None:
         p = np.ascontiguousarray(patches, np.float32).reshape(-1, self.patch_size, self.patch_size)
         self._native.check(self._native.lib().rpsf_builder_load_patches(self._handle, len(p), self._native._ptr(p)))
@@ -448,6 +483,80 @@ class _Stack:
             self.close()
         except Exception:  # noqa: BLE001  (interpreter shutdown)
             pass
+
+
+def _first_of_equal_keys(corner: np.ndarray) -> np.ndarray:
+    """Equal keys of one frame: ``dict.update`` keeps the first position and the last value - the same patch either way.  The indices of the
+    first star of every distinct float corner, ascending."""
+    _, first = np.unique(corner, axis=0, return_index=True)
+    first.sort()
+    return first
+
+
+def _keep_accepted(keys: dict, frame_index: int, corner: np.ndarray, flags: np.ndarray, patch: int) -> None:
+    """After the patch kernel of one frame: ``corner`` are the float corners of the patches it was given, ``flags`` its verdicts.  The
+    accepted ones are keyed in their order; a degenerate ring is the caller's error."""
+    if np.any(flags == DEGENERATE_RING):
+        bad = corner[flags == DEGENERATE_RING][0] + patch / 2
+        msg = (f"Frame {frame_index}: the patch of the star at {tuple(float(v) for v in bad)} has fewer than three border pixels below "
+               "its centre (or all on one line), so no background plane can be fitted.")
+        raise PSFBuilderError(msg)
+    for row, col in corner[flags == ACCEPTED].tolist():
+        keys[(frame_index, row, col)] = len(keys)
+
+
+def _cells_of_stack(stack, keys: dict, shape: tuple[int, int], size: int, scale: int, average_method: str, percentile: float, cleanup: str,
+                    return_patches: bool) -> tuple:
+    """Everything ``build`` does with a filled stack while the handle lives: the covering, the membership, B2 (and B3 with
+    ``cleanup="device"``) and the patches.  ``(corners, offsets, cells, patches)``; the cells are cleaned when ``cleanup == "device"``."""
+    patch = size * scale
+    if scale == 1:
+        corners = calculate_covering(shape, size)
+    else:  # builder.py:225-227 as it stands: the scaled shape times the scale
+        scaled = scaled_shape(shape, scale)
+        corners = calculate_covering((scaled[0] * scale, scaled[1] * scale), patch)
+    offsets, members = cell_membership(np.array([k[1:] for k in keys], np.float64).reshape(-1, 2), corners, patch)
+    method = "median" if (average_method == "percentile" and percentile == 50) else average_method
+    if cleanup == "device":
+        cells = model_on_device(stack, method, percentile, offsets, members)
+    else:
+        cells = stack.average(method, percentile, offsets, members)
+    patches = None
+    if return_patches:
+        values = stack.patches().astype(np.float64)
+        patches = {key: values[index] for key, index in keys.items()}
+    return corners, offsets, cells, patches
+
+
+def _build_result(corners, offsets, cells, patches, cleanup: str, return_patches: bool):
+    """``build``'s return values from what ``_cells_of_stack`` left."""
+    counts = {tuple(corner): int(offsets[c + 1] - offsets[c]) for c, corner in enumerate(corners)}
+    coordinates = [(corner[0], corner[1]) for corner in corners]
+    values = cells if cleanup == "device" else np.stack([clean_cell(cell) for cell in cells])
+    psf = ArrayPSF(IndexedCube(coordinates, values))
+    return (psf, counts, patches) if return_patches else (psf, counts)
+
+
+def _keeps(keep, counts: list[int]) -> list[np.ndarray]:
+    """``keep=`` of ``build_subtracted`` as one boolean array per frame (None: every row)."""
+    if keep is None:
+        return [np.ones(n, bool) for n in counts]
+    if isinstance(keep, np.ndarray) and keep.ndim == 1 and len(counts) == 1:
+        keep = [keep]
+    if len(keep) != len(counts):
+        msg = f"keep has {len(keep)} entries for {len(counts)} frames"
+        raise ValueError(msg)
+    result = []
+    for i, (k, n) in enumerate(zip(keep, counts)):
+        k = np.asarray(k)
+        if k.dtype != np.bool_:
+            msg = f"keep[{i}] must be booleans, not {k.dtype}"
+            raise TypeError(msg)
+        if k.shape != (n,):
+            msg = f"keep[{i}] has shape {k.shape} for the {n} stars of frame {i}"
+            raise ValueError(msg)
+        result.append(k)
+    return result
 
 
 class ArrayPSFBuilder:
@@ -615,9 +724,7 @@ class ArrayPSFBuilder:
                         positions = star_finder.refine_detections(finder, positions, self._refine_sigma)
                     found.append(positions)
                 corner, rounded, shift = star_geometry(positions, patch)
-                # equal keys of one frame: dict.update keeps the first position and the last value - the same patch either way
-                _, first = np.unique(corner, axis=0, return_index=True)
-                first.sort()
+                first = _first_of_equal_keys(corner)
                 if fused:
                     flags = stack.add_frame_device(finder.frame_ptr(), seen_shape, rounded[first], shift[first], saturation_threshold,
                                                    star_minimum, star_maximum) if len(first) else np.zeros(0, np.uint8)
@@ -627,28 +734,9 @@ class ArrayPSFBuilder:
                                                    star_maximum)
                 else:
                     flags = stack.add_frame(frame, rounded[first], shift[first], saturation_threshold, star_minimum, star_maximum)
-                if np.any(flags == DEGENERATE_RING):
-                    bad = corner[first][flags == DEGENERATE_RING][0] + patch / 2
-                    msg = (f"Frame {i}: the patch of the star at {tuple(float(v) for v in bad)} has fewer than three border pixels below "
-                           "its centre (or all on one line), so no background plane can be fitted.")
-                    raise PSFBuilderError(msg)
-                for row, col in corner[first][flags == ACCEPTED].tolist():
-                    keys[(i, row, col)] = len(keys)
-            if scale == 1:
-                corners = calculate_covering(frames[0].shape, size)
-            else:  # builder.py:225-227 as it stands: the scaled shape times the scale
-                scaled = scaled_shape(frames[0].shape, scale)
-                corners = calculate_covering((scaled[0] * scale, scaled[1] * scale), patch)
-            offsets, members = cell_membership(np.array([k[1:] for k in keys], np.float64).reshape(-1, 2), corners, patch)
-            method = "median" if (average_method == "percentile" and percentile == 50) else average_method
-            if cleanup == "device":
-                cleaned = model_on_device(stack, method, percentile, offsets, members)
-            else:
-                cells = stack.average(method, percentile, offsets, members)
-            patches = None
-            if return_patches:
-                values = stack.patches().astype(np.float64)
-                patches = {key: values[index] for key, index in keys.items()}
+                _keep_accepted(keys, i, corner[first], flags, patch)
+            corners, offsets, cells, patches = _cells_of_stack(stack, keys, tuple(frames[0].shape), size, scale, average_method, percentile,
+                                                               cleanup, return_patches)
         finally:
             if stack is not None:
                 stack.close()
@@ -656,9 +744,118 @@ class ArrayPSFBuilder:
                 finder.close()
         if fused:
             self._found_stars = found
+        return _build_result(corners, offsets, cells, patches, cleanup, return_patches)
 
-        counts = {tuple(corner): int(offsets[c + 1] - offsets[c]) for c, corner in enumerate(corners)}
-        coordinates = [(corner[0], corner[1]) for corner in corners]
-        values = cleaned if cleanup == "device" else np.stack([clean_cell(cell) for cell in cells])
-        psf = ArrayPSF(IndexedCube(coordinates, values))
-        return (psf, counts, patches) if return_patches else (psf, counts)
+    def build_subtracted(self, images, fits, psf, radius: float, *, flux=None, cells=None, keep=None, average_method: str = "median",
+                         percentile: float = 50, saturation_threshold: float = np.inf, star_minimum: float = 0,
+                         star_maximum: float = np.inf, return_patches: bool = False):
+        """``build(images, stars=...)`` with the fitted neighbours of every star taken out of its patch (kernel B1n, DESIGN.md 3.6
+        "Neighbour-subtracted patches"): the rebuild of the loop build, fit, remove the neighbours, rebuild.  The return values are
+        ``build``'s.
+
+        ``fits``, ``psf``, ``radius``, ``flux`` and ``cells`` are ``subtract_stars``': per frame what ``fit_stars`` / ``fit_positions`` /
+        ``fit_groups`` return, taken by ``row, col, flux, cell`` - flagged rows, whose flux is NaN, drop out of the subtraction set by
+        themselves - or plain positions with ``flux=`` (and optionally ``cells=``).  ``psf`` is the model the stars are drawn with
+        (its cells need not be ``psf_size`` wide), ``0 < radius <= min(64, N_m / 2 - 1)`` the disc a star is drawn in.  ``keep``: one
+        boolean array per frame (one array for a single frame) saying which rows are CUT as patches; every drawn row is still subtracted
+        as a neighbour, so ``keep=[f["residual_fraction"] < 0.1 for f in fits]`` drops the stars that fit their cell badly.  A row that
+        is cut but not drawn is cut with every drawn star taken out.
+
+        The patch of row ``i`` is, bit for bit, the patch ``build`` cuts at that position from the float32 frame
+        ``subtract_stars(frame, fits, psf, radius)`` gives with the flux of row ``i`` set to NaN; where no drawn star's disc reaches
+        another star's patch the result is ``build(images, stars=positions)``.  Everything after the patches - the keys and the
+        first-of-equal-keys rule, the covering, the averaging, the clean-up according to ``cleanup=`` - is ``build``'s own code.  Host
+        frames and device frames as in ``build``.  The caveats of ``subtract_stars`` hold: bilinear interpolation, the model cut at
+        ``radius``, no per-star background.  ``psf_size`` above 128 and ``interpolation_scale`` are not implemented
+        (``NotImplementedError``); a ``psf`` whose samples live on another device than the builder is a ``ValueError``."""
+        from regularizepsf_amd import stars as star_module
+
+        size = self._psf_size
+        if size > MAX_PATCH:
+            msg = f"psf_size = {size} is not implemented for neighbour-subtracted patches: kernel B1n stops at {MAX_PATCH} pixels"
+            raise NotImplementedError(msg)
+        if average_method not in AVERAGE_METHODS:
+            msg = f"Unknown method {average_method}."
+            raise PSFBuilderError(msg)
+        held = getattr(psf, "_fft_dev", None)
+        if held is not None and held[1] != self._device:
+            msg = f"psf lives on device {held[1]}, the builder on device {self._device}"
+            raise ValueError(msg)
+        cleanup = self._cleanup
+        frames = _device_frames(images, self._device)
+        on_device = frames is not None
+        if not on_device:
+            frames = _frames(images)
+        shape = tuple(frames[0].shape)
+        positions, fluxes, cells, values, radius, _ = star_module._render_inputs(fits, len(frames), psf, radius, flux, cells, np.float32)
+        keeps = _keeps(keep, [len(p) for p in positions])
+        self._found_stars = None
+        stack = model = None
+        try:
+            stack = _Stack(size, self._device, sum(int(k.sum()) for k in keeps))
+            model = star_module._Model(values, self._device)
+            keys: dict[tuple[int, float, float], int] = {}
+            for i, (frame, p, f, c, k) in enumerate(zip(frames, positions, fluxes, cells, keeps)):
+                own = np.flatnonzero(k)
+                corner, rounded, shift = star_geometry(p[own], size)
+                first = _first_of_equal_keys(corner)
+                dense = _dense_f32(frame) if on_device else None  # (kept alive until B1n has run)
+                flags = stack.add_frame_subtracted(dense.ptr if on_device else frame, shape, model, p, f, c, radius, own[first],
+                                                   rounded[first], shift[first], saturation_threshold, star_minimum, star_maximum)
+                _keep_accepted(keys, i, corner[first], flags, size)
+            corners, offsets, averaged, patches = _cells_of_stack(stack, keys, shape, size, 1, average_method, percentile, cleanup,
+                                                                  return_patches)
+        finally:
+            if stack is not None:
+                stack.close()
+            if model is not None:
+                model.close()
+        return _build_result(corners, offsets, averaged, patches, cleanup, return_patches)
+
+    def build_iterative(self, images, stars, radius: float, *, iterations: int = 2, fit: str = "groups", keep=None, **build_keywords):
+        """The loop build, fit, remove the neighbours, rebuild: ``psf = build(images, stars=stars)``, then ``iterations`` times ``fits =
+        fit_groups(images, stars, psf, radius)`` (``fit="groups"``; ``fit_stars`` for ``fit="stars"``) and ``psf = build_subtracted(images,
+        fits, psf, radius, keep=...)``.  ``(psf, counts, fits)`` of the last round.  ``keep``: None, what ``build_subtracted`` takes, or a
+        callable that makes it from the round's ``fits``.  ``build_keywords``: ``average_method``, ``percentile``,
+        ``saturation_threshold``, ``star_minimum`` and ``star_maximum``, given to every build; ``interpolation_scale`` is ``build``'s
+        keyword and is refused here as ``build`` refuses what it does not implement (``NotImplementedError``), whatever its value.  A driver over the public calls and
+        nothing else: the fits run with their defaults on the builder's device."""
+        from regularizepsf_amd import stars as star_module
+
+        if fit not in ("groups", "stars"):
+            msg = f'fit must be "groups" or "stars", not {fit!r}'
+            raise ValueError(msg)
+        if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or iterations < 1:
+            msg = f"iterations must be an integer of at least 1, not {iterations!r}"
+            raise ValueError(msg)
+        if "interpolation_scale" in build_keywords:
+            msg = "interpolation_scale is not implemented for neighbour-subtracted patches: the patches are cut from the frames as they are"
+            raise NotImplementedError(msg)
+        allowed = ("average_method", "percentile", "saturation_threshold", "star_minimum", "star_maximum")
+        if set(build_keywords) - set(allowed):
+            msg = f"build_iterative takes the build keywords {allowed}, not {sorted(set(build_keywords) - set(allowed))}"
+            raise TypeError(msg)
+        if self._psf_size > MAX_PATCH:
+            msg = f"psf_size = {self._psf_size} is not implemented for neighbour-subtracted patches: kernel B1n stops at {MAX_PATCH} pixels"
+            raise NotImplementedError(msg)
+        fitter = star_module.fit_groups if fit == "groups" else star_module.fit_stars
+        psf, counts = self.build(images, stars=stars, **build_keywords)
+        fits = None
+        for _ in range(int(iterations)):
+            fits = fitter(images, stars, psf, radius, device=self._device)
+            psf, counts = self.build_subtracted(images, fits, psf, radius, keep=keep(fits) if callable(keep) else keep, **build_keywords)
+        return psf, counts, fits
+
+
+def build_subtracted(images, fits, psf, radius: float, *, psf_size: int | None = None, device: int = 0, cleanup: str = "host", **keywords):
+    """``ArrayPSFBuilder(psf_size, device, cleanup=cleanup).build_subtracted(images, fits, psf, radius, **keywords)`` as a function;
+    ``psf_size=None`` cuts the patches at the size of the model's cells."""
+    from regularizepsf_amd.stars import model_cube
+
+    size = model_cube(psf)[1].shape[1] if psf_size is None else psf_size
+    return ArrayPSFBuilder(size, device, cleanup=cleanup).build_subtracted(images, fits, psf, radius, **keywords)
+
+
+def build_iterative(images, stars, radius: float, *, psf_size: int, device: int = 0, cleanup: str = "host", **keywords):
+    """``ArrayPSFBuilder(psf_size, device, cleanup=cleanup).build_iterative(images, stars, radius, **keywords)`` as a function."""
+    return ArrayPSFBuilder(psf_size, device, cleanup=cleanup).build_iterative(images, stars, radius, **keywords)

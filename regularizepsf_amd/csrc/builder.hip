@@ -13,6 +13,10 @@
 //                               float64 patch of that size does not fit LDS: a launch is min(items, slots) workgroups of 1024 threads,
 //                               workgroup b works on items b, b + slots, ... in its own slot of a workspace in global memory that
 //                               belongs to the handle.  B2 and the append kernel are size-generic and serve both.
+//   B1n builder_patch_sub_kernel  rpsf_builder_add_frame_subtracted / _device_subtracted, and only then: B1 with its gather replaced by phase 1n
+//                               of rpsf_core_builder_sub.hpp - every pixel of the patch takes out the fitted stars on the patch's own
+//                               neighbour list (built on the host, one list per patch) while it is gathered; everything after the gather is
+//                               B1's own functions.  B1's launch shape and LDS block, one chunk of star records behind it.
 //   rpsf_builder_add_frame_device runs B1 on a dense float32 frame that is already on the device (a finder's, DESIGN.md 3.11, or the caller's).
 //   A scaled builder (rpsf_builder_create_scaled, interpolation_scale = s of the reference) runs B1 and B2 at P = N s on frames that
 //   csrc/scale.hip upscales on the device, brings every averaged P x P cell back to N x N with its kernel B4, and runs B3 at N.
@@ -32,6 +36,7 @@
 #include <vector>
 
 #include "rpsf_core_builder.hpp"
+#include "rpsf_core_builder_sub.hpp"
 #include "rpsf_core_builder_wide.hpp"
 #include "rpsf_core_cleanup.hpp"
 #include "rpsf_core_cleanup_wide.hpp"
@@ -57,6 +62,51 @@ __global__ __launch_bounds__(THREADS) void builder_patch_kernel(B1Params q) {
   const Lds s = carve(builder_lds, N);
   b1_tables(tid, N, q.frac[2 * star], q.frac[2 * star + 1], s);
   b1_gather(tid, THREADS, N, q.image, q.height, q.width, q.corners[2 * star], q.corners[2 * star + 1], s);
+  __syncthreads();
+  b1_prefilter(tid, N, 0, s);
+  __syncthreads();
+  b1_prefilter(tid, N, 1, s);
+  __syncthreads();
+  double v[MAX_PPT];
+  for (int axis = 0; axis < 2; ++axis) {
+    b1_taps_read(tid, THREADS, N, axis, s, v);
+    __syncthreads();
+    b1_taps_write(tid, THREADS, N, s, v);
+    __syncthreads();
+  }
+  b1_scan(tid, THREADS, N, s);
+  __syncthreads();
+  b1_plane(tid, N, s);
+  __syncthreads();
+  b1_finish(tid, THREADS, N, q.saturation, s, q.staging + (size_t)star * N * N);
+  __syncthreads();
+  if (tid == 0) q.flags[star] = b1_verdict(N, q.star_minimum, q.star_maximum, s);
+}
+
+// B1n: B1 with phase 1 replaced (rpsf_core_builder_sub.hpp).  The trip count of the chunk loop is the patch's, the same for every thread of the
+// workgroup: every thread takes part in every barrier.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void builder_patch_sub_kernel(B1Params q, rpsfbn::Sub sub) {
+  extern __shared__ double builder_lds[];
+  const int N = q.N, tid = threadIdx.x, star = blockIdx.x;
+  const Lds s = carve(builder_lds, N);
+  const rpsfbn::Chunk chunk = rpsfbn::carve_chunk(builder_lds, N);
+  const int rr = q.corners[2 * star], rc = q.corners[2 * star + 1];
+  b1_tables(tid, N, q.frac[2 * star], q.frac[2 * star + 1], s);
+  const long long begin = sub.offsets[star], end = sub.offsets[star + 1];
+  if (begin == end) {  // (the same for every thread of the workgroup) nothing to take out: B1's own gather, whose values phase 1n's are when s = 0.0
+    b1_gather(tid, THREADS, N, q.image, q.height, q.width, rr, rc, s);
+  } else {
+    rpsfbn::b1n_begin(tid, THREADS, N, s);
+    for (long long at = begin; at < end; at += rpsfbn::CHUNK) {
+      const int len = end - at < rpsfbn::CHUNK ? (int)(end - at) : rpsfbn::CHUNK;
+      rpsfbn::b1n_stage(tid, sub, at, len, chunk);
+      __syncthreads();
+      rpsfbn::b1n_add(tid, THREADS, N, q.height, q.width, rr, rc, sub, len, chunk, s);
+      __syncthreads();
+    }
+    rpsfbn::b1n_gather(tid, THREADS, N, q.image, q.height, q.width, rr, rc, s);
+  }
   __syncthreads();
   b1_prefilter(tid, N, 0, s);
   __syncthreads();
@@ -167,6 +217,10 @@ struct rpsf_builder {
   Buf<double> frac, cells, cleaned;
   Buf<uint8_t> flags, clean_flags;
   Buf<int64_t> offsets;
+  // B1n: the subtraction set of the frame and the patches' neighbour lists
+  Buf<double> sub_pos, sub_flux;
+  Buf<int> sub_cell, sub_index;
+  Buf<long long> sub_offsets;
   hipEvent_t ev[2] = {nullptr, nullptr};
   double patch_ms = 0, average_ms = 0, clean_ms = 0;
   ~rpsf_builder() {
@@ -306,7 +360,7 @@ static int check_stars(const rpsf_builder* b, int height, int width, int n_stars
 
 static int patches_of_frame(rpsf_builder* b, const float* frame_dev, int height, int width, int n_stars, const int32_t* corners_i32,
                             const double* frac_f64, double saturation_threshold, double star_minimum, double star_maximum,
-                            uint8_t* accepted_u8_host);
+                            uint8_t* accepted_u8_host, const rpsfbn::Sub* sub = nullptr);
 
 extern "C" int rpsf_builder_add_frame(rpsf_builder* b, const void* image_host, int image_is_f64, int height, int width, int n_stars,
                                       const int32_t* corners_i32, const double* frac_f64, double saturation_threshold,
@@ -366,10 +420,10 @@ extern "C" int rpsf_builder_add_frame_device(rpsf_builder* b, const float* frame
                           accepted_u8_host);
 }
 
-// B1 on frame_dev (height x width float32, dense, on the builder's device) and the append of what it accepts
+// B1 - or, with `sub`, B1n - on frame_dev (height x width float32, dense, on the builder's device) and the append of what it accepts
 static int patches_of_frame(rpsf_builder* b, const float* frame_dev, int height, int width, int n_stars, const int32_t* corners_i32,
                             const double* frac_f64, double saturation_threshold, double star_minimum, double star_maximum,
-                            uint8_t* accepted_u8_host) {
+                            uint8_t* accepted_u8_host, const rpsfbn::Sub* sub) {
   const int N = b->N;
   const size_t npix = (size_t)N * N;
   HIP_TRY(b->corners.reserve(2 * (size_t)n_stars));
@@ -383,7 +437,11 @@ static int patches_of_frame(rpsf_builder* b, const float* frame_dev, int height,
   if (b->wide)
     if (const int rc = wide_workspace(b)) return rc;
   HIP_TRY(hipEventRecord(b->ev[0], nullptr));
-  if (b->wide) {
+  if (sub && N > 64) {  // (never a wide handle: the entry points refuse it)
+    hipLaunchKernelGGL(builder_patch_sub_kernel<1024>, dim3(n_stars), dim3(1024), rpsfbn::lds_bytes(N), nullptr, q, *sub);
+  } else if (sub) {
+    hipLaunchKernelGGL(builder_patch_sub_kernel<256>, dim3(n_stars), dim3(256), rpsfbn::lds_bytes(N), nullptr, q, *sub);
+  } else if (b->wide) {
     const int grid = n_stars < rpsfbw::slots_for(N) ? n_stars : rpsfbw::slots_for(N);
     hipLaunchKernelGGL(builder_patch_wide_kernel, dim3(grid), dim3(rpsfbw::THREADS), rpsfbw::lds_bytes(N), nullptr, q, n_stars,
                        b->workspace.p);
@@ -408,6 +466,106 @@ static int patches_of_frame(rpsf_builder* b, const float* frame_dev, int height,
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   b->count += source.size();
+  return RPSF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ B1n (Neighbour-subtracted patches)
+// what both entry points check and do: `frame_dev` is the device frame, or null for the host frame `image_host`
+static int add_frame_subtracted(rpsf_builder* b, const float* frame_dev, const void* image_host, int image_is_f64, int height, int width,
+                                const rpsf_stars_model* model, size_t n_all, const double* positions_host, const double* flux_host,
+                                const int32_t* cells_host, double radius, int n_stars, const int32_t* own_i32, const int32_t* corners_i32,
+                                const double* frac_f64, double saturation_threshold, double star_minimum, double star_maximum,
+                                uint8_t* accepted_u8_host) {
+  const char* name = frame_dev ? "rpsf_builder_add_frame_device_subtracted: " : "rpsf_builder_add_frame_subtracted: ";
+  if (!b || (!frame_dev && !image_host)) return fail(RPSF_E_BADARG, std::string(name) + "null argument");
+  if (n_all && (!model || !positions_host || !flux_host || !cells_host)) return fail(RPSF_E_BADARG, std::string(name) + "null argument");
+  if (n_stars > 0 && (!own_i32 || !corners_i32 || !frac_f64 || !accepted_u8_host)) return fail(RPSF_E_BADARG, std::string(name) + "null argument");
+  if (height < 2 || width < 2) return fail(RPSF_E_BADARG, std::string(name) + "a frame needs at least 2 x 2 pixels");
+  if (n_stars < 0) return fail(RPSF_E_BADARG, std::string(name) + "n_stars is negative");
+  if (const char* why = rpsfn::render_problem(radius, rpsfn::MODE_MODEL)) return fail(RPSF_E_BADARG, std::string(name) + why);
+  if (n_all > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, std::string(name) + "more than 2^30 stars in one call");
+  for (size_t i = 0; i < n_all; ++i)
+    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
+      return fail(RPSF_E_BADARG, std::string(name) + "position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
+  for (int k = 0; k < n_stars; ++k)
+    if (own_i32[k] < -1 || (own_i32[k] >= 0 && (size_t)own_i32[k] >= n_all))
+      return fail(RPSF_E_BADARG, std::string(name) + "own[" + std::to_string(k) + "] is neither -1 nor a star of the set");
+  // the handles are looked at from here on: what the builder cannot do at all comes before what is wrong with the model
+  if (b->wide) return fail(RPSF_E_UNSUPPORTED, std::string(name) + "a wide builder (129 to 256 pixels) cuts no neighbour-subtracted patches");
+  if (b->scale > 1) return fail(RPSF_E_UNSUPPORTED, std::string(name) + "a scaled builder cuts no neighbour-subtracted patches");
+  int model_device = 0, n_cells = 0, model_n = 0;
+  const double* cube = nullptr;
+  if (n_all) {
+    rpsf_detail_stars_model_view(model, &model_device, &n_cells, &model_n, &cube);
+    if (!(radius <= rpsff::max_fit_radius(model_n)))
+      return fail(RPSF_E_BADARG, std::string(name) + "radius " + std::to_string(radius) + " is above min(64, N / 2 - 1) of the model's N = " +
+                                     std::to_string(model_n));
+  }
+  if (n_all && model_device != b->device) return fail(RPSF_E_BADARG, std::string(name) + "the model is on another device than the builder");
+  if (n_stars == 0) return RPSF_OK;
+  if (const int rc = check_stars(b, height, width, n_stars, corners_i32, frac_f64)) return rc;
+  HIP_TRY(hipSetDevice(b->device));
+  if (!frame_dev) {
+    const size_t fpix = (size_t)height * width;
+    HIP_TRY(b->frame.reserve(fpix));
+    if (const int rc = upload_frame_f32(b->frame.p, image_host, image_is_f64, fpix)) return rc;
+    frame_dev = b->frame.p;
+  }
+  if (n_all == 0)  // nothing to take out: B1 itself
+    return patches_of_frame(b, frame_dev, height, width, n_stars, corners_i32, frac_f64, saturation_threshold, star_minimum, star_maximum,
+                            accepted_u8_host);
+  std::vector<long long> offsets;
+  std::vector<int> index;
+  rpsfbn::neighbour_lists(height, width, b->N, (size_t)n_stars, corners_i32, own_i32, n_all, positions_host, flux_host, cells_host, n_cells,
+                          radius, offsets, index);
+  HIP_TRY(b->sub_pos.reserve(2 * n_all));
+  HIP_TRY(b->sub_flux.reserve(n_all));
+  HIP_TRY(b->sub_cell.reserve(n_all));
+  HIP_TRY(b->sub_offsets.reserve(offsets.size()));
+  HIP_TRY(b->sub_index.reserve(index.empty() ? 1 : index.size()));
+  HIP_TRY(hipMemcpy(b->sub_pos.p, positions_host, 2 * n_all * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->sub_flux.p, flux_host, n_all * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->sub_cell.p, cells_host, n_all * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->sub_offsets.p, offsets.data(), offsets.size() * sizeof(long long), hipMemcpyHostToDevice));
+  if (!index.empty()) HIP_TRY(hipMemcpy(b->sub_index.p, index.data(), index.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (b->N > 64) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&builder_patch_sub_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)rpsfbn::lds_bytes(MAX_N)));
+  } else {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&builder_patch_sub_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)rpsfbn::lds_bytes(64)));
+  }
+  const rpsfbn::Sub sub{cube, model_n, radius * radius, model_n / 2.0 - 0.5, b->sub_pos.p, b->sub_flux.p, b->sub_cell.p, b->sub_offsets.p,
+                        b->sub_index.p};
+  return patches_of_frame(b, frame_dev, height, width, n_stars, corners_i32, frac_f64, saturation_threshold, star_minimum, star_maximum,
+                          accepted_u8_host, &sub);
+}
+
+extern "C" int rpsf_builder_add_frame_subtracted(rpsf_builder* b, const void* image_host, int image_is_f64, int height, int width,
+                                                 const rpsf_stars_model* model, size_t n_all, const double* positions_host,
+                                                 const double* flux_host, const int32_t* cells_host, double radius, int n_stars,
+                                                 const int32_t* own_i32, const int32_t* corners_i32, const double* frac_f64,
+                                                 double saturation_threshold, double star_minimum, double star_maximum,
+                                                 uint8_t* accepted_u8_host) {
+  return add_frame_subtracted(b, nullptr, image_host, image_is_f64, height, width, model, n_all, positions_host, flux_host, cells_host, radius,
+                              n_stars, own_i32, corners_i32, frac_f64, saturation_threshold, star_minimum, star_maximum, accepted_u8_host);
+}
+
+extern "C" int rpsf_builder_add_frame_device_subtracted(rpsf_builder* b, const float* frame_dev, int height, int width,
+                                                        const rpsf_stars_model* model, size_t n_all, const double* positions_host,
+                                                        const double* flux_host, const int32_t* cells_host, double radius, int n_stars,
+                                                        const int32_t* own_i32, const int32_t* corners_i32, const double* frac_f64,
+                                                        double saturation_threshold, double star_minimum, double star_maximum,
+                                                        uint8_t* accepted_u8_host) {
+  if (!frame_dev) return fail(RPSF_E_BADARG, "rpsf_builder_add_frame_device_subtracted: null argument");
+  return add_frame_subtracted(b, frame_dev, nullptr, 0, height, width, model, n_all, positions_host, flux_host, cells_host, radius, n_stars,
+                              own_i32, corners_i32, frac_f64, saturation_threshold, star_minimum, star_maximum, accepted_u8_host);
+}
+
+extern "C" int rpsf_builder_subtract_info(int* chunk, int* bucket, size_t* lds_bytes_128) {
+  if (chunk) *chunk = rpsfbn::CHUNK;
+  if (bucket) *bucket = rpsfbn::BUCKET;
+  if (lds_bytes_128) *lds_bytes_128 = rpsfbn::lds_bytes(MAX_N);
   return RPSF_OK;
 }
 

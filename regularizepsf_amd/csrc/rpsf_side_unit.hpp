@@ -15,6 +15,8 @@
 
 RPSF_HIDDEN int rpsf_detail_fail(int code, const std::string& msg);  // rpsf.hip: sets rpsf_last_error of the calling thread
 static inline int fail(int code, const std::string& msg) { return rpsf_detail_fail(code, msg); }
+// stars.hip: what another unit may know of a model handle (builder.hip draws the neighbours of kernel B1n from it); the values stay the model's
+RPSF_HIDDEN void rpsf_detail_stars_model_view(const rpsf_stars_model* model, int* device, int* n_cells, int* N, const double** values_dev);
 #define HIP_TRY(expr)                                                                                               \
   do {                                                                                                              \
     hipError_t e_ = (expr);                                                                                         \

@@ -810,6 +810,10 @@ extern "C" int rpsf_stars_model_create(int device, size_t n_cells, int N, const 
   return RPSF_OK;
 }
 
+void rpsf_detail_stars_model_view(const rpsf_stars_model* m, int* device, int* n_cells, int* N, const double** values_dev) {
+  *device = m->device, *n_cells = m->n_cells, *N = m->N, *values_dev = m->values.p;
+}
+
 extern "C" void rpsf_stars_model_destroy(rpsf_stars_model* m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
