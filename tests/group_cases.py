@@ -312,7 +312,7 @@ def case(name: str) -> dict:
 @functools.lru_cache(maxsize=None)
 def _reference(name: str, mesh_bytes: bytes | None, radius: float) -> tuple:
     c = case(name)
-    level_f = None if mesh_bytes is None else np.frombuffer(mesh_bytes).reshape(-(-SHAPE[0] // c["box"]), -(-SHAPE[1] // c["box"]))
+    level_f = None if mesh_bytes is None else np.frombuffer(mesh_bytes).reshape(-(-c["frame"].shape[0] // c["box"]), -(-c["frame"].shape[1] // c["box"]))
     designs = []
     out = ref_fit_groups(c["frame"], c["mask"], c["box"], level_f, c["cube"], c["positions"], c["cells"], radius, c["fit_background"],
                          c["background"], c["link"], c["max_group"], designs)

@@ -24,42 +24,7 @@ from tests import builder_sub_cases as bc
 pytestmark = pytest.mark.gpu
 
 
-def _psf(case):
-    return rp.IndexedCube([(0, 16 * k) for k in range(len(case["cube"]))], np.asarray(case["cube"]))
-
-
-def _subtracted(case, on_device=False):
-    """Kernel B1n on a case: (flags of every patch, the accepted float32 patches, B1n's device time)."""
-    stack, model = bld._Stack(case["n"], 0, 4), stars._Model(np.asarray(case["cube"]), 0)
-    try:
-        shape = case["frame"].shape
-        frame = to_device(np.asarray(case["frame"])) if on_device else np.asarray(case["frame"])
-        flags = stack.add_frame_subtracted(frame.ptr if on_device else frame, shape, model, case["pos"], case["flux"], case["cell"], case["radius"],
-                                           case["own"], case["rounded"], case["shift"], *case["thresholds"])
-        return flags, stack.patches(), stack.kernel_ms()[0]
-    finally:
-        stack.close()
-        model.close()
-
-
-def _composed(case, rows=None):
-    """The reference of the issue: per patch S10's residual into a device frame with the own star's flux set to NaN, then B1 on that frame
-    with that one star.  (flags, the accepted patches in order)."""
-    psf, shape = _psf(case), case["frame"].shape
-    out = device_empty(shape, np.float32, 0)
-    stack = bld._Stack(case["n"], 0, 4)
-    try:
-        flags = []
-        for k in range(len(case["own"])) if rows is None else rows:
-            flux = np.array(case["flux"])
-            if case["own"][k] >= 0:
-                flux[case["own"][k]] = np.nan
-            rp.subtract_stars(np.asarray(case["frame"]), [np.asarray(case["pos"])], psf, case["radius"], flux=[flux], cells=[np.asarray(case["cell"])],
-                              out=out)
-            flags.append(stack.add_frame_device(out.ptr, shape, case["rounded"][k:k + 1], case["shift"][k:k + 1], *case["thresholds"])[0])
-        return np.array(flags, np.uint8), stack.patches()
-    finally:
-        stack.close()
+_subtracted, _composed = bc.gpu_subtracted, bc.gpu_composed
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1. composition
