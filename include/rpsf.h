@@ -874,6 +874,44 @@ int rpsf_stars_fit_groups_ms(const rpsf_stars* finder, double* ms);
 /* The columns of a row, the largest group, and the groups a workgroup of S11 takes; any pointer may be NULL. */
 int rpsf_stars_fit_groups_info(int* columns, int* max_group, int* groups_per_workgroup);
 
+/* WEIGHTED FITS (kernel S12): rpsf_stars_fit with one weight per pixel, w = 1 / v, and the formal variances of what it
+ * fits.  rpsf_stars_fit's arguments, state rules, return codes and messages, its box, walk, disc, model m, residual d, summation order and
+ * flags.  THE VARIANCE v of a pixel p is a float64, from one of two sources:
+ *   RPSF_STARS_VARIANCE_MAP (0)    v = (double)var[p]: a float32 frame of the finder's shape that rpsf_stars_variance_host / _view brought
+ *                                  to the device (RPSF_E_STATE before such a call).  The two take the route and the rounding of
+ *                                  rpsf_stars_background_host / _view - float64 is rounded to float32 once, a view may have any dtype and
+ *                                  strides of rpsf_view - into a buffer of the finder that is allocated at the first call and freed with
+ *                                  the finder.  They launch no kernel S1 and change nothing else of the finder; the variance frame stays
+ *                                  until the next such call, whatever frames the finder is given in between.
+ *   RPSF_STARS_VARIANCE_MODEL (1)  v = sky_variance + (img[p] > 0 ? (double)img[p] : 0.0) / gain, from the raw float32 pixel, not from d.
+ *                                  sky_variance >= 0 and finite, gain > 0 (+inf: no photon term), not sky_variance == 0 with gain == +inf;
+ *                                  anything else is RPSF_E_BADARG, before anything is launched.  (In MAP mode the two are not read.)
+ * w = 1.0 / v.  A pixel is USABLE when rpsf_stars_fit's rule holds (finite, not masked, on the frame) and w > 0 and w is finite: a v that
+ * is NaN, <= 0, +inf or so small that w overflows takes the pixel out of the fit.  It still counts in n_all and Sm_all and shows as lower
+ * coverage; there is no flag of its own.  PASS 1, per usable pixel, in this order:  wm = w m, wd = w d, Sm += m, Sw += w, Swm += wm,
+ * Swmm += wm m, Swd += wd, Swdm += wd m, Swdd += wd d.  THE SOLVE: with fit_background D = Sw Swmm - Swm Swm, f = (Sw Swdm - Swm Swd) / D,
+ * bg = (Swd - f Swm) / Sw, var_f = Sw / D, var_bg = Swmm / D, cov = - Swm / D; without, D = Swmm, f = Swdm / D, bg = 0, var_f = 1 / D,
+ * var_bg = cov = 0.  FLAGS are rpsf_stars_fit's (TOO_FEW on the usable count n); with any flag f, bg, the three variances and PASS 2's
+ * columns are NaN and the peak sits at (-1, -1).  PASS 2, with e = d - (f m + bg): chi2 = sum w (e e); abs_res = sum |e| and the peak of e
+ * are unweighted, rpsf_stars_fit's.  No square root is taken on the device.  With v = 1 everywhere f, bg, chi2, abs_res and the peak are
+ * rpsf_stars_fit's bit for bit; with v = 2^k everywhere f, bg, abs_res and the peak stay, chi2 is 2^-k times and var_f = 2^k (n / D) of
+ * rpsf_stars_fit's sums, exactly.  A row of out_host is RPSF_STARS_FIT_WEIGHTED_COLUMNS float64:
+ *   y, x, cell, flags, n, n_all, Sm, Sm_all, Sw, Swm, Swmm, Swd, Swdm, Swdd, f, bg, var_f, var_bg, cov, chi2, abs_res, peak_res, peak_e,
+ *   peak_row, peak_col.
+ * n == 0 launches nothing and needs no pointers.  No atomics, no workgroup waits for another, two runs agree bit for bit; nothing of the
+ * finder is replaced.  This is not a PSF-photometry package's fit: the position is given and not fitted, the interpolation is bilinear, the
+ * model is cut at R, and the variances are formal - what the given v imply and nothing else. */
+#define RPSF_STARS_FIT_WEIGHTED_COLUMNS 25
+#define RPSF_STARS_VARIANCE_MAP 0
+#define RPSF_STARS_VARIANCE_MODEL 1
+int rpsf_stars_variance_host(rpsf_stars* finder, const void* variance_host, int variance_is_f64);
+int rpsf_stars_variance_view(rpsf_stars* finder, const rpsf_view* variance);
+int rpsf_stars_fit_weighted(rpsf_stars* finder, const rpsf_stars_model* model, size_t n, const double* positions_host,
+                            const int32_t* cells_host, double radius, int fit_background, int use_mesh, int variance_mode,
+                            double sky_variance, double gain, double* out_host);
+/* Device time of the last S12, milliseconds; 0 when it launched nothing. */
+int rpsf_stars_fit_weighted_ms(const rpsf_stars* finder, double* ms);
+
 /* rpsf_builder_add_frame on a dense float32 frame that is already on the builder's device - a finder's (rpsf_stars_frame) or the caller's
  * own; it is only read, nothing is uploaded but the star list.  On a scaled builder the frame is the SCALED one and height and width are
  * its. */

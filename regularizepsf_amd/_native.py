@@ -195,6 +195,11 @@ _PROTOTYPES = {
     "rpsf_stars_fit_groups": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_double, c_int, c_int, c_double, c_int, c_void_p]),
     "rpsf_stars_fit_groups_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rpsf_stars_fit_groups_info": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "rpsf_stars_variance_host": (c_int, [c_void_p, c_void_p, c_int]),
+    "rpsf_stars_variance_view": (c_int, [c_void_p, POINTER(View)]),
+    "rpsf_stars_fit_weighted": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_double, c_int, c_int, c_int, c_double, c_double,
+                                        c_void_p]),
+    "rpsf_stars_fit_weighted_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rpsf_builder_add_frame_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double, c_double,
                                               c_void_p]),
     "rpsf_builder_add_frame_subtracted": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,

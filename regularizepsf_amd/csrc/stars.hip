@@ -42,6 +42,10 @@
 //                              (rpsf_core_stars_group.hpp), one wave per group fits its members together (the driver of
 //                              rpsf_core_stars_fit_group.hpp), and stars_fit_kernel fits every star that is alone; both write rows of
 //                              their own and nothing the other kernels read
+//   S12 stars_fit_weighted_kernel  rpsf_stars_fit_weighted, and only then: S8 with one weight per pixel, 1 / v with v from the finder's
+//                              variance frame (rpsf_stars_variance_host / _view) or from sky_variance + max(pixel, 0) / gain, and the
+//                              formal variances of flux and background (the driver of rpsf_core_stars_fit_weighted.hpp); it writes rows
+//                              of its own and nothing the other kernels read
 //
 // The phases are the drivers of rpsf_core_stars.hpp.  Launches follow one another on the null stream; no workgroup ever waits for
 // another one, and the only atomics are integer min / max / add - labels and moments are the same on every run.
@@ -57,6 +61,7 @@
 #include "rpsf_core_stars_deblend.hpp"
 #include "rpsf_core_stars_fit.hpp"
 #include "rpsf_core_stars_fit_group.hpp"
+#include "rpsf_core_stars_fit_weighted.hpp"
 #include "rpsf_core_stars_fitpos.hpp"
 #include "rpsf_core_stars_group.hpp"
 #include "rpsf_core_stars_mesh.hpp"
@@ -89,6 +94,10 @@ static_assert(rpsfj::GROUP_COLUMNS == RPSF_STARS_FIT_GROUPS_COLUMNS && rpsfq::MA
                   rpsfq::FLAG_CROWDED == RPSF_STARS_FIT_CROWDED,
               "the group columns, the largest group and the crowded flag of rpsf_core_stars_fit_group.hpp and include/rpsf.h");
 static_assert(rpsfj::s11_lds_bytes() <= 64 * 1024 && rpsfj::s11_lds_bytes() % 16 == 0, "S11's records fit the LDS a launch gets without asking");
+static_assert(rpsfw::FITW_COLUMNS == RPSF_STARS_FIT_WEIGHTED_COLUMNS && rpsfw::VARIANCE_MAP == RPSF_STARS_VARIANCE_MAP &&
+                  rpsfw::VARIANCE_MODEL == RPSF_STARS_VARIANCE_MODEL,
+              "the weighted fit's columns and variance modes of rpsf_core_stars_fit_weighted.hpp and include/rpsf.h");
+static_assert(rpsfw::s12_lds_bytes() <= 64 * 1024 && rpsfw::s12_lds_bytes() % 16 == 0, "S12's records fit the LDS a launch gets without asking");
 
 static_assert(rpsfn::MODE_MODEL == RPSF_STARS_RENDER_MODEL && rpsfn::MODE_RESIDUAL == RPSF_STARS_RENDER_RESIDUAL &&
                   rpsfn::MODE_RESIDUAL_MESH == RPSF_STARS_RENDER_RESIDUAL_MESH,
@@ -211,6 +220,13 @@ __global__ __launch_bounds__(WALK_THREADS) void stars_fit_group_kernel(Frame fr,
   rpsfj::s11_fit_group(ctx, fr, L, use_mesh, model, fit, pos, cell, groups, (long)blockIdx.x * WALK_WAVES, stars_lds, out);
 }
 
+__global__ __launch_bounds__(WALK_THREADS) void stars_fit_weighted_kernel(Frame fr, const double* L, const int* none, int use_mesh,
+                                                                          rpsff::Model model, rpsff::Fit fit, rpsfw::Variance var,
+                                                                          const double* pos, const int* cell, long count, double* out) {
+  GpuCtx ctx;
+  rpsfw::s12_fit_weighted(ctx, fr, L, none, use_mesh, model, fit, var, pos, cell, count, (long)blockIdx.x * WALK_WAVES, stars_lds, out);
+}
+
 // S10's context: the accumulator of a thread's pixel is a register of that thread
 struct RenderCtx : GpuCtx {
   double s;
@@ -316,6 +332,12 @@ struct rpsf_stars {
   Buf<int> group_cell, group_members, group_lone_cell;
   Buf<long long> group_starts;
   double group_ms = 0;
+  // S12 (rpsf_stars_fit_weighted): likewise its own, and the variance frame of rpsf_stars_variance_host / _view (allocated by the first)
+  Buf<float> variance;
+  bool have_variance = false;
+  Buf<double> fitw_pos, fitw_out;
+  Buf<int> fitw_cell;
+  double fitw_ms = 0;
   // the deblend option: everything below is allocated by the first call that needs it
   bool deblend = false;
   double contrast = 0.005, prominence = 1.0;
@@ -1251,5 +1273,82 @@ extern "C" int rpsf_stars_frame(rpsf_stars* s, const float** frame_dev, int* hei
 extern "C" int rpsf_stars_mesh_ms(const rpsf_stars* s, double* ms) {
   if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
   *ms = s->mesh_ms;
+  return RPSF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ S12 (Weighted fits)
+// The variance frame takes the frame's own route into a float32 buffer of its own: no S1, no mask, and the frame, the meshes, the
+// detections and `generation` stay what they were.
+extern "C" int rpsf_stars_variance_view(rpsf_stars* s, const rpsf_view* variance) {
+  if (!s || !variance) return fail(RPSF_E_BADARG, "null argument");
+  bool empty = false;
+  if (const char* why = rpsfconv::view_problem(variance, false, &empty)) return fail(RPSF_E_BADARG, std::string("variance: ") + why);
+  if (variance->rows != s->H || variance->cols != s->W)
+    return fail(RPSF_E_BADARG, "the view is " + std::to_string(variance->rows) + " x " + std::to_string(variance->cols) + ", the finder's frame " +
+                                   std::to_string(s->H) + " x " + std::to_string(s->W));
+  HIP_TRY(hipSetDevice(s->device));
+  s->have_variance = false;
+  HIP_TRY(s->variance.reserve((size_t)s->npix()));
+  if (rpsfconv::dense_f32(*variance)) {  // the same bits, device to device; the caller's array is only ever read
+    HIP_TRY(hipMemcpyAsync(s->variance.p, variance->data, (size_t)s->npix() * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+  } else if (const int rc = rpsf_conv_gather(*variance, 1, 0, s->variance.p, 0, nullptr)) {  // C1
+    return rc;
+  }
+  s->have_variance = true;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_variance_host(rpsf_stars* s, const void* variance_host, int variance_is_f64) {
+  if (!s || !variance_host) return fail(RPSF_E_BADARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  s->have_variance = false;
+  HIP_TRY(s->variance.reserve((size_t)s->npix()));
+  if (const int rc = upload_frame_f32(s->variance.p, variance_host, variance_is_f64, (size_t)s->npix())) return rc;
+  s->have_variance = true;
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_fit_weighted(rpsf_stars* s, const rpsf_stars_model* model, size_t n, const double* positions_host,
+                                       const int32_t* cells_host, double radius, int fit_background, int use_mesh, int variance_mode,
+                                       double sky_variance, double gain, double* out_host) {
+  if (!s || !model || (n && (!positions_host || !cells_host || !out_host))) return fail(RPSF_E_BADARG, "null argument");
+  if (const char* why = rpsff::fit_problem(radius, fit_background)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit_weighted: ") + why);
+  if (const char* why = rpsfw::variance_problem(variance_mode, sky_variance, gain))
+    return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit_weighted: ") + why);
+  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_fit_weighted: more than 2^30 positions in one call");
+  for (size_t i = 0; i < n; ++i)
+    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
+      return fail(RPSF_E_BADARG, "rpsf_stars_fit_weighted: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
+  if (!(radius <= rpsff::max_fit_radius(model->N)))
+    return fail(RPSF_E_BADARG, "rpsf_stars_fit_weighted: radius " + std::to_string(radius) + " is above min(64, N / 2 - 1) of the model's N = " +
+                                   std::to_string(model->N));
+  if (model->device != s->device) return fail(RPSF_E_BADARG, "rpsf_stars_fit_weighted: the model is on another device than the finder");
+  if (!s->have_mesh) return fail(RPSF_E_STATE, "rpsf_stars_fit_weighted before a rpsf_stars_background_view / _host / _scaled of the frame");
+  if (variance_mode == RPSF_STARS_VARIANCE_MAP && !s->have_variance)
+    return fail(RPSF_E_STATE, "rpsf_stars_fit_weighted with RPSF_STARS_VARIANCE_MAP before a rpsf_stars_variance_view / _host");
+  s->fitw_ms = 0;
+  if (n == 0) return RPSF_OK;  // nothing to launch
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(s->fitw_pos.reserve(2 * n));
+  HIP_TRY(s->fitw_cell.reserve(n));
+  HIP_TRY(s->fitw_out.reserve(RPSF_STARS_FIT_WEIGHTED_COLUMNS * n));
+  HIP_TRY(hipMemcpy(s->fitw_pos.p, positions_host, 2 * n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->fitw_cell.p, cells_host, n * sizeof(int32_t), hipMemcpyHostToDevice));
+  const rpsff::Model cube{model->values.p, model->n_cells, model->N};
+  const rpsff::Fit fit = rpsff::make_fit(radius, fit_background, model->N);
+  const rpsfw::Variance var{variance_mode == RPSF_STARS_VARIANCE_MAP ? s->variance.p : nullptr, variance_mode, sky_variance, gain};
+  if (const int rc = timed(s, &s->fitw_ms, [&] {
+        hipLaunchKernelGGL(stars_fit_weighted_kernel, dim3((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS),
+                           rpsfw::s12_lds_bytes(), nullptr, s->view(), s->level_f.p, s->none.p, use_mesh != 0, cube, fit, var, s->fitw_pos.p,
+                           s->fitw_cell.p, (long)n, s->fitw_out.p);
+      }))
+    return rc;
+  HIP_TRY(hipMemcpy(out_host, s->fitw_out.p, RPSF_STARS_FIT_WEIGHTED_COLUMNS * n * sizeof(double), hipMemcpyDeviceToHost));
+  return RPSF_OK;
+}
+
+extern "C" int rpsf_stars_fit_weighted_ms(const rpsf_stars* s, double* ms) {
+  if (!s || !ms) return fail(RPSF_E_BADARG, "null argument");
+  *ms = s->fitw_ms;
   return RPSF_OK;
 }

@@ -59,6 +59,12 @@ constant, positions fixed (kernel S11, ``rpsf_stars_fit_groups``; DESIGN.md 3.7 
 the host.  It uses ``fit_stars``' and ``subtract_stars``' definitions, so the three agree bit for bit where they meet, and it shares
 their limits: uniform weights, bilinear interpolation, the model cut at ``R``, the cell fixed.  Positions are not fitted jointly, and
 nothing guards near-coincident stars but ``DEGENERATE`` at a non-positive pivot.
+
+``fit_stars_weighted`` is ``fit_stars`` with a weight ``1 / v`` per pixel and the formal errors of flux and background (kernel S12,
+``rpsf_stars_fit_weighted``; DESIGN.md 3.7 "Weighted fits"): ``v`` from a variance map or from ``sky_variance + max(pixel, 0) / gain``, a pixel
+without a usable variance left out like a masked one, ``chi2`` in units of the variances, ``flux_err``, ``snr`` and ``chi2_reduced`` per star.
+With ``v = 1`` it is ``fit_stars`` bit for bit.  Positions are fixed, the model is bilinear and cut at ``R``, the errors are what the given
+variances imply and nothing else, and ``fit_positions`` and ``fit_groups`` stay unweighted.
 """
 
 from __future__ import annotations
@@ -96,6 +102,10 @@ FITPOS_RAN_AWAY, FITPOS_NOT_CONVERGED, FITPOS_SINGULAR, FITPOS_SKIPPED = 1, 2, 4
 # a row of kernel S11 (RPSF_STARS_FIT_GROUPS_COLUMNS float64): S8's columns, then the group's; the flag of rpsf_stars_link_groups
 GROUP_COLUMNS = (*FIT_COLUMNS, "group", "group_size", "group_n", "group_chi2", "group_abs_res")
 CROWDED, MAX_GROUP = 16, 8
+# a row of kernel S12 (RPSF_STARS_FIT_WEIGHTED_COLUMNS float64; S8's flags) and its variance modes (RPSF_STARS_VARIANCE_*)
+FITW_COLUMNS = ("row", "col", "cell", "flags", "n_use", "n_all", "sm", "sm_all", "sw", "swm", "swmm", "swd", "swdm", "swdd", "flux", "background",
+                "var_flux", "var_background", "cov", "chi2", "abs_res", "peak_res", "peak_e", "peak_row", "peak_col")
+VARIANCE_MAP, VARIANCE_MODEL = 0, 1
 # the modes of kernel S10 (RPSF_STARS_RENDER_* of include/rpsf.h)
 RENDER_MODEL, RENDER_RESIDUAL, RENDER_RESIDUAL_MESH = 0, 1, 2
 DEBLEND_OPTIONS = {"deblend": False, "deblend_contrast": 0.005, "deblend_prominence": 1.0}  # contrast: sep's deblend_cont
@@ -292,6 +302,46 @@ class _Finder:
         """Device time of the last S8; 0.0 when it launched nothing."""
         ms = ctypes.c_double(0)
         self._native.check(self._native.lib().rpsf_stars_fit_ms(self._handle, ctypes.byref(ms)))
+        return ms.value
+
+    def variance(self, frame) -> None:
+        """The variance frame of ``fit_weighted``'s map mode: a host array (uploaded, float64 rounded to float32 once) or a 2-D
+        ``DeviceArray`` (read where it lies), of the finder's shape.  Nothing else of the finder changes; it stays until the next call."""
+        n = self._native
+        if isinstance(frame, np.ndarray):
+            if frame.shape != self.shape:
+                msg = f"A variance frame of shape {frame.shape} does not fit a finder of shape {self.shape}"
+                raise IncorrectShapeError(msg)
+            if frame.dtype != np.float32:
+                frame = frame.astype(np.float64, copy=False)
+            frame = np.ascontiguousarray(frame)
+            n.check(n.lib().rpsf_stars_variance_host(self._handle, n._ptr(frame), int(frame.dtype == np.float64)))
+        else:
+            frame.synchronize()  # the finder's launches are on the null stream
+            view = frame._view2d()
+            n.check(n.lib().rpsf_stars_variance_view(self._handle, ctypes.byref(view)))
+
+    def fit_weighted(self, model, positions: np.ndarray, cells, radius: float, fit_background: bool = True, use_mesh: bool = True,
+                     sky_variance: float | None = None, gain: float = np.inf) -> np.ndarray:
+        """Kernel S12 on the frame given to ``background_device`` / ``background_scaled`` last, S8's arguments: ``sky_variance`` None takes
+        the variance frame given to ``variance`` last, a number the noise model ``sky_variance + max(pixel, 0) / gain``.
+        (k, len(FITW_COLUMNS)) float64.  Nothing of the finder is replaced."""
+        n = self._native
+        positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 2)
+        cells = np.ascontiguousarray(cells, np.int32).ravel()
+        if len(cells) != len(positions):
+            msg = f"{len(cells)} cells for {len(positions)} positions"
+            raise ValueError(msg)
+        out = np.empty((len(positions), len(FITW_COLUMNS)))
+        mode, sky = (VARIANCE_MAP, 0.0) if sky_variance is None else (VARIANCE_MODEL, float(sky_variance))
+        n.check(n.lib().rpsf_stars_fit_weighted(self._handle, model._handle, len(positions), n._ptr(positions), n._ptr(cells), float(radius),
+                                                int(bool(fit_background)), int(bool(use_mesh)), mode, sky, float(gain), n._ptr(out)))
+        return out
+
+    def fit_weighted_ms(self) -> float:
+        """Device time of the last S12; 0.0 when it launched nothing."""
+        ms = ctypes.c_double(0)
+        self._native.check(self._native.lib().rpsf_stars_fit_weighted_ms(self._handle, ctypes.byref(ms)))
         return ms.value
 
     def fit_positions(self, model, positions: np.ndarray, cells, radius: float, fit_background: bool = True, max_iter: int = 16,
@@ -1111,6 +1161,170 @@ def fit_stars(images, stars, psf, radius: float, mask=None, *, background: str =
         for frame, m, p, c in zip(frames, masks, positions, cells):
             finder.background_device(frame, m)
             out.append(fit_from_sums(finder.fit(model, p, c, radius, bool(fit_background), background == "mesh"), bool(fit_background)))
+        return out
+    finally:
+        if model is not None:
+            model.close()
+        finder.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------- weighted fits
+WEIGHTED_FIT_FIELDS = (*FIT_FIELDS, "sw", "swm", "flux_err", "background_err", "flux_background_cov", "snr", "chi2_reduced")
+
+
+def weighted_fit_dtype() -> np.dtype:
+    """The structured dtype of ``fit_stars_weighted``: ``fit_dtype``'s fields with their kinds, then ``sw, swm, flux_err, background_err,
+    flux_background_cov, snr, chi2_reduced`` (float64)."""
+    kinds = {name: fit_dtype()[name] for name in FIT_FIELDS}
+    return np.dtype([(name, kinds.get(name, np.float64)) for name in WEIGHTED_FIT_FIELDS])
+
+
+def weighted_fit_from_sums(rows: np.ndarray, fit_background: bool = True) -> np.ndarray:
+    """The structured result (``weighted_fit_dtype``) of S12's rows, everything derived in NumPy float64: ``fit_from_sums``' ``coverage``,
+    ``dof``, ``residual_fraction`` and booleans; ``smm, sd, sdm, sdd`` are the weighted sums ``sum w m m, sum w d, sum w d m, sum w d d``;
+    ``flux_err = sqrt(var_flux)``, ``background_err = sqrt(var_background)``, ``flux_background_cov``, ``snr = flux / flux_err``,
+    ``chi2_reduced = chi2 / dof`` (NaN when ``dof <= 0``) and ``rms = sqrt(chi2_reduced)``."""
+    rows = np.asarray(rows, np.float64).reshape(-1, len(FITW_COLUMNS))
+    col = {name: rows[:, j] for j, name in enumerate(FITW_COLUMNS)}
+    out = np.empty(len(rows), weighted_fit_dtype())
+    for name in ("row", "col", "flux", "background", "chi2", "abs_res", "peak_res", "peak_e", "peak_row", "peak_col", "sm", "sm_all", "sw", "swm"):
+        out[name] = col[name]
+    for name, source in (("smm", "swmm"), ("sd", "swd"), ("sdm", "swdm"), ("sdd", "swdd"), ("flux_background_cov", "cov")):
+        out[name] = col[source]
+    for name in ("cell", "flags", "n_use", "n_all"):
+        out[name] = col[name].astype(np.int32)
+    out["dof"] = out["n_use"] - (2 if fit_background else 1)
+    for name, bit in (("no_mesh", NO_MESH), ("too_few", TOO_FEW), ("degenerate", DEGENERATE), ("bad_cell", BAD_CELL)):
+        out[name] = (out["flags"] & bit) != 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dof = out["dof"].astype(np.float64)
+        out["coverage"] = col["sm"] / col["sm_all"]
+        out["chi2_reduced"] = np.where(dof > 0, col["chi2"] / np.where(dof > 0, dof, np.nan), np.nan)
+        out["rms"] = np.sqrt(out["chi2_reduced"])
+        out["residual_fraction"] = col["abs_res"] / (np.abs(col["flux"]) * np.abs(col["sm"]))
+        out["flux_err"] = np.sqrt(col["var_flux"])
+        out["background_err"] = np.sqrt(col["var_background"])
+        out["snr"] = col["flux"] / out["flux_err"]
+    return out
+
+
+def _variance_frames(variance, frames: list, device: int) -> list:
+    """One variance frame per frame of ``frames``: host arrays for host frames, 2-D ``DeviceArray`` s for device frames."""
+    from regularizepsf_amd.device_array import as_device_array
+
+    on_device = not isinstance(frames[0], np.ndarray)
+    shape = tuple(frames[0].shape)
+    many = isinstance(variance, (list, tuple))
+    given = list(variance) if many else [variance]
+    if not given:
+        msg = "variance is an empty list"
+        raise ValueError(msg)
+    if any(is_device_array(v) for v in given) != on_device or (on_device and not all(is_device_array(v) for v in given)):
+        msg = ("variance and images must live in the same place: host arrays with host frames, device arrays with device frames "
+               "(to_host / to_device bring one to the other)")
+        raise TypeError(msg)
+    if on_device:
+        given = [as_device_array(v, device, what="variance") for v in given]
+    else:
+        given = [np.asarray(v) for v in given]
+        for v in given:
+            if np.iscomplexobj(v) or v.dtype.kind not in "fiub":
+                msg = f"variance must hold real numbers, not {v.dtype}"
+                raise TypeError(msg)
+    if not many and given[0].ndim == 3:
+        given = [given[0][i] for i in range(given[0].shape[0])]
+        many = True
+    if not many:
+        given = given * len(frames)
+    if len(given) != len(frames):
+        msg = f"variance has {len(given)} entries for {len(frames)} frames"
+        raise ValueError(msg)
+    for v in given:
+        if tuple(v.shape) != shape:
+            msg = f"A variance frame of shape {tuple(v.shape)} does not fit frames of shape {shape}"
+            raise IncorrectShapeError(msg)
+    return given
+
+
+def fit_stars_weighted(images, stars, psf, radius: float, mask=None, *, variance=None, sky_variance: float | None = None,
+                       gain: float | None = None, background: str = "mesh", box: int = 64, fit_background: bool = True, cells=None,
+                       device: int = 0) -> list[np.ndarray]:
+    """``fit_stars`` with one weight per pixel, ``w = 1 / v``, and the formal errors of what it fits: a list of NumPy structured arrays
+    (``weighted_fit_dtype``), one per frame and one row per position.  The dtype holds every field of ``fit_dtype`` by name, so
+    ``cell_fit_summary``, ``subtract_stars``, ``build_subtracted`` and its ``keep=`` take the result as it is, and adds ``sw, swm, flux_err,
+    background_err, flux_background_cov, snr, chi2_reduced``.
+
+    ``images``, ``stars``, ``psf``, ``radius``, ``mask``, ``background``, ``box``, ``fit_background``, ``cells`` and ``device`` are
+    ``fit_stars``'.  The variance ``v`` of a pixel comes from exactly one of two sources (anything else is a ``ValueError``):
+
+    ``variance``: a map - one array of the frames' shape for all frames, or one per frame (a list, or a 3-D array).  Host arrays go with host
+    frames; ``DeviceArray`` s, or objects with ``__cuda_array_interface__``, with the dtypes and strides ``apply`` takes, go with device
+    frames; mixing the two is a ``TypeError``, a wrong shape an ``IncorrectShapeError``.  The map is rounded to float32 once, as a frame
+    is, and ``v = (double) map[p]``.
+
+    ``sky_variance`` (and ``gain``): the noise model ``v = sky_variance + max(pixel, 0) / gain`` on the raw float32 pixel, not on the
+    background-subtracted one.  ``sky_variance >= 0`` and finite, ``gain > 0``; ``gain=None`` is ``+inf`` and drops the photon term, and
+    then ``sky_variance`` must be positive.  ``gain`` is only allowed with ``sky_variance``.
+
+    Kernel S12 (``rpsf_stars_fit_weighted``; DESIGN.md 3.7 "Weighted fits") is S8 with weights: the same box, disc ``q <= R^2``, model
+    ``m``, residual ``d``, summation order and flags.  A pixel is usable when ``fit_stars``' rule holds (finite, unmasked, on the frame)
+    and ``w = 1 / v`` is positive and finite: a ``v`` that is NaN, ``<= 0``, ``+inf`` or so small that ``w`` overflows takes the pixel out
+    of the fit.  It still counts in ``n_all`` and ``sm_all`` and shows as lower ``coverage``; there is no flag of its own.  Over the usable
+    pixels: ``n_use``, ``sm = sum m`` (unweighted, so ``coverage = sm / sm_all`` keeps its meaning), ``sw = sum w``, ``swm = sum w m``,
+    and in the fields ``smm, sd, sdm, sdd`` the weighted sums ``sum w m^2, sum w d, sum w d m, sum w d^2``.  With ``fit_background``:
+    ``D = sw smm - swm^2``, ``flux = (sw sdm - swm sd) / D``, ``background = (sd - flux swm) / sw``, ``var(flux) = sw / D``,
+    ``var(background) = smm / D``, ``flux_background_cov = - swm / D``; without: ``D = smm``, ``flux = sdm / D``, ``background = 0``,
+    ``var(flux) = 1 / D``, the other two 0.  Flags are ``fit_stars``' (``TOO_FEW`` on ``n_use``, ``DEGENERATE`` on ``D``); with any of
+    them ``flux``, ``background``, the errors and the residual's columns are NaN.  With ``e = d - (flux m + background)``: ``chi2 = sum w
+    e^2``; ``abs_res = sum |e|``, ``residual_fraction`` and the peak are unweighted, ``fit_stars``'.  Derived here in NumPy float64
+    (``weighted_fit_from_sums``): ``flux_err = sqrt(var(flux))``, ``background_err``, ``snr = flux / flux_err``, ``dof = n_use - 2``
+    (``- 1`` without a fitted background), ``chi2_reduced = chi2 / dof`` (NaN when ``dof <= 0``) and ``rms = sqrt(chi2_reduced)``.
+
+    With ``v = 1`` everywhere ``flux``, ``background``, ``chi2``, ``abs_res`` and the peak are ``fit_stars``' bit for bit.  With ``v = 2^k``
+    everywhere ``flux``, ``background``, ``abs_res`` and the peak stay, ``chi2`` is ``2^-k`` times ``fit_stars``' and ``var(flux)`` is
+    ``2^k n / D`` of ``fit_stars``' sums, exactly.
+
+    What this is NOT: positions are fixed, not fitted (``refine_stars`` and ``fit_positions`` supply them); the model is bilinear and cut at
+    ``R``; the errors are formal - what the given variances imply for a linear fit, and nothing else: no model error, no position error, no
+    correlation between pixels, and wrong variances give wrong errors; ``fit_positions`` and ``fit_groups`` stay unweighted.
+    """
+    if (variance is None) == (sky_variance is None):
+        msg = "give the pixel variances either as a map (variance=) or as a noise model (sky_variance=, gain=), not both and not neither"
+        raise ValueError(msg)
+    if gain is not None and sky_variance is None:
+        msg = "gain belongs to the noise model: it is only allowed with sky_variance"
+        raise ValueError(msg)
+    if sky_variance is not None:
+        try:
+            sky_variance, gain = float(sky_variance), np.inf if gain is None else float(gain)
+        except (TypeError, ValueError) as error:
+            msg = f"sky_variance and gain must be numbers, not {sky_variance!r} and {gain!r}"
+            raise ValueError(msg) from error
+        if not (sky_variance >= 0.0 and np.isfinite(sky_variance)):
+            msg = f"sky_variance must be finite and not negative, got {sky_variance}"
+            raise ValueError(msg)
+        if not gain > 0.0:
+            msg = f"gain must be positive (None or inf: no photon term), got {gain}"
+            raise ValueError(msg)
+        if sky_variance == 0.0 and np.isinf(gain):
+            msg = "sky_variance = 0 without a gain leaves no variance at all"
+            raise ValueError(msg)
+    frames, masks, positions, cells, values, radius = _fit_inputs(images, stars, psf, radius, mask, background, box, fit_background, cells,
+                                                                  device)
+    variances = [None] * len(frames) if variance is None else _variance_frames(variance, frames, device)
+    finder = _Finder(frames[0].shape, box, device)
+    model = None
+    try:
+        model = _Model(values, device)
+        out, last = [], None
+        for frame, m, p, c, v in zip(frames, masks, positions, cells, variances):
+            finder.background_device(frame, m)
+            if v is not None and v is not last:  # (one map for all frames goes up once)
+                finder.variance(v)
+                last = v
+            rows = finder.fit_weighted(model, p, c, radius, bool(fit_background), background == "mesh", sky_variance,
+                                       np.inf if gain is None else gain)
+            out.append(weighted_fit_from_sums(rows, bool(fit_background)))
         return out
     finally:
         if model is not None:
