@@ -111,8 +111,14 @@ enum {
   RPSF_OPT_HEAD_KPREFETCH = 9, /* 0 / 1: persistent launches of a 256-pixel plan - the head summing workgroups touch the transfer kernel of the
                                  first round's patches before they sum (default 0: measured a loss; ignored by other plans).
                                  Changes no value of the result. */
-  RPSF_OPT_SAT_GROUP = 10     /* 0 automatic (scratch under 1 GiB), else 1..65535 frames per frame-group of the batched device
+  RPSF_OPT_SAT_GROUP = 10,    /* 0 automatic (scratch under 1 GiB), else 1..65535 frames per frame-group of the batched device
                                  saturation route.  Changes no value of the result. */
+  RPSF_OPT_PIPELINE = 11      /* 0 / 1: back-to-back rpsf_apply_device calls of a 256-pixel plan with stream == NULL alternate between two streams
+                                 of the plan, so that the head of one apply runs under the tail of the last (default 1 for 256-pixel plans, ignored
+                                 by the others).  Applies still complete in call order per pixel; everything else
+                                 the plan does joins the two streams first.  A plan whose stream handle was taken (rpsf_plan_stream) keeps
+                                 to one stream until the option is set to 1 again; a plan with a CU mask keeps to one for good.  Changes no
+                                 value of the result. */
 };
 int rpsf_plan_set_option(rpsf_plan* plan, int option, int value);
 int rpsf_plan_sweep_info(const rpsf_plan* plan, int* regions, long* jobs, long* patch_slots, int* slabs_per_phase);
@@ -132,7 +138,8 @@ int rpsf_plan_set_reserved_cus(rpsf_plan* plan, int cus);
  * units set in `mask` (bit i of word i / 32, hipExtStreamCreateWithCUMask's numbering; `words` uint32), its persistent launches are
  * sized for them; rpsf_stream_create makes a stream masked to whatever the caller passes (NULL: unmasked).  The pipelined seam exchange
  * gives RCCL's kernels and K4 a handful of CUs of their own this way (rpsf_plan_set_reserved_cus only leaves CUs unclaimed - a kernel
- * dispatched a moment before the persistent launch still lands on CUs that launch is waiting for). */
+ * dispatched a moment before the persistent launch still lands on CUs that launch is waiting for).  A masked plan gives up its second
+ * launch lane, which is not masked: RPSF_OPT_PIPELINE has no effect on it from then on. */
 int rpsf_plan_set_cu_mask(rpsf_plan* plan, const uint32_t* mask, int words);
 int rpsf_stream_create(int device, const uint32_t* mask, int words, void** stream);
 int rpsf_stream_destroy(void* stream);
@@ -272,7 +279,9 @@ int rpsf_saturation_fill_batch_device(rpsf_plan* plan, const float* images_host,
  * (uncovered ones with 0).  image_dev / out_dev must be ordinary device memory of the plan's device
  * (hipMalloc: coarse-grained) - the atomic overlap-add mode uses hardware float atomics, which
  * fine-grained or host-mapped memory does not support.  A plan serves one apply at a time: a call on a
- * different stream than the previous one waits for that one (the plan's scratch is shared). */
+ * different stream than the previous one waits for that one (the plan's scratch is shared).  With stream == NULL, back-to-back applies of a
+ * 256-pixel plan may overlap head under tail (RPSF_OPT_PIPELINE); they complete in call order per pixel, and every other call on the plan,
+ * rpsf_device_synchronize included, sees them complete as before. */
 int rpsf_apply_device(rpsf_plan* plan, const void* image_dev, void* out_dev, const rpsf_geometry* geom, void* stream);
 /* Run `iters` back-to-back device-resident applies on the plan's stream, each bracketed by HIP events of its own, one
  * synchronisation at the end (the launches queue up as in a caller's loop): total_ms[i] covers the whole apply
@@ -419,7 +428,8 @@ int rpsf_saturation_fill_masked_device(rpsf_plan* plan, const float* images_host
                                        int n_masks, size_t mask_frame_bytes, int64_t mask_row_stride, int64_t mask_col_stride,
                                        int fill_nonfinite, float* padded_host, uint8_t* masks_host, int* groups_per_frame_or_null,
                                        int* masked_per_frame_or_null);
-/* The plan's own stream (hipStream_t), for callers that enqueue follow-up work such as the seam exchange. */
+/* The plan's own stream (hipStream_t), for callers that enqueue follow-up work such as the seam exchange.  The plan cannot know what a caller
+ * puts on it: the call joins the plan's two launch lanes (RPSF_OPT_PIPELINE) and the plan keeps to this one stream from then on. */
 void* rpsf_plan_stream(rpsf_plan* plan);
 
 /* ArrayPSFTransform.construct arithmetic, transform.py:78-82:

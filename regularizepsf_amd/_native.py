@@ -346,7 +346,7 @@ class Plan:
         check(lib().rpsf_plan_set_overlap_mode(self._handle, {"auto": 0, "atomic": 1, "planes": 2, "direct": 3, "sweep": 4}[mode]))
 
     OPTIONS = {"persist": 1, "fuse": 2, "k_cached": 3, "plane_nt": 4, "host_bands": 5, "stream_group": 6, "stream_depth": 7, "debug_orphan": 8,
-               "head_kprefetch": 9, "sat_group": 10}
+               "head_kprefetch": 9, "sat_group": 10, "pipeline": 11}
 
     def set_option(self, name: str, value: int) -> None:
         """Pin a launch option of the plan (include/rpsf.h, RPSF_OPT_*): what tests and callers may choose instead of environment variables."""

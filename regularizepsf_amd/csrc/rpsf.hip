@@ -59,6 +59,17 @@ static int dispatch_v3(int N, F&& f) {
 }
 static bool has_v3(int N) { return sweep_patch_size(N); }
 
+// The plan's error word: page-locked, set by a kernel whose bounded wait ran out (1: the sweep kernel's jobs, 2: the gate of the persistent 256-pixel
+// kernel) and read by rpsf_detail_sweep_check.  A view's kernels report through its parent's word.
+static int ensure_error_word(rpsf_plan* p) {
+  SweepPath& sw = p->sweep;
+  if (p->parent || sw.err) return RPSF_OK;
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sw.err.p), 64, hipHostMallocMapped));
+  std::memset(sw.err, 0, 64);
+  HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&sw.d_err), sw.err, 0));
+  return RPSF_OK;
+}
+
 // Regions and job lists of the sweep kernel for `target_regions` workgroups (rpsf_plan3.hpp); replaces the plan's previous lists
 static int build_sweep_lists(rpsf_plan* p, int target_regions) {
   const int nli = p->nti - 1, nlj = p->ntj - 1;
@@ -75,11 +86,7 @@ static int build_sweep_lists(rpsf_plan* p, int target_regions) {
     HIP_TRY(sw.d_zero.alloc(16));
     HIP_TRY(hipMemset(sw.d_zero, 0, 64));
   }
-  if (!p->parent && !sw.err) {  // (a view's kernel reports through its parent's word)
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sw.err.p), 64, hipHostMallocMapped));
-    std::memset(sw.err, 0, 64);
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&sw.d_err), sw.err, 0));
-  }
+  if (const int rc = ensure_error_word(p); rc != RPSF_OK) return rc;
   p->sweep.n_regions = (int)plan.regions.size(), p->sweep.ks = plan.ks, p->sweep.slabs = plan.slabs, p->sweep.patch_slots = plan.patch_slots;
   p->sweep.ok = true;
 #if defined(RPSF3_STAMPS) || defined(RPSF3_DUMP)
@@ -118,10 +125,13 @@ static int setup_lattice(rpsf_plan* p) {
     HIP_TRY(p->patch.d_sum_order.upload(t.sum_order.data(), t.sum_order.size()));
     HIP_TRY(p->patch.d_tile_done.alloc(t.sum_order.size()));
     HIP_TRY(hipMemset(p->patch.d_tile_done, 0, t.sum_order.size() * sizeof(uint32_t)));
-    HIP_TRY(p->patch.d_sum_queue.alloc(1));
-    HIP_TRY(hipMemset(p->patch.d_sum_queue, 0, sizeof(uint32_t)));
-    HIP_TRY(p->patch.d_xq.alloc(8 * 32));
-    HIP_TRY(hipMemset(p->patch.d_xq, 0, 8 * 32 * sizeof(uint32_t)));
+    // (queue words: a set per launch lane - two launches that draw at once must not take each other's positions, rpsf_lanes.hpp)
+    HIP_TRY(p->patch.d_sum_queue.alloc(2 * 32));
+    HIP_TRY(hipMemset(p->patch.d_sum_queue, 0, 2 * 32 * sizeof(uint32_t)));
+    HIP_TRY(p->patch.d_xq.alloc(2 * 8 * 32));
+    HIP_TRY(hipMemset(p->patch.d_xq, 0, 2 * 8 * 32 * sizeof(uint32_t)));
+    HIP_TRY(p->patch.d_tile_summed.alloc(t.sum_order.size()));
+    HIP_TRY(hipMemset(p->patch.d_tile_summed, 0, t.sum_order.size() * sizeof(uint32_t)));
     std::copy_n(t.prefetch_first, 9, p->patch.prefetch_first);
     HIP_TRY(p->patch.d_prefetch_tiles.alloc(std::max<size_t>(1, t.prefetch_tiles.size())));
     HIP_TRY(hipMemcpy(p->patch.d_prefetch_tiles, t.prefetch_tiles.data(), t.prefetch_tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -352,6 +362,16 @@ int rpsf_detail_plan_create_impl(rpsf_plan** out, int device, int patch_size, in
     HIP_TRY(hipEventCreateWithFlags(&p->ev_busy, hipEventDisableTiming));
     rl = setup_lattice(p);
     if (rl != RPSF_OK) return rl;
+    if (p->patch.v2 && N == 256) {  // the gated kernel reports a wait that ran out; a plan that is not a view gets the second lane (RPSF_OPT_PIPELINE)
+      rl = ensure_error_word(p);
+      if (rl != RPSF_OK) return rl;
+      if (!parent && p->lattice) {
+        HIP_TRY(hipStreamCreateWithFlags(&p->lane1, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&p->ev_lane, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
+        p->patch.lanes.enabled = true;
+      }
+    }
     if (p->sweep.ok) {
       rl = dispatch_v3(N, [&]<class C>() -> int {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
@@ -395,7 +415,35 @@ extern "C" int rpsf_plan_create(rpsf_plan** out, int device, int patch_size, int
   return rpsf_detail_plan_create_impl(out, device, patch_size, n_patches, coords_rc, nullptr, nullptr);
 }
 
-extern "C" void* rpsf_plan_stream(rpsf_plan* p) { return p ? (void*)p->stream : nullptr; }
+// Join the launch lanes of the plan (of a view: its parent's): the public stream waits for what the second lane holds, and whatever is enqueued on
+// the public stream next runs behind every apply so far, as it always did (rpsf_lanes.hpp).  Costs nothing while the second lane is idle.
+int rpsf_detail_join_lanes(rpsf_plan* p) {
+  rpsf_plan* r = p->parent ? p->parent : p;
+  if (!r->patch.lanes.join()) return RPSF_OK;
+  HIP_TRY(hipSetDevice(r->device));
+  HIP_TRY(hipEventRecord(r->ev_lane, r->lane1));
+  HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_lane, 0));
+  return RPSF_OK;
+}
+
+// The host-array, saturation and mask entry points start with a clean error word: an error a caller of the device entry points never collected
+// is not theirs, and is dropped here.  Called behind the join of the lanes; device applies the caller left in flight are waited for first (the
+// public stream covers both lanes then), so that a wait of theirs that runs out is neither blamed on this call nor wiped half-way.
+void rpsf_detail_clear_error(rpsf_plan* p) {
+  rpsf_plan* r = p->parent ? p->parent : p;
+  volatile uint32_t* word = r->sweep.err;
+  if (!word) return;
+  if (r->busy_valid && r->stream) (void)hipStreamSynchronize(r->stream);
+  *word = 0;
+}
+
+// The handle of the public stream.  What the caller enqueues there is unknown to the plan, so from here on its applies stay on that one stream.
+extern "C" void* rpsf_plan_stream(rpsf_plan* p) {
+  if (!p) return nullptr;
+  (void)rpsf_detail_join_lanes(p);
+  (p->parent ? p->parent : p)->patch.lanes.exposed = true;
+  return (void*)p->stream;
+}
 
 extern "C" void rpsf_plan_destroy(rpsf_plan* p) { delete p; }
 
@@ -460,6 +508,7 @@ static int install_transfer(rpsf_plan* p, const KSource& src, int first, int cou
 extern "C" int rpsf_plan_set_transfer(rpsf_plan* p, const float* k_host) {
   if (!p || !k_host) return fail(RPSF_E_BADARG, "null argument");
   HIP_TRY(hipSetDevice(p->device));
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;  // (rpsf_lanes.hpp: everything but a pipelined apply joins first)
   const cf* k = reinterpret_cast<const cf*>(k_host);
   if (p->generic) return install_transfer(p, KSource{k, hipMemcpyHostToDevice}, 0, p->n_patches);
   // the packers read K from the device: it goes up 64 MiB at a time
@@ -479,6 +528,7 @@ extern "C" int rpsf_plan_set_transfer(rpsf_plan* p, const float* k_host) {
 extern "C" int rpsf_plan_set_transfer_device(rpsf_plan* p, const void* k_dev) {
   if (!p || !k_dev) return fail(RPSF_E_BADARG, "null argument");
   HIP_TRY(hipSetDevice(p->device));
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;  // (rpsf_lanes.hpp: everything but a pipelined apply joins first)
   return install_transfer(p, KSource{reinterpret_cast<const cf*>(k_dev)}, 0, p->n_patches);
 }
 
@@ -486,6 +536,7 @@ extern "C" int rpsf_plan_set_transfer_device(rpsf_plan* p, const void* k_dev) {
 extern "C" int rpsf_plan_set_transfer_spectra_device(rpsf_plan* p, const void* s_c64_dev, const void* t_c64_dev, double alpha, double epsilon) {
   if (!p || !s_c64_dev || !t_c64_dev) return fail(RPSF_E_BADARG, "null argument");
   HIP_TRY(hipSetDevice(p->device));
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;  // (rpsf_lanes.hpp: everything but a pipelined apply joins first)
   return install_transfer(p, KSource{nullptr, hipMemcpyDeviceToDevice, reinterpret_cast<const cf*>(s_c64_dev), reinterpret_cast<const cf*>(t_c64_dev),
                                      alpha, epsilon}, 0, p->n_patches);
 }
@@ -585,6 +636,11 @@ struct PatchLaunch {
   int k_prefetch;                        // persistent, 256-pixel plan: first-round K prefetch by the head summing workgroups (0 / 1)
   uint32_t xq_base[8], xq_draws[8];      // persistent: where this launch's draws from the slot queue of each XCD start, and how many it makes
   uint32_t sum_queue_base, sum_queue_draws;  // fused and persistent: the same for the tile queue
+  // the launch lane (rpsf_lanes.hpp, committed by launch_apply): whose queue words the launch draws from, what its tile sums publish and whether its
+  // patches wait for the previous apply's
+  int lane;
+  bool gate;
+  uint32_t seq;
 };
 
 // A patch launch is one grid of at most 2^31 - 1 workgroups: one per frame and patch_teams() patches of each chunk
@@ -622,7 +678,7 @@ static PatchLaunch patch_launch_for(const rpsf_plan* p, const float* d_img, cons
   if (p->patch.plane_nt_opt >= 0) L.plane_nt = p->patch.plane_nt_opt != 0 && N128 && p->patch.k_cached;  // (RPSF_OPT_PLANE_NT)
   const int tune_frames = b.frames;  // (the settings of a single apply measured worse here: 0.203 vs 0.186 ms per frame at 8 x 4096^2)
   L.sum_first = sum_first_for(p, tune_frames);
-  L.sum_queue_base = p->patch.sum_queue_base;
+  // (where the launch's draws start - sum_queue_base, xq_base - depends on the lane it takes: launch_apply fills them in, rpsf_lanes.hpp)
   // persistent form: as many patch workgroups as the chip holds beside the summing ones; each works through the slots
   // of its XCD's chunk and ends as a summing workgroup itself (no workgroups behind the patches).
   // FORWARD PROGRESS.  HIP promises neither that a grid is resident as a whole nor an order of dispatch, and other launches
@@ -638,7 +694,9 @@ static PatchLaunch patch_launch_for(const rpsf_plan* p, const float* d_img, cons
   // workgroups alone fill the chip (tests: test_two_persistent_plans_on_two_streams, 256- and 128-pixel plans).
   // (queue positions of an XCD: chunk slots x frames, the frames of a slot side by side)
   const int rows = std::min(L.chunk * b.frames, std::max(1, (p->patch.round_capacity - L.sum_first - p->patch.reserved_cus) / 8));
-  if (!(p->patch.persist && rows > 0 && hot_geometry(p, d_img, g, b.im_stride))) {
+  // (the gated kernel - the persistent 256-pixel one - stores the output through one 32-bit buffer offset, as every fused launch does its planes)
+  const bool out_span_ok = !N256 || (size_t)g.out_rows * g.ld_out * sizeof(float) < ((size_t)1 << 32);
+  if (!(p->patch.persist && rows > 0 && out_span_ok && hot_geometry(p, d_img, g, b.im_stride))) {
     L.form = PatchLaunch::FUSED;
     const int nsum = std::max(8, std::min(count, p->patch.round_capacity)) + L.sum_first;  // at the tail: as many summing workgroups as the chip holds
     L.sum_queue_draws = (uint32_t)(count + nsum);  // every workgroup draws one position past the end
@@ -668,7 +726,6 @@ static PatchLaunch patch_launch_for(const rpsf_plan* p, const float* d_img, cons
     if (N128) L.stagger_ticks = tune_frames == 1 && p->n_patches >= 4096 ? 600 : 0;
   }
   for (int x = 0; x < 8; ++x) {
-    L.xq_base[x] = p->patch.xq_base[x];
     // draws of this launch: one per slot and frame, plus the one past the end that tells each of the chunk's workgroups to stop
     // (the first sum_first / 8 positions of a chunk go to the head summing workgroups without a draw when those compute a patch first)
     const int slots_x = std::min(L.chunk, std::max(0, p->n_patches - x * L.chunk)) * b.frames;
@@ -711,11 +768,13 @@ static PatchParams patch_params(const rpsf_plan* p, const PatchLaunch& L, const 
   TileSum& ts = pp.ts;
   fill_plane_sum(ts, p, d_out, g, b);
   ts.half = p->N / 2, ts.cover = p->d_cover, ts.tiles = p->patch.d_sum_order, ts.count = n_tiles * b.frames;
-  ts.done = p->patch.d_tile_done, ts.epoch = p->patch.done_epoch;
+  ts.done = p->patch.d_tile_done, ts.epoch = p->patch.lanes.done_epoch;
   ts.n_frames = b.frames, ts.n_tiles = (uint32_t)n_tiles, ts.n_tiles_listed = (uint32_t)n_tiles, ts.frame_major = L.frame_major;
-  ts.queue = p->patch.d_sum_queue, ts.queue_base = L.sum_queue_base;
+  ts.queue = p->patch.d_sum_queue + L.lane * 32, ts.queue_base = L.sum_queue_base;
+  ts.summed = p->patch.d_tile_summed, ts.seq = L.seq;  // (read by the gated kernel alone, like the next three)
+  ts.gate_on = L.gate ? 1u : 0u, ts.gate_want = L.seq - 1, ts.err = o->sweep.d_err;
   if (L.form != PatchLaunch::PERSISTENT) return pp;
-  pp.persist = L.rows, pp.xq = p->patch.d_xq;
+  pp.persist = L.rows, pp.xq = p->patch.d_xq + L.lane * 8 * 32;
   pp.head_patches = L.head_patches, pp.prefetch = L.prefetch, pp.prefetch_tiles = p->patch.d_prefetch_tiles;
   pp.k_prefetch = L.k_prefetch, pp.k_patches = o->n_patches;
   for (int x = 0; x < 9; ++x) pp.prefetch_first[x] = p->patch.prefetch_first[x];
@@ -870,8 +929,14 @@ static int launch_sweep(rpsf_plan* p, const float* d_img, float* d_out, const rp
 // One apply.  ev_k0 / ev_k1 (optional) bracket the patch-kernel launches for timing.
 // In this order: every refusal; growth of the plan's scratch (harmless before a launch that fails); the decision, which reads the scratch sizes; then
 // what a launch must not be refused after - epochs, counter restarts, queue positions -; the clear; the launches.
+// may_pipeline: the caller is an entry point that leaves the stream to the plan and enqueues nothing behind the apply itself (rpsf_apply_device,
+// rpsf_apply_device_loop_ms) - such an apply may take the plan's second lane (rpsf_lanes.hpp); every other apply joins the lanes first.
 int rpsf_detail_launch_apply(rpsf_plan* p, const float* d_img, float* d_out, const rpsf_geometry& g, hipStream_t st,
-                             hipEvent_t ev_k0, hipEvent_t ev_k1, Batch b) {
+                             hipEvent_t ev_k0, hipEvent_t ev_k1, Batch b, bool may_pipeline) {
+  // (a view joins its parent's lanes - it runs on the parent's stream - and has none of its own; for the applies that may be pipelined the lane
+  // book decides below, once the form of the launch is known)
+  if (!may_pipeline || p->parent || !p->patch.lanes.enabled)
+    if (const int rc = rpsf_detail_join_lanes(p); rc != RPSF_OK) return rc;
   if (p->generic) return launch_apply_generic(p, d_img, d_out, g, st, ev_k0, ev_k1, b);
   const OverlapKind kind = rpsf_detail_overlap_kind(p);
   if (kind == OV_SWEEP) {
@@ -929,7 +994,45 @@ int rpsf_detail_launch_apply(rpsf_plan* p, const float* d_img, float* d_out, con
     L = patch_launch_for<T>(p, d_img, g, b, fused);
     return RPSF_OK;
   });
-  // ---- nothing refuses the launch from here on: the plan's epochs, counters and queue positions advance ----
+  // atomics accumulate into the output; the tile sums and the direct mode's fix-up write lattice tiles only
+  const bool clear = kind == OV_ATOMIC || ((kind == OV_DIRECT || fused) && !rpsf_detail_lattice_covers_window(p, g));
+  // ---- nothing refuses the launch from here on: the plan's lanes, epochs, counters and queue positions advance ----
+  // The lane (rpsf_lanes.hpp).  Two applies of the plan may be in flight only when both run the gated kernel - the persistent 256-pixel one, whose
+  // tile sums and patches order every tile between them - on a single frame, on the plan's own stream, with nothing else enqueued around the
+  // launch: no clear of the output, no restart of the tile counters, no timing events, no other stream to serialise against.
+  const bool gated_kernel = L.form == PatchLaunch::PERSISTENT && p->patch.v2 && p->N == 256;
+  const bool hot = may_pipeline && gated_kernel && !p->parent && b.frames == 1 && st == p->stream && !p->multi_stream && !clear && !ev_k0 && !ev_k1 &&
+                   !p->patch.lanes.epoch_restarts(b.frames);
+  const LaneRange img_range{reinterpret_cast<uintptr_t>(d_img),
+                            reinterpret_cast<uintptr_t>(d_img + (size_t)std::max(0, g.image_rows - 1) * g.ld_image + g.width)};
+  const LaneRange out_range{reinterpret_cast<uintptr_t>(d_out), reinterpret_cast<uintptr_t>(d_out + (size_t)std::max(0, g.out_rows - 1) * g.ld_out + g.width)};
+  LaneLayout layout;
+  layout.v[0] = g.width, layout.v[1] = g.out_row0, layout.v[2] = g.out_rows, layout.v[3] = g.origin_row, layout.v[4] = g.origin_col;
+  layout.v[5] = (int64_t)p->patch.planes_floats;
+  const LaneBook book_before = p->patch.lanes;
+  const LanePick pick = p->patch.lanes.begin(hot, gated_kernel, img_range, out_range, layout);
+  {  // (a stream operation that fails leaves no launch behind: the book goes back to where it was, or the next gate would wait for nobody)
+    hipError_t e = hipSuccess;
+    if (pick.join) {  // (only a plan with a second lane can have it busy)
+      e = hipEventRecord(p->ev_lane, p->lane1);
+      if (e == hipSuccess) e = hipStreamWaitEvent(p->stream, p->ev_lane, 0);
+    }
+    if (e == hipSuccess && pick.fork) e = hipEventRecord(p->ev_fork, p->stream);
+    if (e == hipSuccess && pick.wait_fork) e = hipStreamWaitEvent(p->lane1, p->ev_fork, 0);
+    if (e != hipSuccess) {
+      p->patch.lanes = book_before;
+      (void)hipDeviceSynchronize();  // (whatever the lanes hold is over before anything else runs: the restored book may say "joined" or not)
+      p->patch.lanes.join();
+      return fail(RPSF_E_HIP, std::string("launch lanes: ") + hipGetErrorString(e));
+    }
+  }
+  hipStream_t run = pick.lane == 1 ? p->lane1 : st;  // (everything below but the patch launch of a pipelined apply is enqueued on st == run)
+  L.lane = pick.lane, L.gate = pick.gate, L.seq = pick.seq, L.sum_queue_base = pick.sum_queue_base;
+  for (int x = 0; x < 8; ++x) L.xq_base[x] = pick.xq_base[x];
+  LaneDraws draws;
+  for (int x = 0; x < 8; ++x) draws.xq[x] = L.xq_draws[x];
+  draws.sum = L.sum_queue_draws;
+  p->patch.lanes.commit(pick, draws);
   if (kind == OV_DIRECT && ++p->patch.epoch >= (1u << 24) - 1) {  // the epoch field of the flag words is 24 bits wide
     HIP_TRY(hipMemsetAsync(p->patch.d_flags, 0, n_tiles * p->patch.flag_frames * sizeof(uint32_t), st));
     HIP_TRY(hipMemsetAsync(p->patch.d_chunk_xcc, 0, 8 * sizeof(uint32_t), st));
@@ -939,19 +1042,14 @@ int rpsf_detail_launch_apply(rpsf_plan* p, const float* d_img, float* d_out, con
     // A launch advances the counters of frames [0, b.frames) only, and a tile is complete at epoch x contributors: when the frame
     // count differs from the previous fused launch's (batch -> single apply -> batch, or the short last group of a batch) the
     // counters of the higher frames would lag behind the epoch for ever - and the summing workgroups would wait for ever.
-    // Start a new count whenever the frame count changes (and when the epoch would overflow the counters).
-    const bool restart = b.frames != p->patch.done_last_frames || p->patch.done_epoch + 1 >= (1u << 29);  // the counters hold epoch * contributors
-    if (restart) HIP_TRY(hipMemsetAsync(p->patch.d_tile_done, 0, n_tiles * p->patch.done_frames * sizeof(uint32_t), st));
-    p->patch.done_last_frames = b.frames;
-    p->patch.done_epoch = restart ? 1 : p->patch.done_epoch + 1;
+    // Start a new count whenever the frame count changes (and when the epoch would overflow the counters): LaneBook::next_epoch.
+    // (such a launch is never pipelined: the lanes are joined, the clear runs behind every earlier apply)
+    if (p->patch.lanes.next_epoch(b.frames).restart)
+      HIP_TRY(hipMemsetAsync(p->patch.d_tile_done, 0, n_tiles * p->patch.done_frames * sizeof(uint32_t), st));
   }
-  for (int x = 0; x < 8; ++x) p->patch.xq_base[x] += L.xq_draws[x];
-  p->patch.sum_queue_base += L.sum_queue_draws;
-  // atomics accumulate into the output; the tile sums and the direct mode's fix-up write lattice tiles only
-  const bool clear = kind == OV_ATOMIC || ((kind == OV_DIRECT || fused) && !rpsf_detail_lattice_covers_window(p, g));
   if (const int rc = clear ? clear_window(d_out, g, b, st) : RPSF_OK; rc != RPSF_OK) return rc;
   if (ev_k0) HIP_TRY(hipEventRecord(ev_k0, st));
-  int rc = launch_patches(p, L, d_img, d_out, g, kind, st, b);
+  int rc = launch_patches(p, L, d_img, d_out, g, kind, run, b);
   if (rc != RPSF_OK) return rc;
   if (ev_k1) HIP_TRY(hipEventRecord(ev_k1, st));
   if (kind == OV_PLANES && !fused) rc = launch_sum(p, d_out, g, st, b);
@@ -967,6 +1065,7 @@ extern "C" int rpsf_plan_set_overlap_mode(rpsf_plan* p, int mode) {
   if (mode == 4 && !p->sweep.ok) return fail(RPSF_E_STATE, "the sweep kernel needs a 16-, 32- or 64-pixel patch on a complete lattice of at least 2 x 2 patches");
   if (mode == 2 && !p->lattice) return fail(RPSF_E_STATE, "colour planes need a regular half-overlap lattice of patch corners");
   if (mode == 3 && !p->patch.direct_ok) return fail(RPSF_E_STATE, "direct overlap-add needs a regular half-overlap lattice and a 128- or 256-pixel patch");
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;
   p->overlap_mode = mode;
   rpsf_detail_drop_bands(p);
   return RPSF_OK;
@@ -974,6 +1073,7 @@ extern "C" int rpsf_plan_set_overlap_mode(rpsf_plan* p, int mode) {
 
 extern "C" int rpsf_plan_set_option(rpsf_plan* p, int option, int value) {
   if (!p) return fail(RPSF_E_BADARG, "null plan");
+  if (const int rc = rpsf_detail_join_lanes(p); rc != RPSF_OK) return rc;
   switch (option) {
     case RPSF_OPT_PERSIST:
       if (value != 0 && value != 1) return fail(RPSF_E_BADARG, "RPSF_OPT_PERSIST takes 0 or 1");
@@ -1011,6 +1111,14 @@ extern "C" int rpsf_plan_set_option(rpsf_plan* p, int option, int value) {
       if (value < 0 || value > 65535) return fail(RPSF_E_BADARG, "RPSF_OPT_SAT_GROUP takes 0 (automatic) or 1..65535");
       p->sat_group_opt = value;
       return RPSF_OK;  // (no launch of the correction depends on it: the band views stay)
+    case RPSF_OPT_PIPELINE:
+      if (value != 0 && value != 1) return fail(RPSF_E_BADARG, "RPSF_OPT_PIPELINE takes 0 or 1");
+      if (p->parent) return fail(RPSF_E_STATE, "a view runs on its parent's stream");
+      p->patch.lanes.enabled = value != 0 && p->lane1 != nullptr;  // (plans without the gated kernel have one lane whatever the option says)
+      // (setting it to 1 is the caller's word that nothing of theirs is enqueued on the plan's stream any more: a plan that went to one lane
+      // because its stream handle was taken - rpsf_plan_stream - is armed again; a CU mask keeps it on one lane, see rpsf_plan_set_cu_mask)
+      if (value != 0) p->patch.lanes.exposed = false;
+      break;
     case RPSF_OPT_DEBUG_ORPHAN:
       if (value < 0) return fail(RPSF_E_BADARG, "RPSF_OPT_DEBUG_ORPHAN takes 0 (off) or a positive modulus");
       p->patch.orphan_mod = value;
@@ -1025,6 +1133,7 @@ extern "C" int rpsf_plan_set_sweep_regions(rpsf_plan* p, int target_regions) {
   if (!p || target_regions < 1 || target_regions > (1 << 20)) return fail(RPSF_E_BADARG, "target_regions must be 1..2^20");
   if (!p->sweep.ok) return fail(RPSF_E_STATE, "the sweep kernel needs a 16-, 32- or 64-pixel patch on a complete lattice of at least 2 x 2 patches");
   HIP_TRY(hipSetDevice(p->device));
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;  // (rpsf_lanes.hpp: everything but a pipelined apply joins first)
   HIP_TRY(hipStreamSynchronize(p->stream));
   HIP_TRY(hipDeviceSynchronize());  // (applies on other streams may still read the old lists)
   rpsf_detail_drop_bands(p);
@@ -1084,6 +1193,7 @@ extern "C" int rpsf_plan_set_cu_mask(rpsf_plan* p, const uint32_t* mask, int wor
   for (int i = 0; i < words; ++i) cus += __builtin_popcount(mask[i]);
   if (cus < 8) return fail(RPSF_E_BADARG, "the mask must leave the plan at least 8 compute units");
   HIP_TRY(hipSetDevice(p->device));
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;  // (rpsf_lanes.hpp: everything but a pipelined apply joins first)
   HIP_TRY(hipStreamSynchronize(p->stream));
   rpsf_detail_drop_bands(p);
   hipStream_t masked = nullptr;
@@ -1095,6 +1205,14 @@ extern "C" int rpsf_plan_set_cu_mask(rpsf_plan* p, const uint32_t* mask, int wor
   (void)hipStreamDestroy(p->stream);
   p->stream = masked;
   p->busy_valid = false;
+  // Every launch of the plan stays inside the mask: the second launch lane is an unmasked stream, so a masked plan keeps to one lane, for good
+  // (the lanes were joined above; RPSF_OPT_PIPELINE cannot switch them back on without the stream).
+  p->patch.lanes.enabled = false;
+  if (p->lane1) {
+    (void)hipStreamSynchronize(p->lane1);
+    (void)hipStreamDestroy(p->lane1);
+    p->lane1 = nullptr;
+  }
   if (p->cu_count > 0) p->patch.round_capacity = p->patch.round_capacity / p->cu_count * cus;
   p->cu_count = cus;
   return RPSF_OK;
@@ -1138,7 +1256,9 @@ extern "C" int rpsf_apply_device(rpsf_plan* p, const void* image_dev, void* out_
   if (rc != RPSF_OK) return rc;
   HIP_TRY(hipSetDevice(p->device));
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : p->stream;
-  return rpsf_detail_launch_apply(p, reinterpret_cast<const float*>(image_dev), reinterpret_cast<float*>(out_dev), *geom, st, nullptr);
+  // (stream == NULL leaves the stream to the plan: back-to-back applies of a 256-pixel plan may then overlap head under tail, rpsf_lanes.hpp)
+  return rpsf_detail_launch_apply(p, reinterpret_cast<const float*>(image_dev), reinterpret_cast<float*>(out_dev), *geom, st, nullptr, nullptr, Batch(),
+                                  /*may_pipeline*/ stream == nullptr);
 }
 
 
@@ -1186,6 +1306,7 @@ extern "C" int rpsf_apply_batch_device(rpsf_plan* p, const void* images_dev, voi
   int rc = check_batch(p, images_dev, outs_dev, n_frames, image_stride, out_stride, geom);
   if (rc != RPSF_OK) return rc;
   HIP_TRY(hipSetDevice(p->device));
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;  // (rpsf_lanes.hpp: everything but a pipelined apply joins first)
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : p->stream;
   return rpsf_detail_launch_batch(p, reinterpret_cast<const float*>(images_dev), reinterpret_cast<float*>(outs_dev), n_frames,
                       image_stride, out_stride, *geom, st);
@@ -1237,6 +1358,7 @@ extern "C" int rpsf_apply_batch_device_timed(rpsf_plan* p, const void* images_de
   int rc = check_batch(p, images_dev, outs_dev, n_frames, image_stride, out_stride, geom);
   if (rc != RPSF_OK) return rc;
   HIP_TRY(hipSetDevice(p->device));
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;  // (rpsf_lanes.hpp: everything but a pipelined apply joins first)
   return timed_loop(p, iters, total_ms, kernel_ms, [&](hipEvent_t k0, hipEvent_t k1) {
     return rpsf_detail_launch_batch(p, reinterpret_cast<const float*>(images_dev), reinterpret_cast<float*>(outs_dev), n_frames, image_stride,
                         out_stride, *geom, p->stream, k0, k1);
@@ -1248,7 +1370,10 @@ extern "C" int rpsf_apply_batch_device_timed(rpsf_plan* p, const void* images_de
 int rpsf_detail_sweep_check(rpsf_plan* p) {
   volatile uint32_t* word = owner(p)->sweep.err;
   if (!word || *word == 0) return RPSF_OK;
+  const uint32_t what = *word;
   *word = 0;
+  if (what == 2)
+    return fail(RPSF_E_HIP, "patch kernel: an apply waited for the tile sums of the plan's previous apply beyond the bound (internal protocol error; the output of this apply is not valid)");
   return fail(RPSF_E_HIP, "sweep kernel: a job waited for the jobs it follows beyond the bound (internal protocol error; the output of this apply is not valid)");
 }
 
@@ -1268,6 +1393,7 @@ extern "C" int rpsf_apply_device_timed(rpsf_plan* p, const void* image_dev, void
   int rc = rpsf_detail_check_geometry(p, geom);
   if (rc != RPSF_OK) return rc;
   HIP_TRY(hipSetDevice(p->device));
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;  // (rpsf_lanes.hpp: everything but a pipelined apply joins first)
   return timed_loop(p, iters, total_ms, kernel_ms, [&](hipEvent_t k0, hipEvent_t k1) {
     return rpsf_detail_launch_apply(p, reinterpret_cast<const float*>(image_dev), reinterpret_cast<float*>(out_dev), *geom, p->stream, k0, k1);
   });
@@ -1285,11 +1411,18 @@ extern "C" int rpsf_apply_device_loop_ms(rpsf_plan* p, const void* image_dev, vo
   int rc = rpsf_detail_check_geometry(p, geom);
   if (rc != RPSF_OK) return rc;
   HIP_TRY(hipSetDevice(p->device));
+  // (the event pair brackets both launch lanes: the start is recorded behind a join, and the lanes are joined again in front of the stop; the
+  // applies in between are the ones rpsf_apply_device makes)
+  rc = rpsf_detail_join_lanes(p);
+  if (rc != RPSF_OK) return rc;
   HIP_TRY(hipEventRecord(p->ev[0], p->stream));
   for (int i = 0; i < iters; ++i) {
-    rc = rpsf_detail_launch_apply(p, reinterpret_cast<const float*>(image_dev), reinterpret_cast<float*>(out_dev), *geom, p->stream, nullptr);
+    rc = rpsf_detail_launch_apply(p, reinterpret_cast<const float*>(image_dev), reinterpret_cast<float*>(out_dev), *geom, p->stream, nullptr, nullptr,
+                                  Batch(), /*may_pipeline*/ true);
     if (rc != RPSF_OK) return rc;
   }
+  rc = rpsf_detail_join_lanes(p);
+  if (rc != RPSF_OK) return rc;
   HIP_TRY(hipEventRecord(p->ev[3], p->stream));
   HIP_TRY(hipEventSynchronize(p->ev[3]));
   float ms = 0.f;

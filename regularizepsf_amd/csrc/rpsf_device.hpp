@@ -12,6 +12,7 @@
 #include "rpsf_core2.hpp"
 #include "rpsf_core3.hpp"
 #include "rpsf_plan3.hpp"
+#include "rpsf_lanes.hpp"
 
 using namespace rpsf;
 

@@ -253,7 +253,7 @@ static int host_one_frame_banded(rpsf_plan* p, const void* image, int in_f64, vo
     pool.run(std::max(1, (frame_workers > 0 ? std::min(frame_workers, pool.width()) : pool.width()) / every), worker, conductor, every);
   }
   if (trace)
-    std::fprintf(stderr, "[rpsf host frame] %zu chunks, %d bands, %zu + %zu pieces: last chunk enqueued %.3f ms, first piece back %.3f, last %.3f, total %.3f ms\\n",
+    std::fprintf(stderr, "[rpsf host frame] %zu chunks, %d bands, %zu + %zu pieces: last chunk enqueued %.3f ms, first piece back %.3f, last %.3f, total %.3f ms\n",
                  chunks.size(), B, n_in, (size_t)out_avail.load(), t_enqueued, t_first_out, t_last_out, ms_since(t_start));
   if (err != hipSuccess) return rpsf_detail_drain_after_error(p, err, "host frame");
   return rpsf_detail_sweep_check(p);
@@ -523,6 +523,9 @@ static int check_host_call(rpsf_plan* p, const void* a, const void* b, int n_fra
   int rc = rpsf_detail_check_geometry(p, g);
   if (rc != RPSF_OK) return rc;
   HIP_TRY(hipSetDevice(p->device));
+  // every host-array entry point: the plan's launch lanes are joined first (rpsf_lanes.hpp), and an error word nobody collected is not this call's
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;
+  rpsf_detail_clear_error(p);
   return RPSF_OK;
 }
 

@@ -39,6 +39,12 @@ struct TileSum {
   size_t planes_frame_floats, out_frame_floats;
   int frame_major;           // the list runs frame after frame (persistent batches of large frames) instead of tile after tile
   uint32_t n_tiles_listed;   // entries of `tiles` (= count / frames)
+  // gated kernel (patch_kernel2_256p; rpsf_lanes.hpp): per tile, the sequence number of the last apply whose sum of the tile is
+  // complete - its plane values consumed, its output lines performed - which the patches of the next apply wait for in front of their plane stores
+  uint32_t* summed;
+  uint32_t seq;
+  uint32_t gate_on, gate_want;  // the previous apply may still be in flight (gate_on): it publishes gate_want = seq - 1
+  uint32_t* err;                // page-locked word: 2 = a gate wait ran out
 };
 __device__ __forceinline__ uint32_t sum_entry(const TileSum& p, uint32_t i) {
   if (p.n_frames <= 1) return p.tiles[i];
@@ -79,10 +85,16 @@ __device__ __forceinline__ void plane_store16_wt(__amdgpu_buffer_rsrc_t r, size_
   __builtin_amdgcn_raw_buffer_store_b128(q, r, (int)(float_offset * sizeof(float)), 0, PLANE_AUX_STORE);
 }
 
+// Output stores of the gated kernel: write-through (sc1) and streaming, so that once the storing wave's vmcnt has drained the lines are performed
+// at the device's memory and no dirty copy of them is left in this XCD's L2 - a later apply, summing the same tile on another XCD while this launch
+// still runs, then cannot be overwritten by a late write-back of this launch's.
+__device__ __forceinline__ void out_store16_wt(__amdgpu_buffer_rsrc_t r, size_t float_offset, rpsf_f4 v) { plane_store16_aux<16 | 2>(r, float_offset, v); }
+
 // UN: groups in flight per thread (4 x UN sixteen-byte loads);  KNOWN_FUSED: the caller is a fused launch (the persistent kernels), so the
-// plane loads are the write-through-aware ones without a run-time choice in front of each
-template <int UN = 8, bool KNOWN_FUSED = false>
-__device__ __forceinline__ void sum_tile(const TileSum& p0, uint32_t entry_any_lane, int tid, int nthreads, bool known_complete = false) {
+// plane loads are the write-through-aware ones without a run-time choice in front of each;  GATED: the kernel whose tile sums publish p.seq
+// in p.summed[tile] (TileSum) - the output goes out write-through, and the tile is published once every wave's stores have drained
+template <int UN, bool KNOWN_FUSED, bool GATED>
+__device__ __forceinline__ void sum_tile_values(const TileSum& p0, uint32_t entry_any_lane, int tid, int nthreads, bool known_complete) {
   typedef float f4 __attribute__((ext_vector_type(4)));
   // The entry is the same in every lane (the whole workgroup sums one tile), but it comes out of LDS or a strided loop, so the compiler has to assume
   // otherwise - and then the tile's coverage mask is a vector value and every "is this plane present" choice of the 32 loads a v_cndmask on VCC, which
@@ -124,6 +136,11 @@ __device__ __forceinline__ void sum_tile(const TileSum& p0, uint32_t entry_any_l
   // the division (until round 5 they fell to the pixel-by-pixel path: four agent-scope loads per pixel).
   if (vec) {
     const __amdgpu_buffer_rsrc_t rsrc = plane_rsrc(p.planes);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t orsrc = plane_rsrc(GATED ? p.out : p.planes);  // (the output of a fused launch: under 4 GiB, as the planes are)
+    auto ostore = [&](size_t o, f4 acc) RPSF_AI {
+      if constexpr (GATED) out_store16_wt(orsrc, o, acc);
+      else __builtin_nontemporal_store(acc, reinterpret_cast<f4*>(p.out + o));
+    };
     const int total = gw * (y1 - y0);
     // (UN = 8: 32 sixteen-byte loads per thread - a whole tile per pass for the patch kernels' workgroup sizes)
     if ((gw & (gw - 1)) == 0) {
@@ -150,7 +167,7 @@ __device__ __forceinline__ void sum_tile(const TileSum& p0, uint32_t entry_any_l
 #pragma unroll
           for (int k = 0; k < 4; ++k)
             if ((cov >> k) & 1) acc += v[u][k];
-          __builtin_nontemporal_store(acc, reinterpret_cast<f4*>(p.out + (size_t)(y0 + row_of(i) - p.row0) * p.ld_out + x0 + (col_of(i) << 2)));
+          ostore((size_t)(y0 + row_of(i) - p.row0) * p.ld_out + x0 + (col_of(i) << 2), acc);
         }
       }
     } else {  // a clipped tile: the same 16-byte accesses, one group per thread and step (a compact loop: these are a few tiles per frame, and a second
@@ -165,7 +182,7 @@ __device__ __forceinline__ void sum_tile(const TileSum& p0, uint32_t entry_any_l
             const size_t o = off + k * p.plane_stride;
             acc += fused ? plane_load16_wt(rsrc, o) : __builtin_nontemporal_load(reinterpret_cast<const f4*>(p.planes + o));
           }
-        __builtin_nontemporal_store(acc, reinterpret_cast<f4*>(p.out + (size_t)(y0 + row - p.row0) * p.ld_out + x0 + (col << 2)));
+        ostore((size_t)(y0 + row - p.row0) * p.ld_out + x0 + (col << 2), acc);
       }
     }
   } else {
@@ -180,8 +197,47 @@ __device__ __forceinline__ void sum_tile(const TileSum& p0, uint32_t entry_any_l
           const float* src = p.planes + k * p.plane_stride + yl * p.ld_planes + x;
           acc += fused ? __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(src), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : *src;
         }
-      p.out[yl * p.ld_out + x] = acc;
+      if constexpr (GATED) __hip_atomic_store(reinterpret_cast<unsigned*>(p.out + yl * p.ld_out + x), __float_as_uint(acc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else p.out[yl * p.ld_out + x] = acc;
     }
+  }
+}
+// PUBLISH (gated kernel): publish the tile here, behind a drain of every wave's stores; the queue loop of sum_tiles_worker publishes a tile a round
+// later instead, when the drain costs nothing
+template <int UN = 8, bool KNOWN_FUSED = false, bool GATED = false, bool PUBLISH = true>
+__device__ __forceinline__ void sum_tile(const TileSum& p, uint32_t entry_any_lane, int tid, int nthreads, bool known_complete = false) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (GATED) {
+    // A tile NO patch covers (a thinned lattice) is complete from the start, and no patch of this launch has waited at the gate for it: its
+    // zeros wait here for the previous apply's, so that every tile sum of an apply comes behind the previous apply's sum of the same tile - and an
+    // apply that has ended means every earlier one has published all its tiles.  (Bounded like the patches' gate; workgroup-uniform.)
+    const uint32_t tile = __builtin_amdgcn_readfirstlane(entry_any_lane) & 0xffffffu;
+    if (p.gate_on && (p.cover[tile] & 15) == 0) {
+      if (tid == 0) {
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        while (!lane_seq_reached(__hip_atomic_load(p.summed + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), p.gate_want)) {
+          if (__builtin_amdgcn_s_memrealtime() - t0 > 40000000ull) {
+            __hip_atomic_store(p.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            break;
+          }
+          __builtin_amdgcn_s_sleep(8);
+        }
+      }
+      __syncthreads();
+    }
+  }
+#endif
+  sum_tile_values<UN, KNOWN_FUSED, GATED>(p, entry_any_lane, tid, nthreads, known_complete);
+  if constexpr (GATED && PUBLISH) {
+    // Publish the tile (single-frame launches: the entry is the tile).  Every wave drains its own write-through output stores - its plane loads
+    // have returned long before, their values are what it stored - then one barrier, then ONE relaxed agent-scope store of the sequence number:
+    // the payload is performed before the flag is issued, which is all a release has to mean here (no dirty line is left to write back).
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0 && p.summed)
+      __hip_atomic_store(p.summed + (__builtin_amdgcn_readfirstlane(entry_any_lane) & 0xffffffu), p.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
   }
 }
 // workgroup `block` of `nblocks` co-operating ones works through the list: in fixed strides, or - fused mode, where the
@@ -192,10 +248,10 @@ __device__ __forceinline__ void sum_tile(const TileSum& p0, uint32_t entry_any_l
 struct NoSideJob {
   __device__ __forceinline__ bool operator()() const { return false; }
 };
-template <class BETWEEN = NoSideJob, int UN = 8, bool KNOWN_FUSED = false>
+template <class BETWEEN = NoSideJob, int UN = 8, bool KNOWN_FUSED = false, bool GATED = false>
 __device__ __forceinline__ void sum_tiles_worker(const TileSum& p, int block, int nblocks, BETWEEN&& between = BETWEEN()) {
   if (!p.queue) {
-    for (int i = block; i < p.count; i += nblocks) sum_tile<UN, KNOWN_FUSED>(p, p.tiles[i], threadIdx.x, blockDim.x);
+    for (int i = block; i < p.count; i += nblocks) sum_tile<UN, KNOWN_FUSED, GATED>(p, p.tiles[i], threadIdx.x, blockDim.x);
     return;
   }
   // A workgroup holds up to SUM_LOOKAHEAD drawn tiles and sums whichever of them is complete first, instead of waiting for the
@@ -208,7 +264,17 @@ __device__ __forceinline__ void sum_tiles_worker(const TileSum& p, int block, in
   int npend = 0;
   bool exhausted = false;
   bool side_job = true;
+  // Gated kernel: the tile summed in the previous round is published in THIS round.  Every wave drains its write-through output stores at the
+  // top of the round - while thread 0 polls the counters of the pending tiles, a round trip of its own that the other waves wait out at the
+  // barrier anyway - and behind that barrier thread 0 stores the sequence number: the payload is performed before the flag is issued, which is
+  // all a release has to mean here (no dirty line is left to write back), and no store acknowledgement is waited for with nothing else to do.
+  // A workgroup publishes its last tile in the round that finds the queue empty, before it returns.
+  [[maybe_unused]] uint32_t unpublished = 0xffffffffu;  // (workgroup-uniform)
   for (;;) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (GATED)
+      if (unpublished != 0xffffffffu) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
     if (side_job) side_job = between();
     if (threadIdx.x == 0) {
       uint32_t chosen = 0xffffffffu;
@@ -240,10 +306,16 @@ __device__ __forceinline__ void sum_tiles_worker(const TileSum& p, int block, in
     }
     __syncthreads();
     const uint32_t tile = pick;
+    if constexpr (GATED) {
+      if (unpublished != 0xffffffffu && threadIdx.x == 0 && p.summed)
+        __hip_atomic_store(p.summed + (unpublished & 0xffffffu), p.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      unpublished = 0xffffffffu;
+    }
     __syncthreads();
     if (tile == 0xffffffffu) return;
     if (tile == 0xfffffffeu) continue;
-    sum_tile<UN, KNOWN_FUSED>(p, tile, threadIdx.x, blockDim.x, true);
+    sum_tile<UN, KNOWN_FUSED, GATED, false>(p, tile, threadIdx.x, blockDim.x, true);
+    if constexpr (GATED) unpublished = tile;
   }
 }
 
@@ -300,6 +372,8 @@ struct PatchParams {
   int k_prefetch;    // persistent launches of the 256-pixel plan: the head summing workgroups first touch the K of the first round's patches
                      // (rpsf_kernels2.hpp, prefetch_first_round_k)
   int k_patches;     // ... patches the K allocation behind g / gs holds
+  // (gated kernel, patch_kernel2_256p: ts.gate_on - in front of the plane stores of a pass every tile of the patch must carry at least ts.gate_want
+  // in ts.summed, rpsf_lanes.hpp)
 };
 
 template <class C>

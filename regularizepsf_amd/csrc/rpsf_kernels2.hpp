@@ -263,6 +263,9 @@ __device__ __forceinline__ void patch_body2(const PatchParams& p, REENTER&& reen
   // (the tile sums of the persistent kernels are compiled for "fused" - no run-time choice between two kinds of load in front of each of the 32 of a pass:
   // config 2 -2 %; in the 256-pixel kernel -1.2 % at 4096^2 and nothing at 8192^2 once the sums index by shift and mask, profiles/r04t, r04aa)
   constexpr bool SUM_KNOWN_FUSED = HOT;
+  // The gated kernel (the persistent 256-pixel one): its tile sums publish a sequence number per tile and its patches wait, where the launcher says
+  // so, for the previous apply's in front of their plane stores - two applies of one plan can then be in flight (rpsf_lanes.hpp)
+  constexpr bool GATED = HOT && PERSIST && C::SPLIT_ROWS;
   const bool again = PERSIST && ((blockIdx.x >> 30) & 1u);
   if constexpr (dev::STAMPS)  // ... and which workgroup this is (its block index at dispatch, kept in LDS across re-entries: stamp 15)
     // (an unused word of the bin-pair table: bit 31 clear, so the walk of the self-paired bins ignores it; written again behind the table staging below)
@@ -327,12 +330,12 @@ __device__ __forceinline__ void patch_body2(const PatchParams& p, REENTER&& reen
         // ... and, ahead of it, the first round's K (workgroup-uniform, once per launch; not where the head workgroups compute a patch first)
         if (p.k_prefetch && p.head_patches == 0) prefetch_first_round_k<C>(p, blk);
         ImagePrefetch<C> prefetch(p, blk, p.prefetch && p.n_frames <= 1);
-        sum_tiles_worker<ImagePrefetch<C>&, 8, SUM_KNOWN_FUSED>(p.ts, 0, 1, prefetch);
+        sum_tiles_worker<ImagePrefetch<C>&, 8, SUM_KNOWN_FUSED, GATED>(p.ts, 0, 1, prefetch);
         prefetch.finish();
         return;
       }
     }
-    sum_tiles_worker<NoSideJob, 8, SUM_KNOWN_FUSED>(p.ts, 0, 1);
+    sum_tiles_worker<NoSideJob, 8, SUM_KNOWN_FUSED, GATED>(p.ts, 0, 1);
     return;
   }
   ImageView im = p.im;
@@ -421,6 +424,11 @@ __device__ __forceinline__ void patch_body2(const PatchParams& p, REENTER&& reen
   // slot's descriptor and touches one dword of each of the next patch's 2048 lines, a transform stage ahead of its gather - new frames 0.2095 -> 0.204 ms,
   // but the repeated frame of the headline loop 0.1916 -> 0.200: the descriptor's scalar load sits on the chain right behind a barrier.  The opt-in
   // prefetch by the head summing workgroups does better on new frames, 0.201, at no cost to the repeated one.  Not kept.)
+  // Gated kernel: the tile under quadrant tu & 3 of this patch (lattice_build: (li + (q >> 1)) * ntj + lj + (q & 1)), from the corner - no load
+  [[maybe_unused]] auto gate_tile = [&]() RPSF_AI {
+    const int li = (pr - p.ts.lat_r0) / (N / 2), lj = (pc - p.ts.lat_c0) / (N / 2);
+    return (li + ((tu >> 1) & 1)) * p.ts.ntj + lj + (tu & 1);
+  };
   [[maybe_unused]] auto draw_next = [&]() RPSF_AI {
     if constexpr (PERSIST) {
       if (HOT || p.tile_done) {
@@ -428,6 +436,11 @@ __device__ __forceinline__ void patch_body2(const PatchParams& p, REENTER&& reen
         if (tu == 0 && !head_patch)
           drawn = __hip_atomic_fetch_add(p.xq + (pb & 7) * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - p.xq_base[pb & 7] +
                   (p.head_patches ? (unsigned)(p.sum_first >> 3) : 0u);
+        // Gate (gate_on: the previous apply of the plan may still be in flight): lanes 4 ... 7 of EVERY wave request the sequence numbers of the
+        // patch's four tiles here, a whole inverse transform ahead of the plane stores they guard - each wave checks for itself, so the values
+        // cross no barrier and no LDS, and the wait in front of their use finds them long returned.  (`drawn` is idle in these lanes.)
+        if constexpr (GATED)
+          if (p.ts.gate_on && (tu & 60) == 4) drawn = __hip_atomic_load(p.ts.summed + gate_tile(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
   };
@@ -572,6 +585,28 @@ __device__ __forceinline__ void patch_body2(const PatchParams& p, REENTER&& reen
     if constexpr (MID_DRAW) {
       if (tu == 0) *reinterpret_cast<unsigned*>(park) = drawn;
       if (tu < 4) reinterpret_cast<unsigned*>(park)[1 + tu] = (unsigned)frame * p.n_tiles + quad_tile(qword);
+    }
+    if constexpr (GATED) {
+      // The gate: no plane store of this wave before the previous apply has summed the four tiles under the patch (rpsf_lanes.hpp, DESIGN.md
+      // 3.3).  In a frame loop the answer has been "yes" for a hundred microseconds; a wave that finds a tile not there yet re-polls it between naps.
+      // Bounded like the sweep kernel's waits (0.4 s of 10 ns ticks): a wait that runs out sets the plan's error word and goes on, so a broken
+      // protocol ends as a loud error and never as a hang.
+      if (p.ts.gate_on) {  // (workgroup-uniform)
+        bool late = (tu & 60) == 4 && !lane_seq_reached(drawn, p.ts.gate_want);
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(late) != 0, 0)) {
+          const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+          const int tile = gate_tile();
+          do {
+            __builtin_amdgcn_s_sleep(8);
+            if (late) late = !lane_seq_reached(__hip_atomic_load(p.ts.summed + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), p.ts.gate_want);
+            if (__builtin_amdgcn_s_memrealtime() - t0 > 40000000ull) {
+              if (late) __hip_atomic_store(p.ts.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+              break;
+            }
+          } while (__builtin_amdgcn_ballot_w64(late) != 0);
+        }
+        asm volatile("" ::: "memory");  // (compiler-only: the stores below stay below)
+      }
     }
     store_patch2<C, HOT>(
         t, v, ov, ov, plane, pr, pc, win, nullptr, add, []<int R1, int C1>(const float* a) RPSF_AI { return *reinterpret_cast<const f32x4*>(a); },

@@ -15,6 +15,7 @@
 
 #include "rpsf_device.hpp"
 #include "rpsf_hostpipe.hpp"
+#include "rpsf_lanes.hpp"
 #include "rpsf_lattice.hpp"
 #include "rpsf_saturation.hpp"
 #include "rpsf_side_unit.hpp"
@@ -117,13 +118,14 @@ struct PatchPath {
   // Fused plane sum (second-generation kernels, one frame, aligned geometry): the workgroups behind the patches in the
   // grid sum a lattice tile as soon as all its contributors have published their (write-through) plane stores, so
   // the sum runs on the CUs the partial last round leaves idle and no second kernel is needed.
-  DevBuf<uint32_t> d_tile_done;   // per tile: contributors done, never reset (epoch * contributors after every apply)
+  DevBuf<uint32_t> d_tile_done;   // per tile: contributors done, never reset (epoch * contributors after every apply; the epoch: lanes.done_epoch)
   DevBuf<uint32_t> d_sum_order;   // all tiles, the ones whose contributors run first first
-  uint32_t done_epoch = 0;
   size_t done_frames = 1;            // frames the tile counters are sized for (batches: one set per frame)
-  int done_last_frames = 1;          // frames of the last fused launch (the counters restart when the number changes)
-  DevBuf<uint32_t> d_sum_queue;   // position in d_sum_order, never reset
-  uint32_t sum_queue_base = 0;
+  DevBuf<uint32_t> d_sum_queue;   // position in d_sum_order, never reset: one word per launch lane, each on a 128-byte line of its own
+  // Launch lanes (rpsf_lanes.hpp): which stream an apply takes, where the lanes join, the queue positions each lane's launches own, the epoch of
+  // the tile counters and the sequence number of the gate
+  LaneBook lanes;
+  DevBuf<uint32_t> d_tile_summed;  // per tile: sequence number of the last apply whose sum of the tile is complete (gated kernel: patch_kernel2_256p)
   bool no_fuse = false;
   int sum_first = -1;                // RPSF_SUM_FIRST override of sum_first_for(), -1 = none
   bool prefetch = false;             // persistent launches: head summing workgroups touch the image first (RPSF_PREFETCH)
@@ -137,8 +139,7 @@ struct PatchPath {
   bool persist = false;
   bool k_cached = false;             // 128-pixel persistent launches take patch_kernel2_128pc (plain loads of the pair words): see rpsf_plan_create
   int reserved_cus = 0;              // persistent launches leave this many CUs without a patch workgroup (rpsf_plan_set_reserved_cus)
-  DevBuf<uint32_t> d_xq;          // 8 counters, one per 128-byte line
-  uint32_t xq_base[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  DevBuf<uint32_t> d_xq;          // 8 counters per launch lane, one per 128-byte line (their bases: lanes.xq_base)
   DevBuf<uint4> d_quads;        // per processing-order slot: quadrant words (rpsf_core.hpp, store_patch_direct)
   DevBuf<uint8_t> d_tile_info;  // per lattice tile: static side mask | 16 if any patch covers it
   DevBuf<uint32_t> d_flags;     // per (frame, tile)
@@ -176,8 +177,15 @@ struct PlanStream {
   bool borrowed_stream = false;  // a view runs on its parent's
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_busy = nullptr;    // end of the last apply (applies on different streams are serialised); recorded once the plan has seen a second stream
+  // the second launch lane (rpsf_lanes.hpp; 256-pixel plans that are not views): its stream, the end of its work (recorded at a join) and the point
+  // of the public stream it was last forked from
+  hipStream_t lane1 = nullptr;
+  hipEvent_t ev_lane = nullptr, ev_fork = nullptr;
   ~PlanStream() {
     if (ev_busy) (void)hipEventDestroy(ev_busy);
+    if (ev_lane) (void)hipEventDestroy(ev_lane);
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (lane1) (void)hipStreamDestroy(lane1);
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
     if (stream && !borrowed_stream) (void)hipStreamDestroy(stream);
@@ -238,6 +246,7 @@ struct rpsf_plan : PlanStream {
   ~rpsf_plan() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
+    if (lane1) (void)hipStreamSynchronize(lane1);
     if (ev_view) (void)hipEventDestroy(ev_view);
     bands.clear();
   }
@@ -329,7 +338,9 @@ RPSF_HIDDEN OverlapKind rpsf_detail_overlap_kind(const rpsf_plan* p);
 RPSF_HIDDEN int rpsf_detail_check_geometry(const rpsf_plan* p, const rpsf_geometry* g);
 RPSF_HIDDEN bool rpsf_detail_lattice_covers_window(const rpsf_plan* p, const rpsf_geometry& g);
 RPSF_HIDDEN int rpsf_detail_launch_apply(rpsf_plan* p, const float* d_img, float* d_out, const rpsf_geometry& g, hipStream_t st,
-                                         hipEvent_t ev_k0, hipEvent_t ev_k1 = nullptr, Batch b = Batch());
+                                         hipEvent_t ev_k0, hipEvent_t ev_k1 = nullptr, Batch b = Batch(), bool may_pipeline = false);
+RPSF_HIDDEN int rpsf_detail_join_lanes(rpsf_plan* p);
+RPSF_HIDDEN void rpsf_detail_clear_error(rpsf_plan* p);
 RPSF_HIDDEN int rpsf_detail_launch_batch(rpsf_plan* p, const float* d_imgs, float* d_outs, int n_frames, size_t im_stride, size_t out_stride,
                                          const rpsf_geometry& g, hipStream_t st, hipEvent_t ev_k0 = nullptr, hipEvent_t ev_k1 = nullptr);
 RPSF_HIDDEN int rpsf_detail_plan_create_impl(rpsf_plan** out, int device, int patch_size, int n_patches, const int32_t* coords_rc, rpsf_plan* parent,

@@ -208,6 +208,10 @@ static int check_saturated_call(rpsf_plan* p, const void* a, const void* b, int 
   if (pad_mode < 0 || pad_mode > RPSF_PAD_WRAP) return fail(RPSF_E_BADARG, "unknown pad mode");
   if (dilation < 1 || neighborhood_width < 0) return fail(RPSF_E_BADARG, "dilation must be >= 1 and the neighbourhood width >= 0 (other values: the NumPy route)");
   if (!p->have_k) return fail(RPSF_E_STATE, "no transfer kernel installed (call rpsf_plan_set_transfer first)");
+  // every saturation and mask entry point: the plan's launch lanes are joined first (rpsf_lanes.hpp), and an error word nobody collected is not
+  // this call's
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;
+  rpsf_detail_clear_error(p);
   return RPSF_OK;
 }
 
@@ -563,6 +567,7 @@ static int apply_views(rpsf_plan* p, const rpsf_view* images, const rpsf_view* o
   }
   if (rc != RPSF_OK) return rc;
   HIP_TRY(hipSetDevice(p->device));
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;  // (device-array views: conversions and copies run on the public stream around the apply)
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : p->stream;
   const size_t npix = (size_t)H * W, stage_stride = (npix + 3) / 4 * 4;  // (every staged frame starts on 16 bytes)
   const bool staged = !in.direct || !out.direct;
@@ -759,6 +764,8 @@ static int sat_fill_frames(rpsf_plan* p, const float* images_host, int n_frames,
   const long PH = (long)height + 4L * p->N, PW = (long)width + 4L * p->N;
   if (PH * PW >= ((long)1 << 31)) return fail(RPSF_E_UNSUPPORTED, "padded frame too large for this entry point");
   HIP_TRY(hipSetDevice(p->device));
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;
+  rpsf_detail_clear_error(p);
   if (!p->sat_dev) p->sat_dev.reset(rpsf_sat_create());
   SatDevice* sd = p->sat_dev.get();
   const SatCall call{height, width, p->N, pad_mode, dilation, neighborhood_width, threshold, 0, 0, 1};
@@ -831,6 +838,8 @@ extern "C" int rpsf_saturation_fill_masked_device(rpsf_plan* p, const float* ima
                   (size_t)(height - 1) * mask_row_stride + (size_t)(width - 1) * mask_col_stride + 1 > mask_frame_bytes))
     return fail(RPSF_E_BADARG, "mask: the strides do not fit mask_frame_bytes");
   HIP_TRY(hipSetDevice(p->device));
+  if (const int jrc = rpsf_detail_join_lanes(p); jrc != RPSF_OK) return jrc;
+  rpsf_detail_clear_error(p);
   DevBuf<uint8_t> d_masks;
   std::vector<rpsf_view> views((size_t)n_masks);
   if (n_masks) HIP_TRY(d_masks.upload(masks_in_host, mask_frame_bytes * n_masks));
