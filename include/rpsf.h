@@ -121,6 +121,12 @@ enum {
                                  value of the result. */
 };
 int rpsf_plan_set_option(rpsf_plan* plan, int option, int value);
+/* The launch lanes of the plan (of a view: its parent's), read-only and host-side: info[0], info[1] the pipelined applies begun so far on the
+ * plan's public stream and on its second stream, info[2] those of them that were begun while the previous apply might still run (they wait
+ * for its tile sums), info[3] the times an operation that is not a pipelined apply found the second stream busy and made the public stream
+ * wait for it, info[4] whether RPSF_OPT_PIPELINE is in force (0 / 1), info[5] whether the plan keeps to one stream because its stream handle
+ * was taken (0 / 1).  Enqueues nothing and waits for nothing. */
+int rpsf_plan_lane_info(const rpsf_plan* plan, long info[6]);
 int rpsf_plan_sweep_info(const rpsf_plan* plan, int* regions, long* jobs, long* patch_slots, int* slabs_per_phase);
 /* Row bands the last single host frame (rpsf_apply_host / rpsf_apply, one frame) was cut into: 0 = it went as a whole.  A frame of B bands
  * cannot take less than PCIe's duplex time x (1 + 1/B) (bench.py's e2e.pcie_floor_ms). */

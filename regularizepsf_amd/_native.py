@@ -88,6 +88,7 @@ _PROTOTYPES = {
     "rpsf_plan_set_sweep_regions": (c_int, [c_void_p, c_int]),
     "rpsf_plan_set_option": (c_int, [c_void_p, c_int, c_int]),
     "rpsf_plan_host_bands": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "rpsf_plan_lane_info": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_long)]),
     "rpsf_plan_sweep_info": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_long), ctypes.POINTER(c_int)]),
     "rpsf_plan_set_stagger": (c_int, [c_void_p, c_int]),
     "rpsf_plan_set_image_prefetch": (c_int, [c_void_p, c_int]),
@@ -361,6 +362,13 @@ class Plan:
         jobs, slots = ctypes.c_long(0), ctypes.c_long(0)
         check(lib().rpsf_plan_sweep_info(self._handle, ctypes.byref(regions), ctypes.byref(jobs), ctypes.byref(slots), ctypes.byref(slabs)))
         return {"regions": regions.value, "jobs": jobs.value, "patch_slots": slots.value, "slabs_per_phase": slabs.value}
+
+    def lane_info(self) -> dict:
+        """The launch lanes (rpsf_plan_lane_info): pipelined applies begun on either stream, those that wait at the gate, joins that found
+        the second stream busy, and whether the pipeline is enabled / the plan's stream handle exposed.  Host counters: nothing is enqueued."""
+        v = (ctypes.c_long * 6)()
+        check(lib().rpsf_plan_lane_info(self._handle, v))
+        return {"lane0": v[0], "lane1": v[1], "gated": v[2], "joins": v[3], "enabled": bool(v[4]), "exposed": bool(v[5])}
 
     def host_bands(self) -> int:
         """Row bands the last single host frame was cut into (0: it went as a whole)."""

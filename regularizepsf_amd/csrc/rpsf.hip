@@ -1144,6 +1144,12 @@ extern "C" int rpsf_plan_host_bands(const rpsf_plan* p, int* bands) {
   *bands = p->last_host_bands;
   return RPSF_OK;
 }
+// The lane report: what the lane book (rpsf_lanes.hpp) has decided so far.  Reads host fields only - no stream operation, no join.
+extern "C" int rpsf_plan_lane_info(const rpsf_plan* p, long info[6]) {
+  if (!p || !info) return fail(RPSF_E_BADARG, "null argument");
+  (p->parent ? p->parent : p)->patch.lanes.info(info);
+  return RPSF_OK;
+}
 extern "C" int rpsf_plan_sweep_info(const rpsf_plan* p, int* regions, long* jobs, long* patch_slots, int* slabs_per_phase) {
   if (!p) return fail(RPSF_E_BADARG, "null plan");
   if (regions) *regions = p->sweep.ok ? p->sweep.n_regions : 0;

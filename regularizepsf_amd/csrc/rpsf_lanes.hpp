@@ -75,12 +75,18 @@ struct LaneBook {
   bool lane1_forked = false;    // lane 1 has waited for the fork event recorded since the last join
   LaneRange last_img, last_out;  // the caller's buffers of the last pipelined apply
   LaneLayout last_layout;        // ... and where its planes lie
+  // The lane report (rpsf_plan_lane_info): host-side counts that nothing reads but a caller who asks - pipelined applies begun on either lane,
+  // those of them that wait at the gate, and the joins that found lane 1 busy.  No decision depends on them.
+  long begun[2] = {0, 0};
+  long begun_gated = 0;
+  long joins_due = 0;
 
   // Everything that is not a pipelined apply calls this first.  True: lane 1 has work in flight - record its end and let the public stream wait.
   // Whatever the caller enqueues next goes to the public stream, so lane 1 has to be forked from it again before its next launch.
   bool join() {
     const bool due = lane1_busy;
     lane1_busy = false, last_lane = -1, public_dirty = true;
+    if (due) ++joins_due;
     return due;
   }
 
@@ -115,11 +121,18 @@ struct LaneBook {
         lane1_forked = true, lane1_busy = true;
       }
       last_lane = k.lane, last_img = img, last_out = out, last_layout = layout;
+      ++begun[k.lane];
+      if (k.gate) ++begun_gated;
     }
     if (gated_kernel) k.seq = ++seq;
     for (int x = 0; x < 8; ++x) k.xq_base[x] = xq_base[k.lane][x];
     k.sum_queue_base = sum_queue_base[k.lane];
     return k;
+  }
+
+  // out (6): pipelined applies begun on lane 0, on lane 1, those begun with `gate` set, joins that were due, enabled, exposed
+  void info(long out[6]) const {
+    out[0] = begun[0], out[1] = begun[1], out[2] = begun_gated, out[3] = joins_due, out[4] = enabled ? 1 : 0, out[5] = exposed ? 1 : 0;
   }
 
   // The launch is on its way: its lane's queue counters will end `draws` further on

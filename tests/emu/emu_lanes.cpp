@@ -12,6 +12,7 @@ extern "C" void emu_lanes_reset(int enabled, uint32_t seq, uint32_t done_epoch) 
 }
 extern "C" void emu_lanes_enable(int enabled) { g_book.enabled = enabled != 0; }
 extern "C" void emu_lanes_expose() { g_book.exposed = true; }
+extern "C" void emu_lanes_set_exposed(int exposed) { g_book.exposed = exposed != 0; }  // (RPSF_OPT_PIPELINE set to 1 again arms the lanes)
 extern "C" int emu_lanes_join() { return g_book.join() ? 1 : 0; }
 extern "C" int emu_lanes_epoch_restarts(int frames) { return g_book.epoch_restarts(frames) ? 1 : 0; }
 // out (2): epoch, restart
@@ -37,5 +38,11 @@ extern "C" void emu_lanes_commit(int lane, const uint32_t* xq_draws, uint32_t su
   for (int x = 0; x < 8; ++x) d.xq[x] = xq_draws[x];
   d.sum = sum_draws;
   g_book.commit(k, d);
+}
+// out (6): as rpsf_plan_lane_info - applies begun on lane 0, on lane 1, begun with the gate set, joins that were due, enabled, exposed
+extern "C" void emu_lanes_info(int64_t* out) {
+  long v[6];
+  g_book.info(v);
+  for (int i = 0; i < 6; ++i) out[i] = v[i];
 }
 extern "C" int emu_lanes_seq_reached(uint32_t have, uint32_t want) { return lane_seq_reached(have, want) ? 1 : 0; }

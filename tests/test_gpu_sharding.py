@@ -124,3 +124,96 @@ def test_sharded_step_world_2_rccl_same_device():
     if refused:
         pytest.skip(f"RCCL refuses a world of two ranks on one device here: {refused[0]}")
     _check(results)
+
+
+# ---- the sharded step straight behind pipelined applies of the band's plan (RPSF_OPT_PIPELINE) --------------------------------
+def _pipelined_worker(rank, world, port, form, queue):
+    """k = 1, 2, 3 pipelined applies of the band's main plan into two buffers in turn, then ``step()`` with no synchronise in between: the step's
+    own apply, its waits, K4 and the seam exchange go onto the plan's stream handle behind an apply that is in flight on the second lane.
+    Reference: the same calls with the option off and a synchronise behind each.  Everything is compared here, bit for bit; the lane report's
+    deltas go back to the test."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import torch.distributed as dist
+
+    import bench
+    from regularizepsf_amd import _native
+    from regularizepsf_amd.sharding import ShardedApply
+    from tests import pipeline_cases as pc
+
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        coords, k, image = _case()
+        sh = ShardedApply(coords, lambda idx: k[idx], N, H, W, rank, world, 0, bench.GlooSeam(rank, world, 0), overlap=pc.SHARDED_FORMS[form])
+        b, g = sh.band, sh.geometry
+        rows = image[b.image_row0 : b.image_row0 + b.image_rows]
+        sh.upload_rows(rows)
+        others = [_native.DeviceBuffer(rows.nbytes).upload(np.ascontiguousarray(rows[::-1]) * np.float32(i + 2)) for i in range(3)]  # the prefix's frames
+        outs = [_native.DeviceBuffer(g.out_rows * W * 4) for _ in range(2)]
+        fill = np.full((g.out_rows, W), -1.0, np.float32)
+        report = {}
+        for n in (1, 2, 3):
+            results = {}
+            for pipelined in (False, True):
+                sh.synchronize()
+                for o in outs:
+                    o.upload(fill)
+                sh.plan.set_option("pipeline", int(pipelined))  # (1: the caller's word that nothing of theirs is on the plan's stream any more)
+                before = sh.plan.lane_info()
+                for i in range(n):
+                    sh.plan.apply_device(others[i].ptr, outs[i & 1].ptr, g)
+                    if not pipelined:
+                        sh.synchronize()
+                sh.step()
+                info = sh.plan.lane_info()
+                lanes = tuple(info[key] - before[key] for key in ("lane0", "lane1", "gated", "joins"))
+                results[pipelined] = [sh.owned_rows(), sh.spill_rows()] + [o.download((g.out_rows, W)) for o in outs]
+                if pipelined:
+                    report[n] = {"lanes": lanes, "exposed": info["exposed"], "enabled": info["enabled"],
+                                 "same": [pc.same_bytes(x, y) for x, y in zip(results[True], results[False])],
+                                 "fresh": not np.array_equal(results[True][0][: min(b.own_rows, g.out_rows)], results[True][2][: min(b.own_rows, g.out_rows)])
+                                 and (n < 2 or not np.array_equal(results[True][2], results[True][3])) and not np.array_equal(results[True][2], fill)}
+                else:
+                    report[n, "reference lanes"] = lanes
+        queue.put((rank, "ok", report))
+        dist.barrier()
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(900, method="thread")
+@pytest.mark.parametrize("form", ["sequence", "overlap", "pipeline"])
+def test_sharded_step_behind_pipelined_applies(form):
+    import multiprocessing as mp
+
+    from tests import pipeline_cases as pc
+
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    queue = ctx.Queue()
+    procs = [ctx.Process(target=_pipelined_worker, args=(r, 2, port, form, queue)) for r in range(2)]
+    for p in procs:
+        p.start()
+    results = {}
+    try:
+        for _ in range(2):
+            rank, status, payload = queue.get(timeout=600)
+            results[rank] = (status, payload)
+    finally:
+        for p in procs:
+            p.join(timeout=60)
+            if p.is_alive():
+                p.kill()
+    for rank in (0, 1):
+        status, report = results[rank]
+        assert status == "ok"
+        for n in pc.PREFIXES:
+            got, expected = report[n], pc.EXPECTED[f"sharded_{form}-r{rank}-k{n}"]
+            print(f"LANES | sharded step, {form}, rank {rank}, prefix {n} | {got['lanes']} | expected {expected} | exposed {got['exposed']}, enabled {got['enabled']}")
+            assert report[n, "reference lanes"] == (0, 0, 0, 0)
+            assert all(got["same"]), (form, rank, n, got["same"])  # owned rows, spill, both prefix outputs
+            assert got["fresh"], "the prefix outputs and the band's rows must differ from one another"
+            assert got["lanes"] == expected
+            assert got["exposed"] and got["enabled"] == (form != "pipeline")

@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import pipeline_cases as pc
 from tests.lattice_cases import lattice, thinned
 from tests.test_lattice_host import _build as lattice_build
 from tests.test_lattice_host import lib as lattice_lib  # noqa: F401  (the fixture that builds the lattice emulator)
@@ -44,6 +45,8 @@ def lib():
     so.emu_lanes_commit.argtypes = [ctypes.c_int, VP, ctypes.c_uint32]
     so.emu_lanes_seq_reached.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     so.emu_lanes_next_epoch.argtypes = [ctypes.c_int, VP]
+    so.emu_lanes_info.argtypes = [VP]
+    so.emu_lanes_set_exposed.argtypes = [ctypes.c_int]
     return so
 
 
@@ -69,8 +72,10 @@ class Model:
         """set_transfer, an option, a batch, a synchronise ... : joins, then works on the public stream.  Returns what it runs behind."""
         return self.join()
 
-    def apply(self, hot, gated, frames, img, out, draws, layout=WHOLE):
-        restart = bool(self.lib.emu_lanes_epoch_restarts(frames))
+    def apply(self, hot, gated, frames, img, out, draws, layout=WHOLE, fused=True):
+        """fused=False: a launch whose plane sum is a kernel of its own (or that has none): no tile counters, no epoch - and never the gated kernel."""
+        assert fused or not (hot or gated)
+        restart = fused and bool(self.lib.emu_lanes_epoch_restarts(frames))
         hot = hot and gated and frames == 1 and not restart  # (rpsf.hip, launch_apply: such a launch is never pipelined)
         k = np.zeros(16, np.int64)
         lay = np.asarray(layout, np.int64)
@@ -83,12 +88,13 @@ class Model:
         if wait_fork:
             self.clock[1] |= self.fork
         e = np.zeros(2, np.int64)
-        self.lib.emu_lanes_next_epoch(frames, e.ctypes.data_as(VP))
+        if fused:
+            self.lib.emu_lanes_next_epoch(frames, e.ctypes.data_as(VP))
         xq = np.asarray(draws[:8], np.uint32)
         self.lib.emu_lanes_commit(lane, xq.ctypes.data_as(VP), int(draws[8]))
         me = len(self.applies)
         a = dict(lane=lane, pred=set(self.clock[lane]), hot=hot, gate=bool(gate), seq=seq, want=want, epoch=int(e[0]), restart=bool(e[1]),
-                 gated=gated, img=img, out=out, layout=tuple(layout), base=[int(v) for v in k[8:16]] + [int(k[7])], draws=list(draws), joined=bool(join), frames=frames)
+                 gated=gated, img=img, out=out, layout=tuple(layout), base=[int(v) for v in k[8:16]] + [int(k[7])], draws=list(draws), joined=bool(join), frames=frames, fused=fused)
         self.applies.append(a)
         self.clock[lane] = self.clock[lane] | a["pred"] | {me}
         return a
@@ -137,6 +143,8 @@ def check(model):
                 assert a["base"][q] == 0
             ends[a["lane"]][q] = (a["base"][q] + a["draws"][q]) % U32
         # epochs: + 1 per fused launch, a new count (the counters are cleared) only behind everything; none repeats within a count
+        if not a["fused"]:
+            continue
         if a["restart"]:
             assert before <= a["pred"] and a["epoch"] == 1
             seen_epochs = [1]
@@ -286,3 +294,119 @@ def test_the_gate_guards_the_tiles_the_counters_count(lattice_lib):
             assert tile.min() >= 0 and tile.max() < t["nti"] * t["ntj"]
         checked += 1
     assert checked >= 25
+
+
+# ---- the lane report (rpsf_plan_lane_info) and the sequences of tests/pipeline_cases.py -----------------------------------------------------
+def lane_info(lib):
+    v = np.zeros(6, np.int64)
+    lib.emu_lanes_info(v.ctypes.data_as(VP))
+    return [int(x) for x in v]
+
+
+@pytest.mark.parametrize("seed", range(20))
+def test_the_lane_report_counts_the_random_sequences(lib, seed):
+    """Lane 0 and lane 1 sum to the pipelined applies, the gated count is the applies that may run beside their predecessor or behind it on
+    the other lane, and a join is counted exactly when lane 1 held work the public stream did not wait for yet."""
+    rng = np.random.default_rng(1000 + seed)
+    m = Model(lib)
+    bufs = [(i * 1000, i * 1000 + 900) for i in range(6)]
+    want = dict(lane=[0, 0], gated=0, joins=0)
+    busy = False  # lane 1 holds an apply no join has covered yet
+    for _ in range(400):
+        r = rng.random()
+        before = lane_info(lib)
+        if r < 0.75:
+            i, o = rng.choice(len(bufs), 2, replace=False)
+            a = m.apply(True, True, 1, bufs[i], bufs[o], [3] * 9, LAYOUTS[int(rng.integers(len(LAYOUTS)))] if rng.random() < 0.15 else WHOLE)
+            pipelined = a["hot"] and bool(before[4]) and not before[5]
+            if a["joined"] or not pipelined:
+                want["joins"] += busy
+                busy = False
+            if pipelined:
+                want["lane"][a["lane"]] += 1
+                want["gated"] += a["gate"]
+                busy = busy or a["lane"] == 1
+            else:
+                assert not a["gate"] and a["lane"] == 0
+        elif r < 0.85:
+            m.apply(False, True, int(rng.integers(1, 4)), bufs[0], bufs[1], [3] * 9)
+            want["joins"] += busy
+            busy = False
+        elif r < 0.95:
+            m.other()
+            want["joins"] += busy
+            busy = False
+        else:
+            m.other()
+            want["joins"] += busy
+            busy = False
+            lib.emu_lanes_enable(int(rng.random() < 0.7))
+        got = lane_info(lib)
+        assert got[:4] == [want["lane"][0], want["lane"][1], want["gated"], want["joins"]]
+        assert got[1] == sum(1 for a in m.applies if a["lane"] == 1)  # (nothing but a pipelined apply ever takes lane 1)
+    check(m)
+    assert want["lane"][1] > 20 and want["joins"] > 10, "the sequences must exercise lane 1 and joins that are due"
+
+
+BUFFERS = {name: (i * 10000, i * 10000 + 9000) for i, name in enumerate(["f0", "f1", "f2", "f3", "top", "o0", "o1"])}
+BUFFERS["o1"] = (BUFFERS["o0"][1], BUFFERS["o0"][1] + 9000)  # the two outputs are one allocation
+SCRIPT_LAYOUTS = {"whole": WHOLE, "top": LAYOUTS[1]}
+
+
+def replay(lib, script):
+    """A script of tests/pipeline_cases.py on the model: the lane report's deltas, after the invariants of every apply have been checked."""
+    m = Model(lib)
+    multi = False
+    for token in script:
+        what = token[0]
+        if what == "hot":
+            m.apply(not multi, True, 1, BUFFERS[token[1]], BUFFERS[token[2]], [3] * 9, SCRIPT_LAYOUTS[token[3]])
+        elif what == "cold":
+            _, frames, fused, gated = token
+            m.apply(False, gated, frames, (0, 1), (2, 3), [3] * 9, fused=fused)
+        elif what == "join":
+            m.other()
+        elif what == "enable":
+            lib.emu_lanes_enable(token[1])
+        elif what == "expose":
+            lib.emu_lanes_set_exposed(token[1])
+        elif what == "multi":
+            multi = True
+        else:
+            assert what == "nop", token
+    check(m)
+    return tuple(lane_info(lib)[:4])
+
+
+def test_the_sequences_of_the_gpu_tests_give_the_lane_reports_they_expect(lib):
+    scripts = pc.sequences()
+    assert set(scripts) == set(pc.EXPECTED)
+    wrong = {name: (replay(lib, script), pc.EXPECTED[name]) for name, script in scripts.items() if replay(lib, script) != pc.EXPECTED[name]}
+    assert not wrong, wrong
+    # by hand: forty hot applies alternate, all but the first wait at the gate, nothing joins; one operation behind a busy lane 1 joins once
+    assert pc.EXPECTED["loop"] == (20, 20, 39, 0)
+    assert pc.EXPECTED["set_transfer_device-k2"] == (3, 2, 3, 1) and pc.EXPECTED["set_transfer_device-k1"] == (3, 1, 2, 0)
+    for k in pc.PREFIXES:  # every sandwich's prefix leaves lane 1 busy from two applies on, and its operation meets it
+        for name, o in pc.OPS_BY_NAME.items():
+            joins = pc.EXPECTED[f"{name}-k{k}"][3]
+            if name == "setters_without_join":
+                assert joins == 0
+            else:
+                assert joins >= (1 if k >= 2 else 0), (name, k)
+
+
+def test_every_entry_point_that_takes_a_plan_is_accounted_for():
+    """A new entry point cannot arrive without the decision: which case runs it behind pipelined applies, or why it touches no stream."""
+    import re
+
+    header = (ROOT / "include" / "rpsf.h").read_text()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    names = set(re.findall(r"\b(rpsf_\w+)\s*\(\s*(?:const\s+)?rpsf_plan\s*\*\s*\w", header))
+    assert len(names) > 40 and "rpsf_apply_device" in names and "rpsf_plan_lane_info" in names and "rpsf_plan_create" not in names
+    assert names == set(pc.COVERAGE), (sorted(names - set(pc.COVERAGE)), sorted(set(pc.COVERAGE) - names))
+    known = set(pc.OPS_BY_NAME) | {"loop", "growth", "rounds", "destroy"}
+    for name, (kind, value) in pc.COVERAGE.items():
+        if kind == "cases":
+            assert value and set(value) <= known, name
+        else:
+            assert kind == "no stream" and len(value) > 10, name
