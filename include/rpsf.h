@@ -14,9 +14,9 @@
  *   - applies of distinct plans on distinct streams may run on the device at the same time.  The launches of the
  *     128- and 256-pixel plans are persistent (workgroups that stay resident and draw patches from queues) and contain
  *     workgroups that wait for others of the same launch; they need no particular number of resident workgroups to
- *     finish - every patch is drawn from a queue by whichever workgroups are resident - as long as the few (<= 128)
- *     summing workgroups at the head of all concurrent launches together leave one compute unit free
- *     (csrc/rpsf.hip, launch_patches, "FORWARD PROGRESS").
+ *     finish - every patch is drawn from a queue by whichever workgroups are resident - as long as the few (<= 160)
+ *     summing workgroups at the head of all concurrent launches together leave one compute unit free on every XCD
+ *     (csrc/rpsf_launch.hpp, launch_decide, "FORWARD PROGRESS"; rpsf_plan_set_cu_mask below for plans on a part of the chip).
  */
 #ifndef RPSF_H
 #define RPSF_H
@@ -145,7 +145,14 @@ int rpsf_plan_set_reserved_cus(rpsf_plan* plan, int cus);
  * sized for them; rpsf_stream_create makes a stream masked to whatever the caller passes (NULL: unmasked).  The pipelined seam exchange
  * gives RCCL's kernels and K4 a handful of CUs of their own this way (rpsf_plan_set_reserved_cus only leaves CUs unclaimed - a kernel
  * dispatched a moment before the persistent launch still lands on CUs that launch is waiting for).  A masked plan gives up its second
- * launch lane, which is not masked: RPSF_OPT_PIPELINE has no effect on it from then on. */
+ * launch lane, which is not masked: RPSF_OPT_PIPELINE has no effect on it from then on.  A mask of fewer than 8 CUs is refused (RPSF_E_BADARG), but a mask is
+ * meant to take a FEW CUs off the chip (the sharded step: 8 of 256).  The fused launches put up to 32 (256-pixel plan) or 160 (128-pixel
+ * plan, four to a CU) head summing workgroups in front of the patches by the amount of work alone, and need room beside them, on every
+ * XCD, for a patch workgroup: on a plan masked to fewer than 40 CUs (256-pixel plan) or 42 CUs (128-pixel plan) an apply of 512
+ * patch-frames or more may NEVER END, and a mask that leaves some XCD only a few CUs is no safer at a larger count
+ * (csrc/rpsf_launch.hpp, FORWARD PROGRESS; tests/test_launch_host.py records where a model of the launch stalls).  An apply on a caller's
+ * own masked stream is NOT sized by that stream's mask - the library cannot see it - but by the plan's own CU count (the device's, or the
+ * last rpsf_plan_set_cu_mask), and the same limits apply to that stream's CUs. */
 int rpsf_plan_set_cu_mask(rpsf_plan* plan, const uint32_t* mask, int words);
 int rpsf_stream_create(int device, const uint32_t* mask, int words, void** stream);
 int rpsf_stream_destroy(void* stream);

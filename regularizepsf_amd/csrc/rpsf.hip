@@ -600,20 +600,6 @@ static void fill_plane_sum(P& s, const rpsf_plan* p, float* d_out, const rpsf_ge
   s.lat_r0 = p->lat_r0 + g.origin_row, s.lat_c0 = p->lat_c0 + g.origin_col, s.ntj = p->ntj;
 }
 
-// Summing workgroups that run beside the patches from the start of a fused launch (multiple of 8: one per XCD), by the
-// amount of work in the launch.  256-pixel plan (512-thread workgroups, one per CU): r02y, a band of 520 patches 130-138 us
-// with 8, 131-146 with 32; r02av, plane stores kept in the Infinity Cache: 4096^2 0.193 / 0.190 / 0.196 ms with 8 / 16 / 24,
-// 8192^2 0.78 / 0.77 / 0.74 / 0.765 ms with 8 / 16 / 32 / 48 - the sooner a tile is summed, the likelier its planes are still
-// cached.  128-pixel plan (128-thread workgroups, four per CU): 4096^2 0.217 / 0.214 / 0.212 / 0.206 ms with 16 / 64 / 96 / 128
-// against 0.218 ms with the separate sum kernel; 2048^2 0.067 ms with 0 ... 24 against 0.069; 8 x 2048^2 0.372 / 0.360 / 0.352 /
-// 0.343 / 0.340 ms with 8 / 32 / 64 / 128 / 192 against 0.362.
-static int sum_first_for(const rpsf_plan* p, int frames) {
-  if (p->patch.sum_first >= 0) return p->patch.sum_first;
-  const long work = (long)p->n_patches * frames;
-  if (p->N == 128) return work >= 4096 ? 160 : work >= 2048 ? 128 : work >= 512 ? 8 : 0;  // (160 from 4096 patch-frames on: -2 ... -4 %, profiles/r04bf)
-  return work >= 2048 ? 32 : work >= 1024 ? 16 : work >= 512 ? 8 : 0;
-}
-
 // What the persistent kernels are compiled for (hot_geometry, rpsf_lattice.hpp), for this plan, image and frame stride
 static bool hot_geometry(const rpsf_plan* p, const float* d_img, const rpsf_geometry& g, size_t im_stride) {
   const bool aligned16 = im_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(d_img) & 15) == 0 && p->patch.planes_floats % 4 == 0;
@@ -622,20 +608,9 @@ static bool hot_geometry(const rpsf_plan* p, const float* d_img, const rpsf_geom
 
 // What the patch launch of one apply is: decided by patch_launch_for from the plan as it stands, committed by launch_apply (the queue positions the
 // launch takes) and turned into PatchParams and a kernel by launch_patches.
-struct PatchLaunch {
-  // first generation / second generation, patches only / fused: summing workgroups behind (and sum_first beside) the patches / persistent: patch
-  // workgroups that draw their slots from per-XCD queues and end as summing ones
-  enum Form { GEN1, GEN2, FUSED, PERSISTENT } form;
-  enum Variant { PLAIN, K_CACHED, K_CACHED_PLANES_NT } variant;  // persistent: PersistentKernel2's fn / fn_k_cached / fn_k_cached_planes_nt
-  unsigned grid;      // workgroups
-  int chunk;          // patches per XCD chunk
-  int patch_blocks;   // second generation: workgroups [sum_first, sum_first + patch_blocks) of a launch that is not persistent process patches
-  int stagger_ticks, stagger_blocks;
-  int sum_first, frame_major, plane_nt;  // fused and persistent
-  int rows, head_patches, prefetch;      // persistent: patch workgroups per XCD, ...
-  int k_prefetch;                        // persistent, 256-pixel plan: first-round K prefetch by the head summing workgroups (0 / 1)
-  uint32_t xq_base[8], xq_draws[8];      // persistent: where this launch's draws from the slot queue of each XCD start, and how many it makes
-  uint32_t sum_queue_base, sum_queue_draws;  // fused and persistent: the same for the tile queue
+struct PatchLaunch : LaunchDecision {  // (rpsf_launch.hpp: the form, the grid, the workgroups of each role and the draws from every queue word)
+  uint32_t xq_base[8];      // persistent: where this launch's draws from the slot queue of each XCD start
+  uint32_t sum_queue_base;  // fused and persistent: the same for the tile queue
   // the launch lane (rpsf_lanes.hpp, committed by launch_apply): whose queue words the launch draws from, what its tile sums publish and whether its
   // patches wait for the previous apply's
   int lane;
@@ -643,97 +618,27 @@ struct PatchLaunch {
   uint32_t seq;
 };
 
-// A patch launch is one grid of at most 2^31 - 1 workgroups: one per frame and patch_teams() patches of each chunk
-static bool patch_launch_too_large(const rpsf_plan* p, int frames) {
-  const int teams = patch_teams(p->N);
-  return (size_t)8 * (chunk_patches(p->n_patches, teams) / teams) * frames > 0x7fffffffu;
-}
-
+// The plan and the apply as launch_decide (rpsf_launch.hpp) sees them; the arithmetic - and the FORWARD PROGRESS argument of the persistent form - is there.
 // fused: the plane sum runs in this launch (see PatchPath::d_tile_done)
 template <class T>
 static PatchLaunch patch_launch_for(const rpsf_plan* p, const float* d_img, const rpsf_geometry& g, Batch b, bool fused) {
-  constexpr bool N256 = T::V2 && T::Cfg::N == 256, N128 = T::V2 && T::Cfg::N == 128;
-  PatchLaunch L{};
-  L.chunk = chunk_patches(p->n_patches, T::TEAMS);
-  L.stagger_ticks = std::max(0, p->patch.stagger_us) * 100;
-  L.grid = (unsigned)((size_t)8 * (L.chunk / T::TEAMS) * b.frames);  // (patch_launch_too_large: it fits)
-  L.form = T::V2 ? PatchLaunch::GEN2 : PatchLaunch::GEN1;
-  L.stagger_blocks = T::V2 ? p->patch.round_capacity : p->cu_count * std::max(1, 512 / T::WG);
-  L.patch_blocks = T::V2 ? (int)L.grid : 0;  // (the first-generation kernel does not read it)
-  if (!fused) return L;                      // (fused: second-generation plans only, launch_apply)
-  const int count = p->nti * p->ntj * b.frames;  // positions of the tile list
-  // Persistent batches whose planes would not fit the Infinity Cache side by side run frame after frame in one launch: every
-  // frame keeps the cache behaviour of a single apply, and the next frame's patches take the CUs the previous one's last
-  // patches leave idle (RPSF_FRAME_MAJOR=0/1 overrides).
-  bool frame_major = N256 && p->patch.persist && b.frames > 1 && p->n_patches >= 1024 &&
-                     16.0 * (double)p->patch.planes_floats * b.frames > 256.0 * 1048576.0;  // (8 x 2048^2: 0.056 ms per frame side by side, 0.061 in turn)
-  if (const char* e = dev_env("RPSF_FRAME_MAJOR"))  // development sweeps: 0 = never, 2 = any persistent batch
-    frame_major = std::atoi(e) == 2 ? (p->patch.persist && b.frames > 1) : (frame_major && std::atoi(e) != 0);
-  L.frame_major = frame_major ? 1 : 0;
-  // Frames of a batch side by side keep the planes of ALL of them live at once (8 x 2048^2: 537 MB against a 256 MiB Infinity Cache): the 128-pixel
-  // kernels then store them with the streaming hint - 0.3156 -> 0.3009 ms (-4.7 %); a single frame loses 8 % that way, and so does the 256-pixel
-  // plan at either size (profiles/r04bd).  RPSF_PLANE_NT=0/1 overrides (development sweeps).
-  // (needs the plain-load form of K - a batch shares it - and planes well beyond the Infinity Cache: 4 x 2048^2, 268 MB, still loses 3 %; 6 x, 403 MB, gains 5 %)
-  L.plane_nt = N128 && p->patch.k_cached && b.frames > 1 && !frame_major && 16.0 * (double)p->patch.planes_floats * b.frames > 300.0 * 1048576.0;
-  if (p->patch.plane_nt_opt >= 0) L.plane_nt = p->patch.plane_nt_opt != 0 && N128 && p->patch.k_cached;  // (RPSF_OPT_PLANE_NT)
-  const int tune_frames = b.frames;  // (the settings of a single apply measured worse here: 0.203 vs 0.186 ms per frame at 8 x 4096^2)
-  L.sum_first = sum_first_for(p, tune_frames);
-  // (where the launch's draws start - sum_queue_base, xq_base - depends on the lane it takes: launch_apply fills them in, rpsf_lanes.hpp)
-  // persistent form: as many patch workgroups as the chip holds beside the summing ones; each works through the slots
-  // of its XCD's chunk and ends as a summing workgroup itself (no workgroups behind the patches).
-  // FORWARD PROGRESS.  HIP promises neither that a grid is resident as a whole nor an order of dispatch, and other launches
-  // (a second plan on another stream, RCCL's kernels) may hold CUs.  What this launch needs: (1) every patch slot is drawn
-  // from its chunk's queue - none is tied to a particular workgroup - so the slots of chunk x are worked off by whichever
-  // workgroups with blockIdx % 8 == x are resident, and a workgroup turns to summing only when its chunk's queue is empty,
-  // i.e. when every remaining patch of the chunk is in the hands of a resident workgroup that does not wait for anything;
-  // (2) summing workgroups wait (poll + s_sleep) only for tiles whose patches are drawn or will be drawn by (1).  So the
-  // launch completes as soon as, for every chunk, ONE patch workgroup gets a CU: in dispatch order the first sum_first + 8
-  // workgroups.  The only workgroups that hold a CU without progress of their own are the sum_first head summing ones (<= 32 of
-  // 512 threads for the 256-pixel plan; up to 160 of 128 threads - four to a CU, 40 CUs' worth - for the 128-pixel plan from 4096
-  // patch-frames on, sum_first_for); concurrent persistent launches therefore cannot starve one another unless their head summing
-  // workgroups alone fill the chip (tests: test_two_persistent_plans_on_two_streams, 256- and 128-pixel plans).
-  // (queue positions of an XCD: chunk slots x frames, the frames of a slot side by side)
-  const int rows = std::min(L.chunk * b.frames, std::max(1, (p->patch.round_capacity - L.sum_first - p->patch.reserved_cus) / 8));
+  constexpr bool N256 = T::V2 && T::Cfg::N == 256;
+  LaunchInput in;
+  in.N = p->N, in.gen2 = T::V2, in.wg_threads = T::WG;
+  in.n_patches = p->n_patches, in.tiles = p->nti * p->ntj, in.frames = b.frames;
+  in.cu_count = p->cu_count, in.round_capacity = p->patch.round_capacity;
+  in.wgs_per_cu = std::max(1, p->patch.round_capacity / (std::max(1, p->cu_count) * T::TEAMS));  // (rpsf_plan_create: the occupancy of the patch kernel)
+  in.reserved_cus = p->patch.reserved_cus, in.sum_first = p->patch.sum_first, in.head_patches = p->patch.head_patches;
+  in.persist = p->patch.persist, in.fused = fused;
+  in.hot_geometry = fused && hot_geometry(p, d_img, g, b.im_stride);
   // (the gated kernel - the persistent 256-pixel one - stores the output through one 32-bit buffer offset, as every fused launch does its planes)
-  const bool out_span_ok = !N256 || (size_t)g.out_rows * g.ld_out * sizeof(float) < ((size_t)1 << 32);
-  if (!(p->patch.persist && rows > 0 && out_span_ok && hot_geometry(p, d_img, g, b.im_stride))) {
-    L.form = PatchLaunch::FUSED;
-    const int nsum = std::max(8, std::min(count, p->patch.round_capacity)) + L.sum_first;  // at the tail: as many summing workgroups as the chip holds
-    L.sum_queue_draws = (uint32_t)(count + nsum);  // every workgroup draws one position past the end
-    L.grid += (unsigned)nsum;
-    return L;
-  }
-  L.form = PatchLaunch::PERSISTENT, L.rows = rows;
-  L.variant = !p->patch.k_cached ? PatchLaunch::PLAIN : L.plane_nt ? PatchLaunch::K_CACHED_PLANES_NT : PatchLaunch::K_CACHED;
-  // a head summing workgroup would idle through the first patch period (no tile is complete before that): it computes one patch
-  // of its XCD's chunk first (RPSF_HEAD_PATCHES=0: off)
-  L.head_patches = p->patch.head_patches;
-  L.prefetch = p->patch.prefetch && p->patch.d_prefetch_tiles ? 1 : 0;
-  L.k_prefetch = N256 && !L.head_patches ? p->patch.k_prefetch : 0;
-  // persistent workgroups keep the phase they start with: holding the resident ones back by up to 10 us spreads the
-  // store bursts of the chip over the patch period (profiles/r02ai, r02ak: -2..3 % from four rounds of patches on; with the
-  // plane stores kept in the Infinity Cache, r02av: 0.210 / 0.208 / 0.193 / 0.190 / 0.189 / 0.191 / 0.195 ms at 0 / 5 / 8 / 10 / 12 / 15 / 20 us)
-  // (and smaller launches too: 2048^2 0.0811 -> 0.0787 ms, 3072^2 0.138 -> 0.131 ms, a band of 520 patches 128 -> 121 us)
-  // (long launches take more: 8192^2 0.736 / 0.726 / 0.714 / 0.703 / 0.698 / 0.719 ms at 6 / 12 / 18 / 24 / 30 / 36 us)
-  // (round 4, seven-barrier pass, profiles/r04az: 4096^2 at 12 / 16 / 20 us - the repeated frame 0.1835 / 0.1843 / 0.1880 ms, a NEW frame every step
-  // 0.2019 / 0.1962 / 0.1933: 16 us from 1024 patches of the 256-pixel plan on; 8192^2 0.714 / 0.688 / 0.691 / 0.690 at 12 / 16 / 20 / 24)
-  if (p->patch.stagger_us < 0 && (long)p->n_patches * tune_frames >= 256) {
-    const long work = (long)p->n_patches * tune_frames;
-    L.stagger_ticks = work >= 2048 ? 2400 : (work >= 1024 && N256) ? 1600 : 1200;
-    // The 128-pixel plan - four workgroups per CU, out of step with one another anyway - is better off WITHOUT it since round 4 (profiles/r04ba):
-    // 2048^2 0.0655 -> 0.0603 ms (-8 %), 3072^2 -6 %, 8 x 2048^2 0.3252 -> 0.3198; only single frames of 4096^2 and more still take a short one
-    // (6 us: -1 ... -3 %).
-    if (N128) L.stagger_ticks = tune_frames == 1 && p->n_patches >= 4096 ? 600 : 0;
-  }
-  for (int x = 0; x < 8; ++x) {
-    // draws of this launch: one per slot and frame, plus the one past the end that tells each of the chunk's workgroups to stop
-    // (the first sum_first / 8 positions of a chunk go to the head summing workgroups without a draw when those compute a patch first)
-    const int slots_x = std::min(L.chunk, std::max(0, p->n_patches - x * L.chunk)) * b.frames;
-    L.xq_draws[x] = (uint32_t)(std::max(0, slots_x - (L.head_patches ? L.sum_first / 8 : 0)) + rows);
-  }
-  const int wgs = L.sum_first + 8 * rows;
-  L.sum_queue_draws = (uint32_t)(count + wgs);  // every workgroup draws one position past the end
-  L.grid = (unsigned)wgs;
+  in.out_span_ok = !N256 || (size_t)g.out_rows * g.ld_out * sizeof(float) < ((size_t)1 << 32);
+  in.planes_floats = p->patch.planes_floats, in.k_cached = p->patch.k_cached, in.plane_nt_opt = p->patch.plane_nt_opt;
+  if (const char* e = dev_env("RPSF_FRAME_MAJOR")) in.frame_major_opt = std::atoi(e) == 2 ? 2 : std::atoi(e) != 0 ? 1 : 0;  // development sweeps: 0 = never, 2 = any persistent batch
+  in.stagger_us = p->patch.stagger_us;
+  in.prefetch = p->patch.prefetch && p->patch.d_prefetch_tiles, in.k_prefetch = p->patch.k_prefetch;
+  PatchLaunch L{};
+  static_cast<LaunchDecision&>(L) = launch_decide(in);
   return L;
 }
 
@@ -947,7 +852,7 @@ int rpsf_detail_launch_apply(rpsf_plan* p, const float* d_img, float* d_out, con
   if (kind == OV_DIRECT && !p->patch.direct_ok) return fail(RPSF_E_STATE, "direct overlap-add needs a lattice and a 128- or 256-pixel patch");
   if (kind == OV_DIRECT && (size_t)g.out_rows * g.ld_out * sizeof(float) >= ((size_t)1 << 32))
     return fail(RPSF_E_UNSUPPORTED, "direct overlap-add addresses the output through a 32-bit buffer offset: frame too large");
-  if (patch_launch_too_large(p, b.frames)) return fail(RPSF_E_BADARG, "batch too large for one launch");
+  if (patch_launch_too_large(p->N, p->n_patches, b.frames)) return fail(RPSF_E_BADARG, "batch too large for one launch");
   // Fused plane sum: what the plan must have, and the geometry the summing workgroups are written for (fused_geometry, rpsf_lattice.hpp)
   const bool fused = kind == OV_PLANES && p->patch.v2 && p->patch.fuse_pays && p->patch.d_tile_done && !p->patch.no_fuse && b.frames <= 255 &&
                      fused_geometry(g, p->lat_c0, (reinterpret_cast<uintptr_t>(d_out) & 15) == 0);

@@ -15,14 +15,10 @@
 
 #include "../../include/rpsf.h"
 #include "rpsf_core.hpp"
+#include "rpsf_launch.hpp"  // patch_teams(), chunk_patches(): the processing order and the tile order are cut by the chunk the launches index by
 
 namespace rpsf {
 
-// Patches one workgroup of the patch kernels processes (first generation: 64-thread workgroups shared by several small patches), and
-// the patches per XCD chunk that follow from it: an eighth of the plan's, in whole workgroups.  The processing order, the prefetch
-// lists and the fused tile order are cut by it (lattice_build) and the kernels index by it (PatchParams::chunk).
-constexpr int patch_teams(int N) { return N * N / 2 / 64 >= 64 ? 1 : 64 / (N * N / 2 / 64); }
-inline int chunk_patches(int n_patches, int teams) { return ((n_patches + 7) / 8 + teams - 1) / teams * teams; }
 // Patch sizes the sweep kernel (third generation) is compiled for
 constexpr bool sweep_patch_size(int N) { return N == 64 || N == 32 || N == 16; }
 
