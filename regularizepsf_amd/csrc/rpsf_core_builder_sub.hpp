@@ -132,8 +132,8 @@ inline void neighbour_lists(int H, int W, int N, size_t n_patches, const int32_t
     boxes[j] = Box{1, 0, 1, 0};
     if (!rpsfn::star_rendered(flux[j], cell[j], n_cells)) continue;
     const double y = pos[2 * j], x = pos[2 * j + 1];
-    long r0 = (long)std::floor(y - R) - 1, r1 = (long)std::ceil(y + R) + 1;
-    long c0 = (long)std::floor(x - R) - 1, c1 = (long)std::ceil(x + R) + 1;
+    const rpsfk::DiscBox box = rpsfk::disc_box(y, x, R);  // (the caller has checked position_ok: the box is far from an int's range)
+    long r0 = box.r0, r1 = box.r1, c0 = box.c0, c1 = box.c1;
     if (r0 < 0) r0 = 0;
     if (c0 < 0) c0 = 0;
     if (r1 > H - 1) r1 = H - 1;

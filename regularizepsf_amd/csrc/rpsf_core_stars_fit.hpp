@@ -26,6 +26,8 @@ enum { F_SM, F_SM_ALL, F_SMM, F_SD, F_SDM, F_SDD, F_SUMS };  // sum m (usable), 
 enum { COL_F = (int)COL_FSUMS + (int)F_SUMS, COL_BG, COL_CHI2, COL_ABS_RES, COL_PEAK_RES, COL_PEAK_E, COL_PEAK_ROW, COL_PEAK_COL };
 static_assert((int)COL_PEAK_COL + 1 == FIT_COLUMNS, "a row is the four scalars, the two counts, the six sums, f, bg and the six residual columns");
 enum { R_CHI2, R_ABS, R_PEAK, R_SUMS };  // pass 2's fields, in pass 1's words: sum e e, sum |e|, the signed e of the peak
+enum { RES_CHI2, RES_ABS, RES_PEAK, RES_PEAK_E, RES_PEAK_ROW, RES_PEAK_COL };  // the six residual columns that end a row, from its chi2 on
+static_assert((int)COL_CHI2 + RES_PEAK_COL == (int)COL_PEAK_COL && (int)R_CHI2 == RES_CHI2 && (int)R_ABS == RES_ABS, "pass 2's sums are its first columns");
 
 struct Model {
   const double* cube;  // n_cells x N x N
@@ -58,59 +60,66 @@ RPSFS_HD double model_at(const double* C, int N, double h, double pr, double pc)
   return ((1.0 - a) * ((1.0 - b) * p[0] + b * p[1])) + (a * ((1.0 - b) * p[N] + b * p[N + 1]));
 }
 
-// the total order of the residual's peak: larger |e| (a NaN counts as +inf), then the smaller linear index
-RPSFS_HD double peak_key(double e) {
-  const double a = std::fabs(e);
-  return a == a ? a : (double)INFINITY;
-}
-struct Peak {
-  double e;
-  long long at;
-};
-RPSFS_HD void see_residual(Peak& s, double e, long long at) {
-  if (at < 0) return;
-  const double k = peak_key(e), have = peak_key(s.e);
-  if (s.at < 0 || k > have || (k == have && at < s.at)) s.e = e, s.at = at;
-}
-
-// ------------------------------------------------------------------------------------------------ the records in LDS
-// One record per lane and one per group of 8 lanes, field-major as S6's and S7's (field f of record i of n is word f n + i): F_SUMS
-// doubles, the peak's linear index (64 bits, < 0: no pixel yet), then n and n_all.  Pass 2 puts its R_SUMS doubles into the first words
-// of pass 1's.  Behind them what the first lane of each wave hands to its lanes after the solve: f, bg and whether pass 2 runs.
-enum { FS_F, FS_BG, FS_DOUBLES };
-RPSFS_HD constexpr size_t s8_record_bytes() { return (size_t)F_SUMS * 8 + 8 + 2 * 4; }
-constexpr size_t S8_STATE_BYTES = ((size_t)WALK_WAVES * (FS_DOUBLES * 8 + 4) + 15) & ~(size_t)15;
-RPSFS_HD constexpr size_t s8_lds_bytes() { return (size_t)(WALK_THREADS + WALK_WAVES * 8) * s8_record_bytes() + S8_STATE_BYTES; }
-static_assert((int)R_SUMS <= (int)F_SUMS, "pass 2's fields lie in pass 1's words");
-
-struct FRecords {  // n records at `base` (a multiple of 16 bytes: n is a multiple of 4)
-  double* d;
-  long long* at;
-  int* cnt;
-  int n;
-  RPSFS_HD FRecords(void* base, int n_) : d(static_cast<double*>(base)), n(n_) {
-    at = reinterpret_cast<long long*>(d + (size_t)F_SUMS * n_);
-    cnt = reinterpret_cast<int*>(at + n_);
+// ------------------------------------------------------------------------------------------------ the weights of a fit
+// s8_fit and s12_fit_weighted (rpsf_core_stars_fit_weighted.hpp) are ONE driver, fit_disc, over a weight policy chosen at compile time.
+// A policy says how many sums a lane keeps (SUMS; the first two are Sm over the usable pixels and Sm_all over the whole disc), how many
+// variances the solve adds to a row (VARIANCES), what a usable pixel weighs and whether that leaves it out (weigh), what it adds to the
+// sums (add) and to chi2 (chi2_term), and THE SOLVE (false: DEGENERATE).  The uniform policy is S8: it carries no weight at all.
+struct UniformWeights {
+  static constexpr int SUMS = F_SUMS, VARIANCES = 0;
+  struct Weight {};
+  RPSFS_HD bool weigh(const Frame&, size_t, Weight&) const { return true; }
+  RPSFS_HD static void add(double* s, Weight, double m, double d) { s[F_SM] += m, s[F_SMM] += m * m, s[F_SD] += d, s[F_SDM] += d * m, s[F_SDD] += d * d; }
+  RPSFS_HD static double chi2_term(Weight, double e) { return e * e; }
+  // with background D = n Smm - Sm Sm, f = (n Sdm - Sm Sd) / D, bg = (Sd - f Sm) / n; without it D = Smm, f = Sdm / Smm, bg = 0
+  RPSFS_HD static bool solve(const double* s, int n_use, int background, double& f, double& bg, double*) {
+    const double n = (double)n_use;
+    const double D = background ? n * s[F_SMM] - s[F_SM] * s[F_SM] : s[F_SMM];
+    if (!finite_d(D) || D <= 0.0) return false;
+    if (background) {
+      f = (n * s[F_SDM] - s[F_SM] * s[F_SD]) / D;
+      bg = (s[F_SD] - f * s[F_SM]) / n;
+    } else {
+      f = s[F_SDM] / D;
+      bg = 0.0;
+    }
+    return true;
   }
 };
 
-// One workgroup, WALK_WAVES positions from `first` on, one wave each.  pos[2 i ..] = (y, x), cell[i] its cell of the cube.  The box runs
-// from floor(y - R) - 1 to ceil(y + R) + 1 and likewise in x, not clipped to the frame; lane j takes its pixels j, j + 64, ... in raster
-// order.  For pixel (r, c): pr = r - y, pc = c - x, q = pr pr + pc pc; it is in the disc when q <= R R (n_all, and m = model_at into
-// Sm_all), and then, when it lies on the frame and is usable (n), with d the residual against the mesh (use_mesh) or the pixel itself:
-// Sm += m, Smm += m m, Sd += d, Sdm += d m, Sdd += d d.  The 64 partial records fold as 8 groups of 8, each in lane order, and the 8
-// groups in order.  THE SOLVE, in the wave's first lane, in this order: with background D = n Smm - Sm Sm, f = (n Sdm - Sm Sd) / D,
-// bg = (Sd - f Sm) / n; without it D = Smm, f = Sdm / Smm, bg = 0.  TOO_FEW: n < 3 (with background) or n < 1; else DEGENERATE: D not
-// finite or D <= 0; either way f, bg and pass 2's columns are NaN (the peak at (-1, -1)).  PASS 2 walks the same pixels in the same order
-// with e = d - (f m + bg): chi2 = sum e e, abs_res = sum |e|, and the peak by see_residual's order.
+// ------------------------------------------------------------------------------------------------ the records in LDS
+// LaneRecords (rpsf_core_stars_disc.hpp) of the policy's sums, the peak's linear index, then n and n_all.  Pass 2 puts its R_SUMS doubles
+// into the first words of pass 1's.  Behind them what the first lane of each wave hands to its lanes after the solve: f, bg and whether
+// pass 2 runs.
+enum { FS_F, FS_BG, FS_DOUBLES };
+template <class W>
+using FitRecords = LaneRecords<W::SUMS, true, 2>;
+constexpr size_t S8_STATE_BYTES = ((size_t)WALK_WAVES * (FS_DOUBLES * 8 + 4) + 15) & ~(size_t)15;
+template <class W>
+RPSFS_HD constexpr size_t fit_lds_bytes() {
+  return walk_records_bytes<FitRecords<W>>() + S8_STATE_BYTES;
+}
+RPSFS_HD constexpr size_t s8_record_bytes() { return FitRecords<UniformWeights>::bytes(); }
+RPSFS_HD constexpr size_t s8_lds_bytes() { return fit_lds_bytes<UniformWeights>(); }
+static_assert((int)R_SUMS <= (int)F_SUMS, "pass 2's fields lie in pass 1's words");
+
+// One workgroup, WALK_WAVES positions from `first` on, one wave each.  pos[2 i ..] = (y, x), cell[i] its cell of the cube.  The walk is
+// walk_disc's over disc_box(y, x, R).  A pixel of the disc counts in n_all, and m = model_at into Sm_all; when it lies on the frame, is
+// usable and the policy's weigh() keeps it (n), with d the residual against the mesh (use_mesh) or the pixel itself, the policy adds to
+// its sums - S8's: Sm += m, Smm += m m, Sd += d, Sdm += d m, Sdd += d d.  The fold is the disc header's.  TOO_FEW: n < 3 (with
+// background) or n < 1; else the policy's SOLVE in the wave's first lane, DEGENERATE: D not finite or D <= 0; either way f, bg, the
+// variances and pass 2's columns are NaN (the peak at (-1, -1)).  PASS 2 walks the same pixels in the same order with
+// e = d - (f m + bg): chi2 = sum of the policy's chi2_term (S8's: e e), abs_res = sum |e|, and the peak by see_residual's order.
 // With use_mesh and none[0] set (NO_MESH) or a cell outside 0 .. n_cells - 1 (BAD_CELL) only the counts are taken - neither `L` nor the
 // cube is read - and every sum, f, bg and pass 2's columns are NaN.
-template <class Ctx>
-RPSFS_HD void s8_fit(Ctx& ctx, const Frame& fr, const double* L, const int* none, int use_mesh, const Model& model, const Fit& fit,
-                     const double* pos, const int* cell, long count, long first, void* lds, double* out) {
-  const FRecords acc(lds, WALK_THREADS);
-  const FRecords acc2(static_cast<char*>(lds) + WALK_THREADS * s8_record_bytes(), WALK_WAVES * 8);
-  double* st = reinterpret_cast<double*>(static_cast<char*>(lds) + (WALK_THREADS + WALK_WAVES * 8) * s8_record_bytes());
+// A row: S8's four scalars and two counts, the policy's sums, f, bg, its variances, then the six residual columns.
+template <class W, class Ctx>
+RPSFS_HD void fit_disc(Ctx& ctx, const Frame& fr, const double* L, const int* none, int use_mesh, const Model& model, const Fit& fit,
+                       const W& weights, const double* pos, const int* cell, long count, long first, void* lds, double* out) {
+  constexpr int C_F = (int)COL_FSUMS + W::SUMS, C_VAR = C_F + 2, C_RES = C_VAR + W::VARIANCES, COLUMNS = C_RES + 6;
+  const FitRecords<W> acc(lds, WALK_THREADS);
+  const FitRecords<W> acc2(static_cast<char*>(lds) + WALK_THREADS * FitRecords<W>::bytes(), WALK_GROUPS);
+  double* st = reinterpret_cast<double*>(static_cast<char*>(lds) + walk_records_bytes<FitRecords<W>>());
   int* go = reinterpret_cast<int*>(st + FS_DOUBLES * WALK_WAVES);
   const bool no_mesh = use_mesh && none[0] != 0;
   const bool subtract = use_mesh && !no_mesh;
@@ -120,51 +129,37 @@ RPSFS_HD void s8_fit(Ctx& ctx, const Frame& fr, const double* L, const int* none
   ctx.each([&](int tid) {  // pass 1
     const long i = first + tid / WALK_LANES;
     const int lane = tid % WALK_LANES;
-    double s[F_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double s[W::SUMS] = {};
     int n_use = 0, n_all = 0;
     if (i < count) {
       const double y = pos[2 * i], x = pos[2 * i + 1];
       const int k = cell[i];
       const bool counts_only = no_mesh || k < 0 || k >= model.n_cells;
       const double* C = counts_only ? nullptr : model.cube + (size_t)k * cell_words;
-      const int r0 = (int)std::floor(y - fit.R) - 1, r1 = (int)std::ceil(y + fit.R) + 1;
-      const int c0 = (int)std::floor(x - fit.R) - 1, c1 = (int)std::ceil(x + fit.R) + 1;
-      const long bw = c1 - c0 + 1, npx = (long)(r1 - r0 + 1) * bw;
-      for (long j = lane; j < npx; j += WALK_LANES) {
-        const int r = r0 + (int)(j / bw), c = c0 + (int)(j % bw);
-        const double pr = (double)r - y, pc = (double)c - x;
-        const double q = pr * pr + pc * pc;
-        if (!(q <= fit.R2)) continue;
-        ++n_all;
-        double m = 0.0;
-        if (!counts_only) m = model_at(C, N, fit.h, pr, pc), s[F_SM_ALL] += m;
-        if (r < 0 || r >= fr.H || c < 0 || c >= fr.W) continue;
-        const size_t p = (size_t)r * fr.W + c;
-        if (!usable(fr.img, fr.mask, p)) continue;
-        ++n_use;
-        if (counts_only) continue;
-        const double d = subtract ? (double)fr.img[p] - background_at(fr, mesh, r, c) : (double)fr.img[p];
-        s[F_SM] += m, s[F_SMM] += m * m, s[F_SD] += d, s[F_SDM] += d * m, s[F_SDD] += d * d;
-      }
+      double m = 0.0;
+      walk_disc(
+          fr, disc_box(y, x, fit.R), y, x, fit.R2, lane,
+          [&](double pr, double pc) {
+            ++n_all;
+            m = 0.0;
+            if (!counts_only) m = model_at(C, N, fit.h, pr, pc), s[F_SM_ALL] += m;
+          },
+          [&](int r, int c, size_t p, double, double, double) {
+            typename W::Weight w;
+            if (!weights.weigh(fr, p, w)) return;
+            ++n_use;
+            if (counts_only) return;
+            const double d = subtract ? (double)fr.img[p] - background_at(fr, mesh, r, c) : (double)fr.img[p];
+            W::add(s, w, m, d);
+          });
     }
 #pragma unroll
-    for (int f = 0; f < F_SUMS; ++f) acc.d[f * WALK_THREADS + tid] = s[f];
+    for (int f = 0; f < W::SUMS; ++f) acc.d[f * WALK_THREADS + tid] = s[f];
     acc.cnt[tid] = n_use, acc.cnt[WALK_THREADS + tid] = n_all;
   });
   ctx.each([&](int tid) {  // 64 partials to 8
-    const int wave = tid / WALK_LANES, lane = tid % WALK_LANES;
-    if (lane >= 8) return;
-    const int G = WALK_WAVES * 8, i0 = wave * WALK_LANES + 8 * lane, g = wave * 8 + lane;
-    for (int f = 0; f < F_SUMS; ++f) {
-      double v = 0.0;
-      for (int j = 0; j < 8; ++j) v += acc.d[f * WALK_THREADS + i0 + j];
-      acc2.d[f * G + g] = v;
-    }
-    for (int f = 0; f < 2; ++f) {
-      int v = 0;
-      for (int j = 0; j < 8; ++j) v += acc.cnt[f * WALK_THREADS + i0 + j];
-      acc2.cnt[f * G + g] = v;
-    }
+    if (tid % WALK_LANES >= 8) return;
+    fold_sums_64to8(acc, acc2, tid, W::SUMS), fold_counts_64to8(acc, acc2, tid, 2);
   });
   ctx.each([&](int tid) {  // 8 to 1, and the wave's first lane solves
     const int wave = tid / WALK_LANES;
@@ -172,56 +167,33 @@ RPSFS_HD void s8_fit(Ctx& ctx, const Frame& fr, const double* L, const int* none
     const long i = first + wave;
     go[wave] = 0;
     if (i >= count) return;
-    const int G = WALK_WAVES * 8, g0 = wave * 8;
-    double s[F_SUMS];
-    for (int f = 0; f < F_SUMS; ++f) {
-      double v = 0.0;
-      for (int j = 0; j < 8; ++j) v += acc2.d[f * G + g0 + j];
-      s[f] = v;
-    }
+    double s[W::SUMS];
     int cnt[2];
-    for (int f = 0; f < 2; ++f) {
-      int v = 0;
-      for (int j = 0; j < 8; ++j) v += acc2.cnt[f * G + g0 + j];
-      cnt[f] = v;
-    }
+    fold_sums_8to1(acc2, wave, W::SUMS, s), fold_counts_8to1(acc2, wave, 2, cnt);
     const double nan = std::nan("");
     const int k = cell[i];
     int flags = (no_mesh ? FLAG_NO_MESH : 0) | (k < 0 || k >= model.n_cells ? FLAG_BAD_CELL : 0);
-    double f = nan, bg = nan;
+    double f = nan, bg = nan, var[W::VARIANCES + 1];
+    for (int c = 0; c < W::VARIANCES; ++c) var[c] = nan;
     if (flags == 0) {
-      const double n = (double)cnt[0];
       if (cnt[0] < (fit.background ? 3 : 1)) {
         flags |= FLAG_TOO_FEW;
-      } else if (fit.background) {
-        const double D = n * s[F_SMM] - s[F_SM] * s[F_SM];
-        if (!finite_d(D) || D <= 0.0) {
-          flags |= FLAG_DEGENERATE;
-        } else {
-          f = (n * s[F_SDM] - s[F_SM] * s[F_SD]) / D;
-          bg = (s[F_SD] - f * s[F_SM]) / n;
-        }
-      } else {
-        const double D = s[F_SMM];
-        if (!finite_d(D) || D <= 0.0) {
-          flags |= FLAG_DEGENERATE;
-        } else {
-          f = s[F_SDM] / D;
-          bg = 0.0;
-        }
+      } else if (!W::solve(s, cnt[0], fit.background, f, bg, var)) {
+        flags |= FLAG_DEGENERATE;
       }
     }
     const bool sums = (flags & (FLAG_NO_MESH | FLAG_BAD_CELL)) == 0;
-    double* o = out + (size_t)FIT_COLUMNS * i;
+    double* o = out + (size_t)COLUMNS * i;
     o[COL_FY] = pos[2 * i], o[COL_FX] = pos[2 * i + 1], o[COL_CELL] = (double)k, o[COL_FFLAGS] = (double)flags;
     o[COL_N] = (double)cnt[0], o[COL_NALL] = (double)cnt[1];
-    for (int c = 0; c < F_SUMS; ++c) o[COL_FSUMS + c] = sums ? s[c] : nan;
-    o[COL_F] = f, o[COL_BG] = bg;
+    for (int c = 0; c < W::SUMS; ++c) o[COL_FSUMS + c] = sums ? s[c] : nan;
+    o[C_F] = f, o[C_F + 1] = bg;
+    for (int c = 0; c < W::VARIANCES; ++c) o[C_VAR + c] = var[c];
     if (flags == 0) {
       st[FS_F * WALK_WAVES + wave] = f, st[FS_BG * WALK_WAVES + wave] = bg, go[wave] = 1;
     } else {
-      o[COL_CHI2] = o[COL_ABS_RES] = o[COL_PEAK_RES] = o[COL_PEAK_E] = nan;
-      o[COL_PEAK_ROW] = o[COL_PEAK_COL] = -1.0;
+      o[C_RES + RES_CHI2] = o[C_RES + RES_ABS] = o[C_RES + RES_PEAK] = o[C_RES + RES_PEAK_E] = nan;
+      o[C_RES + RES_PEAK_ROW] = o[C_RES + RES_PEAK_COL] = -1.0;
     }
   });
   ctx.each([&](int tid) {  // pass 2: the same pixels in the same order
@@ -231,57 +203,41 @@ RPSFS_HD void s8_fit(Ctx& ctx, const Frame& fr, const double* L, const int* none
     const double y = pos[2 * i], x = pos[2 * i + 1];
     const double f = st[FS_F * WALK_WAVES + wave], bg = st[FS_BG * WALK_WAVES + wave];
     const double* C = model.cube + (size_t)cell[i] * cell_words;
-    const int r0 = (int)std::floor(y - fit.R) - 1, r1 = (int)std::ceil(y + fit.R) + 1;
-    const int c0 = (int)std::floor(x - fit.R) - 1, c1 = (int)std::ceil(x + fit.R) + 1;
-    const long bw = c1 - c0 + 1, npx = (long)(r1 - r0 + 1) * bw;
     double chi2 = 0.0, abs_res = 0.0;
     Peak seen{0.0, -1};
-    for (long j = lane; j < npx; j += WALK_LANES) {
-      const int r = r0 + (int)(j / bw), c = c0 + (int)(j % bw);
-      const double pr = (double)r - y, pc = (double)c - x;
-      const double q = pr * pr + pc * pc;
-      if (!(q <= fit.R2)) continue;
-      if (r < 0 || r >= fr.H || c < 0 || c >= fr.W) continue;
-      const size_t p = (size_t)r * fr.W + c;
-      if (!usable(fr.img, fr.mask, p)) continue;
+    walk_disc(fr, disc_box(y, x, fit.R), y, x, fit.R2, lane, [&](int r, int c, size_t p, double pr, double pc, double) {
+      typename W::Weight w;
+      if (!weights.weigh(fr, p, w)) return;
       const double m = model_at(C, N, fit.h, pr, pc);
       const double d = subtract ? (double)fr.img[p] - background_at(fr, mesh, r, c) : (double)fr.img[p];
       const double e = d - (f * m + bg);
-      chi2 += e * e, abs_res += std::fabs(e);
+      chi2 += W::chi2_term(w, e), abs_res += std::fabs(e);
       see_residual(seen, e, (long long)p);
-    }
+    });
     acc.d[R_CHI2 * WALK_THREADS + tid] = chi2, acc.d[R_ABS * WALK_THREADS + tid] = abs_res;
     acc.d[R_PEAK * WALK_THREADS + tid] = seen.e, acc.at[tid] = seen.at;
   });
   ctx.each([&](int tid) {  // 64 partials to 8
-    const int wave = tid / WALK_LANES, lane = tid % WALK_LANES;
-    if (lane >= 8 || !go[wave]) return;
-    const int G = WALK_WAVES * 8, i0 = wave * WALK_LANES + 8 * lane, g = wave * 8 + lane;
-    for (int f = 0; f < R_PEAK; ++f) {
-      double v = 0.0;
-      for (int j = 0; j < 8; ++j) v += acc.d[f * WALK_THREADS + i0 + j];
-      acc2.d[f * G + g] = v;
-    }
-    Peak seen{0.0, -1};
-    for (int j = 0; j < 8; ++j) see_residual(seen, acc.d[R_PEAK * WALK_THREADS + i0 + j], acc.at[i0 + j]);
-    acc2.d[R_PEAK * G + g] = seen.e, acc2.at[g] = seen.at;
+    if (tid % WALK_LANES >= 8 || !go[tid / WALK_LANES]) return;
+    fold_sums_64to8(acc, acc2, tid, R_PEAK), fold_peak_64to8(acc, acc2, tid, R_PEAK);
   });
   ctx.each([&](int tid) {  // 8 to 1
     const int wave = tid / WALK_LANES;
     if (tid % WALK_LANES != 0 || !go[wave]) return;
-    const int G = WALK_WAVES * 8, g0 = wave * 8;
-    double* o = out + (size_t)FIT_COLUMNS * (first + wave);
-    for (int f = 0; f < R_PEAK; ++f) {
-      double v = 0.0;
-      for (int j = 0; j < 8; ++j) v += acc2.d[f * G + g0 + j];
-      o[COL_CHI2 + f] = v;
-    }
-    Peak seen{0.0, -1};
-    for (int j = 0; j < 8; ++j) see_residual(seen, acc2.d[R_PEAK * G + g0 + j], acc2.at[g0 + j]);
+    double* o = out + (size_t)COLUMNS * (first + wave) + C_RES;
+    fold_sums_8to1(acc2, wave, R_PEAK, o);  // RES_CHI2, RES_ABS
+    const Peak seen = fold_peak_8to1(acc2, wave, R_PEAK);
     // (flags == 0 has n >= 1: there is a pixel)
-    o[COL_PEAK_RES] = std::fabs(seen.e), o[COL_PEAK_E] = seen.e;
-    o[COL_PEAK_ROW] = (double)(seen.at / fr.W), o[COL_PEAK_COL] = (double)(seen.at % fr.W);
+    o[RES_PEAK] = std::fabs(seen.e), o[RES_PEAK_E] = seen.e;
+    o[RES_PEAK_ROW] = (double)(seen.at / fr.W), o[RES_PEAK_COL] = (double)(seen.at % fr.W);
   });
+}
+
+// S8: the fit with uniform weights, rows of FIT_COLUMNS
+template <class Ctx>
+RPSFS_HD void s8_fit(Ctx& ctx, const Frame& fr, const double* L, const int* none, int use_mesh, const Model& model, const Fit& fit,
+                     const double* pos, const int* cell, long count, long first, void* lds, double* out) {
+  fit_disc(ctx, fr, L, none, use_mesh, model, fit, UniformWeights{}, pos, cell, count, first, lds, out);
 }
 
 }  // namespace rpsff

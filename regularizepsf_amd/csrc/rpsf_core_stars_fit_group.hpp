@@ -48,29 +48,19 @@ struct GroupList {
 };
 
 // ------------------------------------------------------------------------------------------------ the records in LDS
-// The fold's records, field-major as S8's (field f of record i of n is word f n + i): FOLD_BATCH doubles per lane and per group of 8
-// lanes - pass 1's G_FIELDS sums go through them FOLD_BATCH at a time -, the peak's linear index and two counts.  Behind them the state
+// The fold's records are LaneRecords (rpsf_core_stars_disc.hpp): FOLD_BATCH doubles per lane and per group of 8 lanes - pass 1's
+// G_FIELDS sums go through them FOLD_BATCH at a time -, the peak's linear index and two counts.  Behind them the state
 // of the workgroup's WALK_WAVES groups: pass 1's totals, the system of the solve (the matrix, the right-hand side, the unknowns: they are
 // indexed at run time, which registers cannot be), the constant, and g, n, the flags and whether pass 2 takes residuals.
 constexpr int FOLD_BATCH = 18;
 static_assert(G_FIELDS % FOLD_BATCH == 0 && (int)M_FIELDS <= FOLD_BATCH, "pass 1 folds in whole batches, pass 2 in one");
 enum { GS_TOTALS = 0, GS_MATRIX = G_FIELDS, GS_RHS = GS_MATRIX + MAX_UNKNOWNS * MAX_UNKNOWNS, GS_X = GS_RHS + MAX_UNKNOWNS, GS_BG = GS_X + MAX_UNKNOWNS, GS_DOUBLES };
 enum { GI_G, GI_N, GI_FLAGS, GI_GO, GI_INTS };
-RPSFS_HD constexpr size_t s11_record_bytes() { return (size_t)FOLD_BATCH * 8 + 8 + 2 * 4; }
+using GRecords = LaneRecords<FOLD_BATCH, true, 2>;
+RPSFS_HD constexpr size_t s11_record_bytes() { return GRecords::bytes(); }
 constexpr size_t S11_STATE_BYTES = ((size_t)WALK_WAVES * (GS_DOUBLES * 8 + GI_INTS * 4) + 15) & ~(size_t)15;
-RPSFS_HD constexpr size_t s11_lds_bytes() { return (size_t)(WALK_THREADS + WALK_WAVES * 8) * s11_record_bytes() + S11_STATE_BYTES; }
+RPSFS_HD constexpr size_t s11_lds_bytes() { return walk_records_bytes<GRecords>() + S11_STATE_BYTES; }
 static_assert(s11_lds_bytes() <= 64 * 1024 && s11_lds_bytes() % 16 == 0, "S11's records fit the LDS a launch gets without asking");
-
-struct GRecords {  // n records at `base` (a multiple of 16 bytes: n is a multiple of 4)
-  double* d;
-  long long* at;
-  int* cnt;
-  int n;
-  RPSFS_HD GRecords(void* base, int n_) : d(static_cast<double*>(base)), n(n_) {
-    at = reinterpret_cast<long long*>(d + (size_t)FOLD_BATCH * n_);
-    cnt = reinterpret_cast<int*>(at + n_);
-  }
-};
 
 // THE SOLVE at a runtime order K <= MAX_UNKNOWNS: S9's solve_ldl with the same order of elimination and substitution.  A is the
 // symmetric matrix in rows of MAX_UNKNOWNS (its upper triangle is read and overwritten), b the right-hand side.  False at a pivot that is
@@ -97,7 +87,6 @@ RPSFS_HD bool solve_ldl_n(int K, double* A, double* b, double* x) {
 // constant): the lanes' partials into the records, 64 partials to 8, 8 to 1 into the wave's totals; the count goes with the first batch.
 template <int f0, class Ctx>
 RPSFS_HD void s11_fold(Ctx& ctx, const GRecords& acc, const GRecords& acc2, double* st, int* sti) {
-  const int G8 = WALK_WAVES * 8;
   ctx.each([&](int tid) {
     const Lane& s = ctx.regs(tid);
 #pragma unroll
@@ -105,34 +94,15 @@ RPSFS_HD void s11_fold(Ctx& ctx, const GRecords& acc, const GRecords& acc2, doub
     if (f0 == 0) acc.cnt[tid] = s.n;
   });
   ctx.each([&](int tid) {  // 64 partials to 8
-    const int wave = tid / WALK_LANES, lane = tid % WALK_LANES;
-    if (lane >= 8) return;
-    const int i0 = wave * WALK_LANES + 8 * lane, g8 = wave * 8 + lane;
-    for (int f = 0; f < FOLD_BATCH; ++f) {
-      double v = 0.0;
-      for (int j = 0; j < 8; ++j) v += acc.d[f * WALK_THREADS + i0 + j];
-      acc2.d[f * G8 + g8] = v;
-    }
-    if (f0 == 0) {
-      int v = 0;
-      for (int j = 0; j < 8; ++j) v += acc.cnt[i0 + j];
-      acc2.cnt[g8] = v;
-    }
+    if (tid % WALK_LANES >= 8) return;
+    fold_sums_64to8(acc, acc2, tid, FOLD_BATCH);
+    if (f0 == 0) fold_counts_64to8(acc, acc2, tid, 1);
   });
   ctx.each([&](int tid) {  // 8 to 1, into the wave's totals
     const int wave = tid / WALK_LANES;
     if (tid % WALK_LANES != 0) return;
-    double* tot = st + (size_t)wave * GS_DOUBLES + GS_TOTALS;
-    for (int f = 0; f < FOLD_BATCH; ++f) {
-      double v = 0.0;
-      for (int j = 0; j < 8; ++j) v += acc2.d[f * G8 + wave * 8 + j];
-      tot[f0 + f] = v;
-    }
-    if (f0 == 0) {
-      int v = 0;
-      for (int j = 0; j < 8; ++j) v += acc2.cnt[wave * 8 + j];
-      sti[GI_N * WALK_WAVES + wave] = v;
-    }
+    fold_sums_8to1(acc2, wave, FOLD_BATCH, st + (size_t)wave * GS_DOUBLES + GS_TOTALS + f0);
+    if (f0 == 0) fold_counts_8to1(acc2, wave, 1, sti + GI_N * WALK_WAVES + wave);
   });
 }
 
@@ -140,17 +110,17 @@ RPSFS_HD void s11_fold(Ctx& ctx, const GRecords& acc, const GRecords& acc2, doub
 // members of a group index them.  Every member's cell lies inside the model and use_mesh comes with a valid mesh (the driver sends every
 // other star through S8).  Member b's disc HOLDS pixel (r, c) when, with pr = r - y_b, pc = c - x_b, q = pr pr + pc pc: q <= R R.
 //
-// PASS 1.  For a = 0 .. g - 1: member a's box as S8 walks it (floor(y - R) - 1 .. ceil(y + R) + 1, likewise in x, not clipped), lane j
-// takes its pixels j, j + 64, ... in raster order.  A pixel counts when disc a holds it, no disc b < a does - every pixel of the union
-// is OWNED by the first member that holds it -, it lies on the frame and is usable.  With d S8's d and m_b = model_at of member b for
-// the members (ascending) that hold it: n += 1, Sd += d, Sdd += d d, Sm[b] += m_b, Sdm[b] += d m_b, and for c >= b, both holding:
-// A[b][c] += m_b m_c.  A lane's partial sums run on across the members.  They fold as S8's: 64 partials to 8 groups of 8 in lane order,
-// then the 8 in order.
+// PASS 1.  For a = 0 .. g - 1: member a's disc_box (rpsf_core_stars_disc.hpp), lane j takes its pixels j, j + 64, ... in raster order.  A
+// pixel counts when disc a holds it, no disc b < a does - every pixel of the union is OWNED by the first member that holds it -, it lies on
+// the frame and is usable.  With d S8's d and m_b = model_at of member b for the members (ascending) that hold it: n += 1, Sd += d, Sdd +=
+// d d, Sm[b] += m_b, Sdm[b] += d m_b, and for c >= b, both holding: A[b][c] += m_b m_c.  A lane's partial sums run on across the members.
+// They fold by the disc header's steps.
 // THE SOLVE, in the wave's first lane.  The unknowns are f_0 .. f_{g-1}, then the constant when fit.background: p = g + background.
 // The matrix is A bordered by Sm and n, the right-hand side Sdm, then Sd.  TOO_FEW: n < p.  Else solve_ldl_n; DEGENERATE: a pivot not
 // finite or <= 0, or an unknown not finite.  Either flag goes to every member and leaves NaN in f, bg and the residual's columns.
-// PASS 2.  For a = 0 .. g - 1, member a's box exactly as S8's pass 1 walks that star alone: n_all and Sm_all over the disc, and on its
-// usable pixels n_use, Sm, Smm, Sd, Sdm, Sdd - S8's row of that star, bit for bit.  Without a flag also e = d - (S + bg) with S = 0.0,
+// PASS 2.  For a = 0 .. g - 1, walk_disc over member a's disc as S8's pass 1 walks that star alone: n_all and Sm_all over the disc, and on
+// its usable pixels n_use and, through UniformWeights::add - the function S8's pass 1 calls -, Sm, Smm, Sd, Sdm, Sdd: S8's row of that
+// star, bit for bit.  Without a flag also e = d - (S + bg) with S = 0.0,
 // then S += f_b * m_b over the members b (ascending) that hold the pixel - S10's sum -: chi2 += e e, abs_res += |e|, the peak by
 // see_residual; and on the pixels a owns the group's gchi2 += e e, gabs += |e|, whose lane partials run on across the members and fold
 // once, after the last.  A member without a usable pixel has no peak: peak_res and peak_e NaN at (-1, -1).
@@ -160,14 +130,13 @@ template <class Ctx>
 RPSFS_HD void s11_fit_group(Ctx& ctx, const Frame& fr, const double* L, int use_mesh, const Model& model, const Fit& fit, const double* pos,
                             const int* cell, const GroupList& groups, long first, void* lds, double* out) {
   const GRecords acc(lds, WALK_THREADS);
-  const GRecords acc2(static_cast<char*>(lds) + WALK_THREADS * s11_record_bytes(), WALK_WAVES * 8);
-  double* st = reinterpret_cast<double*>(static_cast<char*>(lds) + (WALK_THREADS + WALK_WAVES * 8) * s11_record_bytes());
+  const GRecords acc2(static_cast<char*>(lds) + WALK_THREADS * s11_record_bytes(), WALK_GROUPS);
+  double* st = reinterpret_cast<double*>(static_cast<char*>(lds) + walk_records_bytes<GRecords>());
   int* sti = reinterpret_cast<int*>(st + (size_t)GS_DOUBLES * WALK_WAVES);
   const bool subtract = use_mesh != 0;
   const Mesh mesh{L, fr.nbx, 0, 0};
   const int N = model.N;
   const size_t cell_words = (size_t)N * N;
-  const int G8 = WALK_WAVES * 8;
   ctx.each([&](int tid) {  // pass 1
     const int wave = tid / WALK_LANES, lane = tid % WALK_LANES;
     Lane& s = ctx.regs(tid);
@@ -188,11 +157,9 @@ RPSFS_HD void s11_fit_group(Ctx& ctx, const Frame& fr, const double* L, int use_
     for (int a = 0; a < g; ++a) {
       const int ia = groups.members[m0 + a];
       const double ya = pos[2 * (size_t)ia], xa = pos[2 * (size_t)ia + 1];
-      const int r0 = (int)std::floor(ya - fit.R) - 1, r1 = (int)std::ceil(ya + fit.R) + 1;
-      const int c0 = (int)std::floor(xa - fit.R) - 1, c1 = (int)std::ceil(xa + fit.R) + 1;
-      const long bw = c1 - c0 + 1, npx = (long)(r1 - r0 + 1) * bw;
-      for (long j = lane; j < npx; j += WALK_LANES) {
-        const int r = r0 + (int)(j / bw), c = c0 + (int)(j % bw);
+      const DiscBox box = disc_box(ya, xa, fit.R);
+      for (long j = lane; j < box.npx; j += WALK_LANES) {
+        const int r = box.r0 + (int)(j / box.bw), c = box.c0 + (int)(j % box.bw);
         const double pra = (double)r - ya, pca = (double)c - xa;
         const double qa = pra * pra + pca * pca;
         if (!(qa <= fit.R2)) continue;
@@ -270,47 +237,41 @@ RPSFS_HD void s11_fit_group(Ctx& ctx, const Frame& fr, const double* L, int use_
       const int ia = members[a];
       const double y = pos[2 * (size_t)ia], x = pos[2 * (size_t)ia + 1];
       const double* C = model.cube + (size_t)cell[ia] * cell_words;
-      const int r0 = (int)std::floor(y - fit.R) - 1, r1 = (int)std::ceil(y + fit.R) + 1;
-      const int c0 = (int)std::floor(x - fit.R) - 1, c1 = (int)std::ceil(x + fit.R) + 1;
-      const long bw = c1 - c0 + 1, npx = (long)(r1 - r0 + 1) * bw;
       double s[F_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       int n_use = 0, n_all = 0;
       double chi2 = 0.0, abs_res = 0.0, gchi2 = keep.v[0], gabs = keep.v[1];
       Peak seen{0.0, -1};
-      for (long j = lane; j < npx; j += WALK_LANES) {
-        const int r = r0 + (int)(j / bw), c = c0 + (int)(j % bw);
-        const double pr = (double)r - y, pc = (double)c - x;
-        const double q = pr * pr + pc * pc;
-        if (!(q <= fit.R2)) continue;
-        ++n_all;
-        const double m = model_at(C, N, fit.h, pr, pc);
-        s[F_SM_ALL] += m;
-        if (r < 0 || r >= fr.H || c < 0 || c >= fr.W) continue;
-        const size_t p = (size_t)r * fr.W + c;
-        if (!usable(fr.img, fr.mask, p)) continue;
-        ++n_use;
-        const double d = subtract ? (double)fr.img[p] - background_at(fr, mesh, r, c) : (double)fr.img[p];
-        s[F_SM] += m, s[F_SMM] += m * m, s[F_SD] += d, s[F_SDM] += d * m, s[F_SDD] += d * d;
-        if (!go) continue;
-        double S = 0.0;
-        bool owned = true;
-        for (int b = 0; b < g; ++b) {
-          if (b == a) {
-            S += w[GS_X + b] * m;
-            continue;
-          }
-          const int ib = members[b];
-          const double prb = (double)r - pos[2 * (size_t)ib], pcb = (double)c - pos[2 * (size_t)ib + 1];
-          const double qb = prb * prb + pcb * pcb;
-          if (!(qb <= fit.R2)) continue;
-          S += w[GS_X + b] * model_at(model.cube + (size_t)cell[ib] * cell_words, N, fit.h, prb, pcb);
-          if (b < a) owned = false;
-        }
-        const double e = d - (S + bg);
-        chi2 += e * e, abs_res += std::fabs(e);
-        see_residual(seen, e, (long long)p);
-        if (owned) gchi2 += e * e, gabs += std::fabs(e);
-      }
+      double m = 0.0;
+      walk_disc(
+          fr, disc_box(y, x, fit.R), y, x, fit.R2, lane,
+          [&](double pr, double pc) {
+            ++n_all;
+            m = model_at(C, N, fit.h, pr, pc), s[F_SM_ALL] += m;
+          },
+          [&](int r, int c, size_t p, double, double, double) {
+            ++n_use;
+            const double d = subtract ? (double)fr.img[p] - background_at(fr, mesh, r, c) : (double)fr.img[p];
+            UniformWeights::add(s, {}, m, d);  // S8's own sums
+            if (!go) return;
+            double S = 0.0;
+            bool owned = true;
+            for (int b = 0; b < g; ++b) {
+              if (b == a) {
+                S += w[GS_X + b] * m;
+                continue;
+              }
+              const int ib = members[b];
+              const double prb = (double)r - pos[2 * (size_t)ib], pcb = (double)c - pos[2 * (size_t)ib + 1];
+              const double qb = prb * prb + pcb * pcb;
+              if (!(qb <= fit.R2)) continue;
+              S += w[GS_X + b] * model_at(model.cube + (size_t)cell[ib] * cell_words, N, fit.h, prb, pcb);
+              if (b < a) owned = false;
+            }
+            const double e = d - (S + bg);
+            chi2 += e * e, abs_res += std::fabs(e);
+            see_residual(seen, e, (long long)p);
+            if (owned) gchi2 += e * e, gabs += std::fabs(e);
+          });
       keep.v[0] = gchi2, keep.v[1] = gabs;
 #pragma unroll
       for (int f = 0; f < F_SUMS; ++f) acc.d[f * WALK_THREADS + tid] = s[f];
@@ -321,44 +282,21 @@ RPSFS_HD void s11_fit_group(Ctx& ctx, const Frame& fr, const double* L, int use_
     ctx.each([&](int tid) {  // 64 partials to 8
       const int wave = tid / WALK_LANES, lane = tid % WALK_LANES;
       if (lane >= 8 || a >= sti[GI_G * WALK_WAVES + wave]) return;
-      const int i0 = wave * WALK_LANES + 8 * lane, g8 = wave * 8 + lane;
-      for (int f = 0; f < M_PEAK; ++f) {
-        double v = 0.0;
-        for (int j = 0; j < 8; ++j) v += acc.d[f * WALK_THREADS + i0 + j];
-        acc2.d[f * G8 + g8] = v;
-      }
-      for (int f = 0; f < 2; ++f) {
-        int v = 0;
-        for (int j = 0; j < 8; ++j) v += acc.cnt[f * WALK_THREADS + i0 + j];
-        acc2.cnt[f * G8 + g8] = v;
-      }
-      Peak seen{0.0, -1};
-      for (int j = 0; j < 8; ++j) see_residual(seen, acc.d[M_PEAK * WALK_THREADS + i0 + j], acc.at[i0 + j]);
-      acc2.d[M_PEAK * G8 + g8] = seen.e, acc2.at[g8] = seen.at;
+      fold_sums_64to8(acc, acc2, tid, M_PEAK), fold_counts_64to8(acc, acc2, tid, 2), fold_peak_64to8(acc, acc2, tid, M_PEAK);
     });
     ctx.each([&](int tid) {  // 8 to 1, and member a's row
       const int wave = tid / WALK_LANES;
       const int g = sti[GI_G * WALK_WAVES + wave];
       if (tid % WALK_LANES != 0 || a >= g) return;
-      const int g0 = wave * 8, flags = sti[GI_FLAGS * WALK_WAVES + wave];
+      const int flags = sti[GI_FLAGS * WALK_WAVES + wave];
       const double* w = st + (size_t)wave * GS_DOUBLES;
       const long long m0 = groups.starts[first + wave];
       const int ia = groups.members[m0 + a];
       double* o = out + (size_t)GROUP_COLUMNS * (size_t)(m0 + a);
       double s[M_PEAK];
-      for (int f = 0; f < M_PEAK; ++f) {
-        double v = 0.0;
-        for (int j = 0; j < 8; ++j) v += acc2.d[f * G8 + g0 + j];
-        s[f] = v;
-      }
       int cnt[2];
-      for (int f = 0; f < 2; ++f) {
-        int v = 0;
-        for (int j = 0; j < 8; ++j) v += acc2.cnt[f * G8 + g0 + j];
-        cnt[f] = v;
-      }
-      Peak seen{0.0, -1};
-      for (int j = 0; j < 8; ++j) see_residual(seen, acc2.d[M_PEAK * G8 + g0 + j], acc2.at[g0 + j]);
+      fold_sums_8to1(acc2, wave, M_PEAK, s), fold_counts_8to1(acc2, wave, 2, cnt);
+      const Peak seen = fold_peak_8to1(acc2, wave, M_PEAK);
       const double nan = std::nan("");
       o[COL_FY] = pos[2 * (size_t)ia], o[COL_FX] = pos[2 * (size_t)ia + 1], o[COL_CELL] = (double)cell[ia], o[COL_FFLAGS] = (double)flags;
       o[COL_N] = (double)cnt[0], o[COL_NALL] = (double)cnt[1];
@@ -386,21 +324,13 @@ RPSFS_HD void s11_fit_group(Ctx& ctx, const Frame& fr, const double* L, int use_
   ctx.each([&](int tid) {
     const int wave = tid / WALK_LANES, lane = tid % WALK_LANES;
     if (lane >= 8 || !sti[GI_GO * WALK_WAVES + wave]) return;
-    const int i0 = wave * WALK_LANES + 8 * lane, g8 = wave * 8 + lane;
-    for (int f = 0; f < 2; ++f) {
-      double v = 0.0;
-      for (int j = 0; j < 8; ++j) v += acc.d[f * WALK_THREADS + i0 + j];
-      acc2.d[f * G8 + g8] = v;
-    }
+    fold_sums_64to8(acc, acc2, tid, 2);
   });
   ctx.each([&](int tid) {
     const int wave = tid / WALK_LANES;
     if (tid % WALK_LANES != 0 || !sti[GI_GO * WALK_WAVES + wave]) return;
     double v[2];
-    for (int f = 0; f < 2; ++f) {
-      v[f] = 0.0;
-      for (int j = 0; j < 8; ++j) v[f] += acc2.d[f * G8 + wave * 8 + j];
-    }
+    fold_sums_8to1(acc2, wave, 2, v);
     const long long m0 = groups.starts[first + wave];
     for (int a = 0; a < sti[GI_G * WALK_WAVES + wave]; ++a) {
       double* o = out + (size_t)GROUP_COLUMNS * (size_t)(m0 + a);

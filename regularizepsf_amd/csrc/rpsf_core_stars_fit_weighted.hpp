@@ -59,214 +59,49 @@ RPSFS_HD double weight_at(const Variance& var, const float* img, size_t p) {
 // v that is NaN, <= 0, +inf or so small that 1 / v overflows: the pixel is left out like a masked one
 RPSFS_HD bool weight_ok(double w) { return w > 0.0 && finite_d(w); }
 
-// ------------------------------------------------------------------------------------------------ the records in LDS
-// S8's layout with W_SUMS doubles per record; behind the records what the first lane of each wave hands to its lanes: f, bg, whether
-// pass 2 runs.
-RPSFS_HD constexpr size_t s12_record_bytes() { return (size_t)W_SUMS * 8 + 8 + 2 * 4; }
-RPSFS_HD constexpr size_t s12_lds_bytes() { return (size_t)(WALK_THREADS + WALK_WAVES * 8) * s12_record_bytes() + S8_STATE_BYTES; }
-
-struct WRecords {  // n records at `base` (a multiple of 16 bytes: n is a multiple of 4)
-  double* d;
-  long long* at;
-  int* cnt;
-  int n;
-  RPSFS_HD WRecords(void* base, int n_) : d(static_cast<double*>(base)), n(n_) {
-    at = reinterpret_cast<long long*>(d + (size_t)W_SUMS * n_);
-    cnt = reinterpret_cast<int*>(at + n_);
+// ------------------------------------------------------------------------------------------------ the variance policy of fit_disc
+// A usable pixel whose w is not weight_ok is left out like a masked one.  Then, with m and d S8's:  wm = w m, wd = w d, Sm += m, Sw += w,
+// Swm += wm, Swmm += wm m, Swd += wd, Swdm += wd m, Swdd += wd d.  THE SOLVE, in this order: with background D = Sw Swmm - Swm Swm,
+// f = (Sw Swdm - Swm Swd) / D, bg = (Swd - f Swm) / Sw, var_f = Sw / D, var_bg = Swmm / D, cov = - Swm / D; without it D = Swmm,
+// f = Swdm / D, bg = 0, var_f = 1 / D, var_bg = cov = 0.  The flags are S8's.  Pass 2's chi2 = sum w (e e); abs_res and the peak are
+// unweighted.
+struct VarianceWeights {
+  static constexpr int SUMS = W_SUMS, VARIANCES = 3;
+  using Weight = double;
+  Variance var;
+  RPSFS_HD bool weigh(const Frame& fr, size_t p, Weight& w) const { return weight_ok(w = weight_at(var, fr.img, p)); }
+  RPSFS_HD static void add(double* s, Weight w, double m, double d) {
+    const double wm = w * m, wd = w * d;
+    s[W_SM] += m, s[W_SW] += w, s[W_SWM] += wm, s[W_SWMM] += wm * m, s[W_SWD] += wd, s[W_SWDM] += wd * m, s[W_SWDD] += wd * d;
+  }
+  RPSFS_HD static double chi2_term(Weight w, double e) { return w * (e * e); }
+  RPSFS_HD static bool solve(const double* s, int, int background, double& f, double& bg, double* v) {  // v: var_f, var_bg, cov
+    const double D = background ? s[W_SW] * s[W_SWMM] - s[W_SWM] * s[W_SWM] : s[W_SWMM];
+    if (!finite_d(D) || D <= 0.0) return false;
+    if (background) {
+      f = (s[W_SW] * s[W_SWDM] - s[W_SWM] * s[W_SWD]) / D;
+      bg = (s[W_SWD] - f * s[W_SWM]) / s[W_SW];
+      v[0] = s[W_SW] / D, v[1] = s[W_SWMM] / D, v[2] = -s[W_SWM] / D;
+    } else {
+      f = s[W_SWDM] / D;
+      bg = 0.0;
+      v[0] = 1.0 / D, v[1] = 0.0, v[2] = 0.0;
+    }
+    return true;
   }
 };
+static_assert((int)W_SM == (int)F_SM && (int)W_SM_ALL == (int)F_SM_ALL, "the first two sums are S8's");
+static_assert((int)WCOL_VAR_F + VarianceWeights::VARIANCES == (int)WCOL_CHI2, "the variances stand between bg and chi2");
 
-// One workgroup, WALK_WAVES positions from `first` on, one wave each: s8_fit's box, walk and disc.  A pixel of the disc counts in n_all and
-// Sm_all as S8's; it is usable (n) when it lies on the frame, S8's usable() holds and w = 1 / v has w > 0 and finite.  Then, with m and d
-// S8's:  wm = w m, wd = w d, Sm += m, Sw += w, Swm += wm, Swmm += wm m, Swd += wd, Swdm += wd m, Swdd += wd d.  The fold is S8's.
-// THE SOLVE, in the wave's first lane, in this order: with background D = Sw Swmm - Swm Swm, f = (Sw Swdm - Swm Swd) / D,
-// bg = (Swd - f Swm) / Sw, var_f = Sw / D, var_bg = Swmm / D, cov = - Swm / D; without it D = Swmm, f = Swdm / D, bg = 0, var_f = 1 / D,
-// var_bg = cov = 0.  The flags are S8's: TOO_FEW at n < 3 (with background) or n < 1, else DEGENERATE when D is not finite or D <= 0.
-// PASS 2 walks the same pixels in the same order with e = d - (f m + bg): chi2 = sum w (e e), abs_res = sum |e| and S8's peak of e, both
-// unweighted.
+// S8's records with W_SUMS doubles per record, and S8's state behind them
+RPSFS_HD constexpr size_t s12_record_bytes() { return FitRecords<VarianceWeights>::bytes(); }
+RPSFS_HD constexpr size_t s12_lds_bytes() { return fit_lds_bytes<VarianceWeights>(); }
+
+// S12: fit_disc with the variance policy, rows of FITW_COLUMNS
 template <class Ctx>
 RPSFS_HD void s12_fit_weighted(Ctx& ctx, const Frame& fr, const double* L, const int* none, int use_mesh, const Model& model, const Fit& fit,
                                const Variance& var, const double* pos, const int* cell, long count, long first, void* lds, double* out) {
-  const WRecords acc(lds, WALK_THREADS);
-  const WRecords acc2(static_cast<char*>(lds) + WALK_THREADS * s12_record_bytes(), WALK_WAVES * 8);
-  double* st = reinterpret_cast<double*>(static_cast<char*>(lds) + (WALK_THREADS + WALK_WAVES * 8) * s12_record_bytes());
-  int* go = reinterpret_cast<int*>(st + FS_DOUBLES * WALK_WAVES);
-  const bool no_mesh = use_mesh && none[0] != 0;
-  const bool subtract = use_mesh && !no_mesh;
-  const Mesh mesh{L, fr.nbx, 0, 0};
-  const int N = model.N;
-  const size_t cell_words = (size_t)N * N;
-  ctx.each([&](int tid) {  // pass 1
-    const long i = first + tid / WALK_LANES;
-    const int lane = tid % WALK_LANES;
-    double s[W_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    int n_use = 0, n_all = 0;
-    if (i < count) {
-      const double y = pos[2 * i], x = pos[2 * i + 1];
-      const int k = cell[i];
-      const bool counts_only = no_mesh || k < 0 || k >= model.n_cells;
-      const double* C = counts_only ? nullptr : model.cube + (size_t)k * cell_words;
-      const int r0 = (int)std::floor(y - fit.R) - 1, r1 = (int)std::ceil(y + fit.R) + 1;
-      const int c0 = (int)std::floor(x - fit.R) - 1, c1 = (int)std::ceil(x + fit.R) + 1;
-      const long bw = c1 - c0 + 1, npx = (long)(r1 - r0 + 1) * bw;
-      for (long j = lane; j < npx; j += WALK_LANES) {
-        const int r = r0 + (int)(j / bw), c = c0 + (int)(j % bw);
-        const double pr = (double)r - y, pc = (double)c - x;
-        const double q = pr * pr + pc * pc;
-        if (!(q <= fit.R2)) continue;
-        ++n_all;
-        double m = 0.0;
-        if (!counts_only) m = model_at(C, N, fit.h, pr, pc), s[W_SM_ALL] += m;
-        if (r < 0 || r >= fr.H || c < 0 || c >= fr.W) continue;
-        const size_t p = (size_t)r * fr.W + c;
-        if (!usable(fr.img, fr.mask, p)) continue;
-        const double w = weight_at(var, fr.img, p);
-        if (!weight_ok(w)) continue;
-        ++n_use;
-        if (counts_only) continue;
-        const double d = subtract ? (double)fr.img[p] - background_at(fr, mesh, r, c) : (double)fr.img[p];
-        const double wm = w * m, wd = w * d;
-        s[W_SM] += m, s[W_SW] += w, s[W_SWM] += wm, s[W_SWMM] += wm * m, s[W_SWD] += wd, s[W_SWDM] += wd * m, s[W_SWDD] += wd * d;
-      }
-    }
-#pragma unroll
-    for (int f = 0; f < W_SUMS; ++f) acc.d[f * WALK_THREADS + tid] = s[f];
-    acc.cnt[tid] = n_use, acc.cnt[WALK_THREADS + tid] = n_all;
-  });
-  ctx.each([&](int tid) {  // 64 partials to 8
-    const int wave = tid / WALK_LANES, lane = tid % WALK_LANES;
-    if (lane >= 8) return;
-    const int G = WALK_WAVES * 8, i0 = wave * WALK_LANES + 8 * lane, g = wave * 8 + lane;
-    for (int f = 0; f < W_SUMS; ++f) {
-      double v = 0.0;
-      for (int j = 0; j < 8; ++j) v += acc.d[f * WALK_THREADS + i0 + j];
-      acc2.d[f * G + g] = v;
-    }
-    for (int f = 0; f < 2; ++f) {
-      int v = 0;
-      for (int j = 0; j < 8; ++j) v += acc.cnt[f * WALK_THREADS + i0 + j];
-      acc2.cnt[f * G + g] = v;
-    }
-  });
-  ctx.each([&](int tid) {  // 8 to 1, and the wave's first lane solves
-    const int wave = tid / WALK_LANES;
-    if (tid % WALK_LANES != 0) return;
-    const long i = first + wave;
-    go[wave] = 0;
-    if (i >= count) return;
-    const int G = WALK_WAVES * 8, g0 = wave * 8;
-    double s[W_SUMS];
-    for (int f = 0; f < W_SUMS; ++f) {
-      double v = 0.0;
-      for (int j = 0; j < 8; ++j) v += acc2.d[f * G + g0 + j];
-      s[f] = v;
-    }
-    int cnt[2];
-    for (int f = 0; f < 2; ++f) {
-      int v = 0;
-      for (int j = 0; j < 8; ++j) v += acc2.cnt[f * G + g0 + j];
-      cnt[f] = v;
-    }
-    const double nan = std::nan("");
-    const int k = cell[i];
-    int flags = (no_mesh ? FLAG_NO_MESH : 0) | (k < 0 || k >= model.n_cells ? FLAG_BAD_CELL : 0);
-    double f = nan, bg = nan, var_f = nan, var_bg = nan, cov = nan;
-    if (flags == 0) {
-      if (cnt[0] < (fit.background ? 3 : 1)) {
-        flags |= FLAG_TOO_FEW;
-      } else if (fit.background) {
-        const double D = s[W_SW] * s[W_SWMM] - s[W_SWM] * s[W_SWM];
-        if (!finite_d(D) || D <= 0.0) {
-          flags |= FLAG_DEGENERATE;
-        } else {
-          f = (s[W_SW] * s[W_SWDM] - s[W_SWM] * s[W_SWD]) / D;
-          bg = (s[W_SWD] - f * s[W_SWM]) / s[W_SW];
-          var_f = s[W_SW] / D, var_bg = s[W_SWMM] / D, cov = -s[W_SWM] / D;
-        }
-      } else {
-        const double D = s[W_SWMM];
-        if (!finite_d(D) || D <= 0.0) {
-          flags |= FLAG_DEGENERATE;
-        } else {
-          f = s[W_SWDM] / D;
-          bg = 0.0;
-          var_f = 1.0 / D, var_bg = 0.0, cov = 0.0;
-        }
-      }
-    }
-    const bool sums = (flags & (FLAG_NO_MESH | FLAG_BAD_CELL)) == 0;
-    double* o = out + (size_t)FITW_COLUMNS * i;
-    o[COL_FY] = pos[2 * i], o[COL_FX] = pos[2 * i + 1], o[COL_CELL] = (double)k, o[COL_FFLAGS] = (double)flags;
-    o[COL_N] = (double)cnt[0], o[COL_NALL] = (double)cnt[1];
-    for (int c = 0; c < W_SUMS; ++c) o[WCOL_SUMS + c] = sums ? s[c] : nan;
-    o[WCOL_F] = f, o[WCOL_BG] = bg, o[WCOL_VAR_F] = var_f, o[WCOL_VAR_BG] = var_bg, o[WCOL_COV] = cov;
-    if (flags == 0) {
-      st[FS_F * WALK_WAVES + wave] = f, st[FS_BG * WALK_WAVES + wave] = bg, go[wave] = 1;
-    } else {
-      o[WCOL_CHI2] = o[WCOL_ABS_RES] = o[WCOL_PEAK_RES] = o[WCOL_PEAK_E] = nan;
-      o[WCOL_PEAK_ROW] = o[WCOL_PEAK_COL] = -1.0;
-    }
-  });
-  ctx.each([&](int tid) {  // pass 2: the same pixels in the same order
-    const int wave = tid / WALK_LANES, lane = tid % WALK_LANES;
-    if (!go[wave]) return;
-    const long i = first + wave;
-    const double y = pos[2 * i], x = pos[2 * i + 1];
-    const double f = st[FS_F * WALK_WAVES + wave], bg = st[FS_BG * WALK_WAVES + wave];
-    const double* C = model.cube + (size_t)cell[i] * cell_words;
-    const int r0 = (int)std::floor(y - fit.R) - 1, r1 = (int)std::ceil(y + fit.R) + 1;
-    const int c0 = (int)std::floor(x - fit.R) - 1, c1 = (int)std::ceil(x + fit.R) + 1;
-    const long bw = c1 - c0 + 1, npx = (long)(r1 - r0 + 1) * bw;
-    double chi2 = 0.0, abs_res = 0.0;
-    Peak seen{0.0, -1};
-    for (long j = lane; j < npx; j += WALK_LANES) {
-      const int r = r0 + (int)(j / bw), c = c0 + (int)(j % bw);
-      const double pr = (double)r - y, pc = (double)c - x;
-      const double q = pr * pr + pc * pc;
-      if (!(q <= fit.R2)) continue;
-      if (r < 0 || r >= fr.H || c < 0 || c >= fr.W) continue;
-      const size_t p = (size_t)r * fr.W + c;
-      if (!usable(fr.img, fr.mask, p)) continue;
-      const double w = weight_at(var, fr.img, p);
-      if (!weight_ok(w)) continue;
-      const double m = model_at(C, N, fit.h, pr, pc);
-      const double d = subtract ? (double)fr.img[p] - background_at(fr, mesh, r, c) : (double)fr.img[p];
-      const double e = d - (f * m + bg);
-      chi2 += w * (e * e), abs_res += std::fabs(e);
-      see_residual(seen, e, (long long)p);
-    }
-    acc.d[R_CHI2 * WALK_THREADS + tid] = chi2, acc.d[R_ABS * WALK_THREADS + tid] = abs_res;
-    acc.d[R_PEAK * WALK_THREADS + tid] = seen.e, acc.at[tid] = seen.at;
-  });
-  ctx.each([&](int tid) {  // 64 partials to 8
-    const int wave = tid / WALK_LANES, lane = tid % WALK_LANES;
-    if (lane >= 8 || !go[wave]) return;
-    const int G = WALK_WAVES * 8, i0 = wave * WALK_LANES + 8 * lane, g = wave * 8 + lane;
-    for (int f = 0; f < R_PEAK; ++f) {
-      double v = 0.0;
-      for (int j = 0; j < 8; ++j) v += acc.d[f * WALK_THREADS + i0 + j];
-      acc2.d[f * G + g] = v;
-    }
-    Peak seen{0.0, -1};
-    for (int j = 0; j < 8; ++j) see_residual(seen, acc.d[R_PEAK * WALK_THREADS + i0 + j], acc.at[i0 + j]);
-    acc2.d[R_PEAK * G + g] = seen.e, acc2.at[g] = seen.at;
-  });
-  ctx.each([&](int tid) {  // 8 to 1
-    const int wave = tid / WALK_LANES;
-    if (tid % WALK_LANES != 0 || !go[wave]) return;
-    const int G = WALK_WAVES * 8, g0 = wave * 8;
-    double* o = out + (size_t)FITW_COLUMNS * (first + wave);
-    for (int f = 0; f < R_PEAK; ++f) {
-      double v = 0.0;
-      for (int j = 0; j < 8; ++j) v += acc2.d[f * G + g0 + j];
-      o[WCOL_CHI2 + f] = v;
-    }
-    Peak seen{0.0, -1};
-    for (int j = 0; j < 8; ++j) see_residual(seen, acc2.d[R_PEAK * G + g0 + j], acc2.at[g0 + j]);
-    // (flags == 0 has n >= 1: there is a pixel)
-    o[WCOL_PEAK_RES] = std::fabs(seen.e), o[WCOL_PEAK_E] = seen.e;
-    o[WCOL_PEAK_ROW] = (double)(seen.at / fr.W), o[WCOL_PEAK_COL] = (double)(seen.at % fr.W);
-  });
+  fit_disc(ctx, fr, L, none, use_mesh, model, fit, VarianceWeights{var}, pos, cell, count, first, lds, out);
 }
 
 }  // namespace rpsfw

@@ -116,37 +116,29 @@ RPSFS_HD bool newton_step(const double* s, int n, double& dy, double& dx) {
 }
 
 // ------------------------------------------------------------------------------------------------ the records in LDS
-// One record per lane and one per group of 8 lanes, field-major as S7's and S8's (field f of record i of n is word f n + i): the P_SUMS
-// sums, then the count n.  Behind them the state of the workgroup's WALK_WAVES stars, which the first lane of each wave writes and every
-// lane of the wave reads after the barrier: the position, the last step, niter, the flags and the mode (S7's MODE_DONE / MODE_ITERATE).
+// LaneRecords (rpsf_core_stars_disc.hpp) of the P_SUMS sums, then the count n.  Behind them the state of the workgroup's WALK_WAVES stars,
+// which the first lane of each wave writes and every lane of the wave reads after the barrier: the position, the last step, niter, the
+// flags and the mode (S7's MODE_DONE / MODE_ITERATE).
 enum { PS_Y, PS_X, PS_DY, PS_DX, PS_DOUBLES };
 enum { PS_NITER, PS_FLAGS, PS_MODE, PS_INTS };
-RPSFS_HD constexpr size_t s9_record_bytes() { return (size_t)P_SUMS * 8 + 4; }
+using PRecords = LaneRecords<P_SUMS, false, 1>;
+RPSFS_HD constexpr size_t s9_record_bytes() { return PRecords::bytes(); }
 constexpr size_t S9_STATE_BYTES = ((size_t)WALK_WAVES * (PS_DOUBLES * 8 + PS_INTS * 4) + 15) & ~(size_t)15;
-RPSFS_HD constexpr size_t s9_lds_bytes() { return (size_t)(WALK_THREADS + WALK_WAVES * 8) * s9_record_bytes() + S9_STATE_BYTES; }
+RPSFS_HD constexpr size_t s9_lds_bytes() { return walk_records_bytes<PRecords>() + S9_STATE_BYTES; }
 static_assert(s9_lds_bytes() <= 64 * 1024 && s9_lds_bytes() % 16 == 0, "S9's records fit the LDS a launch gets without asking");
 static_assert((WALK_THREADS * s9_record_bytes()) % 16 == 0 && ((WALK_THREADS + WALK_WAVES * 8) * s9_record_bytes()) % 16 == 0,
               "the group records and the state start at multiples of 16 bytes");
 
-struct PRecords {  // n records at `base` (a multiple of 16 bytes: n is a multiple of 4)
-  double* d;
-  int* cnt;
-  int n;
-  RPSFS_HD PRecords(void* base, int n_) : d(static_cast<double*>(base)), cnt(reinterpret_cast<int*>(d + (size_t)P_SUMS * n_)), n(n_) {}
-};
-
 // One workgroup, WALK_WAVES positions from `first` on, one wave each.  pos[2 i ..] = (y, x), cell[i] its cell of the cube, fixed for the
-// whole iteration.  A WALK at p = (y, x) covers S8's box (floor(y - R) - 1 to ceil(y + R) + 1, likewise in x, not clipped to the frame),
-// lane j takes its pixels j, j + 64, ... in raster order.  For pixel (r, c): pr = r - y, pc = c - x, q = pr pr + pc pc; when q <= R R and
-// the pixel lies on the frame and is usable (n), with d the residual against the mesh (use_mesh) or the pixel itself and (m, g_u, g_v) =
-// sample_at:  Smm += m m, Sm += m, Smu += m g_u, Smv += m g_v, Su += g_u, Sv += g_v, Suu += g_u g_u, Suv += g_u g_v, Svv += g_v g_v,
-// Sdm += d m, Sd += d, Sdu += d g_u, Sdv += d g_v.  The 64 partial records fold as 8 groups of 8, each in lane order, and the 8 groups in
-// order.  THE DECISION, in the wave's first lane: with background the unknowns are (f, bg, a_u, a_v), the matrix rows (Smm Sm Smu Smv),
-// (. n Su Sv), (. . Suu Suv), (. . . Svv) and the right-hand side (Sdm Sd Sdu Sdv); without it the row and column of the constant drop
-// out.  SINGULAR: n below the number of unknowns, solve_ldl fails, or dy = -a_u / f, dx = -a_v / f is not finite; the star stops where it
-// is and the last step stays what it was.  Else each of dy, dx is clamped to [-max_step, max_step] and becomes the last step; p' = p +
-// (dy, dx); RAN_AWAY: (p' - p_0)^2 > max_shift^2, the star stops at p.  Else p' is accepted, niter += 1; dy dy + dx dx < eps eps: converged;
-// else niter == max_iter: NOT_CONVERGED.
+// whole iteration.  A WALK at p = (y, x) is walk_disc over disc_box(y, x, R) (rpsf_core_stars_disc.hpp), S8's.  For a pixel of the disc
+// that lies on the frame and is usable (n), with d the residual against the mesh (use_mesh) or the pixel itself and (m, g_u, g_v) =
+// sample_at:  Smm += m m, Sm += m, Smu += m g_u, Smv += m g_v, Su += g_u, Sv += g_v, Suu += g_u g_u, Suv += g_u g_v, Svv += g_v g_v, Sdm +=
+// d m, Sd += d, Sdu += d g_u, Sdv += d g_v.  The fold is the disc header's.  THE DECISION, in the wave's first lane: with background the
+// unknowns are (f, bg, a_u, a_v), the matrix rows (Smm Sm Smu Smv), (. n Su Sv), (. . Suu Suv), (. . . Svv) and the right-hand side (Sdm Sd
+// Sdu Sdv); without it the row and column of the constant drop out.  SINGULAR: n below the number of unknowns, solve_ldl fails, or dy =
+// -a_u / f, dx = -a_v / f is not finite; the star stops where it is and the last step stays what it was.  Else each of dy, dx is clamped to
+// [-max_step, max_step] and becomes the last step; p' = p + (dy, dx); RAN_AWAY: (p' - p_0)^2 > max_shift^2, the star stops at p.  Else p'
+// is accepted, niter += 1; dy dy + dx dx < eps eps: converged; else niter == max_iter: NOT_CONVERGED.
 //
 // THE ITERATION runs in ROUNDS of three each(), as S7's: the walk, the fold, and the decision of the wave's first lane, which publishes
 // the new position through LDS.  Every round ends in barriers, so its trip count is the same for every thread: a round starts only while
@@ -160,8 +152,8 @@ RPSFS_HD void s9_fit_positions(Ctx& ctx, const Frame& fr, const double* L, const
                                const FitPos& fp, const double* pos, const int* cell, long count, long first, void* lds, double* out,
                                double* final_pos) {
   const PRecords acc(lds, WALK_THREADS);
-  const PRecords acc2(static_cast<char*>(lds) + WALK_THREADS * s9_record_bytes(), WALK_WAVES * 8);
-  double* st = reinterpret_cast<double*>(static_cast<char*>(lds) + (WALK_THREADS + WALK_WAVES * 8) * s9_record_bytes());
+  const PRecords acc2(static_cast<char*>(lds) + WALK_THREADS * s9_record_bytes(), WALK_GROUPS);
+  double* st = reinterpret_cast<double*>(static_cast<char*>(lds) + walk_records_bytes<PRecords>());
   int* sti = reinterpret_cast<int*>(st + PS_DOUBLES * WALK_WAVES);
   const bool no_mesh = use_mesh && none[0] != 0;
   const bool subtract = use_mesh && !no_mesh;
@@ -190,26 +182,16 @@ RPSFS_HD void s9_fit_positions(Ctx& ctx, const Frame& fr, const double* L, const
       const long i = first + wave;
       const double y = st[PS_Y * WALK_WAVES + wave], x = st[PS_X * WALK_WAVES + wave];
       const double* C = model.cube + (size_t)cell[i] * cell_words;
-      const int r0 = (int)std::floor(y - fit.R) - 1, r1 = (int)std::ceil(y + fit.R) + 1;
-      const int c0 = (int)std::floor(x - fit.R) - 1, c1 = (int)std::ceil(x + fit.R) + 1;
-      const long bw = c1 - c0 + 1, npx = (long)(r1 - r0 + 1) * bw;
       double s[P_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       int n_use = 0;
-      for (long j = lane; j < npx; j += WALK_LANES) {
-        const int r = r0 + (int)(j / bw), c = c0 + (int)(j % bw);
-        const double pr = (double)r - y, pc = (double)c - x;
-        const double q = pr * pr + pc * pc;
-        if (!(q <= fit.R2)) continue;
-        if (r < 0 || r >= fr.H || c < 0 || c >= fr.W) continue;
-        const size_t p = (size_t)r * fr.W + c;
-        if (!usable(fr.img, fr.mask, p)) continue;
+      walk_disc(fr, disc_box(y, x, fit.R), y, x, fit.R2, lane, [&](int r, int c, size_t p, double pr, double pc, double) {
         ++n_use;
         const Sample t = sample_at(C, N, fit.h, pr, pc);
         const double d = subtract ? (double)fr.img[p] - background_at(fr, mesh, r, c) : (double)fr.img[p];
         s[P_SMM] += t.m * t.m, s[P_SM] += t.m, s[P_SMU] += t.m * t.gu, s[P_SMV] += t.m * t.gv;
         s[P_SU] += t.gu, s[P_SV] += t.gv, s[P_SUU] += t.gu * t.gu, s[P_SUV] += t.gu * t.gv, s[P_SVV] += t.gv * t.gv;
         s[P_SDM] += d * t.m, s[P_SD] += d, s[P_SDU] += d * t.gu, s[P_SDV] += d * t.gv;
-      }
+      });
 #pragma unroll
       for (int f = 0; f < P_SUMS; ++f) acc.d[f * WALK_THREADS + tid] = s[f];
       acc.cnt[tid] = n_use;
@@ -217,29 +199,15 @@ RPSFS_HD void s9_fit_positions(Ctx& ctx, const Frame& fr, const double* L, const
     ctx.each([&](int tid) {  // 64 partials to 8
       const int wave = tid / WALK_LANES, lane = tid % WALK_LANES;
       if (lane >= 8 || sti[PS_MODE * WALK_WAVES + wave] == MODE_DONE) return;
-      const int G = WALK_WAVES * 8, i0 = wave * WALK_LANES + 8 * lane, g = wave * 8 + lane;
-      for (int f = 0; f < P_SUMS; ++f) {
-        double v = 0.0;
-        for (int j = 0; j < 8; ++j) v += acc.d[f * WALK_THREADS + i0 + j];
-        acc2.d[f * G + g] = v;
-      }
-      int v = 0;
-      for (int j = 0; j < 8; ++j) v += acc.cnt[i0 + j];
-      acc2.cnt[g] = v;
+      fold_sums_64to8(acc, acc2, tid, P_SUMS), fold_counts_64to8(acc, acc2, tid, 1);
     });
     ctx.each([&](int tid) {  // 8 to 1, and the wave's first lane decides
       const int wave = tid / WALK_LANES;
       if (tid % WALK_LANES != 0 || sti[PS_MODE * WALK_WAVES + wave] == MODE_DONE) return;
       const long i = first + wave;
-      const int G = WALK_WAVES * 8, g0 = wave * 8;
       double s[P_SUMS];
-      for (int f = 0; f < P_SUMS; ++f) {
-        double v = 0.0;
-        for (int j = 0; j < 8; ++j) v += acc2.d[f * G + g0 + j];
-        s[f] = v;
-      }
       int n = 0;
-      for (int j = 0; j < 8; ++j) n += acc2.cnt[g0 + j];
+      fold_sums_8to1(acc2, wave, P_SUMS, s), fold_counts_8to1(acc2, wave, 1, &n);
       const double y = st[PS_Y * WALK_WAVES + wave], x = st[PS_X * WALK_WAVES + wave];
       int flags = sti[PS_FLAGS * WALK_WAVES + wave], niter = sti[PS_NITER * WALK_WAVES + wave];
       bool stop = true;

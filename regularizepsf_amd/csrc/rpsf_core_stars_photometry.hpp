@@ -9,12 +9,12 @@
 // or D1 - D4 read or wrote changes.  No atomics at all, no workgroup waits for another.  Two runs on one input agree bit for bit.
 // This is NOT sep's sum_circle: a sub-sample counts when q <= R R, and masked pixels are left out and reported, not corrected for.
 #pragma once
-#include "rpsf_core_stars_shape.hpp"
+#include "rpsf_core_stars_disc.hpp"
 
 #pragma clang fp contract(off)
 
 namespace rpsfp {
-using namespace rpsfs;
+using namespace rpsfk;
 
 constexpr int MAX_RADII = 8, MAX_SUBPIX = 8;
 constexpr double MAX_RADIUS = 64.0, MAX_COORD = 1048576.0;  // |y|, |x| < 2^20: every pixel index of a box is an int far from overflow
@@ -72,23 +72,15 @@ struct Records {  // n records for m radii at `base` (a multiple of 16 bytes: n 
 
 // records i0 ... i0 + 7 of `src` in index order into record i of `dst`: the sums added, the peak folded with see_peak's order
 RPSFS_HD void s6_fold8(const Records& src, int i0, const Records& dst, int i, int m) {
-  for (int f = 0; f < m + SUMS; ++f) {
-    double s = 0.0;
-    for (int j = 0; j < 8; ++j) s += src.d[f * src.n + i0 + j];
-    dst.d[f * dst.n + i] = s;
-  }
+  for (int f = 0; f < m + SUMS; ++f) dst.d[f * dst.n + i] = sum8(src.d + f * src.n + i0);
   rpsfh::Seen seen = rpsfh::nothing_seen();
   for (int j = 0; j < 8; ++j) rpsfh::see_peak(seen, src.d[(m + SUMS) * src.n + i0 + j], src.at[i0 + j]);
   dst.d[(m + SUMS) * dst.n + i] = seen.peak, dst.at[i] = seen.at;
-  for (int f = 0; f < 2 * m; ++f) {
-    int s = 0;
-    for (int j = 0; j < 8; ++j) s += src.cnt[f * src.n + i0 + j];
-    dst.cnt[f * dst.n + i] = s;
-  }
+  for (int f = 0; f < 2 * m; ++f) dst.cnt[f * dst.n + i] = sum8(src.cnt + f * src.n + i0);
 }
 
-// One workgroup, WALK_WAVES positions from `first` on, one wave each.  pos[2 i ..] = (y, x).  The box runs from floor(y - R_max) - 1 to
-// ceil(y + R_max) + 1 and likewise in x, not clipped to the frame; lane j takes its pixels j, j + 64, ... in raster order.  For pixel
+// One workgroup, WALK_WAVES positions from `first` on, one wave each.  pos[2 i ..] = (y, x).  The box is disc_box(y, x, R_max)
+// (rpsf_core_stars_disc.hpp); lane j takes its pixels j, j + 64, ... in raster order - every pixel of the box, not walk_disc's disc.  For pixel
 // (r, c): pr = r - y, pc = c - x, q_ab = (pr + o_a)(pr + o_a) + (pc + o_b)(pc + o_b), n_k = #{q_ab <= R_k R_k}, w_k = n_k / (s s).
 // N_all_k sums n_k over the box, N_use_k over the usable pixels of the frame; with d the residual against the mesh (use_mesh) or the
 // pixel itself, flux_k = sum w_k d, and with w = w_{m-1}, t = w d: sum w |d|, t pr, t pc, t (pr pr), t (pc pc), t (pr pc), the products
@@ -120,14 +112,12 @@ RPSFS_HD void s6_apertures(Ctx& ctx, const Frame& fr, const double* L, const int
     const int lane = tid % WALK_LANES;
     if (i >= count) return;
     const double y = pos[2 * i], x = pos[2 * i + 1];
-    const int r0 = (int)std::floor(y - ap.rmax) - 1, r1 = (int)std::ceil(y + ap.rmax) + 1;
-    const int c0 = (int)std::floor(x - ap.rmax) - 1, c1 = (int)std::ceil(x + ap.rmax) + 1;
-    const long bw = c1 - c0 + 1, npx = (long)(r1 - r0 + 1) * bw;
+    const DiscBox box = disc_box(y, x, ap.rmax);
     double* sum = acc.d + tid;
     int* cnt = acc.cnt + tid;
     rpsfh::Seen seen = rpsfh::nothing_seen();
-    for (long j = lane; j < npx; j += WALK_LANES) {
-      const int r = r0 + (int)(j / bw), c = c0 + (int)(j % bw);
+    for (long j = lane; j < box.npx; j += WALK_LANES) {
+      const int r = box.r0 + (int)(j / box.bw), c = box.c0 + (int)(j % box.bw);
       const double pr = (double)r - y, pc = (double)c - x;
       int n[MAX_RADII] = {0, 0, 0, 0, 0, 0, 0, 0};
       for (int a = 0; a < s; ++a) {
@@ -170,20 +160,15 @@ RPSFS_HD void s6_apertures(Ctx& ctx, const Frame& fr, const double* L, const int
     const int wave = tid / WALK_LANES;
     const long i = first + wave;
     if (tid % WALK_LANES != 0 || i >= count) return;
-    const int G = WALK_WAVES * 8, g0 = wave * 8;
+    const int G = WALK_GROUPS, g0 = wave * 8;
     const double nan = std::nan("");
     double* o = out + (size_t)columns * i;
     o[0] = pos[2 * i], o[1] = pos[2 * i + 1];
     for (int f = 0; f < m + SUMS; ++f) {  // the fluxes, then the six sums: the output's order but for the counts in between
-      double v = 0.0;
-      for (int j = 0; j < 8; ++j) v += acc2.d[f * G + g0 + j];
+      const double v = sum8(acc2.d + f * G + g0);
       o[2 + (f < m ? f : f + 2 * m)] = no_mesh ? nan : v;
     }
-    for (int f = 0; f < 2 * m; ++f) {
-      int v = 0;
-      for (int j = 0; j < 8; ++j) v += acc2.cnt[f * G + g0 + j];
-      o[2 + m + f] = (double)v;
-    }
+    for (int f = 0; f < 2 * m; ++f) o[2 + m + f] = (double)sum8(acc2.cnt + f * G + g0);
     rpsfh::Seen seen = rpsfh::nothing_seen();
     for (int j = 0; j < 8; ++j) rpsfh::see_peak(seen, acc2.d[(m + SUMS) * G + g0 + j], acc2.at[g0 + j]);
     double* peak = o + 2 + 3 * m + SUMS;

@@ -74,29 +74,21 @@ RPSFS_HD double window_g(double t) {
 }
 
 // ------------------------------------------------------------------------------------------------ the records in LDS
-// One record per lane and one per group of 8 lanes, field-major as S6's (field f of record i of n is word f n + i): the W_SUMS sums, then
-// N_use and N_all.  Behind them the state of the workgroup's WALK_WAVES stars, which the first lane of each wave writes and every lane of
-// the wave reads after the barrier: the position, the last step, niter, the flags and the mode.
+// LaneRecords (rpsf_core_stars_disc.hpp) of the W_SUMS sums, then N_use and N_all.  Behind them the state of the workgroup's WALK_WAVES
+// stars, which the first lane of each wave writes and every lane of the wave reads after the barrier: the position, the last step, niter,
+// the flags and the mode.
 enum { MODE_DONE, MODE_ITERATE, MODE_MEASURE };
 enum { ST_Y, ST_X, ST_DY, ST_DX, ST_DOUBLES };
 enum { ST_NITER, ST_FLAGS, ST_MODE, ST_INTS };
-RPSFS_HD constexpr size_t s7_record_bytes() { return (size_t)W_SUMS * 8 + 2 * 4; }
+using WRecords = LaneRecords<W_SUMS, false, 2>;
+RPSFS_HD constexpr size_t s7_record_bytes() { return WRecords::bytes(); }
 constexpr size_t S7_STATE_BYTES = ((size_t)WALK_WAVES * (ST_DOUBLES * 8 + ST_INTS * 4) + 15) & ~(size_t)15;
-RPSFS_HD constexpr size_t s7_lds_bytes() { return (size_t)(WALK_THREADS + WALK_WAVES * 8) * s7_record_bytes() + S7_STATE_BYTES; }
-
-struct WRecords {  // n records at `base` (a multiple of 16 bytes: n is a multiple of 4)
-  double* d;
-  int* cnt;
-  int n;
-  RPSFS_HD WRecords(void* base, int n_) : d(static_cast<double*>(base)), cnt(reinterpret_cast<int*>(d + (size_t)W_SUMS * n_)), n(n_) {}
-};
+RPSFS_HD constexpr size_t s7_lds_bytes() { return walk_records_bytes<WRecords>() + S7_STATE_BYTES; }
 
 // One workgroup, WALK_WAVES positions from `first` on, one wave each.  pos[2 i ..] = (y, x), sigma[i] its window.  A WALK at p = (y, x):
-// R = 4 sigma, h = 1 / (2 sigma sigma); the box runs from floor(y - R) - 1 to ceil(y + R) + 1 and likewise in x, not clipped to the
-// frame; lane j takes its pixels j, j + 64, ... in raster order.  For pixel (r, c): pr = r - y, pc = c - x, q = pr pr + pc pc; it is in
-// the window when q <= R R (N_all), and then, when it lies on the frame and is usable (N_use), with d the residual against the mesh
-// (use_mesh) or the pixel itself, w = g(q h) and t = w d:  sum t, w |d|, t pr, t pc, t (pr pr), t (pc pc), t (pr pc), the products grouped as
-// written.  The 64 partial records fold as 8 groups of 8, each in lane order, and the 8 groups in order.
+// R = 4 sigma, h = 1 / (2 sigma sigma); walk_disc over disc_box(y, x, R) (rpsf_core_stars_disc.hpp).  A pixel of the window counts in N_all,
+// and then, when it lies on the frame and is usable (N_use), with d the residual against the mesh (use_mesh) or the pixel itself, w = g(q h)
+// and t = w d:  sum t, w |d|, t pr, t pc, t (pr pr), t (pc pc), t (pr pc), the products grouped as written.  The fold is the disc header's.
 //
 // THE ITERATION (rpsf.h) runs in ROUNDS of three each(): the walk, the fold, and the decision of the wave's first lane,
 // which publishes the new position through LDS.  Every round ends in barriers, so its trip count is the same for every thread: a round
@@ -109,8 +101,8 @@ template <class Ctx>
 RPSFS_HD void s7_refine(Ctx& ctx, const Frame& fr, const double* L, const int* none, int use_mesh, const Refine& rf, const double* pos,
                         const double* sigma, long count, long first, void* lds, double* out) {
   const WRecords acc(lds, WALK_THREADS);
-  const WRecords acc2(static_cast<char*>(lds) + WALK_THREADS * s7_record_bytes(), WALK_WAVES * 8);
-  double* st = reinterpret_cast<double*>(static_cast<char*>(lds) + (WALK_THREADS + WALK_WAVES * 8) * s7_record_bytes());
+  const WRecords acc2(static_cast<char*>(lds) + WALK_THREADS * s7_record_bytes(), WALK_GROUPS);
+  double* st = reinterpret_cast<double*>(static_cast<char*>(lds) + walk_records_bytes<WRecords>());
   int* sti = reinterpret_cast<int*>(st + ST_DOUBLES * WALK_WAVES);
   const bool no_mesh = use_mesh && none[0] != 0;
   const bool subtract = use_mesh && !no_mesh;
@@ -136,27 +128,16 @@ RPSFS_HD void s7_refine(Ctx& ctx, const Frame& fr, const double* L, const int* n
       const long i = first + wave;
       const double y = st[ST_Y * WALK_WAVES + wave], x = st[ST_X * WALK_WAVES + wave], sg = sigma[i];
       const double R = WINDOW_RADII * sg, R2 = R * R, h = 1.0 / (2.0 * sg * sg);
-      const int r0 = (int)std::floor(y - R) - 1, r1 = (int)std::ceil(y + R) + 1;
-      const int c0 = (int)std::floor(x - R) - 1, c1 = (int)std::ceil(x + R) + 1;
-      const long bw = c1 - c0 + 1, npx = (long)(r1 - r0 + 1) * bw;
       double s[W_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       int n_use = 0, n_all = 0;
-      for (long j = lane; j < npx; j += WALK_LANES) {
-        const int r = r0 + (int)(j / bw), c = c0 + (int)(j % bw);
-        const double pr = (double)r - y, pc = (double)c - x;
-        const double q = pr * pr + pc * pc;
-        if (!(q <= R2)) continue;
-        ++n_all;
-        if (r < 0 || r >= fr.H || c < 0 || c >= fr.W) continue;
-        const size_t p = (size_t)r * fr.W + c;
-        if (!usable(fr.img, fr.mask, p)) continue;
+      walk_disc(fr, disc_box(y, x, R), y, x, R2, lane, [&](double, double) { ++n_all; }, [&](int r, int c, size_t p, double pr, double pc, double q) {
         ++n_use;
         const double d = subtract ? (double)fr.img[p] - background_at(fr, mesh, r, c) : (double)fr.img[p];
         const double w = window_g(q * h), t = w * d;
         s[W_S] += t, s[W_ABS] += w * std::fabs(d);
         s[W_MR] += t * pr, s[W_MC] += t * pc;
         s[W_MRR] += t * (pr * pr), s[W_MCC] += t * (pc * pc), s[W_MRC] += t * (pr * pc);
-      }
+      });
 #pragma unroll
       for (int f = 0; f < W_SUMS; ++f) acc.d[f * WALK_THREADS + tid] = s[f];
       acc.cnt[tid] = n_use, acc.cnt[WALK_THREADS + tid] = n_all;
@@ -164,35 +145,15 @@ RPSFS_HD void s7_refine(Ctx& ctx, const Frame& fr, const double* L, const int* n
     ctx.each([&](int tid) {  // 64 partials to 8
       const int wave = tid / WALK_LANES, lane = tid % WALK_LANES;
       if (lane >= 8 || sti[ST_MODE * WALK_WAVES + wave] == MODE_DONE) return;
-      const int G = WALK_WAVES * 8, i0 = wave * WALK_LANES + 8 * lane, g = wave * 8 + lane;
-      for (int f = 0; f < W_SUMS; ++f) {
-        double v = 0.0;
-        for (int j = 0; j < 8; ++j) v += acc.d[f * WALK_THREADS + i0 + j];
-        acc2.d[f * G + g] = v;
-      }
-      for (int f = 0; f < 2; ++f) {
-        int v = 0;
-        for (int j = 0; j < 8; ++j) v += acc.cnt[f * WALK_THREADS + i0 + j];
-        acc2.cnt[f * G + g] = v;
-      }
+      fold_sums_64to8(acc, acc2, tid, W_SUMS), fold_counts_64to8(acc, acc2, tid, 2);
     });
     ctx.each([&](int tid) {  // 8 to 1, and the wave's first lane decides
       const int wave = tid / WALK_LANES;
       if (tid % WALK_LANES != 0 || sti[ST_MODE * WALK_WAVES + wave] == MODE_DONE) return;
       const long i = first + wave;
-      const int G = WALK_WAVES * 8, g0 = wave * 8;
       double s[W_SUMS];
-      for (int f = 0; f < W_SUMS; ++f) {
-        double v = 0.0;
-        for (int j = 0; j < 8; ++j) v += acc2.d[f * G + g0 + j];
-        s[f] = v;
-      }
       int cnt[2];
-      for (int f = 0; f < 2; ++f) {
-        int v = 0;
-        for (int j = 0; j < 8; ++j) v += acc2.cnt[f * G + g0 + j];
-        cnt[f] = v;
-      }
+      fold_sums_8to1(acc2, wave, W_SUMS, s), fold_counts_8to1(acc2, wave, 2, cnt);
       const double y = st[ST_Y * WALK_WAVES + wave], x = st[ST_X * WALK_WAVES + wave];
       int flags = sti[ST_FLAGS * WALK_WAVES + wave], niter = sti[ST_NITER * WALK_WAVES + wave];
       bool deliver = sti[ST_MODE * WALK_WAVES + wave] == MODE_MEASURE;

@@ -68,8 +68,8 @@ inline size_t tile_lists(int H, int W, size_t n, const double* pos, const double
     if (!star_rendered(flux[i], cell[i], n_cells)) continue;
     ++rendered;
     const double y = pos[2 * i], x = pos[2 * i + 1];
-    long r0 = (long)std::floor(y - R) - 1, r1 = (long)std::ceil(y + R) + 1;
-    long c0 = (long)std::floor(x - R) - 1, c1 = (long)std::ceil(x + R) + 1;
+    const DiscBox box = disc_box(y, x, R);  // (the caller has checked position_ok: the box is far from an int's range)
+    long r0 = box.r0, r1 = box.r1, c0 = box.c0, c1 = box.c1;
     if (r0 < 0) r0 = 0;
     if (c0 < 0) c0 = 0;
     if (r1 > H - 1) r1 = H - 1;

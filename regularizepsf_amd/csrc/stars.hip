@@ -374,6 +374,50 @@ static int timed(rpsf_stars* s, double* ms, F&& launches) {
   return RPSF_OK;
 }
 
+// a PSF model on the device (rpsf_stars_model_create, S8)
+struct rpsf_stars_model {
+  int device = 0, n_cells = 0, N = 0;
+  Buf<double> values;
+  std::vector<uint8_t> finite;  // per cell: every value is finite (rpsf_stars_fit_groups fits only stars of such cells together)
+};
+
+// ------------------------------------------------------------------------------------------------ a call over n positions
+// What rpsf_stars_fit, _fit_positions, _fit_weighted and _fit_groups check of their model, with the function's `name` in every message.
+static int check_model(const std::string& name, const rpsf_stars* s, const rpsf_stars_model* model, double radius) {
+  if (!(radius <= rpsff::max_fit_radius(model->N)))
+    return fail(RPSF_E_BADARG,
+                name + ": radius " + std::to_string(radius) + " is above min(64, N / 2 - 1) of the model's N = " + std::to_string(model->N));
+  if (model->device != s->device) return fail(RPSF_E_BADARG, name + ": the model is on another device than the finder");
+  return RPSF_OK;
+}
+
+// What S6 - S9, S11 and S12 check alike before they launch, in this order and with the function's `name` in every message: the pointers
+// (`pointers`: none that the call needs is null), the call's own arguments (`why`: what is wrong with them, or null), the 2^30 limit,
+// every position - and after position i what `item(i)` says of the call's other array (RPSF_OK, or it has failed) -, the model (null: the
+// call takes none) and that the frame has its mesh.
+template <class Item>
+static int check_positions_call(const std::string& name, const rpsf_stars* s, bool pointers, const char* why, size_t n, const double* positions_host,
+                                const rpsf_stars_model* model, double radius, Item&& item) {
+  if (!pointers) return fail(RPSF_E_BADARG, "null argument");
+  if (why) return fail(RPSF_E_BADARG, name + ": " + why);
+  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, name + ": more than 2^30 positions in one call");
+  for (size_t i = 0; i < n; ++i) {
+    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
+      return fail(RPSF_E_BADARG, name + ": position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
+    if (const int rc = item(i)) return rc;
+  }
+  if (model)
+    if (const int rc = check_model(name, s, model, radius)) return rc;
+  if (!s->have_mesh) return fail(RPSF_E_STATE, name + " before a rpsf_stars_background_view / _host / _scaled of the frame");
+  return RPSF_OK;
+}
+static int check_positions_call(const std::string& name, const rpsf_stars* s, bool pointers, const char* why, size_t n, const double* positions_host,
+                                const rpsf_stars_model* model = nullptr, double radius = 0.0) {
+  return check_positions_call(name, s, pointers, why, n, positions_host, model, radius, [](size_t) { return RPSF_OK; });
+}
+// one wave per position (or group): the grid of S6 - S9, S11 and S12
+static dim3 walk_grid(size_t n) { return dim3((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES)); }
+
 static void launch_label(rpsf_stars* s) {
   const dim3 tiles((s->W + TILE_C - 1) / TILE_C, (s->H + TILE_R - 1) / TILE_R);
   hipLaunchKernelGGL(stars_label_tile_kernel, tiles, dim3(TILE_THREADS), TILE_R * TILE_C * sizeof(int), nullptr, s->det.p, s->H, s->W,
@@ -732,13 +776,9 @@ extern "C" int rpsf_stars_shape_ms(const rpsf_stars* s, double* ms) {
 // ------------------------------------------------------------------------------------------------ S6 (Apertures)
 extern "C" int rpsf_stars_photometry(rpsf_stars* s, size_t n, const double* positions_host, int m, const double* radii, int subpix,
                                      int use_mesh, double* out_host) {
-  if (!s || (n && (!positions_host || !out_host))) return fail(RPSF_E_BADARG, "null argument");
-  if (const char* why = rpsfp::apertures_problem(m, radii, subpix)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_photometry: ") + why);
-  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_photometry: more than 2^30 positions in one call");
-  for (size_t i = 0; i < n; ++i)
-    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
-      return fail(RPSF_E_BADARG, "rpsf_stars_photometry: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
-  if (!s->have_mesh) return fail(RPSF_E_STATE, "rpsf_stars_photometry before a rpsf_stars_background_view / _host / _scaled of the frame");
+  if (const int rc = check_positions_call("rpsf_stars_photometry", s, s && (!n || (positions_host && out_host)),
+                                          rpsfp::apertures_problem(m, radii, subpix), n, positions_host))
+    return rc;
   s->photometry_ms = 0;
   if (n == 0) return RPSF_OK;  // nothing to launch
   HIP_TRY(hipSetDevice(s->device));
@@ -748,9 +788,8 @@ extern "C" int rpsf_stars_photometry(rpsf_stars* s, size_t n, const double* posi
   HIP_TRY(hipMemcpy(s->phot_pos.p, positions_host, 2 * n * sizeof(double), hipMemcpyHostToDevice));
   const rpsfp::Apertures ap = rpsfp::make_apertures(m, radii, subpix);
   if (const int rc = timed(s, &s->photometry_ms, [&] {
-        hipLaunchKernelGGL(stars_photometry_kernel, dim3((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS),
-                           rpsfp::s6_lds_bytes(m), nullptr, s->view(), s->level_f.p, s->none.p, use_mesh != 0, ap, s->phot_pos.p, (long)n,
-                           s->phot_out.p);
+        hipLaunchKernelGGL(stars_photometry_kernel, walk_grid(n), dim3(WALK_THREADS), rpsfp::s6_lds_bytes(m), nullptr, s->view(), s->level_f.p,
+                           s->none.p, use_mesh != 0, ap, s->phot_pos.p, (long)n, s->phot_out.p);
       }))
     return rc;
   HIP_TRY(hipMemcpy(out_host, s->phot_out.p, columns * n * sizeof(double), hipMemcpyDeviceToHost));
@@ -766,16 +805,13 @@ extern "C" int rpsf_stars_photometry_ms(const rpsf_stars* s, double* ms) {
 // ------------------------------------------------------------------------------------------------ S7 (Windowed positions)
 extern "C" int rpsf_stars_refine(rpsf_stars* s, size_t n, const double* positions_host, const double* sigma_host, int max_iter, double eps,
                                  double max_shift, int use_mesh, double* out_host) {
-  if (!s || (n && (!positions_host || !sigma_host || !out_host))) return fail(RPSF_E_BADARG, "null argument");
-  if (const char* why = rpsfr::refine_problem(max_iter, eps, max_shift)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_refine: ") + why);
-  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_refine: more than 2^30 positions in one call");
-  for (size_t i = 0; i < n; ++i) {
-    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
-      return fail(RPSF_E_BADARG, "rpsf_stars_refine: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
-    if (!rpsfr::sigma_ok(sigma_host[i]))
-      return fail(RPSF_E_BADARG, "rpsf_stars_refine: sigma " + std::to_string(i) + " is not inside 0.5 <= sigma <= 16");
-  }
-  if (!s->have_mesh) return fail(RPSF_E_STATE, "rpsf_stars_refine before a rpsf_stars_background_view / _host / _scaled of the frame");
+  const auto sigma_problem = [&](size_t i) -> int {
+    if (rpsfr::sigma_ok(sigma_host[i])) return RPSF_OK;
+    return fail(RPSF_E_BADARG, "rpsf_stars_refine: sigma " + std::to_string(i) + " is not inside 0.5 <= sigma <= 16");
+  };
+  if (const int rc = check_positions_call("rpsf_stars_refine", s, s && (!n || (positions_host && sigma_host && out_host)),
+                                          rpsfr::refine_problem(max_iter, eps, max_shift), n, positions_host, nullptr, 0.0, sigma_problem))
+    return rc;
   s->refine_ms = 0;
   if (n == 0) return RPSF_OK;  // nothing to launch
   HIP_TRY(hipSetDevice(s->device));
@@ -786,9 +822,8 @@ extern "C" int rpsf_stars_refine(rpsf_stars* s, size_t n, const double* position
   HIP_TRY(hipMemcpy(s->refine_sigma.p, sigma_host, n * sizeof(double), hipMemcpyHostToDevice));
   const rpsfr::Refine rf = rpsfr::make_refine(max_iter, eps, max_shift);
   if (const int rc = timed(s, &s->refine_ms, [&] {
-        hipLaunchKernelGGL(stars_refine_kernel, dim3((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS), rpsfr::s7_lds_bytes(),
-                           nullptr, s->view(), s->level_f.p, s->none.p, use_mesh != 0, rf, s->refine_pos.p, s->refine_sigma.p, (long)n,
-                           s->refine_out.p);
+        hipLaunchKernelGGL(stars_refine_kernel, walk_grid(n), dim3(WALK_THREADS), rpsfr::s7_lds_bytes(), nullptr, s->view(), s->level_f.p,
+                           s->none.p, use_mesh != 0, rf, s->refine_pos.p, s->refine_sigma.p, (long)n, s->refine_out.p);
       }))
     return rc;
   HIP_TRY(hipMemcpy(out_host, s->refine_out.p, RPSF_STARS_REFINE_COLUMNS * n * sizeof(double), hipMemcpyDeviceToHost));
@@ -802,12 +837,6 @@ extern "C" int rpsf_stars_refine_ms(const rpsf_stars* s, double* ms) {
 }
 
 // ------------------------------------------------------------------------------------------------ S8 (Model fits)
-struct rpsf_stars_model {
-  int device = 0, n_cells = 0, N = 0;
-  Buf<double> values;
-  std::vector<uint8_t> finite;  // per cell: every value is finite (rpsf_stars_fit_groups fits only stars of such cells together)
-};
-
 extern "C" int rpsf_stars_model_create(int device, size_t n_cells, int N, const double* values_host, rpsf_stars_model** out) {
   if (!out || !values_host) return fail(RPSF_E_BADARG, "null argument");
   if (!rpsff::model_size_ok(N)) return fail(RPSF_E_BADARG, "rpsf_stars_model_create: the cells must be N x N with 4 <= N <= 256");
@@ -844,17 +873,9 @@ extern "C" void rpsf_stars_model_destroy(rpsf_stars_model* m) {
 
 extern "C" int rpsf_stars_fit(rpsf_stars* s, const rpsf_stars_model* model, size_t n, const double* positions_host, const int32_t* cells_host,
                               double radius, int fit_background, int use_mesh, double* out_host) {
-  if (!s || !model || (n && (!positions_host || !cells_host || !out_host))) return fail(RPSF_E_BADARG, "null argument");
-  if (const char* why = rpsff::fit_problem(radius, fit_background)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit: ") + why);
-  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_fit: more than 2^30 positions in one call");
-  for (size_t i = 0; i < n; ++i)
-    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
-      return fail(RPSF_E_BADARG, "rpsf_stars_fit: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
-  if (!(radius <= rpsff::max_fit_radius(model->N)))
-    return fail(RPSF_E_BADARG, "rpsf_stars_fit: radius " + std::to_string(radius) + " is above min(64, N / 2 - 1) of the model's N = " +
-                                   std::to_string(model->N));
-  if (model->device != s->device) return fail(RPSF_E_BADARG, "rpsf_stars_fit: the model is on another device than the finder");
-  if (!s->have_mesh) return fail(RPSF_E_STATE, "rpsf_stars_fit before a rpsf_stars_background_view / _host / _scaled of the frame");
+  if (const int rc = check_positions_call("rpsf_stars_fit", s, s && model && (!n || (positions_host && cells_host && out_host)),
+                                          rpsff::fit_problem(radius, fit_background), n, positions_host, model, radius))
+    return rc;
   s->fit_ms = 0;
   if (n == 0) return RPSF_OK;  // nothing to launch
   HIP_TRY(hipSetDevice(s->device));
@@ -866,9 +887,8 @@ extern "C" int rpsf_stars_fit(rpsf_stars* s, const rpsf_stars_model* model, size
   const rpsff::Model cube{model->values.p, model->n_cells, model->N};
   const rpsff::Fit fit = rpsff::make_fit(radius, fit_background, model->N);
   if (const int rc = timed(s, &s->fit_ms, [&] {
-        hipLaunchKernelGGL(stars_fit_kernel, dim3((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS), rpsff::s8_lds_bytes(),
-                           nullptr, s->view(), s->level_f.p, s->none.p, use_mesh != 0, cube, fit, s->fit_pos.p, s->fit_cell.p, (long)n,
-                           s->fit_out.p);
+        hipLaunchKernelGGL(stars_fit_kernel, walk_grid(n), dim3(WALK_THREADS), rpsff::s8_lds_bytes(), nullptr, s->view(), s->level_f.p, s->none.p,
+                           use_mesh != 0, cube, fit, s->fit_pos.p, s->fit_cell.p, (long)n, s->fit_out.p);
       }))
     return rc;
   HIP_TRY(hipMemcpy(out_host, s->fit_out.p, RPSF_STARS_FIT_COLUMNS * n * sizeof(double), hipMemcpyDeviceToHost));
@@ -885,20 +905,12 @@ extern "C" int rpsf_stars_fit_ms(const rpsf_stars* s, double* ms) {
 extern "C" int rpsf_stars_fit_positions(rpsf_stars* s, const rpsf_stars_model* model, size_t n, const double* positions_host,
                                         const int32_t* cells_host, double radius, int fit_background, int max_iter, double eps,
                                         double max_shift, double max_step, int use_mesh, double* iter_out_host, double* fit_out_host) {
-  if (!s || !model || (n && (!positions_host || !cells_host || !iter_out_host || !fit_out_host))) return fail(RPSF_E_BADARG, "null argument");
-  if (const char* why = rpsff::fit_problem(radius, fit_background)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit_positions: ") + why);
-  if (const char* why = rpsfg::fitpos_problem(max_iter, eps, max_shift, max_step))
-    return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit_positions: ") + why);
-  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_fit_positions: more than 2^30 positions in one call");
-  for (size_t i = 0; i < n; ++i)
-    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
-      return fail(RPSF_E_BADARG, "rpsf_stars_fit_positions: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
-  if (!(radius <= rpsff::max_fit_radius(model->N)))
-    return fail(RPSF_E_BADARG, "rpsf_stars_fit_positions: radius " + std::to_string(radius) + " is above min(64, N / 2 - 1) of the model's N = " +
-                                   std::to_string(model->N));
-  if (model->device != s->device) return fail(RPSF_E_BADARG, "rpsf_stars_fit_positions: the model is on another device than the finder");
-  if (!s->have_mesh)
-    return fail(RPSF_E_STATE, "rpsf_stars_fit_positions before a rpsf_stars_background_view / _host / _scaled of the frame");
+  const char* why = rpsff::fit_problem(radius, fit_background);
+  if (!why) why = rpsfg::fitpos_problem(max_iter, eps, max_shift, max_step);
+  if (const int rc = check_positions_call("rpsf_stars_fit_positions", s,
+                                          s && model && (!n || (positions_host && cells_host && iter_out_host && fit_out_host)), why, n,
+                                          positions_host, model, radius))
+    return rc;
   s->fitpos_ms = 0;
   if (n == 0) return RPSF_OK;  // nothing to launch
   HIP_TRY(hipSetDevice(s->device));
@@ -913,7 +925,7 @@ extern "C" int rpsf_stars_fit_positions(rpsf_stars* s, const rpsf_stars_model* m
   const rpsff::Fit fit = rpsff::make_fit(radius, fit_background, model->N);
   const rpsfg::FitPos fp = rpsfg::make_fitpos(max_iter, eps, max_shift, max_step);
   if (const int rc = timed(s, &s->fitpos_ms, [&] {
-        const dim3 grid((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES));
+        const dim3 grid = walk_grid(n);
         hipLaunchKernelGGL(stars_fitpos_kernel, grid, dim3(WALK_THREADS), rpsfg::s9_lds_bytes(), nullptr, s->view(), s->level_f.p, s->none.p,
                            use_mesh != 0, cube, fit, fp, s->fitpos_pos.p, s->fitpos_cell.p, (long)n, s->fitpos_iter.p, s->fitpos_final.p);
         // S8 itself at the positions S9 ended at (the null stream orders the two)
@@ -1019,18 +1031,11 @@ extern "C" int rpsf_stars_link_groups(size_t n, const double* positions_host, co
 extern "C" int rpsf_stars_fit_groups(rpsf_stars* s, const rpsf_stars_model* model, size_t n, const double* positions_host,
                                      const int32_t* cells_host, double radius, int fit_background, int use_mesh, double link, int max_group,
                                      double* out_host) {
-  if (!s || !model || (n && (!positions_host || !cells_host || !out_host))) return fail(RPSF_E_BADARG, "null argument");
-  if (const char* why = rpsff::fit_problem(radius, fit_background)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit_groups: ") + why);
-  if (const char* why = rpsfq::group_problem(link, max_group, radius)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit_groups: ") + why);
-  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_fit_groups: more than 2^30 positions in one call");
-  for (size_t i = 0; i < n; ++i)
-    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
-      return fail(RPSF_E_BADARG, "rpsf_stars_fit_groups: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
-  if (!(radius <= rpsff::max_fit_radius(model->N)))
-    return fail(RPSF_E_BADARG, "rpsf_stars_fit_groups: radius " + std::to_string(radius) + " is above min(64, N / 2 - 1) of the model's N = " +
-                                   std::to_string(model->N));
-  if (model->device != s->device) return fail(RPSF_E_BADARG, "rpsf_stars_fit_groups: the model is on another device than the finder");
-  if (!s->have_mesh) return fail(RPSF_E_STATE, "rpsf_stars_fit_groups before a rpsf_stars_background_view / _host / _scaled of the frame");
+  const char* why = rpsff::fit_problem(radius, fit_background);
+  if (!why) why = rpsfq::group_problem(link, max_group, radius);
+  if (const int rc = check_positions_call("rpsf_stars_fit_groups", s, s && model && (!n || (positions_host && cells_host && out_host)), why, n,
+                                          positions_host, model, radius))
+    return rc;
   s->group_ms = 0;
   if (n == 0) return RPSF_OK;  // nothing to launch
   HIP_TRY(hipSetDevice(s->device));
@@ -1071,14 +1076,12 @@ extern "C" int rpsf_stars_fit_groups(rpsf_stars* s, const rpsf_stars_model* mode
   if (const int rc = timed(s, &s->group_ms, [&] {
         // S8's own launch for every star that is alone: its rows are rpsf_stars_fit's
         if (n_lone)
-          hipLaunchKernelGGL(stars_fit_kernel, dim3((unsigned)((n_lone + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS), rpsff::s8_lds_bytes(),
-                             nullptr, s->view(), s->level_f.p, s->none.p, use_mesh != 0, cube, fit, s->group_lone_pos.p, s->group_lone_cell.p,
-                             (long)n_lone, s->group_lone_out.p);
+          hipLaunchKernelGGL(stars_fit_kernel, walk_grid(n_lone), dim3(WALK_THREADS), rpsff::s8_lds_bytes(), nullptr, s->view(), s->level_f.p,
+                             s->none.p, use_mesh != 0, cube, fit, s->group_lone_pos.p, s->group_lone_cell.p, (long)n_lone, s->group_lone_out.p);
         if (n_groups) {
           const rpsfj::GroupList list{s->group_starts.p, s->group_members.p, (long)n_groups};
-          hipLaunchKernelGGL(stars_fit_group_kernel, dim3((unsigned)((n_groups + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS),
-                             rpsfj::s11_lds_bytes(), nullptr, s->view(), s->level_f.p, use_mesh != 0, cube, fit, s->group_pos.p, s->group_cell.p,
-                             list, s->group_out.p);
+          hipLaunchKernelGGL(stars_fit_group_kernel, walk_grid(n_groups), dim3(WALK_THREADS), rpsfj::s11_lds_bytes(), nullptr, s->view(),
+                             s->level_f.p, use_mesh != 0, cube, fit, s->group_pos.p, s->group_cell.p, list, s->group_out.p);
         }
       }))
     return rc;
@@ -1311,19 +1314,11 @@ extern "C" int rpsf_stars_variance_host(rpsf_stars* s, const void* variance_host
 extern "C" int rpsf_stars_fit_weighted(rpsf_stars* s, const rpsf_stars_model* model, size_t n, const double* positions_host,
                                        const int32_t* cells_host, double radius, int fit_background, int use_mesh, int variance_mode,
                                        double sky_variance, double gain, double* out_host) {
-  if (!s || !model || (n && (!positions_host || !cells_host || !out_host))) return fail(RPSF_E_BADARG, "null argument");
-  if (const char* why = rpsff::fit_problem(radius, fit_background)) return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit_weighted: ") + why);
-  if (const char* why = rpsfw::variance_problem(variance_mode, sky_variance, gain))
-    return fail(RPSF_E_BADARG, std::string("rpsf_stars_fit_weighted: ") + why);
-  if (n > ((size_t)1 << 30)) return fail(RPSF_E_UNSUPPORTED, "rpsf_stars_fit_weighted: more than 2^30 positions in one call");
-  for (size_t i = 0; i < n; ++i)
-    if (!rpsfp::position_ok(positions_host[2 * i], positions_host[2 * i + 1]))
-      return fail(RPSF_E_BADARG, "rpsf_stars_fit_weighted: position " + std::to_string(i) + " is not finite or not inside |y|, |x| < 2^20");
-  if (!(radius <= rpsff::max_fit_radius(model->N)))
-    return fail(RPSF_E_BADARG, "rpsf_stars_fit_weighted: radius " + std::to_string(radius) + " is above min(64, N / 2 - 1) of the model's N = " +
-                                   std::to_string(model->N));
-  if (model->device != s->device) return fail(RPSF_E_BADARG, "rpsf_stars_fit_weighted: the model is on another device than the finder");
-  if (!s->have_mesh) return fail(RPSF_E_STATE, "rpsf_stars_fit_weighted before a rpsf_stars_background_view / _host / _scaled of the frame");
+  const char* why = rpsff::fit_problem(radius, fit_background);
+  if (!why) why = rpsfw::variance_problem(variance_mode, sky_variance, gain);
+  if (const int rc = check_positions_call("rpsf_stars_fit_weighted", s, s && model && (!n || (positions_host && cells_host && out_host)), why, n,
+                                          positions_host, model, radius))
+    return rc;
   if (variance_mode == RPSF_STARS_VARIANCE_MAP && !s->have_variance)
     return fail(RPSF_E_STATE, "rpsf_stars_fit_weighted with RPSF_STARS_VARIANCE_MAP before a rpsf_stars_variance_view / _host");
   s->fitw_ms = 0;
@@ -1338,9 +1333,8 @@ extern "C" int rpsf_stars_fit_weighted(rpsf_stars* s, const rpsf_stars_model* mo
   const rpsff::Fit fit = rpsff::make_fit(radius, fit_background, model->N);
   const rpsfw::Variance var{variance_mode == RPSF_STARS_VARIANCE_MAP ? s->variance.p : nullptr, variance_mode, sky_variance, gain};
   if (const int rc = timed(s, &s->fitw_ms, [&] {
-        hipLaunchKernelGGL(stars_fit_weighted_kernel, dim3((unsigned)((n + WALK_WAVES - 1) / WALK_WAVES)), dim3(WALK_THREADS),
-                           rpsfw::s12_lds_bytes(), nullptr, s->view(), s->level_f.p, s->none.p, use_mesh != 0, cube, fit, var, s->fitw_pos.p,
-                           s->fitw_cell.p, (long)n, s->fitw_out.p);
+        hipLaunchKernelGGL(stars_fit_weighted_kernel, walk_grid(n), dim3(WALK_THREADS), rpsfw::s12_lds_bytes(), nullptr, s->view(), s->level_f.p,
+                           s->none.p, use_mesh != 0, cube, fit, var, s->fitw_pos.p, s->fitw_cell.p, (long)n, s->fitw_out.p);
       }))
     return rc;
   HIP_TRY(hipMemcpy(out_host, s->fitw_out.p, RPSF_STARS_FIT_WEIGHTED_COLUMNS * n * sizeof(double), hipMemcpyDeviceToHost));

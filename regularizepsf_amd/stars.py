@@ -69,6 +69,7 @@ variances imply and nothing else, and ``fit_positions`` and ``fit_groups`` stay 
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import numpy as np
@@ -1118,6 +1119,27 @@ def _fit_inputs(images, stars, psf, radius, mask, background, box, fit_backgroun
     return frames, _masks(mask, frames), positions, cells, values, radius
 
 
+@contextlib.contextmanager
+def _fit_session(frames, masks, positions, cells, values, box: int, device: int):
+    """One finder and one model for the frames of a fit: yields ``(finder, model, frames)``, where ``frames`` gives ``(k, positions,
+    cells)`` of frame k once the finder holds that frame and its mesh.  Both handles are closed when the block is left, by a return or by an error."""
+    finder = _Finder(frames[0].shape, box, device)
+    model = None
+    try:
+        model = _Model(values, device)
+
+        def each_frame():
+            for k, (frame, m, p, c) in enumerate(zip(frames, masks, positions, cells)):
+                finder.background_device(frame, m)
+                yield k, p, c
+
+        yield finder, model, each_frame()
+    finally:
+        if model is not None:
+            model.close()
+        finder.close()
+
+
 def fit_stars(images, stars, psf, radius: float, mask=None, *, background: str = "mesh", box: int = 64, fit_background: bool = True,
               cells=None, device: int = 0) -> list[np.ndarray]:
     """Fit every star with the cell of a PSF model it belongs to and report the residual: a list of NumPy structured arrays
@@ -1153,19 +1175,9 @@ def fit_stars(images, stars, psf, radius: float, mask=None, *, background: str =
     """
     frames, masks, positions, cells, values, radius = _fit_inputs(images, stars, psf, radius, mask, background, box, fit_background, cells,
                                                                   device)
-    finder = _Finder(frames[0].shape, box, device)
-    model = None
-    try:
-        model = _Model(values, device)
-        out = []
-        for frame, m, p, c in zip(frames, masks, positions, cells):
-            finder.background_device(frame, m)
-            out.append(fit_from_sums(finder.fit(model, p, c, radius, bool(fit_background), background == "mesh"), bool(fit_background)))
-        return out
-    finally:
-        if model is not None:
-            model.close()
-        finder.close()
+    with _fit_session(frames, masks, positions, cells, values, box, device) as (finder, model, each_frame):
+        return [fit_from_sums(finder.fit(model, p, c, radius, bool(fit_background), background == "mesh"), bool(fit_background))
+                for _, p, c in each_frame]
 
 
 # ---------------------------------------------------------------------------------------------------------------------- weighted fits
@@ -1312,13 +1324,10 @@ def fit_stars_weighted(images, stars, psf, radius: float, mask=None, *, variance
     frames, masks, positions, cells, values, radius = _fit_inputs(images, stars, psf, radius, mask, background, box, fit_background, cells,
                                                                   device)
     variances = [None] * len(frames) if variance is None else _variance_frames(variance, frames, device)
-    finder = _Finder(frames[0].shape, box, device)
-    model = None
-    try:
-        model = _Model(values, device)
+    with _fit_session(frames, masks, positions, cells, values, box, device) as (finder, model, each_frame):
         out, last = [], None
-        for frame, m, p, c, v in zip(frames, masks, positions, cells, variances):
-            finder.background_device(frame, m)
+        for k, p, c in each_frame:
+            v = variances[k]
             if v is not None and v is not last:  # (one map for all frames goes up once)
                 finder.variance(v)
                 last = v
@@ -1326,10 +1335,6 @@ def fit_stars_weighted(images, stars, psf, radius: float, mask=None, *, variance
                                        np.inf if gain is None else gain)
             out.append(weighted_fit_from_sums(rows, bool(fit_background)))
         return out
-    finally:
-        if model is not None:
-            model.close()
-        finder.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------- fitted positions
@@ -1416,21 +1421,13 @@ def fit_positions(images, stars, psf, radius: float, mask=None, *, background: s
             raise ValueError(msg)
     frames, masks, positions, cells, values, radius = _fit_inputs(images, stars, psf, radius, mask, background, box, fit_background, cells,
                                                                   device)
-    finder = _Finder(frames[0].shape, box, device)
-    model = None
-    try:
-        model = _Model(values, device)
+    with _fit_session(frames, masks, positions, cells, values, box, device) as (finder, model, each_frame):
         out = []
-        for frame, m, p, c in zip(frames, masks, positions, cells):
-            finder.background_device(frame, m)
+        for _, p, c in each_frame:
             steps, fits = finder.fit_positions(model, p, c, radius, bool(fit_background), int(max_iter), eps, max_shift, max_step,
                                                background == "mesh")
             out.append(fitpos_from_sums(steps, fits, bool(fit_background)))
         return out
-    finally:
-        if model is not None:
-            model.close()
-        finder.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------- model and residual frames
@@ -1794,17 +1791,9 @@ def fit_groups(images, stars, psf, radius: float, mask=None, *, background: str 
     frames, masks, positions, cells, values, radius = _fit_inputs(images, stars, psf, radius, mask, background, box, fit_background, cells,
                                                                   device)
     link, max_group = _group_options(link, max_group, radius)
-    finder = _Finder(frames[0].shape, box, device)
-    model = None
-    try:
-        model = _Model(values, device)
+    with _fit_session(frames, masks, positions, cells, values, box, device) as (finder, model, each_frame):
         out = []
-        for frame, m, p, c in zip(frames, masks, positions, cells):
-            finder.background_device(frame, m)
+        for _, p, c in each_frame:
             rows = finder.fit_groups(model, p, c, radius, bool(fit_background), background == "mesh", link, max_group)
             out.append(group_fit_from_sums(rows, bool(fit_background), max_group))
         return out
-    finally:
-        if model is not None:
-            model.close()
-        finder.close()

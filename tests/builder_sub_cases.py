@@ -6,14 +6,12 @@ restatement agree bit for bit.  tests/test_gpu_builder_sub.py runs the same case
 import ctypes
 import functools
 import math
-import os
 import pathlib
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 
+from tests import emulib
 from regularizepsf_amd.builder import star_geometry
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -534,25 +532,13 @@ def check_truth(subtracted: tuple, alone: tuple, plain: tuple, frame_max: float,
 
 
 # ---------------------------------------------------------------------------------------------------------------------- the emulator
-def _clang() -> str:
-    clang = "/opt/rocm/lib/llvm/bin/clang++"
-    if not pathlib.Path(clang).exists():
-        clang = shutil.which("clang++") or shutil.which("hipcc")
-    assert clang is not None, "no clang++ to build tests/emu/emu_builder_sub.cpp"
-    return clang
+_clang = emulib.compiler
 
 
 @functools.cache
 def emulator():
     """tests/emu/libemu_builder_sub.so, compiled here when it is missing or older than its sources (as tests/builder_cases.py does)."""
-    src, out = ROOT / "tests" / "emu" / "emu_builder_sub.cpp", ROOT / "tests" / "emu" / "libemu_builder_sub.so"
-    cores = [ROOT / "regularizepsf_amd" / "csrc" / n for n in ("rpsf_core_builder_sub.hpp", "rpsf_core_builder.hpp", "rpsf_core_stars_render.hpp",
-                                                                "rpsf_core_stars_fit.hpp")]
-    if not out.exists() or out.stat().st_mtime < max(p.stat().st_mtime for p in [src, *cores]):
-        fresh = out.with_name(f"libemu_builder_sub.{os.getpid()}.so")
-        subprocess.run([_clang(), "-std=c++20", "-O1", "-shared", "-fPIC", "-o", str(fresh), str(src)], check=True)
-        os.replace(fresh, out)
-    lib = ctypes.CDLL(str(out))
+    lib = emulib.library("emu_builder_sub")
     vp, i, d, q = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_longlong
     lib.emubn_lists.argtypes = [i, i, i, i, vp, vp, i, vp, vp, vp, i, d, vp, vp, q]
     lib.emubn_lists.restype = q

@@ -10,15 +10,13 @@ from __future__ import annotations
 
 import ctypes
 import functools
-import os
 import pathlib
-import shutil
-import subprocess
 
 import numpy as np
 
 from tests import builder_cases as bc
 from tests import cleanup_cases as cc
+from tests import emulib
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 
@@ -39,25 +37,9 @@ PARITY_SIZES = ("n64", "n128")  # cases of builder_cases.SIZE_CASES on which the
 
 
 # ---------------------------------------------------------------------------------------------------------------- emulators
-def _compiled(stem: str, cores: tuple[str, ...]) -> ctypes.CDLL:
-    """tests/emu/lib<stem>.so, compiled when it is missing or older than its sources (as builder_cases.emulator() does).  Without a
-    compiler that is an error, not a skip."""
-    src, out = ROOT / "tests" / "emu" / f"{stem}.cpp", ROOT / "tests" / "emu" / f"lib{stem}.so"
-    sources = [src, *(ROOT / "regularizepsf_amd" / "csrc" / n for n in cores)]
-    if not out.exists() or out.stat().st_mtime < max(p.stat().st_mtime for p in sources):
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        if not pathlib.Path(clang).exists():
-            clang = shutil.which("clang++") or shutil.which("hipcc")
-        assert clang is not None, f"no clang++ to build tests/emu/{stem}.cpp"
-        fresh = out.with_name(f"lib{stem}.{os.getpid()}.so")  # written aside and moved into place: test processes may run side by side
-        subprocess.run([clang, "-std=c++20", "-O1", "-shared", "-fPIC", "-o", str(fresh), str(src)], check=True)
-        os.replace(fresh, out)
-    return ctypes.CDLL(str(out))
-
-
 @functools.cache
 def emulator_b1w():
-    lib = _compiled("emu_builder_wide", ("rpsf_core_builder_wide.hpp", "rpsf_core_builder.hpp"))
+    lib = emulib.library("emu_builder_wide")
     vp, i, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
     lib.emubw_patches.argtypes = [i, vp, i, i, i, vp, vp, d, d, d, i, vp, vp]
     for name in ("emubw_lds_bytes", "emubw_slot_bytes"):
@@ -68,7 +50,7 @@ def emulator_b1w():
 
 @functools.cache
 def emulator_b3w():
-    lib = _compiled("emu_cleanup_wide", ("rpsf_core_cleanup_wide.hpp", "rpsf_core_cleanup.hpp", "rpsf_core_builder.hpp", "rpsf_core_stars.hpp"))
+    lib = emulib.library("emu_cleanup_wide")
     vp, i = ctypes.c_void_p, ctypes.c_int
     lib.emucw_clean.argtypes = [i, i, vp, vp, vp, i]
     for name in ("emucw_lds_bytes", "emucw_slot_bytes"):

@@ -14,6 +14,7 @@ import functools
 
 import numpy as np
 
+from tests import emulib
 from tests import star_cases as sc
 
 ROOT = sc.ROOT
@@ -230,22 +231,7 @@ def one_component_case() -> dict:
 @functools.cache
 def emulator():
     """tests/emu/libemu_deblend.so: the kernels' drivers on the CPU, compiled here when missing or older than its sources."""
-    import os
-    import pathlib
-    import shutil
-    import subprocess
-
-    src, out = ROOT / "tests" / "emu" / "emu_deblend.cpp", ROOT / "tests" / "emu" / "libemu_deblend.so"
-    cores = [ROOT / "regularizepsf_amd" / "csrc" / n for n in ("rpsf_core_stars.hpp", "rpsf_core_stars_deblend.hpp")]
-    if not out.exists() or out.stat().st_mtime < max(src.stat().st_mtime, *(c.stat().st_mtime for c in cores)):
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        if not pathlib.Path(clang).exists():
-            clang = shutil.which("clang++") or shutil.which("hipcc")
-        assert clang is not None, "no clang++ to build tests/emu/emu_deblend.cpp"
-        fresh = out.with_name(f"libemu_deblend.{os.getpid()}.so")
-        subprocess.run([clang, "-std=c++20", "-O1", "-shared", "-fPIC", "-o", str(fresh), str(src)], check=True)
-        os.replace(fresh, out)
-    lib = ctypes.CDLL(str(out))
+    lib = emulib.library("emu_deblend")
     vp, i, d, n = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_long
     lib.emud_basins.argtypes = [vp, vp, i, i, vp]
     lib.emud_detect.argtypes = [vp, vp, i, i, i, vp, d, n, n, i, d, d, vp, n, vp, vp]

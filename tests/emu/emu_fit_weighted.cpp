@@ -10,17 +10,11 @@
 #include <vector>
 
 #include "../../regularizepsf_amd/csrc/rpsf_core_stars_fit_weighted.hpp"
+#include "emu_ctx.hpp"
 
 using namespace rpsfw;
 
 namespace {
-struct CpuCtx {
-  int threads;
-  template <class F>
-  void each(F&& f) {
-    for (int t = 0; t < threads; ++t) f(t);
-  }
-};
 long launches = 0;
 }  // namespace
 

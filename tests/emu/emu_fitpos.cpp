@@ -11,17 +11,11 @@
 #include <vector>
 
 #include "../../regularizepsf_amd/csrc/rpsf_core_stars_fitpos.hpp"
+#include "emu_ctx.hpp"
 
 using namespace rpsfg;
 
 namespace {
-struct CpuCtx {
-  int threads;
-  template <class F>
-  void each(F&& f) {
-    for (int t = 0; t < threads; ++t) f(t);
-  }
-};
 long launches = 0;
 }  // namespace
 

@@ -12,17 +12,11 @@
 #include <vector>
 
 #include "../../regularizepsf_amd/csrc/rpsf_core_stars_fit_group.hpp"
+#include "emu_ctx.hpp"
 
 using namespace rpsfj;
 
 namespace {
-struct CpuCtx {
-  int threads;
-  template <class F>
-  void each(F&& f) {
-    for (int t = 0; t < threads; ++t) f(t);
-  }
-};
 struct GroupCpuCtx : CpuCtx {
   std::vector<Lane> lanes;
   Lane& regs(int t) { return lanes[(size_t)t]; }

@@ -10,18 +10,12 @@
 #include <vector>
 
 #include "../../regularizepsf_amd/csrc/rpsf_core_saturation_batch.hpp"
+#include "emu_ctx.hpp"
 
 using namespace rpsfs;
 using namespace rpsfsatb;
 
 namespace {
-struct CpuCtx {
-  int threads;
-  template <class F>
-  void each(F&& f) {
-    for (int t = 0; t < threads; ++t) f(t);
-  }
-};
 
 // ---------------------------------------------------------------------------------------------------------------- one frame
 struct Filled {

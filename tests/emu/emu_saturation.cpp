@@ -8,18 +8,12 @@
 #include <vector>
 
 #include "../../regularizepsf_amd/csrc/rpsf_core_saturation.hpp"
+#include "emu_ctx.hpp"
 
 using namespace rpsfs;
 using namespace rpsfsat;
 
 namespace {
-struct CpuCtx {
-  int threads;
-  template <class F>
-  void each(F&& f) {
-    for (int t = 0; t < threads; ++t) f(t);
-  }
-};
 
 struct Filled {
   Padded f;

@@ -7,17 +7,11 @@
 #include <vector>
 
 #include "../../regularizepsf_amd/csrc/rpsf_core_stars_shape.hpp"
+#include "emu_ctx.hpp"
 
 using namespace rpsfd;
 
 namespace {
-struct CpuCtx {
-  int threads;
-  template <class F>
-  void each(F&& f) {
-    for (int t = 0; t < threads; ++t) f(t);
-  }
-};
 void label(const uint8_t* det, int H, int W, int32_t* labels) {
   const int tiles_y = (H + TILE_R - 1) / TILE_R, tiles_x = (W + TILE_C - 1) / TILE_C;
   std::vector<int> ll(TILE_R * TILE_C);

@@ -7,17 +7,11 @@
 #include <vector>
 
 #include "../../regularizepsf_amd/csrc/rpsf_core_stars.hpp"
+#include "emu_ctx.hpp"
 
 using namespace rpsfs;
 
 namespace {
-struct CpuCtx {
-  int threads;
-  template <class F>
-  void each(F&& f) {
-    for (int t = 0; t < threads; ++t) f(t);
-  }
-};
 std::vector<uint8_t> mask_or_zeros(const uint8_t* mask, size_t npix) {
   std::vector<uint8_t> m(npix, 0);
   if (mask)

@@ -7,17 +7,11 @@
 #include <vector>
 
 #include "../../regularizepsf_amd/csrc/rpsf_core_stars_mesh.hpp"
+#include "emu_ctx.hpp"
 
 using namespace rpsfm;
 
 namespace {
-struct CpuCtx {
-  int threads;
-  template <class F>
-  void each(F&& f) {
-    for (int t = 0; t < threads; ++t) f(t);
-  }
-};
 
 void select_many(const Source& src, Sel* state, Total* acc, std::vector<uint64_t>& lds) {
   const int nwg = many_workgroups(src.n);

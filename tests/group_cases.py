@@ -20,6 +20,7 @@ import functools
 
 import numpy as np
 
+from tests import emulib
 from regularizepsf_amd import stars
 from tests import fit_cases as fc
 from tests import photometry_cases as pc
@@ -331,25 +332,7 @@ def reference(name: str, level_f, radius: float, with_designs: bool = False):
 @functools.cache
 def emulator():
     """tests/emu/libemu_group.so: the kernel's driver and the grouping on the CPU, compiled here when missing or older than its sources."""
-    import os
-    import pathlib
-    import shutil
-    import subprocess
-
-    src, out = ROOT / "tests" / "emu" / "emu_group.cpp", ROOT / "tests" / "emu" / "libemu_group.so"
-    cores = [ROOT / "regularizepsf_amd" / "csrc" / n for n in ("rpsf_core_stars.hpp", "rpsf_core_stars_deblend.hpp", "rpsf_core_stars_shape.hpp",
-                                                               "rpsf_core_stars_photometry.hpp", "rpsf_core_stars_refine.hpp",
-                                                               "rpsf_core_stars_fit.hpp", "rpsf_core_stars_group.hpp",
-                                                               "rpsf_core_stars_fit_group.hpp")]
-    if not out.exists() or out.stat().st_mtime < max(src.stat().st_mtime, *(c.stat().st_mtime for c in cores)):
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        if not pathlib.Path(clang).exists():
-            clang = shutil.which("clang++") or shutil.which("hipcc")
-        assert clang is not None, "no clang++ to build tests/emu/emu_group.cpp"
-        fresh = out.with_name(f"libemu_group.{os.getpid()}.so")
-        subprocess.run([clang, "-std=c++20", "-O1", "-shared", "-fPIC", "-o", str(fresh), str(src)], check=True)
-        os.replace(fresh, out)
-    lib = ctypes.CDLL(str(out))
+    lib = emulib.library("emu_group")
     vp, i, n, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_double
     lib.emugr_info.argtypes = [vp]
     lib.emugr_link.argtypes = [n, vp, vp, f, i, vp, vp, vp]

@@ -33,6 +33,7 @@ import functools
 
 import numpy as np
 
+from tests import emulib
 from regularizepsf_amd import stars
 from tests import shape_cases as shc
 from tests import star_cases as sc
@@ -201,23 +202,7 @@ def reference(name: str, level_f) -> dict:
 @functools.cache
 def emulator():
     """tests/emu/libemu_photometry.so: the kernel's driver on the CPU, compiled here when missing or older than its sources."""
-    import os
-    import pathlib
-    import shutil
-    import subprocess
-
-    src, out = ROOT / "tests" / "emu" / "emu_photometry.cpp", ROOT / "tests" / "emu" / "libemu_photometry.so"
-    cores = [ROOT / "regularizepsf_amd" / "csrc" / n
-             for n in ("rpsf_core_stars.hpp", "rpsf_core_stars_deblend.hpp", "rpsf_core_stars_shape.hpp", "rpsf_core_stars_photometry.hpp")]
-    if not out.exists() or out.stat().st_mtime < max(src.stat().st_mtime, *(c.stat().st_mtime for c in cores)):
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        if not pathlib.Path(clang).exists():
-            clang = shutil.which("clang++") or shutil.which("hipcc")
-        assert clang is not None, "no clang++ to build tests/emu/emu_photometry.cpp"
-        fresh = out.with_name(f"libemu_photometry.{os.getpid()}.so")
-        subprocess.run([clang, "-std=c++20", "-O1", "-shared", "-fPIC", "-o", str(fresh), str(src)], check=True)
-        os.replace(fresh, out)
-    lib = ctypes.CDLL(str(out))
+    lib = emulib.library("emu_photometry")
     vp, i, n = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
     lib.emuph_info.argtypes = [vp]
     lib.emuph_photometry.argtypes = [vp, vp, i, i, i, vp, i, n, vp, i, vp, i, i, vp]

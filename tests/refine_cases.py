@@ -34,6 +34,7 @@ import math
 
 import numpy as np
 
+from tests import emulib
 from regularizepsf_amd import stars
 from tests import photometry_cases as pc
 from tests import star_cases as sc
@@ -247,23 +248,7 @@ def reference(name: str, level_f, max_iter: int | None = None) -> dict:
 @functools.cache
 def emulator():
     """tests/emu/libemu_refine.so: the kernel's driver on the CPU, compiled here when missing or older than its sources."""
-    import os
-    import pathlib
-    import shutil
-    import subprocess
-
-    src, out = ROOT / "tests" / "emu" / "emu_refine.cpp", ROOT / "tests" / "emu" / "libemu_refine.so"
-    cores = [ROOT / "regularizepsf_amd" / "csrc" / n for n in ("rpsf_core_stars.hpp", "rpsf_core_stars_deblend.hpp", "rpsf_core_stars_shape.hpp",
-                                                               "rpsf_core_stars_photometry.hpp", "rpsf_core_stars_refine.hpp")]
-    if not out.exists() or out.stat().st_mtime < max(src.stat().st_mtime, *(c.stat().st_mtime for c in cores)):
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        if not pathlib.Path(clang).exists():
-            clang = shutil.which("clang++") or shutil.which("hipcc")
-        assert clang is not None, "no clang++ to build tests/emu/emu_refine.cpp"
-        fresh = out.with_name(f"libemu_refine.{os.getpid()}.so")
-        subprocess.run([clang, "-std=c++20", "-O1", "-shared", "-fPIC", "-o", str(fresh), str(src)], check=True)
-        os.replace(fresh, out)
-    lib = ctypes.CDLL(str(out))
+    lib = emulib.library("emu_refine")
     vp, i, n, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_double
     lib.emurf_info.argtypes = [vp]
     lib.emurf_window.argtypes = [n, vp, vp]

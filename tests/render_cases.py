@@ -22,6 +22,7 @@ import functools
 
 import numpy as np
 
+from tests import emulib
 from regularizepsf_amd import stars
 from tests import fit_cases as fc
 from tests import fitpos_cases as fp
@@ -100,24 +101,7 @@ def same_frame(got: np.ndarray, want: np.ndarray) -> bool:
 def emulator():
     """tests/emu/libemu_render.so: the kernel's driver and the host's tile lists on the CPU, compiled here when missing or older than its
     sources."""
-    import os
-    import pathlib
-    import shutil
-    import subprocess
-
-    src, out = ROOT / "tests" / "emu" / "emu_render.cpp", ROOT / "tests" / "emu" / "libemu_render.so"
-    cores = [ROOT / "regularizepsf_amd" / "csrc" / n for n in ("rpsf_core_stars.hpp", "rpsf_core_stars_deblend.hpp", "rpsf_core_stars_shape.hpp",
-                                                               "rpsf_core_stars_photometry.hpp", "rpsf_core_stars_refine.hpp",
-                                                               "rpsf_core_stars_fit.hpp", "rpsf_core_stars_render.hpp")]
-    if not out.exists() or out.stat().st_mtime < max(src.stat().st_mtime, *(c.stat().st_mtime for c in cores)):
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        if not pathlib.Path(clang).exists():
-            clang = shutil.which("clang++") or shutil.which("hipcc")
-        assert clang is not None, "no clang++ to build tests/emu/emu_render.cpp"
-        fresh = out.with_name(f"libemu_render.{os.getpid()}.so")
-        subprocess.run([clang, "-std=c++20", "-O1", "-shared", "-fPIC", "-o", str(fresh), str(src)], check=True)
-        os.replace(fresh, out)
-    lib = ctypes.CDLL(str(out))
+    lib = emulib.library("emu_render")
     vp, i, n, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_double
     lib.emurd_info.argtypes = [vp]
     lib.emurd_lists.argtypes = [i, i, n, i, n, vp, vp, vp, f, vp, vp, n, vp]

@@ -14,6 +14,8 @@ import pathlib
 
 import numpy as np
 
+from tests import emulib
+
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 EIGHT = np.ones((3, 3), int)
 
@@ -232,21 +234,7 @@ def emulator():
     """tests/emu/libemu_stars.so: the kernels' drivers on the CPU.  __graft_entry__.build() compiles it; it is compiled here when it
     is missing or older than its sources.  Without a compiler that is an error, not a skip."""
     import ctypes
-    import os
-    import shutil
-    import subprocess
-
-    src, out = ROOT / "tests" / "emu" / "emu_stars.cpp", ROOT / "tests" / "emu" / "libemu_stars.so"
-    core = ROOT / "regularizepsf_amd" / "csrc" / "rpsf_core_stars.hpp"
-    if not out.exists() or out.stat().st_mtime < max(src.stat().st_mtime, core.stat().st_mtime):
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        if not pathlib.Path(clang).exists():
-            clang = shutil.which("clang++") or shutil.which("hipcc")
-        assert clang is not None, "no clang++ to build tests/emu/emu_stars.cpp"
-        fresh = out.with_name(f"libemu_stars.{os.getpid()}.so")  # written aside and moved into place: test processes may run side by side
-        subprocess.run([clang, "-std=c++20", "-O1", "-shared", "-fPIC", "-o", str(fresh), str(src)], check=True)
-        os.replace(fresh, out)
-    lib = ctypes.CDLL(str(out))
+    lib = emulib.library("emu_stars")
     vp, i, d, n = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_long
     lib.emus_info.argtypes = [vp, vp]
     lib.emus_background.argtypes = [vp, vp, i, i, i, vp, vp]

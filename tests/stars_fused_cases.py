@@ -13,6 +13,7 @@ import pathlib
 
 import numpy as np
 
+from tests import emulib
 from tests import star_cases as sc
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -85,21 +86,7 @@ def emulator():
     """tests/emu/libemu_stars_mesh.so: kernel S1b on the CPU.  __graft_entry__.build() compiles it; it is compiled here when it is missing
     or older than its sources.  Without a compiler that is an error, not a skip."""
     import ctypes
-    import os
-    import shutil
-    import subprocess
-
-    src, out = ROOT / "tests" / "emu" / "emu_stars_mesh.cpp", ROOT / "tests" / "emu" / "libemu_stars_mesh.so"
-    core = ROOT / "regularizepsf_amd" / "csrc" / "rpsf_core_stars_mesh.hpp"
-    if not out.exists() or out.stat().st_mtime < max(src.stat().st_mtime, core.stat().st_mtime):
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        if not pathlib.Path(clang).exists():
-            clang = shutil.which("clang++") or shutil.which("hipcc")
-        assert clang is not None, "no clang++ to build tests/emu/emu_stars_mesh.cpp"
-        fresh = out.with_name(f"libemu_stars_mesh.{os.getpid()}.so")  # written aside and moved into place: test processes may run side by side
-        subprocess.run([clang, "-std=c++20", "-O1", "-shared", "-fPIC", "-o", str(fresh), str(src)], check=True)
-        os.replace(fresh, out)
-    lib = ctypes.CDLL(str(out))
+    lib = emulib.library("emu_stars_mesh")
     vp, i, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
     lib.emusm_info.argtypes = [vp, vp, vp]
     lib.emusm_filter_mesh.argtypes = [vp, vp, i, i, d, i, vp, vp, vp, vp, vp]

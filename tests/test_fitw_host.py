@@ -80,8 +80,14 @@ def test_the_core_header_calls_s8s_functions_and_keeps_contraction_off():
     text = (fw.ROOT / "regularizepsf_amd" / "csrc" / "rpsf_core_stars_fit_weighted.hpp").read_text()
     assert '#include "rpsf_core_stars_fit.hpp"' in text and "#pragma clang fp contract(off)" in text and "namespace rpsfw" in text
     code = "\n".join(line.split("//")[0] for line in text.splitlines())
+    # S12 is S8's driver with a weight policy: the header calls fit_disc and defines no walk, fold or pass 2 of its own, and that driver
+    # and the walk under it call S8's functions
+    assert "fit_disc(" in code and "finite_d(" in code and "each(" not in code and "for (" not in code
+    csrc = fw.ROOT / "regularizepsf_amd" / "csrc"
+    shared = "\n".join(line.split("//")[0] for n in ("rpsf_core_stars_fit.hpp", "rpsf_core_stars_disc.hpp") for line in (csrc / n).read_text().splitlines())
+    assert "void fit_disc(" in shared and "void fit_disc(" not in code
     for name in ("model_at(", "see_residual(", "usable(", "background_at(", "finite_d("):
-        assert name in code, name
+        assert name in shared, name
     for definition in ("double model_at(", "void see_residual(", "double peak_key(", "bool usable(", "double background_at(", "bool finite_d(", "sqrt"):
         assert definition not in code, definition
 
